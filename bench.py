@@ -207,6 +207,28 @@ def free_port():
         return sk.getsockname()[1]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """Write each tensor as d/<name>.npy in float32.  When the arrays together exceed DUMP_LIMIT_BYTES, an array over its
+    share is replaced by a fixed seeded sample of its flattened elements (same positions for every run of the same shape).
+    Returns {name: {"shape", "sampled", "elements"}} for the result line."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // max(1, len(arrays))     # room for the .npy headers
+    info = {}
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        shape, sampled = list(a.shape), a.nbytes > share
+        if sampled:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+        info[name] = {"shape": shape, "sampled": sampled, "elements": int(a.size)}
+    return info
+
+
 def self_launch(n):
     """Re-run this command line as n ranks under torch.distributed.run (one node, 127.0.0.1 rendezvous) and pass rank 0's
     JSON line through.  Returns the launcher's exit code."""
@@ -242,7 +264,12 @@ def main():
     ap.add_argument("--no-torch-reference", action="store_true", help="skip the torch-ROCm eager forward of the same graph (yardstick)")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the fp32 parity-mode, inpainting (configs[3]) and 1024x1024 (configs[4]) side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed region returned (rank 0's final latents) as "
+                         "DIR/<name>.npy in float32, so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -334,16 +361,22 @@ def main():
     elapsed, per_rank, lat = timed_region()
     finite = bool(torch.isfinite(lat).all())
     repeats_s = [elapsed]
+    lat_last = lat
     for _ in range(max(0, args.repeats - 1)):
         e_, _, lat_ = timed_region()
         finite = finite and bool(torch.isfinite(lat_).all())
         repeats_s.append(e_)
+        lat_last = lat_
         del lat_
     if world > 1:                                   # every rank's result must be finite, not only rank 0's
         fl = torch.tensor([1 if finite else 0], device=dev, dtype=torch.int32)
         dist.all_reduce(fl, op=dist.ReduceOp.MIN)
         finite = bool(fl.item())
     assert finite, "non-finite latents"
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"latents": lat_last})
+    del lat_last
 
     # ---- the one collective of the path, timed on its own: all-gather of the final latents [B,4,L,L] fp32 per rank ----
     allgather_us = None
@@ -583,6 +616,9 @@ def main():
             "cpu_baseline": cpu,
             "torch_rocm_reference": torch_ref,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped,
+                                     "note": "rank 0's latents returned by the last timed region"}
         if ranks_share_device:
             out["note"] = ("control-flow run: several ranks shared one GPU (LDMSEG_BENCH_BACKEND=gloo); this is NOT a "
                            "multi-GPU measurement")

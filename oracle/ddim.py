@@ -9,7 +9,10 @@ Restates /root/reference/ldmseg/schedulers/ddim_scheduler.py:
   step            <- step                                   (:218-269)
 
 Arithmetic is done with torch CPU fp32 tensors so that 0-d scalar math
-(``x ** 0.5`` on fp32) rounds exactly as the reference does.
+(``x ** 0.5`` on fp32) rounds exactly as the reference does on the same host.
+torch evaluates that square root with MKL's vector math, whose last bit depends
+on the host CPU, so ``OracleDDIM(sqrt=...)`` can substitute the square roots of
+another host (the golden tests pass the generating host's, tests/golden).
 """
 import math
 
@@ -52,7 +55,8 @@ class OracleDDIM:
     def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02,
                  beta_schedule="linear", clip_sample=True, set_alpha_to_one=True,
                  prediction_type="epsilon", clip_sample_range=1.0,
-                 weight="none", max_snr=5.0, **_ignored):
+                 weight="none", max_snr=5.0, sqrt=None, **_ignored):
+        self.sqrt = sqrt if sqrt is not None else (lambda v: v ** 0.5)
         self.T = num_train_timesteps
         self.betas = make_betas(beta_schedule, beta_start, beta_end, num_train_timesteps)
         self.alphas_cumprod = torch.cumprod(1.0 - self.betas, dim=0)
@@ -83,22 +87,23 @@ class OracleDDIM:
     def step(self, model_output, timestep, sample, use_clipped_model_output=False):
         a_t, a_prev = self.coefficients(timestep)
         b_t = 1 - a_t
+        sq = self.sqrt
         if self.prediction_type == "epsilon":
-            x0 = (sample - b_t ** 0.5 * model_output) / a_t ** 0.5
+            x0 = (sample - sq(b_t) * model_output) / sq(a_t)
             eps = model_output
         elif self.prediction_type == "sample":
             x0 = model_output
-            eps = (sample - a_t ** 0.5 * x0) / b_t ** 0.5
+            eps = (sample - sq(a_t) * x0) / sq(b_t)
         elif self.prediction_type == "v_prediction":
-            x0 = (a_t ** 0.5) * sample - (b_t ** 0.5) * model_output
-            eps = (a_t ** 0.5) * model_output + (b_t ** 0.5) * sample
+            x0 = sq(a_t) * sample - sq(b_t) * model_output
+            eps = sq(a_t) * model_output + sq(b_t) * sample
         else:
             raise NotImplementedError
         if self.clip_sample:
             x0 = x0.clamp(-self.clip_sample_range, self.clip_sample_range)
         if use_clipped_model_output:
-            eps = (sample - a_t ** 0.5 * x0) / b_t ** 0.5
-        prev = a_prev ** 0.5 * x0 + (1 - a_prev) ** 0.5 * eps
+            eps = (sample - sq(a_t) * x0) / sq(b_t)
+        prev = sq(a_prev) * x0 + sq(1 - a_prev) * eps
         return prev, x0
 
     def _bcast(self, v, ref):
@@ -109,12 +114,12 @@ class OracleDDIM:
 
     def add_noise(self, x0, noise, timesteps, scale=1.0):
         ac = self.alphas_cumprod.to(x0.dtype)
-        sa = self._bcast(ac[timesteps] ** 0.5, x0)
-        sb = self._bcast((1 - ac[timesteps]) ** 0.5, x0)
+        sa = self._bcast(self.sqrt(ac[timesteps]), x0)
+        sb = self._bcast(self.sqrt(1 - ac[timesteps]), x0)
         return sa * scale * x0 + sb * noise
 
     def remove_noise(self, xt, noise, timesteps, scale=1.0):
         ac = self.alphas_cumprod.to(xt.dtype)
-        sa = self._bcast(ac[timesteps] ** 0.5, xt)
-        sb = self._bcast((1 - ac[timesteps]) ** 0.5, xt)
+        sa = self._bcast(self.sqrt(ac[timesteps]), xt)
+        sb = self._bcast(self.sqrt(1 - ac[timesteps]), xt)
         return (xt - sb * noise) / (sa * scale)

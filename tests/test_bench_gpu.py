@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -14,16 +15,17 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(nproc, extra_env, port):
+def run_bench(nproc, extra_env, port, extra_args=()):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--profile-steps", "0"]
+           "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--profile-steps", "0",
+           *extra_args]
     return subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
 
 
-def test_two_ranks_over_gloo_share_the_device_and_say_so():
-    r = run_bench(2, {"LDMSEG_BENCH_BACKEND": "gloo"}, 29541)
+def test_two_ranks_over_gloo_share_the_device_and_say_so(tmp_path):
+    r = run_bench(2, {"LDMSEG_BENCH_BACKEND": "gloo"}, 29541, ["--dump-outputs", str(tmp_path / "out")])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]            # rank 0 prints ONE line
@@ -46,6 +48,10 @@ def test_two_ranks_over_gloo_share_the_device_and_say_so():
     assert out["timed_regions"]["n"] == 3 and len(out["timed_regions"]["ms_per_step"]) == 3
     assert out["timed_regions"]["ms_per_step"][0] == pytest.approx(out["ms_per_step"], rel=1e-3)
     assert out["timed_regions"]["min_ms_per_step"] <= out["timed_regions"]["median_ms_per_step"]
+    # --dump-outputs: rank 0's latents of the last timed region, float32, finite
+    lat = np.load(tmp_path / "out" / "latents.npy")
+    assert lat.dtype == np.float32 and lat.shape == (8, 4, 64, 64) and np.isfinite(lat).all()
+    assert out["dumped_outputs"]["arrays"]["latents"] == {"shape": [8, 4, 64, 64], "sampled": False, "elements": 8 * 4 * 64 * 64}
 
 
 def test_two_ranks_over_rccl_when_two_devices_are_visible():

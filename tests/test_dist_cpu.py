@@ -95,3 +95,22 @@ def test_bench_direct_form_spawns_ranks_that_refuse_without_a_gpu():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                        capture_output=True, text=True, timeout=300, env=dict(env, LDMSEG_BENCH_BACKEND="gloo"))
     assert r.returncode != 0 and "needs an MI355X" in (r.stderr + r.stdout)       # both ranks started and refused
+
+
+def test_bench_dump_outputs_float32_within_the_size_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (host side): arrays are written as float32 .npy in full while they fit, and as the same seeded
+    sample of positions on every call once they exceed the size limit."""
+    import numpy as np
+    import bench
+    x = torch.randn(2, 4, 8, 8, dtype=torch.float64)
+    info = bench.dump_outputs(str(tmp_path / "full"), {"latents": x})
+    a = np.load(tmp_path / "full" / "latents.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 4, 8, 8) and np.array_equal(a, x.float().numpy())
+    assert info["latents"] == {"shape": [2, 4, 8, 8], "sampled": False, "elements": 512}
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 1024)
+    for d in ("s1", "s2"):
+        info = bench.dump_outputs(str(tmp_path / d), {"latents": x})
+        assert info["latents"]["sampled"] and info["latents"]["elements"] == 256
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= bench.DUMP_LIMIT_BYTES
+    s1, s2 = np.load(tmp_path / "s1" / "latents.npy"), np.load(tmp_path / "s2" / "latents.npy")
+    assert np.array_equal(s1, s2) and np.isin(s1, a).all()

@@ -8,6 +8,34 @@ from oracle import ddim as o_ddim, vae as o_vae, sample as o_sample, unet as o_u
 from conftest import rel_err
 
 
+def golden_sqrt(g):
+    """The fp32 square roots of the host that generated the goldens (torch's 0-d `** 0.5`, as the reference forms them) for
+    every operand the scheduler takes a root of: alphas_cumprod[t] and 1 - alphas_cumprod[t].  torch evaluates that root
+    with MKL's vector math, whose last bit depends on the host CPU; with these the oracle reproduces the reference's bits
+    on any host.  Any other operand is a KeyError."""
+    a = g["alphas_cumprod"]
+    table = dict(zip(a.view(np.uint32).tolist(), g["sqrt_alphas_cumprod"].tolist()))
+    one_minus = dict(zip((np.float32(1) - a).view(np.uint32).tolist(), g["sqrt_one_minus_alphas_cumprod"].tolist()))
+    assert not set(table) & set(one_minus)
+    table.update(one_minus)
+
+    def sqrt(v):
+        x = np.asarray(v.numpy(), dtype=np.float32)
+        r = np.asarray([table[u] for u in x.reshape(-1).view(np.uint32).tolist()], dtype=np.float32)
+        return torch.from_numpy(r.reshape(x.shape))
+    return sqrt
+
+
+def test_host_sqrt_within_one_ulp_of_golden_host(golden, sched_kw):
+    """This host's torch fp32 square roots of the scheduler tables against the generating host's: equal or one ulp apart
+    (MKL's code paths differ in the last bit, e.g. between Intel and AMD CPUs)."""
+    g = golden("scheduler.npz")
+    ac = o_ddim.OracleDDIM(**sched_kw).alphas_cumprod
+    for ops, key in ((ac, "sqrt_alphas_cumprod"), (1 - ac, "sqrt_one_minus_alphas_cumprod")):
+        host = np.asarray([float(ops[i] ** 0.5) for i in range(len(ops))], dtype=np.float32)
+        assert np.abs(host.view(np.int32).astype(np.int64) - g[key].view(np.int32)).max() <= 1, key
+
+
 def test_scheduler_tables_bit_exact(golden, sched_kw):
     g = golden("scheduler.npz")
     s = o_ddim.OracleDDIM(**sched_kw)
@@ -46,7 +74,7 @@ def test_scheduler_known_grids(sched_kw):
 @pytest.mark.parametrize("ucmo", [False, True])
 def test_scheduler_step_bit_exact(golden, sched_kw, pt, clip, ucmo):
     g = golden("scheduler.npz")
-    s = o_ddim.OracleDDIM(**{**sched_kw, "prediction_type": pt, "clip_sample": clip})
+    s = o_ddim.OracleDDIM(**{**sched_kw, "prediction_type": pt, "clip_sample": clip}, sqrt=golden_sqrt(g))
     s.set_timesteps_inference(50)
     eps, x = torch.from_numpy(g["step_eps"]), torch.from_numpy(g["step_x"])
     key = f"{pt}_clip{int(clip)}_ucmo{int(ucmo)}"
@@ -56,8 +84,8 @@ def test_scheduler_step_bit_exact(golden, sched_kw, pt, clip, ucmo):
         assert np.array_equal(x0.numpy(), g[f"step_x0_{key}"][i]), (key, i)
 
 
-def test_scheduler_known_step_values(sched_kw):
-    s = o_ddim.OracleDDIM(**sched_kw)
+def test_scheduler_known_step_values(golden, sched_kw):
+    s = o_ddim.OracleDDIM(**sched_kw, sqrt=golden_sqrt(golden("scheduler.npz")))
     s.set_timesteps_inference(50)
     prev, x0 = s.step(torch.full((1,), -0.25), 999, torch.full((1,), 0.5))
     assert float(prev) == 0.5948936939239502 and float(x0) == 10.978072166442871
@@ -67,7 +95,7 @@ def test_scheduler_known_step_values(sched_kw):
 
 def test_scheduler_noise_ops(golden, sched_kw):
     g = golden("scheduler.npz")
-    s = o_ddim.OracleDDIM(**sched_kw)
+    s = o_ddim.OracleDDIM(**sched_kw, sqrt=golden_sqrt(g))
     x0, noise, t = (torch.from_numpy(g[k]) for k in ("an_x0", "an_noise", "an_t"))
     assert np.array_equal(s.add_noise(x0, noise, t).numpy(), g["an_out"])
     assert np.array_equal(s.add_noise(x0, noise, t, scale=0.5).numpy(), g["an_out_scale"])
@@ -99,7 +127,18 @@ def test_product_scheduler_host_logic(golden, sched_kw):
     s.set_timesteps_inference(50, tmin=500)
     assert np.array_equal(s.timesteps.numpy(), g["timesteps_50_tmin500"])
     s.set_timesteps_inference(50)
-    assert np.array_equal(s.coefficient_table(), g["coef_50"])         # fp32 scalars, bit-exact
+    # fp32 scalars, bit-exact: the reference's formula with this host's square roots (what the reference computes here),
+    # and with the generating host's square roots it gives the reference's own table
+    def table(sqrt):
+        so = o_ddim.OracleDDIM(**sched_kw, sqrt=sqrt)
+        so.set_timesteps_inference(50)
+        rows = []
+        for t in so.timesteps:
+            a_t, a_prev = so.coefficients(t)
+            rows.append([float(sqrt(a_t)), float(sqrt(1 - a_t)), float(sqrt(a_prev)), float(sqrt(1 - a_prev))])
+        return np.asarray(rows, dtype=np.float32)
+    assert np.array_equal(table(golden_sqrt(g)), g["coef_50"])
+    assert np.array_equal(s.coefficient_table(), table(lambda v: v ** 0.5))
     assert s.steps_offset == 19
     for mode in ("none", "max_clamp_snr", "linear", "fixed"):
         s2 = DDIMNoiseScheduler(**{**sched_kw, "weight": mode})
@@ -147,9 +186,17 @@ def test_sample_loop_vs_reference_scheduler(golden, sched_kw, n):
     wmix = torch.from_numpy(g["wmix"])
 
     def eps_net(inp, t):
-        return torch.tanh(torch.nn.functional.conv2d(inp, wmix, padding=1)) * (1.0 + float(t) / 1000.0)
+        # the stand-in network of tests/golden/make_golden.py: elementwise IEEE operations only, the same bits on every host
+        B, C, H, W = inp.shape
+        p = torch.nn.functional.pad(inp, (1, 1, 1, 1))
+        acc = torch.zeros((B, wmix.shape[0], H, W))
+        for c in range(C):
+            for ky in range(3):
+                for kx in range(3):
+                    acc = acc + wmix[:, c, ky, kx].reshape(1, -1, 1, 1) * p[:, c:c + 1, ky:ky + H, kx:kx + W]
+        return acc / (1 + acc.abs()) * (1.0 + float(t) / 1000.0)
 
-    s = o_ddim.OracleDDIM(**sched_kw)
+    s = o_ddim.OracleDDIM(**sched_kw, sqrt=golden_sqrt(golden("scheduler.npz")))
     s.set_timesteps_inference(n)
     out = o_sample.sample(eps_net, s, torch.from_numpy(g[f"rgb_{n}"]), seed=42, self_condition=True)
     assert np.array_equal(out.numpy(), g[f"final_{n}"])
