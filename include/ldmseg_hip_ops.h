@@ -14,7 +14,8 @@ extern "C" {
 #endif
 
 /* F.conv2d(cat([x, x2],1) [after nearest x2 upsample if up], w, bias, stride, padding=k/2); k in {1,3}.
- * ResnetBlock2D.conv1/conv2/conv_shortcut, Downsample2D, Upsample2D, proj_in/out (diffusers 0.16.1). */
+ * ResnetBlock2D.conv1/conv2/conv_shortcut, Downsample2D, Upsample2D, proj_in/out (diffusers 0.16.1).
+ * dtype 0 fp32, 1 bf16, 2 / 3 split-bf16 products on fp32 tensors (3: weights pre-split into hi | lo planes, as the bf16x3 handles). */
 int ldmseg_op_conv2d(const float* x, const float* x2, const float* w, const float* bias, int B, int Ci, int Ci2, int H,
                      int W, int Co, int k, int stride, int up, int dtype, float* out, void* stream);
 /* F.linear (+row bias per image, +residual, SiLU) or the GEGLU feed-forward half when geglu=1 */
@@ -123,8 +124,10 @@ int ldmseg_bench_attention(const float* qkv, int B, int N, int C, int heads, int
  * launch of this process - lets a parity test assert WHICH kernel it just compared with the oracle. */
 int ldmseg_igemm_last_kernel(char* buf, int n);
 /* enable=1 clears and starts a log of the DISTINCT igemm instantiations launched ("igemm<...>" + "/splitk" for K-sliced
- * launches), enable=0 stops it; _read copies them newline-separated.  The parity suite uses it to prove that every
- * instantiation a full-size forward runs is also compared with the oracle by a per-layer test. */
+ * launches; ",x3" / ",x3w" for split-bf16 products) and of the fused GEMM kernels; enable=2 logs every kernel of the UNet
+ * forward path (split-K finish, GroupNorm, LayerNorm statistics, attention too), each named with its template arguments and
+ * run-time form; enable=0 stops it; _read copies them newline-separated.  The parity suite uses it to prove that every
+ * kernel a full-size forward runs is also compared with the oracle by a per-op test. */
 int ldmseg_igemm_log(int enable);
 int ldmseg_igemm_log_read(char* buf, int n);
 

@@ -422,7 +422,8 @@ int run(const void* qkv, void* out, int B, int N, int C, int heads, hipStream_t 
   }
   const int nqb = (N + 64 * QF - 1) / (64 * QF);
   const float scale_log2e = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
-  hipLaunchKernelGGL(kern, dim3(nqb * heads * B), dim3(256), lds, s, (const IO*)qkv, (IO*)out, N, C, heads, scale_log2e);
+  LDMSEG_LAUNCH(X3 ? launch_name("attn_x3<%d,%d>", D, QF) : launch_name("attn<%s,%d,%d>", dtype_tag<T>(), D, QF), kern,
+                dim3(nqb * heads * B), dim3(256), lds, s, (const IO*)qkv, (IO*)out, N, C, heads, scale_log2e);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -384,7 +384,7 @@ int run3(const void* qkv, void* out, int B, int N, int C, int heads, hipStream_t
   }
   const int nqb = (N + 16 * NWV * QF - 1) / (16 * NWV * QF);
   const float scale_log2e = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
-  hipLaunchKernelGGL(kern, dim3(nqb * heads * B), dim3(64 * NWV), lds, s, (const bf16_t*)qkv, (bf16_t*)out, N, C, heads, scale_log2e);
+  LDMSEG_LAUNCH(launch_name("attn3<%d,%d,%d,%d,%d,%d,%d>", D, QF, WPS, NST, PIPE ? 1 : 0, LAZY, NWV), kern, dim3(nqb * heads * B), dim3(64 * NWV), lds, s, (const bf16_t*)qkv, (bf16_t*)out, N, C, heads, scale_log2e);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -320,7 +320,7 @@ int run4(const void* qkv, void* out, int B, int N, int C, int heads, hipStream_t
   }
   const int nqb = (N + 32 * NWV - 1) / (32 * NWV);
   const float scale_log2e = (1.0f / sqrtf((float)D4)) * 1.4426950408889634f;
-  hipLaunchKernelGGL(kern, dim3(nqb * heads * B), dim3(64 * NWV), lds, s, (const bf16_t*)qkv, (bf16_t*)out, N, C, heads, scale_log2e);
+  LDMSEG_LAUNCH(launch_name("attn4<d40,%d,%d,%d>", NST, LAZY, NWV), kern, dim3(nqb * heads * B), dim3(64 * NWV), lds, s, (const bf16_t*)qkv, (bf16_t*)out, N, C, heads, scale_log2e);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

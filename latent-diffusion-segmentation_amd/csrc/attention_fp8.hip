@@ -348,7 +348,7 @@ int run8(const void* qkv, void* kv8, void* out, int B, int N, int C, int heads, 
     const long per_bh = (long)N * (Cfg::DP / 16) * 2;
     int bx = (int)((per_bh + 255) / 256);
     if (bx > 256) bx = 256;
-    hipLaunchKernelGGL((kv_to_fp8_kernel<D, Cfg::DP>), dim3(bx, heads, B), dim3(256), 0, s, (const bf16_t*)qkv, k8, v8, B, N, C, heads);
+    LDMSEG_LAUNCH(launch_name("kv_to_fp8<%d,%d>", D, Cfg::DP), (kv_to_fp8_kernel<D, Cfg::DP>), dim3(bx, heads, B), dim3(256), 0, s, (const bf16_t*)qkv, k8, v8, B, N, C, heads);
   }
   const size_t lds = (size_t)NST * Cfg::STAGE;
   auto kern = attn_fp8_kernel<D, QF, WPS, NST>;
@@ -361,7 +361,7 @@ int run8(const void* qkv, void* kv8, void* out, int B, int N, int C, int heads, 
   }
   const int nqb = (N + 64 * QF - 1) / (64 * QF);
   const float scale_log2e = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
-  hipLaunchKernelGGL(kern, dim3(nqb * heads * B), dim3(256), lds, s, (const bf16_t*)qkv, k8, v8, (bf16_t*)out, N, C, heads,
+  LDMSEG_LAUNCH(launch_name("attn_fp8<%d,%d,%d,%d>", D, QF, WPS, NST), kern, dim3(nqb * heads * B), dim3(256), lds, s, (const bf16_t*)qkv, k8, v8, (bf16_t*)out, N, C, heads,
                      scale_log2e);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -376,26 +376,26 @@ int launch_attention_mx(const void* qkv, void* kv8, void* out, int B, int N, int
   if (!attention_mx_ok(N, C, heads)) return -2;
   unsigned char* k8 = (unsigned char*)kv8;
   unsigned char* v8 = k8 + (size_t)B * heads * (N / kTile) * kKB;
-  hipLaunchKernelGGL(kv_to_mx_kernel, dim3(N / kTile, heads, B), dim3(256), 0, s, (const bf16_t*)qkv, k8, v8, N, C, heads);
+  LDMSEG_LAUNCH("kv_to_mx", kv_to_mx_kernel, dim3(N / kTile, heads, B), dim3(256), 0, s, (const bf16_t*)qkv, k8, v8, N, C, heads);
   const float scale_log2e = (1.0f / sqrtf((float)kD)) * 1.4426950408889634f;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  auto go = [&](auto kern, int nst, int nw, bool* attr) {
+  auto go = [&](auto kern, int nst, int nw, bool fexp, bool* attr) {
     const size_t lds = (size_t)nst * kStage;
     if (!attr[dev]) {
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       attr[dev] = true;
     }
-    hipLaunchKernelGGL(kern, dim3((N / (32 * nw)) * heads * B), dim3(64 * nw), lds, s, (const bf16_t*)qkv, k8, v8, (bf16_t*)out, N, C,
+    LDMSEG_LAUNCH(launch_name("attn_mx<%d,%d,%d>", nst, nw, fexp ? 1 : 0), kern, dim3((N / (32 * nw)) * heads * B), dim3(64 * nw), lds, s, (const bf16_t*)qkv, k8, v8, (bf16_t*)out, N, C,
                        heads, scale_log2e, g_mx_pshift);
   };
   static bool a0[64] = {}, a1[64] = {}, a2[64] = {}, a3[64] = {};
   const int variant = (N % 256 == 0) ? g_mx_variant : (g_mx_variant & 2);      // 8-wave workgroups own 256 queries
   switch (variant) {
-    case 0: go(attn_mx_kernel<3, 4, false>, 3, 4, a0); break;
-    case 1: go(attn_mx_kernel<3, 8, false>, 3, 8, a1); break;
-    case 2: go(attn_mx_kernel<3, 4, true>, 3, 4, a2); break;
-    default: go(attn_mx_kernel<3, 8, true>, 3, 8, a3); break;
+    case 0: go(attn_mx_kernel<3, 4, false>, 3, 4, false, a0); break;
+    case 1: go(attn_mx_kernel<3, 8, false>, 3, 8, false, a1); break;
+    case 2: go(attn_mx_kernel<3, 4, true>, 3, 4, true, a2); break;
+    default: go(attn_mx_kernel<3, 8, true>, 3, 8, true, a3); break;
   }
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }

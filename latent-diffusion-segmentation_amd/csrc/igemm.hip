@@ -24,6 +24,7 @@
 //    Out-of-image taps read a 16-B page of zeros.
 //  * workgroup id -> (m tile, n tile) is remapped so that each XCD (own L2)
 //    owns a contiguous range of tiles.
+#include <cstdarg>
 #include <cstdio>
 #include <set>
 #include <string>
@@ -1231,7 +1232,7 @@ constexpr int kDefaultPolicy = 61;
 }  // namespace
 std::string igemm_dispatch_name(const IgemmDispatch& d);
 namespace {
-bool g_log_on = false;
+int g_log_level = 0;       // igemm_log_enable
 std::set<std::string> g_log;   // distinct instantiations launched while logging is on
 IgemmDispatch g_last{};   // what the last launch_igemm on this thread's process ran (parity tests assert on it)
 int g_dbg = 0;       // ablation flags (profiling experiments only)
@@ -1332,21 +1333,22 @@ int run(const IgemmParams& pin, hipStream_t s) {
     p.cf_poll_ticks = (g_cf_mode & 2) ? 0 : (us ? us : 200) * 100;
   }
   g_last = IgemmDispatch{(int)sizeof(T) == 2 ? DT_BF16 : DT_F32, BM, BN, WM, WN, NST, PIPE ? 1 : 0, LDR,
-                         p.splits > 1 ? p.splits : 1, grid_x, LNF ? 1 : 0, CM ? 1 : 0, p.cf, XT ? 1 : 0, UP4 ? 1 : 0};
-  if (g_log_on) g_log.insert(igemm_dispatch_name(g_last));
+                         p.splits > 1 ? p.splits : 1, grid_x, LNF ? 1 : 0, CM ? 1 : 0, p.cf, XT ? 1 : 0, UP4 ? 1 : 0,
+                         sizeof(T) == 4 ? p.x3 : 0};
   if constexpr (kHasCf) {
     if (p.cf) {
-      hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, NST, PIPE, LDR, LNF, CM, XT, UP4, true>), dim3(grid_x), dim3((WM * WN + LDR) * 64), lds, s, p);
+      LDMSEG_LAUNCH_GEMM(igemm_dispatch_name(g_last), (igemm_kernel<T, BM, BN, WM, WN, NST, PIPE, LDR, LNF, CM, XT, UP4, true>), dim3(grid_x),
+                         dim3((WM * WN + LDR) * 64), lds, s, p);
       return hipGetLastError() == hipSuccess ? 0 : -3;
     }
   }
-  hipLaunchKernelGGL(kern, dim3(grid_x), dim3((WM * WN + LDR) * 64), lds, s, p);
+  LDMSEG_LAUNCH_GEMM(igemm_dispatch_name(g_last), kern, dim3(grid_x), dim3((WM * WN + LDR) * 64), lds, s, p);
   if (p.splits > 1 && !p.no_finish) {
     const int nq = p.n_valid >> 2;
     const int gx = (nq + 63) / 64;
     int gy = (p.M + 3) / 4;
     if (gy > 2048 / gx) gy = 2048 / gx > 0 ? 2048 / gx : 1;
-    hipLaunchKernelGGL(splitk_finish_kernel<T>, dim3(gx, gy), dim3(256), 0, s, p);
+    LDMSEG_LAUNCH(launch_name("splitk_finish<%s>", dtype_tag<T>()), splitk_finish_kernel<T>, dim3(gx, gy), dim3(256), 0, s, p);
   }
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -1458,7 +1460,7 @@ int launch_finish(const IgemmParams& pin, hipStream_t s) {
   const int gx = (nq + 63) / 64;
   int gy = (p.M + 3) / 4;
   if (gy > 2048 / gx) gy = 2048 / gx > 0 ? 2048 / gx : 1;
-  hipLaunchKernelGGL(splitk_finish_kernel<T>, dim3(gx, gy), dim3(256), 0, s, p);
+  LDMSEG_LAUNCH(launch_name("splitk_finish<%s>", dtype_tag<T>()), splitk_finish_kernel<T>, dim3(gx, gy), dim3(256), 0, s, p);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -1566,16 +1568,27 @@ void igemm_set_dbg(int f) { g_dbg = f & 0xff; g_big = (f >> 8) & 63; }   // bits
 int igemm_get_dbg() { return (g_big << 8) | g_dbg; }
 int igemm_default_dbg() { return kDefaultPolicy << 8; }
 IgemmDispatch igemm_last_dispatch() { return g_last; }
-// "igemm<dtype,BM,BN,WM,WN,NST,PIPE,LDR>" + "/splitk" when the launch ran K slices (partial epilogue + finish kernel)
+// "igemm<dtype,BM,BN,WM,WN,NST,PIPE,LDR>" + "/splitk" when the launch ran K slices (partial epilogue + finish kernel); the
+// split-bf16 K loop of an fp32 instantiation is marked ",x3" (hi / lo split of both operands in registers) or ",x3w" (W read as
+// pre-split hi | lo planes)
 std::string igemm_dispatch_name(const IgemmDispatch& d) {
-  char buf[96];
-  std::snprintf(buf, sizeof buf, "igemm<%s,%d,%d,%d,%d,%d,%d,%d%s%s>%s", d.dtype == DT_BF16 ? "bf16" : "f32", d.bm, d.bn, d.wm, d.wn,
+  char buf[112];
+  std::snprintf(buf, sizeof buf, "igemm<%s,%d,%d,%d,%d,%d,%d,%d%s%s%s>%s", d.dtype == DT_BF16 ? "bf16" : "f32", d.bm, d.bn, d.wm, d.wn,
                 d.nst, d.pipe, d.ldr, d.lnf ? ",ln" : "", d.cm ? ",cm" : (d.xt ? ",xt" : (d.up4 ? ",up4" : "")),
-                d.splits > 1 ? (d.cf ? "/splitk-cf" : "/splitk") : "");
+                d.x3 == 2 ? ",x3w" : (d.x3 ? ",x3" : ""), d.splits > 1 ? (d.cf ? "/splitk-cf" : "/splitk") : "");
   return buf;
 }
-void igemm_log_enable(int on) { g_log_on = on != 0; if (on) g_log.clear(); }
-void igemm_log_note(const char* name) { if (g_log_on) g_log.insert(name); }   // kernels of the GEMM family that are not igemm_kernel (tfuse.hip)
+void igemm_log_enable(int level) { g_log_level = level < 0 ? 0 : (level > 2 ? 2 : level); if (g_log_level) g_log.clear(); }
+int igemm_log_level() { return g_log_level; }
+void igemm_log_note(const char* name) { if (g_log_level) g_log.insert(name); }
+std::string launch_name(const char* fmt, ...) {
+  char buf[160];
+  va_list ap;
+  va_start(ap, fmt);
+  std::vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  return buf;
+}
 std::string igemm_log_read() {
   std::string out;
   for (const auto& e : g_log) { out += e; out += '\n'; }

@@ -155,12 +155,31 @@ void igemm_force_cfg(int cfg);   // tuning tool: >= 0 runs every launch with tha
 int igemm_get_dbg();       // current (policy << 8) | ablation flags
 int igemm_default_dbg();   // the shipped value
 // template instantiation + plan of the most recent launch_igemm (test introspection)
-struct IgemmDispatch { int dtype, bm, bn, wm, wn, nst, pipe, ldr, splits, grid, lnf, cm, cf, xt, up4; };   // cf: the K slices were finished inside the launch
+// cf: the K slices were finished inside the launch; x3: IgemmParams::x3 (1 = split-bf16 in the K loop, 2 = W holds hi | lo planes)
+struct IgemmDispatch { int dtype, bm, bn, wm, wn, nst, pipe, ldr, splits, grid, lnf, cm, cf, xt, up4, x3; };
 IgemmDispatch igemm_last_dispatch();
 std::string igemm_dispatch_name(const IgemmDispatch& d);
-void igemm_log_enable(int on);      // start (and clear) / stop recording the distinct instantiations launched
-void igemm_log_note(const char* name);   // recorded while logging is on (the fused feed-forward kernel: "mlp_fused<bf16,proj=P>")
-std::string igemm_log_read();       // newline-separated   // ablation flags (profiling only)   // K-loop ring depth (2, 3, 4) - tuning knob
+// the dispatch log: level 0 = off; 1 = the GEMM family (igemm instantiations, the fused GEMM kernels of tfuse / tproj / tail);
+// 2 = every kernel of the forward path (+ split-K finish, GroupNorm, LayerNorm statistics, attention).  Enabling clears it.
+void igemm_log_enable(int level);
+int igemm_log_level();
+void igemm_log_note(const char* name);   // recorded while logging is on
+std::string igemm_log_read();       // newline-separated
+std::string launch_name(const char* fmt, ...);          // printf into a std::string (the names below)
+template <typename T>
+constexpr const char* dtype_tag() { return sizeof(T) == 2 ? "bf16" : "f32"; }
+// Every kernel launch of the forward path goes through one of these: NAME - the kernel with every template argument and the
+// run-time form that changes the code it runs, so that two launches executing different code never share a name - is recorded
+// in the dispatch log (evaluated only while the log is at LEVEL or above), then the kernel is launched.  LDMSEG_LAUNCH_GEMM: the
+// GEMM family (log level 1); LDMSEG_LAUNCH: every other kernel (level 2).  tests/test_launch_sites_cpu.py rejects bare
+// hipLaunchKernelGGL calls in those sources outside its allow-list.
+#define LDMSEG_LAUNCH_AT(LEVEL, NAME, ...)                                                                  \
+  do {                                                                                                      \
+    if (::ldmseg::igemm_log_level() >= (LEVEL)) ::ldmseg::igemm_log_note(std::string(NAME).c_str());        \
+    hipLaunchKernelGGL(__VA_ARGS__);                                                                        \
+  } while (0)
+#define LDMSEG_LAUNCH_GEMM(NAME, ...) LDMSEG_LAUNCH_AT(1, NAME, __VA_ARGS__)
+#define LDMSEG_LAUNCH(NAME, ...) LDMSEG_LAUNCH_AT(2, NAME, __VA_ARGS__)
 // tile the launcher would pick (for weight padding): N tile size for a given N.
 int igemm_pick_bn(int n_real, int epi);
 

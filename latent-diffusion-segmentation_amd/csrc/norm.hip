@@ -1404,7 +1404,7 @@ int run_gn(const GNParams& pin, hipStream_t s) {
       p.fd_aux = fastdiv_make(vpp);
       p.fd_vx = fastdiv_make(S);
       p.fd_cpg = fastdiv_make(p.groups / GB);
-      hipLaunchKernelGGL((gn_coop_kernel<T, MAXVC, NTC>), dim3(slabs * S), dim3(NTC), 0, s, p, GB);
+      LDMSEG_LAUNCH(launch_name("gn_coop<%s,%d,%d,GB=%d>", dtype_tag<T>(), MAXVC, NTC, GB), (gn_coop_kernel<T, MAXVC, NTC>), dim3(slabs * S), dim3(NTC), 0, s, p, GB);
       return hipGetLastError() == hipSuccess ? 0 : -3;
     }
     p.fd_cpg = fastdiv_make(p.cpg);
@@ -1420,8 +1420,8 @@ int run_gn(const GNParams& pin, hipStream_t s) {
     if (!(g_gn_variant & 33) && p.HW >= 256 && p.cpg % 4 == 0 && p.cpg <= 128 && p.C0 % 4 == 0 && p.C1 % 4 == 0 && acc8 <= 512L * nv_max &&
         (long)p.B * p.groups >= 128) {
       const int upp = p.cpg / 4;                                    // 8-byte accesses per pixel
-      if (acc8 <= 512 * 10) hipLaunchKernelGGL((gn_group_kernel<10, 2>), dim3(p.B * p.groups), dim3(512), 0, s, p, upp, 512 / upp, 512 % upp);
-      else hipLaunchKernelGGL((gn_group_kernel<20, 2>), dim3(p.B * p.groups), dim3(512), 0, s, p, upp, 512 / upp, 512 % upp);
+      if (acc8 <= 512 * 10) LDMSEG_LAUNCH("gn_group<bf16,10,2>", (gn_group_kernel<10, 2>), dim3(p.B * p.groups), dim3(512), 0, s, p, upp, 512 / upp, 512 % upp);
+      else LDMSEG_LAUNCH("gn_group<bf16,20,2>", (gn_group_kernel<20, 2>), dim3(p.B * p.groups), dim3(512), 0, s, p, upp, 512 / upp, 512 % upp);
       return hipGetLastError() == hipSuccess ? 0 : -3;
     }
   }
@@ -1450,13 +1450,13 @@ int run_gn(const GNParams& pin, hipStream_t s) {
       if (!(g_gn_variant & 4) && nv <= 12) {                   // shipped: one reduction, one barrier (gn_one_kernel); measured at
         // B = 8: 8x8 x 1280 6.2 -> 4.1 us, 16x16 x 1280 7.9 -> 6.9 us; with more than 12 vectors per thread the two-pass kernel
         // below is the faster one (16x16 x 1920: 10.2 against 11.4 us)
-        if (nv <= 2) hipLaunchKernelGGL((gn_one_kernel<T, 2>), grid1, dim3(256), 0, s, p, GB);
-        else if (nv <= 6) hipLaunchKernelGGL((gn_one_kernel<T, 6>), grid1, dim3(256), 0, s, p, GB);
-        else hipLaunchKernelGGL((gn_one_kernel<T, 12>), grid1, dim3(256), 0, s, p, GB);
+        if (nv <= 2) LDMSEG_LAUNCH(launch_name("gn_one<%s,2,GB=%d>", dtype_tag<T>(), GB), (gn_one_kernel<T, 2>), grid1, dim3(256), 0, s, p, GB);
+        else if (nv <= 6) LDMSEG_LAUNCH(launch_name("gn_one<%s,6,GB=%d>", dtype_tag<T>(), GB), (gn_one_kernel<T, 6>), grid1, dim3(256), 0, s, p, GB);
+        else LDMSEG_LAUNCH(launch_name("gn_one<%s,12,GB=%d>", dtype_tag<T>(), GB), (gn_one_kernel<T, 12>), grid1, dim3(256), 0, s, p, GB);
         return hipGetLastError() == hipSuccess ? 0 : -3;
       }
       if (p.HW <= 64 && vpp < 10) continue;                    // 8x8 maps with short runs: gn_small measured faster (8.0 vs 9.7 us)
-      hipLaunchKernelGGL((gn_fused_kernel<T, MAXV>), grid, dim3(256), 0, s, p, GB);
+      LDMSEG_LAUNCH(launch_name("gn_fused<%s,%d,GB=%d>", dtype_tag<T>(), MAXV, GB), (gn_fused_kernel<T, MAXV>), grid, dim3(256), 0, s, p, GB);
       return hipGetLastError() == hipSuccess ? 0 : -3;
     }
   }
@@ -1471,7 +1471,7 @@ int run_gn(const GNParams& pin, hipStream_t s) {
     // measured: wins for the 8x8 maps (16 -> 9 us), loses from 16x16 up (its 4-byte strided loads)
     if (cpg % EPU == 0 && p.C0 % EPU == 0 && nunits <= 256 * 12 && (long)p.B * p.groups >= 128) {
       p.fd_aux = fastdiv_make(cpg / EPU);
-      hipLaunchKernelGGL((gn_small_kernel<T, 12>), dim3(p.groups, p.B), dim3(256), 0, s, p);
+      LDMSEG_LAUNCH(launch_name("gn_small<%s,12>", dtype_tag<T>()), (gn_small_kernel<T, 12>), dim3(p.groups, p.B), dim3(256), 0, s, p);
       return hipGetLastError() == hipSuccess ? 0 : -3;
     }
   }
@@ -1483,7 +1483,7 @@ int run_gn(const GNParams& pin, hipStream_t s) {
   // at most 128 chunk partials per lane set (gn_reduce_stats: MAXP = 16 x 8 lanes)
   if (p.nchunk < 1 || p.nchunk > 128 || p.groups > 32) return -2;
   p.per = (p.HW + p.nchunk - 1) / p.nchunk;
-  hipLaunchKernelGGL(gn_partial_kernel<T>, dim3(p.nchunk, p.B), dim3(256), 0, s, p);
+  LDMSEG_LAUNCH(launch_name("gn_partial<%s>", dtype_tag<T>()), gn_partial_kernel<T>, dim3(p.nchunk, p.B), dim3(256), 0, s, p);
   // pixel chunks: >= 4 pixels per thread row, ~2048 workgroups in total
   const int ty = p.ty;
   // 16 pixels per thread row (4 unrolled trips) on the big maps, down to 4 when that would leave fewer than ~512
@@ -1494,7 +1494,7 @@ int run_gn(const GNParams& pin, hipStream_t s) {
   const int cap = max(1, 1024 / p.B);
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(blocks, p.B), dim3(256), 0, s, p);
+  LDMSEG_LAUNCH(launch_name("gn_apply<%s>", dtype_tag<T>()), gn_apply_kernel<T>, dim3(blocks, p.B), dim3(256), 0, s, p);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -1511,10 +1511,10 @@ int run_ln(const void* x, void* y, const float* g, const float* b, int M, int C,
     return dim3(blocks < 1 ? 1 : blocks);
   };
   switch (vpl) {
-    case 1: hipLaunchKernelGGL((layernorm_kernel<T, 1, 4>), grid_for_rpw(4), block, 0, s, (const T*)x, (T*)y, g, b, M, C, eps, silu); break;
-    case 2: hipLaunchKernelGGL((layernorm_kernel<T, 2, 4>), grid_for_rpw(4), block, 0, s, (const T*)x, (T*)y, g, b, M, C, eps, silu); break;
-    case 3: hipLaunchKernelGGL((layernorm_kernel<T, 3, 2>), grid_for_rpw(2), block, 0, s, (const T*)x, (T*)y, g, b, M, C, eps, silu); break;
-    case 4: case 5: hipLaunchKernelGGL((layernorm_kernel<T, 5, 1>), grid_for_rpw(1), block, 0, s, (const T*)x, (T*)y, g, b, M, C, eps, silu); break;
+    case 1: LDMSEG_LAUNCH(launch_name("layernorm<%s,1,4>", dtype_tag<T>()), (layernorm_kernel<T, 1, 4>), grid_for_rpw(4), block, 0, s, (const T*)x, (T*)y, g, b, M, C, eps, silu); break;
+    case 2: LDMSEG_LAUNCH(launch_name("layernorm<%s,2,4>", dtype_tag<T>()), (layernorm_kernel<T, 2, 4>), grid_for_rpw(4), block, 0, s, (const T*)x, (T*)y, g, b, M, C, eps, silu); break;
+    case 3: LDMSEG_LAUNCH(launch_name("layernorm<%s,3,2>", dtype_tag<T>()), (layernorm_kernel<T, 3, 2>), grid_for_rpw(2), block, 0, s, (const T*)x, (T*)y, g, b, M, C, eps, silu); break;
+    case 4: case 5: LDMSEG_LAUNCH(launch_name("layernorm<%s,5,1>", dtype_tag<T>()), (layernorm_kernel<T, 5, 1>), grid_for_rpw(1), block, 0, s, (const T*)x, (T*)y, g, b, M, C, eps, silu); break;
     default: return -2;
   }
   return hipGetLastError() == hipSuccess ? 0 : -3;
@@ -1541,17 +1541,17 @@ int run_rowstats(const void* x, float* stats, int M, int C, float eps, hipStream
       return dim3(blocks < 1 ? 1 : blocks);
     };
     if (!(g_gn_variant & 16)) {       // (tuning bit 4: the one-row-per-wave kernel below)
-      if (nvec <= 40) { hipLaunchKernelGGL((rowstats_kernel<T, 8, RPW>), grid_rows(8 * RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
-      if (nvec <= 80) { hipLaunchKernelGGL((rowstats_kernel<T, 16, RPW>), grid_rows(4 * RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
-      if (nvec <= 160) { hipLaunchKernelGGL((rowstats_kernel<T, 32, RPW>), grid_rows(2 * RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
-      if (nvec <= 320) { hipLaunchKernelGGL((rowstats_kernel<T, 64, RPW>), grid_rows(RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
+      if (nvec <= 40) { LDMSEG_LAUNCH(launch_name("rowstats<%s,8,%d>", dtype_tag<T>(), RPW), (rowstats_kernel<T, 8, RPW>), grid_rows(8 * RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
+      if (nvec <= 80) { LDMSEG_LAUNCH(launch_name("rowstats<%s,16,%d>", dtype_tag<T>(), RPW), (rowstats_kernel<T, 16, RPW>), grid_rows(4 * RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
+      if (nvec <= 160) { LDMSEG_LAUNCH(launch_name("rowstats<%s,32,%d>", dtype_tag<T>(), RPW), (rowstats_kernel<T, 32, RPW>), grid_rows(2 * RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
+      if (nvec <= 320) { LDMSEG_LAUNCH(launch_name("rowstats<%s,64,%d>", dtype_tag<T>(), RPW), (rowstats_kernel<T, 64, RPW>), grid_rows(RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
     }
   }
   switch (vpl) {
-    case 1: hipLaunchKernelGGL((layernorm_kernel<T, 1, 4, true>), grid_for_rpw(4), block, 0, s, xp, (T*)nullptr, nullptr, nullptr, M, C, eps, 0, stats); break;
-    case 2: hipLaunchKernelGGL((layernorm_kernel<T, 2, 4, true>), grid_for_rpw(4), block, 0, s, xp, (T*)nullptr, nullptr, nullptr, M, C, eps, 0, stats); break;
-    case 3: hipLaunchKernelGGL((layernorm_kernel<T, 3, 2, true>), grid_for_rpw(2), block, 0, s, xp, (T*)nullptr, nullptr, nullptr, M, C, eps, 0, stats); break;
-    case 4: case 5: hipLaunchKernelGGL((layernorm_kernel<T, 5, 2, true>), grid_for_rpw(2), block, 0, s, xp, (T*)nullptr, nullptr, nullptr, M, C, eps, 0, stats); break;
+    case 1: LDMSEG_LAUNCH(launch_name("layernorm<%s,1,4,stats>", dtype_tag<T>()), (layernorm_kernel<T, 1, 4, true>), grid_for_rpw(4), block, 0, s, xp, (T*)nullptr, nullptr, nullptr, M, C, eps, 0, stats); break;
+    case 2: LDMSEG_LAUNCH(launch_name("layernorm<%s,2,4,stats>", dtype_tag<T>()), (layernorm_kernel<T, 2, 4, true>), grid_for_rpw(4), block, 0, s, xp, (T*)nullptr, nullptr, nullptr, M, C, eps, 0, stats); break;
+    case 3: LDMSEG_LAUNCH(launch_name("layernorm<%s,3,2,stats>", dtype_tag<T>()), (layernorm_kernel<T, 3, 2, true>), grid_for_rpw(2), block, 0, s, xp, (T*)nullptr, nullptr, nullptr, M, C, eps, 0, stats); break;
+    case 4: case 5: LDMSEG_LAUNCH(launch_name("layernorm<%s,5,2,stats>", dtype_tag<T>()), (layernorm_kernel<T, 5, 2, true>), grid_for_rpw(2), block, 0, s, xp, (T*)nullptr, nullptr, nullptr, M, C, eps, 0, stats); break;
     default: return -2;
   }
   return hipGetLastError() == hipSuccess ? 0 : -3;
@@ -1650,7 +1650,7 @@ int run_finish_gn(const IgemmParams& ip, GNParams p, hipStream_t s) {
   p.fd_aux = fastdiv_make(vpp);
   const dim3 grid((32 / GB) * p.B);
   const long slab = (long)ip.M * ip.N;
-#define LDMSEG_FGN(MV) hipLaunchKernelGGL((finish_gn_kernel<T, MV>), grid, dim3(256), 0, s, p, GB, ip.partial, ip.splits, ip.N, slab, \
+#define LDMSEG_FGN(MV) LDMSEG_LAUNCH(launch_name("finish_gn<%s,%d,GB=%d>", dtype_tag<T>(), MV, GB), (finish_gn_kernel<T, MV>), grid, dim3(256), 0, s, p, GB, ip.partial, ip.splits, ip.N, slab, \
                                           ip.bias, ip.rowbias, ip.rb_stride)
   if (nv <= 2) LDMSEG_FGN(2);
   else if (nv <= 6) LDMSEG_FGN(6);
@@ -1684,7 +1684,7 @@ int run_gn_stats(const GNParams& pin, hipStream_t s) {
   p.fd_vx = fastdiv_make(p.vx);
   if (p.nchunk < 1 || p.nchunk > 128) return -2;
   p.per = (p.HW + p.nchunk - 1) / p.nchunk;
-  hipLaunchKernelGGL(gn_partial_kernel<T>, dim3(p.nchunk, p.B), dim3(256), 0, s, p);
+  LDMSEG_LAUNCH(launch_name("gn_partial<%s>", dtype_tag<T>()), gn_partial_kernel<T>, dim3(p.nchunk, p.B), dim3(256), 0, s, p);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 int launch_groupnorm_stats(const GNParams& p, int dtype, hipStream_t s) {

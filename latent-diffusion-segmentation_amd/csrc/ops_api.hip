@@ -96,6 +96,8 @@ int ldmseg_op_conv2d(const float* x, const float* x2, const float* w, const floa
                      int W, int Co, int k, int stride, int up, int dtype, float* out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   Temp t;
+  const int x3 = dtype == 2 ? 1 : (dtype == 3 ? 2 : 0);   // split-bf16 products on fp32 tensors (3: weights as hi | lo planes)
+  if (x3) dtype = DT_F32;
   const int a = bke(dtype);
   const int c0 = rupi(Ci, a), c1 = Ci2 ? rupi(Ci2, a) : 0;
   if (Ci2 && (Ci % a)) return -2;  // a concat boundary must be K-tile aligned
@@ -129,6 +131,8 @@ int ldmseg_op_conv2d(const float* x, const float* x2, const float* w, const floa
   p.src0 = xp; p.C0 = c0; p.src1 = x2p; p.C1 = c1;
   p.B = B; p.Hi = H; p.Wi = W; p.Ho = Ho; p.Wo = Wo; p.taps = k * k; p.stride = stride; p.up = up;
   p.M = B * Ho * Wo; p.N = Np; p.n_valid = Co; p.W = wp; p.bias = bp; p.out = out; p.epi = EPI_NCHW_F32;
+  p.x3 = x3;
+  if (x3 == 2 && launch_split_planes(wp, (size_t)Np * k * k * ct, s)) return -3;
   if (std::getenv("LDMSEG_OP_TIMING_NHWC")) {   // kernel-timing experiments: the engine's NHWC store epilogue (output discarded)
     p.out = t.get((size_t)p.M * Co * es(dtype)); p.ldo = Co; p.epi = EPI_STORE;
   }

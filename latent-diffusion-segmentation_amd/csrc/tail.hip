@@ -184,8 +184,7 @@ int launch_conv_out_tail(const StepTail& t, hipStream_t s) {
     (void)hipFuncSetAttribute((const void*)conv_out_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     attr_set[dev] = true;
   }
-  igemm_log_note("conv_out_tail<bf16>");
-  hipLaunchKernelGGL(conv_out_tail_kernel, dim3(t.W / kTW, t.H / kTH, t.B), dim3(512), kLds, s, p);
+  LDMSEG_LAUNCH_GEMM("conv_out_tail<bf16>", conv_out_tail_kernel, dim3(t.W / kTW, t.H / kTH, t.B), dim3(512), kLds, s, p);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -604,9 +604,8 @@ int launch_mlp_fused(const void* h, void* out, const void* x2, const void* strea
     (void)hipFuncSetAttribute((const void*)mlp_fused_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     attr_set[dev] = true;
   }
-  igemm_log_note(proj ? "mlp_fused<bf16,proj=1>" : "mlp_fused<bf16,proj=0>");
-  if (proj) hipLaunchKernelGGL(mlp_fused_kernel<true>, grid, block, kLds, s, p);
-  else hipLaunchKernelGGL(mlp_fused_kernel<false>, grid, block, kLds, s, p);
+  if (proj) LDMSEG_LAUNCH_GEMM("mlp_fused<bf16,proj=1>", mlp_fused_kernel<true>, grid, block, kLds, s, p);
+  else LDMSEG_LAUNCH_GEMM("mlp_fused<bf16,proj=0>", mlp_fused_kernel<false>, grid, block, kLds, s, p);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

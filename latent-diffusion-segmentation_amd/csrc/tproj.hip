@@ -448,8 +448,7 @@ int launch_proj_qkv_fused(const void* x, void* h, void* qkv, const void* stream,
     (void)hipFuncSetAttribute((const void*)proj_ln_qkv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     attr_set[dev] = true;
   }
-  igemm_log_note(gn ? "proj_ln_qkv<bf16,gn>" : "proj_ln_qkv<bf16>");
-  hipLaunchKernelGGL(proj_ln_qkv_kernel, dim3(M / kBM), dim3(768), kLds, s, p);
+  LDMSEG_LAUNCH_GEMM(gn ? "proj_ln_qkv<bf16,gn>" : "proj_ln_qkv<bf16>", proj_ln_qkv_kernel, dim3(M / kBM), dim3(768), kLds, s, p);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -148,12 +148,17 @@ def igemm_last_kernel():
     return buf.value.decode()
 
 
+LOG_ALL = 2     # igemm_log level: every kernel of the forward path, not only the GEMM family
+
+
 def igemm_log(enable):
-    lib().ldmseg_igemm_log(1 if enable else 0)
+    """True / 1: log the GEMM family (igemm instantiations, fused GEMM kernels); LOG_ALL: every forward-path kernel; False: off."""
+    lib().ldmseg_igemm_log(int(enable))
 
 
 def igemm_log_read():
-    """Set of distinct igemm instantiations launched since igemm_log(True)."""
+    """Set of distinct kernel names (the dispatch log: igemm instantiations, GroupNorm / attention / fused forms) launched since
+    igemm_log(True)."""
     buf = C.create_string_buffer(1 << 16)
     check(lib().ldmseg_igemm_log_read(buf, 1 << 16), "ldmseg_igemm_log_read")
     return {ln for ln in buf.value.decode().split("\n") if ln}

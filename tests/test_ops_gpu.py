@@ -1266,7 +1266,7 @@ def test_split_bf16_gemm_vs_fp32_reference(L, case):
     assert r == 0, L.lib().ldmseg_last_error()
     torch.cuda.synchronize()
     name = L.igemm_last_kernel()
-    assert name.startswith("igemm<f32,") and ",0,0" in name, name          # a plain-K-loop fp32 instantiation
+    assert name.startswith("igemm<f32,") and ",0,0,x3>" in name, name      # a plain-K-loop fp32 instantiation, in-loop hi / lo split
     e = rel_err(out, ref)
     assert e < 1e-4, (case, name, e)
     # round 6: dtype 3 = the same arithmetic with the weights split into hi | lo planes once, up front (what a bf16x3 handle holds):
@@ -1276,7 +1276,7 @@ def test_split_bf16_gemm_vs_fp32_reference(L, case):
                                 0, 0, 3, P(out3), None)
     assert r == 0, L.lib().ldmseg_last_error()
     torch.cuda.synchronize()
-    assert L.igemm_last_kernel() == name
+    assert L.igemm_last_kernel() == name.replace(",x3>", ",x3w>")           # the same instantiation, reading the weight planes
     assert torch.equal(out3, out), case
 
 
