@@ -70,7 +70,11 @@ typedef struct ldmseg_vae_image ldmseg_vae_image;  /* opaque */
 /* ---- UNet: ldmseg/models/unet.py::UNet (UNet2DConditionModel, SD-1.x topology) ---------- */
 typedef struct {
   int32_t in_channels;      /* 8 | 12 after UNet.modify_encoder (unet.py:178-233); 4 = vanilla */
-  int32_t cross_attention;  /* 0: attn2/norm2 removed (unet.py:83-105, base.yaml:71). 1 is rejected (E_ARG) */
+  int32_t cross_attention;  /* 0: attn2/norm2 removed (unet.py:83-105, base.yaml:71).  1: every transformer block runs
+                             * h = attn2(norm2(h), ctx) + h after attn1 (image_descriptors none / clip_image / clip_image_proj):
+                             * the state dict must hold norm2 and attn2.{to_q, to_k, to_v, to_out.0} of all 16 transformers
+                             * (cross_attention_dim 768) and may hold encoder_hid_proj.{weight, bias} [768, 1024]; such a handle
+                             * runs through ldmseg_unet_forward_ctx / ldmseg_sample_loop_guided only */
   int32_t compute_dtype;    /* LDMSEG_F32 | LDMSEG_BF16 | LDMSEG_BF16X3 */
   int32_t device;           /* HIP device ordinal */
 } ldmseg_unet_cfg;
@@ -99,6 +103,14 @@ int ldmseg_unet_forward(ldmseg_unet* h, const float* x, const int64_t* t_dev, in
 int ldmseg_unet_forward_parts(ldmseg_unet* h, const float* latents, const float* rgb_latents, const float* cond,
                               const int64_t* t_dev, int t_count, int64_t t_host, int B, int L, float* out,
                               void* stream);
+/* UNet.forward(sample, timestep, encoder_hidden_states=ctx).sample of a cross-attention handle (unet.py:281-436 with
+ * attn2 kept).  ctx: [B, S, ctx_dim] fp32 on the device, 1 <= S <= 4096 (77 CLIP text tokens, 257 CLIP-L/14 patch features,
+ * 1 projected image embedding); ctx_dim = 768, or 1024 when the handle holds encoder_hid_proj (applied once per call,
+ * unet.py:319-320).  The context's keys / values for all 16 transformers are computed once per call into the workspace
+ * (planned for the last S / ctx_dim used: a call with another context shape re-plans and may synchronise).  LDMSEG_E_ARG on a
+ * handle without cross-attention; the plain ldmseg_unet_forward / _forward_parts return LDMSEG_E_ARG on a cross handle. */
+int ldmseg_unet_forward_ctx(ldmseg_unet* h, const float* x, const int64_t* t_dev, int t_count, int64_t t_host, int B, int L,
+                            const float* ctx, int S, int ctx_dim, float* out, void* stream);
 /* bf16 mode only: run the self-attention of every level with at least `min_tokens` tokens (H*W) on the fp8 operand path
  * (OCP e4m3 Q/K/V/P on v_mfma_f32_16x16x32_fp8_fp8, fp32 accumulation and statistics) - the "fp8 MFMA attention path" of
  * the 1024x1024 configuration (128x128 latents: 16384 / 4096 tokens at head dims 40 / 80); 0 switches it off (default).
@@ -125,7 +137,8 @@ int ldmseg_unet_cf_fallbacks(ldmseg_unet* h, int64_t* count);
 int ldmseg_unet_gn_backoff(ldmseg_unet* h, int32_t* calls_left);
 /* bytes of device workspace a forward at (B, L) needs (allocated lazily, grown never shrunk) */
 size_t ldmseg_unet_workspace_bytes(const ldmseg_unet* h, int B, int L);
-/* number of parameters held (815,556,484 for the 12-channel default) */
+/* number of parameters held (815,556,484 for the 12-channel default; 859,532,484 for an 8-channel cross-attention handle,
+ * 860,319,684 with encoder_hid_proj) */
 int64_t ldmseg_unet_num_params(const ldmseg_unet* h);
 
 /* ---- seg-VAE: ldmseg/models/vae.py::GeneralVAESeg (gaussian, num_mid_blocks=0) ------------ */
@@ -261,6 +274,17 @@ typedef struct {
  * non-NULL it receives every step's latents [n_steps][B,4,L,L] (return_all_latents). */
 int ldmseg_sample_loop(ldmseg_unet* h, const ldmseg_sample_cfg* cfg, float* latents, const float* rgb_latents,
                        int B, int L, float* all_latents, void* stream);
+/* The sampling loop of a cross-attention handle with classifier-free guidance (trainers_ldm_cond.py:1098-1160); the plain
+ * loop above returns LDMSEG_E_ARG on such a handle.  latents / rgb_latents / all_latents as there, B images.
+ *   multiplier 2: ctx is [2B, S, ctx_dim], uncond half first; the UNet runs on cat([latents]*2) / cat([rgb]*2) (2B images),
+ *                 then noise_pred = uncond + guidance_scale * (cond - uncond), each of the three fp32 ops rounded on its own
+ *                 (torch's order), and the DDIM step runs on B images (last step: pred_original_sample).
+ *   multiplier 1: ctx is [B, S, ctx_dim]; the model output is used as it is (guidance_scale ignored).
+ * The context's keys / values are computed once per call (first step).  LDMSEG_E_ARG for self_condition with multiplier 2
+ * (the reference fails at step 2 there), for the inpainting fields, and as ldmseg_unet_forward_ctx for the context. */
+int ldmseg_sample_loop_guided(ldmseg_unet* h, const ldmseg_sample_cfg* cfg, float* latents, const float* rgb_latents, int B, int L,
+                              const float* ctx, int S, int ctx_dim, int multiplier, float guidance_scale, float* all_latents,
+                              void* stream);
 
 /* ---- bit codec of segment ids: COCO.encode_bitmap / decode_bitmap (ldmseg/data/coco.py:377-390) ---- */
 /* ids [B,HW] int64 -> bits [B,n_bits,HW] fp32 (LSB first; ids == ignore_label -> fill_value), then *mul+add

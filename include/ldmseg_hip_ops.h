@@ -36,6 +36,10 @@ int ldmseg_op_layernorm(const float* x, const float* gamma, const float* beta, i
                         int dtype, float* out, void* stream);
 /* diffusers Attention core on fused qkv [B,N,3C] -> [B,N,C] */
 int ldmseg_op_attention(const float* qkv, int B, int N, int C, int heads, int dtype, float* out, void* stream);
+/* cross-attention core (diffusers Attention with a context, attn2): q [B,N,C], kv = to_k | to_v of the context [B,S,2C]
+ * (channel = head*d + i), heads 8 -> out [B,N,C]; any S >= 1, d = C / heads in {40, 80, 160}; dtype 0 / 1 / 2 */
+int ldmseg_op_attention_cross(const float* q, const float* kv, int B, int N, int S, int C, int heads, int dtype, float* out,
+                              void* stream);
 /* the same on the fp8 (e4m3) operand path of the bf16 mode (K/V pre-quantised, Q and P quantised in the kernel, fp32
  * accumulation; head dim 40 or 80) - BASELINE configs[4].  time_iters > 0 additionally times that many launches (pre-pass
  * + kernel) into *us_per_launch; out may be NULL then. */

@@ -523,7 +523,15 @@ struct TransformerW {
   void* mlp_stream = nullptr;   // 320-channel level, bf16: the feed-forward's weights as one consumption-ordered stream (tfuse.hip)
   void* in_stream = nullptr;    // the same for proj_in | to_q | to_k | to_v (tproj.hip)
   float* in_bias = nullptr;     // [4][C]: proj_in bias | W_q beta | W_k beta | W_v beta
+  // cross-attention handles (ldmseg_unet_cfg::cross_attention = 1): h = attn2(norm2(h), ctx) + h after attn1
+  NormW ln2;
+  ConvW q2;                     // to_q with norm2 folded in (c1 / bias as ConvW qkv)
+  ConvW kv2;                    // to_k | to_v [2C][768], no bias: applied to the context once per call
+  ConvW out2;                   // to_out.0, applied with h as the residual
 };
+constexpr int kCrossDim = 768;        // cross_attention_dim of the SD-1.x UNet
+constexpr int kHidProjIn = 1024;      // encoder_hid_proj: CLIP-L/14 patch features -> kCrossDim
+constexpr int kTransformers = 16;
 
 }  // namespace
 
@@ -545,6 +553,15 @@ struct ldmseg_unet {
   ResnetW down_res[4][2], mid_res[2], up_res[4][3];
   TransformerW down_attn[3][2], mid_attn, up_attn[4][3];  // up_attn[0] unused
   ConvW down_conv[3], up_conv[3];
+  // cross-attention: optional encoder_hid_proj (1024 -> 768) and, per call, the context and where its K|V went
+  ConvW hid_proj;
+  const float* ctx = nullptr;          // [B, ctx_S, ctx_dim] fp32 of the running call (null: plain handle)
+  int ctx_S = 77, ctx_dim = kCrossDim; // shape the workspace is planned for (last call's; 77 text tokens before any call)
+  bool ctx_kv_ready = false;           // ldmseg_sample_loop_guided: the context's K|V is already in the workspace (first step made it)
+  const void* ctx_kv_base = nullptr;   // workspace base that K|V lives in
+  int plan_S = 0, plan_cdim = 0;
+  float* guide_buf = nullptr;          // guided loop: [2B,4,L,L] latents | [2B,4,L,L] rgb latents
+  size_t guide_elems = 0;
   // sampler state
   int plan_B = 0, plan_L = 0, plan_epoch = -1;
   size_t plan_persist = 0, plan_scratch = 0;
@@ -581,6 +598,7 @@ struct ldmseg_unet {
     if (gn_diag_host) (void)hipHostFree(gn_diag_host);
     if (gn_sync) (void)hipFree(gn_sync);
     if (cf_sync) (void)hipFree(cf_sync);
+    if (guide_buf) (void)hipFree(guide_buf);
   }
 };
 
@@ -613,7 +631,63 @@ int build_resnet(Builder& b, const std::string& p, int cin, int cout, int* temb_
   return 0;
 }
 
-int build_transformer(Builder& b, const std::string& p, int C, TransformerW* t) {
+// attn2 of a cross-attention handle: norm2 folded into to_q like norm1 into q|k|v; to_k | to_v as one [2C][768] matrix
+int build_attn2(Builder& b, const std::string& tb, int C, TransformerW* t) {
+  const int dt = b.dt;
+  TRY(b.norm(tb + "norm2", C, &t->ln2));
+  {
+    ConvW& q = t->q2;
+    const int Np = (int)rup(C, igemm_pick_bn(C, EPI_STORE));
+    q.N = Np; q.n_valid = C; q.cin_pad = C; q.taps = 1; q.cout = C;
+    std::vector<int> map(Np);
+    for (int r = 0; r < Np; ++r) map[r] = r < C ? r : -1;
+    int* dmap;
+    TRY(b.upload_ints(map, &dmap));
+    const float* w;
+    TRY(b.wm->get(tb + "attn2.to_q.weight", (int64_t)C * C, &w));
+    TRY(b.arena->alloc(&q.w, (size_t)Np * C * esize(dt)));
+    b.weights(q.w, (size_t)Np * C);
+    TRY(launch_repack_rows_scaled(w, q.w, dmap, Np, C, t->ln2.g, dt, b.s));
+    void* tmp;
+    HIP_TRY(hipMalloc(&tmp, (size_t)Np * C * sizeof(float)));
+    b.temps.push_back(tmp);
+    TRY(launch_repack_rows_scaled(w, tmp, dmap, Np, C, t->ln2.b, DT_F32, b.s));
+    void *pc1, *pc2;
+    TRY(b.arena->alloc(&pc1, (size_t)Np * sizeof(float)));
+    TRY(b.arena->alloc(&pc2, (size_t)Np * sizeof(float)));
+    TRY(launch_rowsum(q.w, nullptr, (float*)pc1, Np, C, dt, b.s));
+    TRY(launch_rowsum(tmp, nullptr, (float*)pc2, Np, C, DT_F32, b.s));
+    q.c1 = (float*)pc1;
+    q.bias = (float*)pc2;
+    b.nparams += (int64_t)C * C;
+  }
+  {
+    ConvW& k = t->kv2;
+    const int Np = (int)rup(2 * C, igemm_pick_bn(2 * C, EPI_STORE));
+    k.N = Np; k.n_valid = 2 * C; k.cin_pad = kCrossDim; k.taps = 1; k.cout = 2 * C;
+    std::vector<int> map(Np);
+    for (int r = 0; r < Np; ++r) map[r] = r < C ? r : -1;
+    int* dmap;
+    TRY(b.upload_ints(map, &dmap));
+    TRY(b.arena->alloc(&k.w, (size_t)Np * kCrossDim * esize(dt)));
+    b.weights(k.w, (size_t)Np * kCrossDim);
+    const float *wk, *wv;
+    TRY(b.wm->get(tb + "attn2.to_k.weight", (int64_t)C * kCrossDim, &wk));
+    TRY(b.wm->get(tb + "attn2.to_v.weight", (int64_t)C * kCrossDim, &wv));
+    // rows [0, C) <- to_k, [C, 2C) <- to_v, the padding rows behind them zero (map -1)
+    TRY(launch_repack_rows(wk, k.w, dmap, C, kCrossDim, dt, b.s));
+    TRY(launch_repack_rows(wv, (char*)k.w + (size_t)C * kCrossDim * esize(dt), dmap, Np - C, kCrossDim, dt, b.s));
+    void* pb;
+    TRY(b.arena->alloc(&pb, (size_t)Np * sizeof(float)));
+    HIP_TRY(hipMemsetAsync(pb, 0, (size_t)Np * sizeof(float), b.s));
+    k.bias = (float*)pb;
+    b.nparams += (int64_t)2 * C * kCrossDim;
+  }
+  TRY(b.conv(tb + "attn2.to_out.0", C, C, 1, C, &t->out2));
+  return 0;
+}
+
+int build_transformer(Builder& b, const std::string& p, int C, TransformerW* t, bool cross = false) {
   t->C = C;
   const int dt = b.dt;
   TRY(b.norm(p + "norm", C, &t->norm));
@@ -650,6 +724,7 @@ int build_transformer(Builder& b, const std::string& p, int C, TransformerW* t) 
     q.bias = (float*)pc2;
   }
   TRY(b.conv(tb + "attn1.to_out.0", C, C, 1, C, &t->attn_out));
+  if (cross) TRY(build_attn2(b, tb, C, t));
   TRY(b.norm(tb + "norm3", C, &t->ln3));
   // GEGLU projection [8C, C]: rows interleaved in 16-row (a | gate) pairs so one lane owns both halves
   {
@@ -735,6 +810,9 @@ int unet_build(ldmseg_unet* u, const WeightMap& wm) {
   const int cp = bke(u->dt);
   if (u->cfg.in_channels > cp) return fail(LDMSEG_E_ARG, "in_channels too large");
   TRY(b.conv("conv_in", kBlockOut[0], u->cfg.in_channels, 3, cp, &u->conv_in));
+  const bool cross = u->cfg.cross_attention != 0;
+  if (cross && wm.m.count("encoder_hid_proj.weight"))       // optional (clip_image descriptors, unet.py:121-122)
+    TRY(b.conv("encoder_hid_proj", kCrossDim, kHidProjIn, 1, kHidProjIn, &u->hid_proj));
   TRY(b.f32_copy("time_embedding.linear_1.weight", (int64_t)kTimeDim * 320, &u->te1_w));
   TRY(b.f32_copy("time_embedding.linear_1.bias", kTimeDim, &u->te1_b));
   TRY(b.f32_copy("time_embedding.linear_2.weight", (int64_t)kTimeDim * kTimeDim, &u->te2_w));
@@ -749,7 +827,7 @@ int unet_build(ldmseg_unet* u, const WeightMap& wm) {
       const std::string p = "down_blocks." + std::to_string(i);
       TRY(build_resnet(b, p + ".resnets." + std::to_string(j) + ".", c, co, &temb_off, &u->down_res[i][j]));
       c = co;
-      if (i < 3) TRY(build_transformer(b, p + ".attentions." + std::to_string(j) + ".", c, &u->down_attn[i][j]));
+      if (i < 3) TRY(build_transformer(b, p + ".attentions." + std::to_string(j) + ".", c, &u->down_attn[i][j], cross));
       skip_ch.push_back(c);
     }
     if (i < 3) {
@@ -758,7 +836,7 @@ int unet_build(ldmseg_unet* u, const WeightMap& wm) {
     }
   }
   TRY(build_resnet(b, "mid_block.resnets.0.", c, c, &temb_off, &u->mid_res[0]));
-  TRY(build_transformer(b, "mid_block.attentions.0.", c, &u->mid_attn));
+  TRY(build_transformer(b, "mid_block.attentions.0.", c, &u->mid_attn, cross));
   TRY(build_resnet(b, "mid_block.resnets.1.", c, c, &temb_off, &u->mid_res[1]));
   for (int i = 0; i < 4; ++i) {
     const int co = kBlockOut[3 - i];
@@ -768,7 +846,7 @@ int unet_build(ldmseg_unet* u, const WeightMap& wm) {
       skip_ch.pop_back();
       TRY(build_resnet(b, p + ".resnets." + std::to_string(j) + ".", c + sk, co, &temb_off, &u->up_res[i][j]));
       c = co;
-      if (i > 0) TRY(build_transformer(b, p + ".attentions." + std::to_string(j) + ".", c, &u->up_attn[i][j]));
+      if (i > 0) TRY(build_transformer(b, p + ".attentions." + std::to_string(j) + ".", c, &u->up_attn[i][j], cross));
     }
     if (i < 3) {
       const std::string key = "up_blocks." + std::to_string(i) + ".upsamplers.0.conv";
@@ -843,7 +921,8 @@ int run_resnet(Exec& ex, const ResnetW& r, const Act& x, const Act* skip, const 
   return 0;
 }
 
-int run_transformer(Exec& ex, const TransformerW& t, const Act& x, Act* out) {
+// kv_ctx: this transformer's K|V of the conditioning context [B*S, 2C] (cross-attention handles), null = no attn2
+int run_transformer(Exec& ex, const TransformerW& t, const Act& x, Act* out, const void* kv_ctx = nullptr, int S = 0) {
   Workspace* ws = ex.ws;
   const size_t m = ws->mark();
   const int C = t.C, N = x.H * x.W, M = ex.B * N;
@@ -905,6 +984,38 @@ int run_transformer(Exec& ex, const TransformerW& t, const Act& x, Act* out) {
     p.M = M; p.N = t.attn_out.N; p.n_valid = C; p.W = t.attn_out.w; p.bias = t.attn_out.bias;
     p.resid = h.p; p.ldr = C; p.out = h.p; p.ldo = C;
     TRY(ex.igemm(p));
+  }
+  if (kv_ctx) {
+    // h = to_out(attn2(norm2(h), ctx)) + h: norm2 folded into to_q (one statistics pass over h), the cross-attention core on the
+    // context's K|V, to_out in place on h.  (The fused 320-channel entry and the fp8 path stay attn1-only.)
+    float* st2 = (float*)ws->scratch((size_t)M * 2 * sizeof(float));
+    TRY(ex.rowstats(h, 1e-5f, st2));
+    Act q2 = ex.new_act(C, x.H, x.W, false);
+    {
+      IgemmParams p;
+      p.src0 = h.p; p.C0 = C; p.B = ex.B; p.Hi = p.Ho = x.H; p.Wi = p.Wo = x.W;
+      p.M = M; p.N = t.q2.N; p.n_valid = C; p.W = t.q2.w; p.bias = t.q2.bias;
+      p.rowstats = st2; p.c1 = t.q2.c1;
+      p.out = q2.p; p.ldo = C;
+      TRY(ex.igemm(p));
+    }
+    Act a2 = ex.new_act(C, x.H, x.W, false);
+    {
+      ProfScope ps(1, ex.s, 4.0 * ex.B * (double)N * S * C, 2.0 * M * C * esize(ex.dt), ex.dry(),
+                   "cross N=" + std::to_string(N) + " S=" + std::to_string(S) + " C=" + std::to_string(C));
+      if (!ex.dry()) {
+        TRY(ex.ws_ok());
+        const int r = launch_attention_cross(q2.p, kv_ctx, a2.p, ex.B, N, S, C, 8, ex.x3 ? 2 : ex.dt, ex.s);
+        if (r) return fail(r == -2 ? LDMSEG_E_SHAPE : LDMSEG_E_HIP, "launch_attention_cross failed");
+      }
+    }
+    {
+      IgemmParams p;
+      p.src0 = a2.p; p.C0 = C; p.B = ex.B; p.Hi = p.Ho = x.H; p.Wi = p.Wo = x.W;
+      p.M = M; p.N = t.out2.N; p.n_valid = C; p.W = t.out2.w; p.bias = t.out2.bias;
+      p.resid = h.p; p.ldr = C; p.out = h.p; p.ldo = C;
+      TRY(ex.igemm(p));
+    }
   }
   if (t.mlp_stream && mlp_fused_ok(C, ex.dt)) {
     // 320-channel level: norm3 -> GEGLU -> ff.net.2 (+h) [-> proj_out (+x)] in one row-local launch (tfuse.hip); the [M, 4C]
@@ -995,6 +1106,46 @@ int unet_forward_impl(ldmseg_unet* u, const float* a, int Ca, const float* b, in
   }
   const int tstride = (per_sample_t && !(u->temb_override && !dry)) ? u->temb_total : 0;
 
+  // --- cross-attention handles: K|V of the context for all 16 transformers (persist: the same offsets in every forward of a
+  // plan, so the guided sampling loop computes them in its first step only) ---
+  const void* kv_ctx[kTransformers] = {};
+  const int S = u->cfg.cross_attention ? u->ctx_S : 0;
+  if (u->cfg.cross_attention) {
+    if (!dry && !u->ctx) return fail(LDMSEG_E_ARG, "cross-attention handle: no context");
+    const TransformerW* tw[kTransformers];
+    int nt = 0;
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 2; ++j) tw[nt++] = &u->down_attn[i][j];
+    tw[nt++] = &u->mid_attn;
+    for (int i = 1; i < 4; ++i) for (int j = 0; j < 3; ++j) tw[nt++] = &u->up_attn[i][j];
+    for (int k = 0; k < kTransformers; ++k) kv_ctx[k] = ws->persist((size_t)B * S * 2 * tw[k]->C * esize(dt));
+    const bool reuse = !dry && u->ctx_kv_ready && u->ctx_kv_base == (const void*)ws->base;
+    if (!reuse) {
+      const size_t m0 = ws->mark();
+      Act c = ex.new_act(u->ctx_dim, S, 1, false);          // [B*S, ctx_dim] in the compute dtype
+      if (dt == DT_F32) {
+        c.p = const_cast<float*>(u->ctx);
+      } else if (!dry) {
+        TRY(ex.ws_ok());
+        TRY(launch_rows_to_dtype(u->ctx, c.p, (size_t)B * S * u->ctx_dim, dt, s));
+      }
+      if (u->ctx_dim == kHidProjIn) {
+        Act c2;
+        TRY(ex.conv(u->hid_proj, c, nullptr, &c2, 1, 0, false, nullptr, 0, nullptr));    // encoder_hid_proj (unet.py:319-320)
+        c = c2;
+      }
+      for (int k = 0; k < kTransformers; ++k) {
+        const ConvW& w = tw[k]->kv2;
+        IgemmParams p;
+        p.src0 = c.p; p.C0 = kCrossDim; p.B = B; p.Hi = p.Ho = S; p.Wi = p.Wo = 1;
+        p.M = B * S; p.N = w.N; p.n_valid = w.n_valid; p.W = w.w; p.bias = w.bias;
+        p.out = const_cast<void*>(kv_ctx[k]); p.ldo = w.n_valid;
+        TRY(ex.igemm(p));
+      }
+      ws->reset(m0);
+      if (!dry) u->ctx_kv_base = ws->base;
+    }
+  }
+
   // --- conv_in on the channel-concatenated fp32 NCHW input ---
   Act xin = ex.new_act(bke(dt), L, L, true);
   // (a re-plan or a workspace reallocation between two steps moves xin: the pointer the tail wrote to must be this one)
@@ -1017,7 +1168,7 @@ int unet_forward_impl(ldmseg_unet* u, const float* a, int Ca, const float* b, in
       TRY(run_resnet(ex, u->down_res[i][j], h, nullptr, temb, tstride, &o));
       h = o;
       if (i < 3) {
-        TRY(run_transformer(ex, u->down_attn[i][j], h, &o));
+        TRY(run_transformer(ex, u->down_attn[i][j], h, &o, kv_ctx[2 * i + j], S));
         h = o;
       }
       skips.push_back(h);
@@ -1032,7 +1183,7 @@ int unet_forward_impl(ldmseg_unet* u, const float* a, int Ca, const float* b, in
   {
     Act o;
     TRY(run_resnet(ex, u->mid_res[0], h, nullptr, temb, tstride, &o)); h = o;
-    TRY(run_transformer(ex, u->mid_attn, h, &o)); h = o;
+    TRY(run_transformer(ex, u->mid_attn, h, &o, kv_ctx[6], S)); h = o;
     TRY(run_resnet(ex, u->mid_res[1], h, nullptr, temb, tstride, &o)); h = o;
   }
   for (int i = 0; i < 4; ++i) {
@@ -1043,7 +1194,7 @@ int unet_forward_impl(ldmseg_unet* u, const float* a, int Ca, const float* b, in
       TRY(run_resnet(ex, u->up_res[i][j], h, &sk, temb, tstride, &o));   // torch.cat([hidden, skip], 1)
       h = o;
       if (i > 0) {
-        TRY(run_transformer(ex, u->up_attn[i][j], h, &o));
+        TRY(run_transformer(ex, u->up_attn[i][j], h, &o, kv_ctx[i > 0 ? 7 + 3 * (i - 1) + j : 0], S));
         h = o;
       }
     }
@@ -1107,13 +1258,15 @@ int ensure_ws(void** mem, size_t* cap, Workspace* ws, size_t need) {
 int unet_forward_checked(ldmseg_unet* u, const float* a, int Ca, const float* b, int Cb, const float* c, int Cc,
                          const int64_t* t_dev, int t_count, int64_t t_host, int B, int L, float* out, hipStream_t s) {
   // measure (cached per shape), (re)allocate, run
-  if (u->plan_B != B || u->plan_L != L || u->plan_epoch != g_plan_epoch) {
+  if (u->plan_B != B || u->plan_L != L || u->plan_epoch != g_plan_epoch || u->plan_S != u->ctx_S || u->plan_cdim != u->ctx_dim) {
     TRY(unet_forward_impl(u, a, Ca, b, Cb, c, Cc, t_dev, t_count, t_host, B, L, out, s, true, 0));
     u->plan_persist = rup(u->ws.persist_peak, 4096);
     u->plan_scratch = rup(u->ws.scratch_peak, 4096);
     u->plan_B = B;
     u->plan_L = L;
     u->plan_epoch = g_plan_epoch;
+    u->plan_S = u->ctx_S;
+    u->plan_cdim = u->ctx_dim;
   }
   {
     const void* before = u->ws_mem;
@@ -1530,7 +1683,7 @@ int ldmseg_unet_create(const ldmseg_unet_cfg* cfg, int n_weights, const char* co
                        const void* const* dev_ptrs, const int64_t* numels, ldmseg_unet** out) {
   g_err.clear();
   if (!cfg || !out) return fail(LDMSEG_E_ARG, "null argument");
-  if (cfg->cross_attention) return fail(LDMSEG_E_ARG, "cross-attention (encoder_hidden_states) is not supported: the reference default removes it (base.yaml:71)");
+  if (cfg->cross_attention != 0 && cfg->cross_attention != 1) return fail(LDMSEG_E_ARG, "cross_attention must be 0 or 1");
   if (cfg->compute_dtype != LDMSEG_F32 && cfg->compute_dtype != LDMSEG_BF16 && cfg->compute_dtype != LDMSEG_BF16X3) return fail(LDMSEG_E_ARG, "bad compute_dtype");
   if (cfg->in_channels != 4 && cfg->in_channels != 8 && cfg->in_channels != 12) return fail(LDMSEG_E_ARG, "in_channels must be 4, 8 or 12");
   DeviceGuard dg(cfg->device);
@@ -1567,6 +1720,7 @@ int ldmseg_unet_forward(ldmseg_unet* h, const float* x, const int64_t* t_dev, in
                         float* out, void* stream) {
   g_err.clear();
   if (!h || !x || !out) return fail(LDMSEG_E_ARG, "null argument");
+  if (h->cfg.cross_attention) return fail(LDMSEG_E_ARG, "cross-attention handle: the context goes through ldmseg_unet_forward_ctx");
   DeviceGuard dg(h->cfg.device);
   return unet_forward_checked(h, x, h->cfg.in_channels, nullptr, 0, nullptr, 0, t_dev, t_count, t_host, B, L, out,
                               (hipStream_t)stream);
@@ -1576,8 +1730,39 @@ int ldmseg_unet_forward_parts(ldmseg_unet* h, const float* latents, const float*
                               const int64_t* t_dev, int t_count, int64_t t_host, int B, int L, float* out, void* stream) {
   g_err.clear();
   if (!h || !latents || !rgb_latents || !out) return fail(LDMSEG_E_ARG, "null argument");
+  if (h->cfg.cross_attention) return fail(LDMSEG_E_ARG, "cross-attention handle: the context goes through ldmseg_unet_forward_ctx");
   DeviceGuard dg(h->cfg.device);
   return unet_forward_checked(h, latents, 4, rgb_latents, 4, cond, cond ? 4 : 0, t_dev, t_count, t_host, B, L, out,
+                              (hipStream_t)stream);
+}
+
+namespace {
+// the context argument of the cross-attention entry points; sets the handle's context for the call
+int set_ctx(ldmseg_unet* h, const float* ctx, int S, int ctx_dim) {
+  if (!h->cfg.cross_attention) return fail(LDMSEG_E_ARG, "handle built without cross-attention: no context");
+  if (!ctx) return fail(LDMSEG_E_ARG, "null context");
+  if (S < 1 || S > 4096) return fail(LDMSEG_E_ARG, "context length S must be in [1, 4096]");
+  if (ctx_dim != kCrossDim && !(ctx_dim == kHidProjIn && h->hid_proj.w))
+    return fail(LDMSEG_E_ARG, "ctx_dim must be 768 (or 1024 on a handle holding encoder_hid_proj)");
+  h->ctx = ctx;
+  h->ctx_S = S;
+  h->ctx_dim = ctx_dim;
+  return 0;
+}
+struct CtxClear {
+  ldmseg_unet* u;
+  ~CtxClear() { u->ctx = nullptr; u->ctx_kv_ready = false; u->ctx_kv_base = nullptr; }
+};
+}  // namespace
+
+int ldmseg_unet_forward_ctx(ldmseg_unet* h, const float* x, const int64_t* t_dev, int t_count, int64_t t_host, int B, int L,
+                            const float* ctx, int S, int ctx_dim, float* out, void* stream) {
+  g_err.clear();
+  if (!h || !x || !out) return fail(LDMSEG_E_ARG, "null argument");
+  TRY(set_ctx(h, ctx, S, ctx_dim));
+  CtxClear cc{h};
+  DeviceGuard dg(h->cfg.device);
+  return unet_forward_checked(h, x, h->cfg.in_channels, nullptr, 0, nullptr, 0, t_dev, t_count, t_host, B, L, out,
                               (hipStream_t)stream);
 }
 
@@ -1814,13 +1999,15 @@ int ldmseg_unet_reserve(ldmseg_unet* h, int B, int L) {
   if (B < 1 || L < 8 || L % 8 != 0) return fail(LDMSEG_E_SHAPE, "L must be a positive multiple of 8, B >= 1");
   DeviceGuard dg(h->cfg.device);
   const int ci = h->cfg.in_channels;
-  if (h->plan_B != B || h->plan_L != L || h->plan_epoch != g_plan_epoch) {
+  if (h->plan_B != B || h->plan_L != L || h->plan_epoch != g_plan_epoch || h->plan_S != h->ctx_S || h->plan_cdim != h->ctx_dim) {
     TRY(unet_forward_impl(h, nullptr, ci, nullptr, 0, nullptr, 0, nullptr, 1, 0, B, L, nullptr, nullptr, true, 0));
     h->plan_persist = rup(h->ws.persist_peak, 4096);
     h->plan_scratch = rup(h->ws.scratch_peak, 4096);
     h->plan_B = B;
     h->plan_L = L;
     h->plan_epoch = g_plan_epoch;
+    h->plan_S = h->ctx_S;
+    h->plan_cdim = h->ctx_dim;
   }
   TRY(ensure_ws(&h->ws_mem, &h->ws_cap, &h->ws, h->plan_persist + h->plan_scratch));
   TRY(loop_reserve(h, (size_t)B * 4 * L * L));
@@ -1829,10 +2016,27 @@ int ldmseg_unet_reserve(ldmseg_unet* h, int B, int L) {
   return 0;
 }
 
+static int gn_backoff_update(ldmseg_unet* h) {
+  if (h->gn_sync) {                  // cooperative GroupNorm back-off: did the previous calls' norms miss their partners?
+    if (!h->gn_diag_host) {
+      HIP_TRY(hipHostMalloc((void**)&h->gn_diag_host, sizeof(unsigned long long)));
+      *h->gn_diag_host = 0;
+    }
+    const unsigned long long cur = *(volatile unsigned long long*)h->gn_diag_host;     // whatever the last finished copy left
+    // (only launches under the full bound count - norm.hip - so the eight short-bound calls decay unconditionally and the
+    // ninth probes the full bound again)
+    if (cur >= h->gn_diag_seen + 256) h->gn_backoff_calls = 8;
+    else if (h->gn_backoff_calls > 0) --h->gn_backoff_calls;
+    h->gn_diag_seen = cur;
+  }
+  return 0;
+}
+
 int ldmseg_sample_loop(ldmseg_unet* h, const ldmseg_sample_cfg* cfg, float* latents, const float* rgb_latents, int B, int L,
                        float* all_latents, void* stream) {
   g_err.clear();
   if (!h || !cfg || !latents || !rgb_latents || !cfg->timesteps || !cfg->coef) return fail(LDMSEG_E_ARG, "null argument");
+  if (h->cfg.cross_attention) return fail(LDMSEG_E_ARG, "cross-attention handle: sample with ldmseg_sample_loop_guided");
   if (cfg->n_steps < 1) return fail(LDMSEG_E_ARG, "n_steps must be >= 1");
   if (B < 1 || L < 8 || L % 8 != 0) return fail(LDMSEG_E_SHAPE, "L must be a positive multiple of 8, B >= 1");
   if (cfg->prediction_type < 0 || cfg->prediction_type > 2) return fail(LDMSEG_E_ARG, "unknown prediction_type");
@@ -1849,18 +2053,7 @@ int ldmseg_sample_loop(ldmseg_unet* h, const ldmseg_sample_cfg* cfg, float* late
   if (selfc) HIP_TRY(hipMemsetAsync(h->cond, 0, n * sizeof(float), s));   // condition = zeros_like(rgb_latents)
   const float* temb_rows = nullptr;
   TRY(loop_time_embeddings(h, cfg->timesteps, cfg->n_steps, s, &temb_rows));
-  if (h->gn_sync) {                  // cooperative GroupNorm back-off: did the previous calls' norms miss their partners?
-    if (!h->gn_diag_host) {
-      HIP_TRY(hipHostMalloc((void**)&h->gn_diag_host, sizeof(unsigned long long)));
-      *h->gn_diag_host = 0;
-    }
-    const unsigned long long cur = *(volatile unsigned long long*)h->gn_diag_host;     // whatever the last finished copy left
-    // (only launches under the full bound count - norm.hip - so the eight short-bound calls decay unconditionally and the
-    // ninth probes the full bound again)
-    if (cur >= h->gn_diag_seen + 256) h->gn_backoff_calls = 8;
-    else if (h->gn_backoff_calls > 0) --h->gn_backoff_calls;
-    h->gn_diag_seen = cur;
-  }
+  TRY(gn_backoff_update(h));
   struct Clear { ldmseg_unet* u; ~Clear() { u->temb_override = nullptr; u->tail_req = nullptr; u->tail_done = false; u->xin_ready = false; u->xin_ptr = nullptr; } } clear{h};     // (also on the error returns below)
   for (int i = 0; i < cfg->n_steps; ++i) {
     h->temb_override = temb_rows + (size_t)i * h->temb_total;
@@ -1888,6 +2081,68 @@ int ldmseg_sample_loop(ldmseg_unet* h, const ldmseg_sample_cfg* cfg, float* late
         TRY(launch_inpaint_paste(latents, cfg->z0_dev, cfg->noise_dev, cfg->known_dev, cfg->paste_coef[2 * i],
                                  cfg->paste_coef[2 * i + 1], B, 4, L * L, s));
     }
+    if (all_latents)
+      HIP_TRY(hipMemcpyAsync(all_latents + (size_t)i * n, latents, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  }
+  if (h->gn_sync && h->gn_diag_host)
+    HIP_TRY(hipMemcpyAsync(h->gn_diag_host, gn_sync_diag_ptr(h->gn_sync), sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  return 0;
+}
+
+int ldmseg_sample_loop_guided(ldmseg_unet* h, const ldmseg_sample_cfg* cfg, float* latents, const float* rgb_latents, int B, int L,
+                              const float* ctx, int S, int ctx_dim, int multiplier, float guidance_scale, float* all_latents,
+                              void* stream) {
+  g_err.clear();
+  if (!h || !cfg || !latents || !rgb_latents || !cfg->timesteps || !cfg->coef) return fail(LDMSEG_E_ARG, "null argument");
+  if (cfg->n_steps < 1) return fail(LDMSEG_E_ARG, "n_steps must be >= 1");
+  if (B < 1 || L < 8 || L % 8 != 0) return fail(LDMSEG_E_SHAPE, "L must be a positive multiple of 8, B >= 1");
+  if (cfg->prediction_type < 0 || cfg->prediction_type > 2) return fail(LDMSEG_E_ARG, "unknown prediction_type");
+  if (multiplier != 1 && multiplier != 2) return fail(LDMSEG_E_ARG, "multiplier must be 1 or 2");
+  for (int i = 0; i < cfg->n_steps; ++i)
+    if (cfg->timesteps[i] < 0) return fail(LDMSEG_E_ARG, "negative timestep");
+  const bool selfc = cfg->self_condition != 0;
+  // (the reference concatenates a B-row condition with 2B-row tensors there and fails at step 2, trainers_ldm_cond.py:1126-1150)
+  if (selfc && multiplier == 2) return fail(LDMSEG_E_ARG, "self_condition with classifier-free guidance (multiplier 2) is not defined");
+  if ((h->cfg.in_channels == 12) != selfc) return fail(LDMSEG_E_ARG, "self_condition needs the 12-channel conv_in (and vice versa)");
+  if (cfg->known_dev || cfg->z0_dev || cfg->noise_dev || cfg->paste_coef) return fail(LDMSEG_E_ARG, "inpainting is not combined with guidance");
+  TRY(set_ctx(h, ctx, S, ctx_dim));
+  CtxClear cc{h};
+  DeviceGuard dg(h->cfg.device);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)B * 4 * L * L;
+  const int BB = multiplier * B;
+  TRY(loop_reserve(h, (size_t)multiplier * n));       // eps of all BB images
+  float *lat2 = nullptr, *rgb2 = nullptr;
+  if (multiplier == 2) {                               // latent_model_input = cat([latents] * 2), rgb likewise (:1122-1133)
+    if (h->guide_elems < 4 * n) {
+      HIP_TRY(hipDeviceSynchronize());
+      if (h->guide_buf) (void)hipFree(h->guide_buf);
+      h->guide_buf = nullptr; h->guide_elems = 0;
+      HIP_TRY(hipMalloc((void**)&h->guide_buf, 4 * n * sizeof(float)));
+      h->guide_elems = 4 * n;
+    }
+    lat2 = h->guide_buf;
+    rgb2 = h->guide_buf + 2 * n;
+    for (int k = 0; k < 2; ++k) {
+      HIP_TRY(hipMemcpyAsync(lat2 + k * n, latents, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+      HIP_TRY(hipMemcpyAsync(rgb2 + k * n, rgb_latents, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+  }
+  if (selfc) HIP_TRY(hipMemsetAsync(h->cond, 0, n * sizeof(float), s));
+  const float* temb_rows = nullptr;
+  TRY(loop_time_embeddings(h, cfg->timesteps, cfg->n_steps, s, &temb_rows));
+  TRY(gn_backoff_update(h));
+  struct Clear { ldmseg_unet* u; ~Clear() { u->temb_override = nullptr; u->xin_ready = false; u->xin_ptr = nullptr; } } clear{h};
+  for (int i = 0; i < cfg->n_steps; ++i) {
+    h->temb_override = temb_rows + (size_t)i * h->temb_total;
+    const float* c = cfg->coef + 4 * i;
+    DdimCoef dc{c[0], c[1], c[2], c[3], cfg->prediction_type, cfg->clip_sample, cfg->clip_sample_range, 0};
+    const bool last = (i == cfg->n_steps - 1);
+    // the model output of all BB images lands in h->eps (no fused step tail: the step needs two images' outputs)
+    TRY(unet_forward_checked(h, multiplier == 2 ? lat2 : latents, 4, multiplier == 2 ? rgb2 : rgb_latents, 4,
+                             selfc ? h->cond : nullptr, selfc ? 4 : 0, nullptr, 1, cfg->timesteps[i], BB, L, h->eps, s));
+    h->ctx_kv_ready = true;                            // the context does not change across steps
+    TRY(launch_guided_step(h->eps, latents, selfc ? h->cond : nullptr, lat2, n, multiplier, guidance_scale, dc, last ? 1 : 0, s));
     if (all_latents)
       HIP_TRY(hipMemcpyAsync(all_latents + (size_t)i * n, latents, n * sizeof(float), hipMemcpyDeviceToDevice, s));
   }

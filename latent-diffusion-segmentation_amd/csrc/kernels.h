@@ -235,6 +235,12 @@ int launch_layernorm(const void* x, void* y, const float* gamma, const float* be
 // dtype 2 = fp32 tensors with the products as three bf16 MFMAs on hi/lo splits (compute_dtype "bf16x3")
 int launch_attention(const void* qkv, void* out, int B, int N, int C, int heads, int dtype, hipStream_t s);
 
+// cross-attention (attention_cross.hip): q [B*N, C], kv = to_k | to_v of the context [B*S, 2C] -> out [B*N, C]; any S >= 1 (keys
+// past S masked), head dims 40 / 80 / 160; dtype 0 / 1 / 2 as launch_attention (every product in fp32 on the VALU)
+int launch_attention_cross(const void* q, const void* kv, void* out, int B, int N, int S, int C, int heads, int dtype, hipStream_t s);
+// fp32 [n] -> compute dtype [n] (the conditioning context at the API boundary)
+int launch_rows_to_dtype(const float* x, void* y, size_t n, int dtype, hipStream_t s);
+
 // Row-local fusion of the transformer feed-forward at the 320-channel level (tfuse.hip): LayerNorm_3 -> GEGLU -> ff.net.2 (+h)
 // [-> proj_out (+x)] in one launch.  mlp_fused_ok: the shape / dtype has the kernel and the mode (debug key 12) allows it.
 bool mlp_fused_ok(int C, int dtype);
@@ -321,6 +327,11 @@ int launch_repack_convt2(const float* w, void* out, int Ci, int Co, int dtype, h
 // DDIM step (ddim_scheduler.py:218-269), elementwise, bit-exact op order
 struct DdimCoef { float sqrt_a_t, sqrt_b_t, sqrt_a_prev, sqrt_b_prev; int pred_type; int clip; float clip_range; int use_clipped; };
 int launch_ddim_step(const float* eps, const float* x, float* prev, float* x0, size_t n, DdimCoef c, hipStream_t s);
+// guided scheduler step (guided.hip): eps [mult*n] (mult 2: uncond | cond halves, combined as uncond + g (cond - uncond), each op
+// rounded), DDIM update of latents [n] in place (last: pred_original_sample); cond <- pred_original_sample and lat2 [2n] <- the
+// new latents in both halves when non-null
+int launch_guided_step(const float* eps, float* latents, float* cond, float* lat2, size_t n, int mult, float g, DdimCoef c,
+                       int last, hipStream_t s);
 // The tail of a denoising step in one launch (tail.hip, bf16): conv_out on a halo-resident pixel tile and, when ddim != 0,
 // the scheduler update, inpainting paste, self-condition write and the next step's packed UNet input in its epilogue.
 struct StepTail {

@@ -355,6 +355,22 @@ int ldmseg_op_attention(const float* qkv, int B, int N, int C, int heads, int dt
   return 0;
 }
 
+int ldmseg_op_attention_cross(const float* q, const float* kv, int B, int N, int S, int C, int heads, int dtype, float* out,
+                              void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (B < 1 || N < 1 || S < 1 || heads < 1 || C % heads) return -2;
+  Temp t;
+  void* qp = t.get((size_t)B * N * C * es(dtype));
+  to_dev_dtype(q, qp, (size_t)B * N * C, dtype, s);
+  void* kp = t.get((size_t)B * S * 2 * C * es(dtype));
+  to_dev_dtype(kv, kp, (size_t)B * S * 2 * C, dtype, s);
+  void* op = t.get((size_t)B * N * C * es(dtype));
+  const int r = launch_attention_cross(qp, kp, op, B, N, S, C, heads, dtype, s);
+  if (r) return r;
+  from_dev_dtype(op, out, (size_t)B * N * C, dtype, s);
+  return 0;
+}
+
 // ConvTranspose2d(k=2,s=2): x NCHW f32 [B,Ci,H,W], w [Ci,Co,2,2] -> NCHW f32 [B,Co,2H,2W]
 int ldmseg_op_convt2(const float* x, const float* w, const float* bias, int B, int Ci, int H, int W, int Co, int dtype,
                      float* out, void* stream) {

@@ -47,6 +47,7 @@ SIGNATURES = {
     "ldmseg_unet_destroy": (None, [_vp]),
     "ldmseg_unet_forward": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp]),
     "ldmseg_unet_forward_parts": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp]),
+    "ldmseg_unet_forward_ctx": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, _i, _i, _vp, _vp]),
     "ldmseg_unet_workspace_bytes": (_sz, [_vp, _i, _i]),
     "ldmseg_unet_num_params": (_i64, [_vp]),
     "ldmseg_vae_create": (_i, [C.POINTER(VAECfg), _i, C.POINTER(C.c_char_p), C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_vp)]),
@@ -65,6 +66,7 @@ SIGNATURES = {
     "ldmseg_unet_gn_backoff": (_i, [_vp, _vp]),
     "ldmseg_unet_cf_fallbacks": (_i, [_vp, _vp]),
     "ldmseg_sample_loop": (_i, [_vp, C.POINTER(SampleCfg), _vp, _vp, _i, _i, _vp, _vp]),
+    "ldmseg_sample_loop_guided": (_i, [_vp, C.POINTER(SampleCfg), _vp, _vp, _i, _i, _vp, _i, _i, _i, C.c_float, _vp, _vp]),
     "ldmseg_vae_image_create": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "ldmseg_vae_image_destroy": (None, [_vp]),
     "ldmseg_vae_image_num_params": (_i64, [_vp]),
@@ -88,6 +90,7 @@ SIGNATURES = {
     "ldmseg_op_groupnorm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp]),
     "ldmseg_op_layernorm": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _i, _vp, _vp]),
     "ldmseg_op_attention": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ldmseg_op_attention_cross": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ldmseg_op_attention_fp8": (_i, [_vp, _i, _i, _i, _i, _vp, _i, C.POINTER(C.c_float), _vp]),
     "ldmseg_op_convt2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ldmseg_op_bilinear2x": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -11,24 +11,28 @@ from typing import Optional
 
 import torch
 
-from .weights import unet_schema, vae_schema
+from .weights import hid_proj_schema, unet_schema, vae_schema
 
 
 def _strip(sd):
     return OrderedDict((k[len("module."):] if k.startswith("module.") else k, v) for k, v in sd.items())
 
 
-def unet_state_from(data: dict, use_ema: bool = False) -> "OrderedDict[str, torch.Tensor]":
-    """Select and validate the UNet tensors of an LDM checkpoint dict."""
+def unet_state_from(data: dict, use_ema: bool = False, cross_attention: bool = False) -> "OrderedDict[str, torch.Tensor]":
+    """Select and validate the UNet tensors of an LDM checkpoint dict.  ``cross_attention=True``: the checkpoint of an
+    ``image_descriptors`` none / clip_image / clip_image_proj run - norm2 and attn2 in every transformer, plus
+    ``encoder_hid_proj.*`` when the checkpoint has it."""
     sd = data["ema"] if use_ema and data.get("ema") is not None else data["unet"]
     if isinstance(sd, dict) and "shadow_params" in sd:
         raise NotImplementedError("diffusers EMAModel state (shadow_params list) is not a state dict")
     sd = _strip(sd)
     in_ch = int(sd["conv_in.weight"].shape[1])
     cross = any(".attn2." in k for k in sd)
-    if cross:
-        raise NotImplementedError("checkpoint has cross-attention (attn2) weights; only image_descriptors=remove is built")
-    schema = unet_schema(in_ch, False)
+    if cross and not cross_attention:
+        raise NotImplementedError("checkpoint has cross-attention (attn2) weights: load it with cross_attention=True")
+    schema = unet_schema(in_ch, bool(cross_attention))
+    if cross_attention and any(k.startswith("encoder_hid_proj.") for k in sd):
+        schema.update(hid_proj_schema())
     out = OrderedDict()
     for k, shp in schema.items():
         if k not in sd:
@@ -65,9 +69,9 @@ def _load(path: str, allow_pickle: Optional[bool] = None):
         return torch.load(path, map_location="cpu", weights_only=False)
 
 
-def load_ldm_checkpoint(path: str, use_ema: bool = False, allow_pickle: Optional[bool] = None):
+def load_ldm_checkpoint(path: str, use_ema: bool = False, allow_pickle: Optional[bool] = None, cross_attention: bool = False):
     data = _load(path, allow_pickle)
-    return {"unet": unet_state_from(data, use_ema), "vae_semseg": vae_state_from(data) if "vae_semseg" in data else None,
+    return {"unet": unet_state_from(data, use_ema, cross_attention), "vae_semseg": vae_state_from(data) if "vae_semseg" in data else None,
             "p": data.get("p"), "step": data.get("step"), "epoch": data.get("epoch")}
 
 

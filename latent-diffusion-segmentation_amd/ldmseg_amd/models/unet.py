@@ -20,15 +20,15 @@ import torch
 
 from .. import _lib
 from ..utils import UNetOutput
-from ..weights import BLOCK_OUT, unet_schema
+from ..weights import BLOCK_OUT, CROSS_DIM, unet_schema
 
 
 class UNet(object):
     def __init__(self, state_dict, in_channels: int = 12, device: Union[str, torch.device] = "cuda:0",
                  compute_dtype: Union[str, torch.dtype] = "bf16", cross_attention: bool = False):
-        if cross_attention:
-            raise NotImplementedError("cross-attention conditioning is removed in the reference default "
-                                      "(image_descriptors: remove, base.yaml:71) and is not built here")
+        # cross_attention=True: the UNet of image_descriptors none / clip_image / clip_image_proj (norm2 -> attn2(ctx) kept in
+        # every transformer, unet.py:83-105 not applied); the state dict may add encoder_hid_proj (1024 -> 768, unet.py:121-122)
+        self.cross_attention = bool(cross_attention)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("UNet needs an MI355X device (no CPU fallback)")
@@ -39,13 +39,15 @@ class UNet(object):
         self.dtype = torch.float32
         self.in_channels = int(in_channels)
         self.config = SimpleNamespace(block_out_channels=list(BLOCK_OUT), in_channels=self.in_channels,
-                                      out_channels=4, attention_head_dim=8, cross_attention_dim=None,
+                                      out_channels=4, attention_head_dim=8,
+                                      cross_attention_dim=CROSS_DIM if self.cross_attention else None,
                                       sample_size=64, layers_per_block=2)
-        missing = [k for k in unet_schema(self.in_channels, False) if k not in state_dict]
+        self.has_encoder_hid_proj = self.cross_attention and "encoder_hid_proj.weight" in state_dict
+        missing = [k for k in unet_schema(self.in_channels, self.cross_attention) if k not in state_dict]
         if missing:
             raise KeyError(f"state dict lacks {len(missing)} UNet tensors, e.g. {missing[:3]}")
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        cfg = _lib.UNetCfg(self.in_channels, 0, self.compute_dtype, idx)
+        cfg = _lib.UNetCfg(self.in_channels, int(self.cross_attention), self.compute_dtype, idx)
         n, names, ptrs, numels, keep = _lib.weight_arrays(state_dict, self.device)
         handle = C.c_void_p()
         with torch.cuda.device(self.device):
@@ -131,7 +133,7 @@ class UNet(object):
 
     def forward(self, sample: torch.Tensor, timestep, encoder_hidden_states: Optional[torch.Tensor] = None,
                 timestep_img=None, return_dict: bool = True, **unused):
-        if encoder_hidden_states is not None:
+        if encoder_hidden_states is not None and not self.cross_attention:
             raise NotImplementedError("encoder_hidden_states must be None (cross-attention removed)")
         x = _lib.require_cuda_f32(sample, "sample")
         B, Cin, H, W = x.shape
@@ -140,14 +142,27 @@ class UNet(object):
         out = torch.empty((B, 4, H, W), device=x.device, dtype=torch.float32)
         keep, tptr, tcount, thost = self._timestep_args(timestep, B)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().ldmseg_unet_forward(self._h, _lib.ptr(x), tptr, tcount, thost, B, H, _lib.ptr(out),
-                                                      _lib.stream_ptr(x.device)), "ldmseg_unet_forward")
+            if encoder_hidden_states is not None:
+                ctx = self._context(encoder_hidden_states, B)
+                _lib.check(_lib.lib().ldmseg_unet_forward_ctx(self._h, _lib.ptr(x), tptr, tcount, thost, B, H, _lib.ptr(ctx),
+                                                              ctx.shape[1], ctx.shape[2], _lib.ptr(out),
+                                                              _lib.stream_ptr(x.device)), "ldmseg_unet_forward_ctx")
+            else:    # (a cross-attention handle refuses this: the reference needs the context too)
+                _lib.check(_lib.lib().ldmseg_unet_forward(self._h, _lib.ptr(x), tptr, tcount, thost, B, H, _lib.ptr(out),
+                                                          _lib.stream_ptr(x.device)), "ldmseg_unet_forward")
         del keep
         if not return_dict:
             return (out,)
         return UNetOutput(sample=out)
 
     __call__ = forward
+
+    def _context(self, encoder_hidden_states, B):
+        """[B, S, 768] (or [B, S, 1024] with encoder_hid_proj) fp32 on the handle's device."""
+        ctx = encoder_hidden_states
+        if not isinstance(ctx, torch.Tensor) or ctx.dim() != 3 or ctx.shape[0] != B:
+            raise ValueError(f"encoder_hidden_states must be [B={B}, S, D]")
+        return ctx.to(device=self.device, dtype=torch.float32).contiguous()
 
     def forward_parts(self, latents, rgb_latents, condition, timestep):
         """Forward on the un-concatenated inputs of the sampler (skips torch.cat, trainers_ldm_cond.py:1128-1138)."""

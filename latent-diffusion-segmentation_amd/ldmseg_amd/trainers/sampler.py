@@ -27,7 +27,8 @@ from .. import _lib
 
 class TrainerDiffusion(object):
     def __init__(self, vae_semseg, unet, noise_scheduler, self_condition: Optional[bool] = None,
-                 device=None, latent_size: int = 64, vae_image=None):
+                 device=None, latent_size: int = 64, vae_image=None, image_descriptor_model=None, textencoder=None,
+                 tokenizer=None):
         self.vae_image = vae_image            # RGB encoder (trainers_ldm_cond.py:58,111); optional here
         self.vae_semseg = vae_semseg
         self.unet_model = unet
@@ -37,9 +38,27 @@ class TrainerDiffusion(object):
         self.args = {'gpu': self.device}
         self.latent_size = latent_size
         self.unet_dtype = torch.float32
-        self.image_descriptor_model = None
-        self.textencoder = None
-        self.tokenizer = None
+        self.weight_dtype = torch.float32
+        # Conditioning models of the cross-attention UNets (:55-127, descriptors.py:66-102): caller-supplied torch modules run
+        # once per batch - an image descriptor model (clip_image / clip_image_proj: returns {'last_feat': [B, D, ...]}) or a
+        # text encoder with its tokenizer (image_descriptors none).  None of them: the UNet runs without a context.
+        if textencoder is not None and image_descriptor_model is not None:
+            raise ValueError("pass either a text encoder or an image descriptor model, not both (:126-127)")
+        if textencoder is not None and tokenizer is None:
+            raise ValueError("a text encoder needs its tokenizer")
+        self.image_descriptor_model = image_descriptor_model
+        self.textencoder = textencoder
+        self.tokenizer = tokenizer
+        for m in (image_descriptor_model, textencoder):
+            if m is not None and hasattr(m, "eval"):
+                m.eval()
+        # imagenet / CLIP pixel statistics (utils.py:355-362, :303-308)
+        self.pixel_mean_in = torch.tensor([0.485, 0.456, 0.406], dtype=torch.float32, device=self.device).view(1, 3, 1, 1)
+        self.pixel_std_in = torch.tensor([0.229, 0.224, 0.225], dtype=torch.float32, device=self.device).view(1, 3, 1, 1)
+        self.pixel_mean_clip = torch.tensor([0.48145466, 0.4578275, 0.40821073], dtype=torch.float32,
+                                            device=self.device).view(1, 3, 1, 1)
+        self.pixel_std_clip = torch.tensor([0.26862954, 0.26130258, 0.27577711], dtype=torch.float32,
+                                           device=self.device).view(1, 3, 1, 1)
 
     # ------------------------------------------------------------------ noise
     @staticmethod
@@ -73,9 +92,20 @@ class TrainerDiffusion(object):
         if repeat_noise:
             latents = latents[0:1].repeat(batch_size, 1, 1, 1)
             original_noise = latents.clone()
+        encoder_hidden_states, multiplier = self.encoder_hidden_states(prompts, rgb_images)
         latents = (latents * scheduler.init_noise_sigma).contiguous()
 
-        if python_loop:
+        if encoder_hidden_states is not None:
+            if self.self_condition and multiplier > 1:
+                # (the reference concatenates the B-row condition with 2B-row tensors and fails at step 2, :1126-1150)
+                raise ValueError("self-conditioning cannot be combined with classifier-free guidance (multiplier 2)")
+            if python_loop:
+                out = self._sample_python_guided(scheduler, latents, rgb, encoder_hidden_states, multiplier, guidance_scale,
+                                                 return_all_latents)
+            else:
+                out = self._sample_native_guided(scheduler, latents, rgb, encoder_hidden_states, multiplier, guidance_scale,
+                                                 return_all_latents)
+        elif python_loop:
             out = self._sample_python(scheduler, latents, rgb, return_all_latents)
         else:
             out = self._sample_native(scheduler, latents, rgb, return_all_latents)
@@ -102,6 +132,89 @@ class TrainerDiffusion(object):
             if return_all:
                 all_latents.append(latents)
         return torch.cat(all_latents, dim=0) if return_all else latents
+
+    # ------------------------------------------------------------------ conditioning (cross-attention UNets)
+    def norm_resize_images(self, x, mode='imagenet'):
+        """:663-675: the descriptor model's input - CLIP: 224x224 bilinear + CLIP statistics; DINO: 518x518 + imagenet."""
+        import torch.nn.functional as F
+        identifier = self.image_descriptor_model.__class__.__name__.lower()
+        if 'clip' in identifier:
+            x = F.interpolate(x, size=(224, 224), mode='bilinear', align_corners=False)
+            x = (x - self.pixel_mean_clip) / self.pixel_std_clip
+        elif 'dino' in identifier:
+            x = F.interpolate(x, size=(518, 518), mode='bilinear', align_corners=False)
+            x = (x - self.pixel_mean_in) / self.pixel_std_in
+        else:
+            x = (x - self.pixel_mean_in) / self.pixel_std_in
+        return x
+
+    @torch.no_grad()
+    def encoder_hidden_states(self, prompts: List[str], rgb_images: Optional[torch.Tensor] = None):
+        """(encoder_hidden_states, multiplier) as sample() builds them (:1098-1119): descriptors [B, S, D] of the images
+        repeated for both halves, or [uncond | text] CLIP embeddings; (None, 1) without a conditioning model."""
+        multiplier = 1
+        ehs = None
+        if self.image_descriptor_model is not None:
+            if rgb_images is None:
+                raise ValueError("an image descriptor model needs rgb_images")
+            x = self.norm_resize_images(rgb_images.to(self.device))
+            d = self.image_descriptor_model(x.to(self.weight_dtype))['last_feat']
+            d = d.view(d.shape[0], d.shape[1], -1).permute(0, 2, 1)
+            ehs = torch.cat([d] * 2).to(torch.float)
+            multiplier = 2
+        if self.textencoder is not None:
+            batch_size = len(prompts)
+            text_input = self.tokenizer(prompts, padding="max_length", max_length=self.tokenizer.model_max_length,
+                                        truncation=True, return_tensors="pt")
+            text_embeddings = self.textencoder(text_input.input_ids.to(device=self.device))[0]
+            max_length = text_input.input_ids.shape[-1]
+            uncond_input = self.tokenizer([""] * batch_size, padding="max_length", max_length=max_length, return_tensors="pt")
+            uncond_embeddings = self.textencoder(uncond_input.input_ids.to(device=self.device))[0]
+            ehs = torch.cat([uncond_embeddings, text_embeddings]).to(torch.float)
+            multiplier = 2
+        return ehs, multiplier
+
+    def _sample_python_guided(self, scheduler, latents, rgb, encoder_hidden_states, multiplier, guidance_scale, return_all):
+        """:1121-1160 step for step: the UNet on multiplier * B images, guidance combine, DDIM step on B."""
+        all_latents = []
+        rgb_latents = torch.cat([rgb] * multiplier)
+        condition = torch.zeros_like(rgb_latents)
+        n = len(scheduler.timesteps)
+        for idx, t in enumerate(scheduler.timesteps):
+            latent_model_input = torch.cat([latents] * multiplier)
+            if self.self_condition:
+                inputs = torch.cat([latent_model_input, rgb_latents, condition], dim=1)
+            else:
+                inputs = torch.cat([latent_model_input, rgb_latents], dim=1)
+            inputs = inputs.to(self.unet_dtype)
+            noise_pred = self.unet_model(inputs, t, encoder_hidden_states=encoder_hidden_states).sample
+            if multiplier > 1:
+                noise_pred_uncond, noise_pred_text = noise_pred.chunk(2)
+                noise_pred = noise_pred_uncond + guidance_scale * (noise_pred_text - noise_pred_uncond)
+            if self.self_condition:
+                condition = scheduler.step(noise_pred, t, latents).pred_original_sample
+            if idx == n - 1:
+                latents = scheduler.step(noise_pred, t, latents).pred_original_sample
+            else:
+                latents = scheduler.step(noise_pred, t, latents).prev_sample
+            if return_all:
+                all_latents.append(latents)
+        return torch.cat(all_latents, dim=0) if return_all else latents
+
+    def _sample_native_guided(self, scheduler, latents, rgb, encoder_hidden_states, multiplier, guidance_scale, return_all):
+        if scheduler.thresholding:
+            raise NotImplementedError
+        cfg, keep = self._loop_cfg(scheduler)
+        B, _, L, _ = rgb.shape
+        lat = latents.clone()
+        ctx = self.unet_model._context(encoder_hidden_states, multiplier * B)
+        allv = torch.empty((cfg.n_steps * B, 4, L, L), device=rgb.device) if return_all else None
+        with torch.cuda.device(rgb.device):
+            _lib.check(_lib.lib().ldmseg_sample_loop_guided(
+                self.unet_model._h, C.byref(cfg), _lib.ptr(lat), _lib.ptr(rgb), B, L, _lib.ptr(ctx), ctx.shape[1], ctx.shape[2],
+                int(multiplier), float(guidance_scale), _lib.ptr(allv), _lib.stream_ptr(rgb.device)), "ldmseg_sample_loop_guided")
+        del keep
+        return allv if return_all else lat
 
     def _loop_cfg(self, scheduler):
         ts = scheduler.timesteps_host()
@@ -287,7 +400,7 @@ class TrainerDiffusion(object):
                          num_inference_steps: int = 50, guidance_scale: float = 7.5, seed: Optional[int] = None,
                          threshold_output: bool = True, threshold_mode: str = "max", scheduler=None, rgb_size: Optional[int] = None,
                          mask_th: float = 0.5, count_th: int = 512, overlap_th: float = 0.5, ignore_label: int = 0,
-                         return_intermediates: bool = False, fused: bool = True):
+                         return_intermediates: bool = False, fused: bool = True, prompts: Optional[List[str]] = None):
         """One batch of `compute_pq` (:1218-1313): RGB images [B,3,S,S] in [0,1] on the GPU -> `processed_results`
         (per image {"panoptic_seg": (panoptic map at the original size (h, w), segments_info)}).
         Pixels -> image-VAE latents -> DDIM sampling -> seg-VAE decoder -> [bilinear x2 -> bilinear to the input size ->
@@ -304,8 +417,9 @@ class TrainerDiffusion(object):
             scheduler.set_timesteps_inference(num_inference_steps)
         rgb_latents, _ = self.encode_inputs(rgb_images, encode_func=self.vae_image.encode,
                                             scaling_factor=self.vae_image.scaling_factor, resize=rgb_size)
-        latents = self.sample([""] * B, num_inference_steps, guidance_scale, seed, rgb_latents=rgb_latents,
-                              scheduler=scheduler, disable_progress_bar=True)
+        # (prompts: data['text'] of the batch, read by a text encoder only; the images feed a descriptor model, :1222-1242)
+        latents = self.sample(list(prompts) if prompts is not None else [""] * B, num_inference_steps, guidance_scale, seed,
+                              rgb_latents=rgb_latents, scheduler=scheduler, disable_progress_bar=True, rgb_images=rgb_images)
         sizes = [(int(s[0]), int(s[1])) for s in im_sizes]
         if fused and not return_intermediates:
             boxes = self.padding_boxes(padding_masks) if padding_masks is not None else None
@@ -353,7 +467,8 @@ class TrainerDiffusion(object):
             masks = data.get("mask")
             masks = masks.to(self.device) if masks is not None else None
             processed = self.predict_panoptic(rgb, sizes, masks, num_inference_steps, guidance_scale, seed,
-                                              threshold_output, threshold_mode, scheduler=scheduler, **post_kw)
+                                              threshold_output, threshold_mode, scheduler=scheduler, prompts=data.get("text"),
+                                              **post_kw)
             evaluator.process(file_names, image_ids, processed)
             if max_iter is not None and batch_idx > max_iter:                                 # (sic, :1332)
                 break

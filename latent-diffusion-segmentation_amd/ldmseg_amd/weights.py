@@ -23,6 +23,12 @@ import torch
 BLOCK_OUT = (320, 640, 1280, 1280)
 TIME_DIM = 1280
 CROSS_DIM = 768
+HID_PROJ_IN = 1024          # CLIP-L/14 patch features (image_descriptors: clip_image)
+
+
+def hid_proj_schema():
+    """encoder_hid_proj = Linear(1024, 768): the optional projection of a cross-attention UNet (unet.py:121-122)."""
+    return OrderedDict([("encoder_hid_proj.weight", (CROSS_DIM, HID_PROJ_IN)), ("encoder_hid_proj.bias", (CROSS_DIM,))])
 
 
 def _resnet(sd, p, cin, cout):
