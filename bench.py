@@ -13,6 +13,13 @@ update), run by ldmseg_sample_loop.  Inputs are resident in HBM when the timed r
 GPU, images are independent, no collective inside the loop; one RCCL all-gather of the final latents
 is timed in the separate images/s figure).  Synthetic data, deterministic random-init weights (no
 checkpoint or dataset exists offline).
+
+A plain run does only what the headline needs: set-up, W warm-up steps, one timed region of K steps, --dump-outputs, the
+result line.  Every side measurement - repeated timed regions, the all-gather, images/s with decode, post-processing, the
+image encoder, the per-family roofline, the other BASELINE configs and precisions, the torch-ROCm yardstick and the CPU
+baseline - runs only with --full (the --no-* options then drop single legs); without it their keys in the line are null.
+
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full
 """
 import argparse
 import json
@@ -95,6 +102,25 @@ def cgroup_cpu_quota():
     except (OSError, ValueError):
         pass
     return None
+
+
+def generate_weights(schema, seed=0, norm_keys=()):
+    """weights.generate(schema, seed, norm_keys=norm_keys), bit for bit, drawn on a thread pool: every tensor comes from a
+    generator seeded by its own key, so the draws are independent of each other and of their order.  torch's CPU rand is
+    serial, and drawn one tensor after another the UNet's 816 M values take several seconds of a plain run's set-up."""
+    from collections import OrderedDict
+    from concurrent.futures import ThreadPoolExecutor
+    from ldmseg_amd import weights
+    try:
+        ncpu = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        ncpu = os.cpu_count() or 1
+    quota = cgroup_cpu_quota()
+    nthreads = max(1, min(16, ncpu, quota or ncpu))
+    keys = sorted(schema, key=lambda k: -torch.Size(schema[k]).numel())          # largest first: the pool stays balanced
+    with ThreadPoolExecutor(max_workers=nthreads) as ex:
+        drawn = dict(zip(keys, ex.map(lambda k: weights.generate({k: schema[k]}, seed=seed, norm_keys=norm_keys)[k], keys)))
+    return OrderedDict((k, drawn[k]) for k in schema)
 
 
 def cpu_baseline(usd, budget_s=32.0):
@@ -257,19 +283,29 @@ def main():
     ap.add_argument("--attention-fp8", type=int, default=0, metavar="MIN_TOKENS",
                     help="bf16 mode: run the attention levels with at least this many tokens on the fp8 (e4m3) operand path "
                          "(BASELINE configs[4]: --batch 4 --latent 128 --attention-fp8 16384)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-images", action="store_true", help="skip the 50-step images/s run")
-    ap.add_argument("--profile-steps", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of K steps each (value = the first; min / median are reported)")
-    ap.add_argument("--no-torch-reference", action="store_true", help="skip the torch-ROCm eager forward of the same graph (yardstick)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (repeated timed regions, all-gather, images/s, post-processing, image "
+                         "encoder, roofline, other configs and precisions, torch-ROCm yardstick, CPU baseline); a plain run "
+                         "times one region of K steps and nothing else")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-images", action="store_true", help="--full: skip the 50-step images/s run and the image encoder")
+    ap.add_argument("--profile-steps", type=int, default=None,
+                    help="steps of the per-family roofline run (default: 3 with --full, 0 without)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of K steps each (value = the first; min / median are reported) (default: 3 with --full, 1 without)")
+    ap.add_argument("--no-torch-reference", action="store_true", help="--full: skip the torch-ROCm eager forward of the same graph (yardstick)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the fp32 parity-mode, inpainting (configs[3]) and 1024x1024 (configs[4]) side measurements")
+                    help="--full: skip the fp32 parity-mode, inpainting (configs[3]) and 1024x1024 (configs[4]) side measurements")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed region returned (rank 0's final latents) as "
                          "DIR/<name>.npy in float32, so that two builds can be compared output for output")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if args.profile_steps is None:
+        args.profile_steps = 3 if args.full else 0
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -314,12 +350,14 @@ def main():
     import ctypes as C
 
     B, L = args.batch, args.latent
-    usd = weights.generate(weights.unet_schema(12, False), seed=0)
-    vsd = weights.generate(weights.vae_schema(), seed=7, norm_keys=weights.VAE_NORM_KEYS)
+    usd = generate_weights(weights.unet_schema(12, False), seed=0)
     unet = UNet(usd, in_channels=12, device=dev, compute_dtype=args.dtype)
     if args.attention_fp8 > 0:
         unet.set_attention_fp8(args.attention_fp8)
-    vae = GeneralVAESeg(vsd, scaling_factor=0.18215, device=dev, compute_dtype=args.dtype)
+    vae = None                                      # only the images/s leg decodes
+    if args.full and not args.no_images:
+        vsd = weights.generate(weights.vae_schema(), seed=7, norm_keys=weights.VAE_NORM_KEYS)
+        vae = GeneralVAESeg(vsd, scaling_factor=0.18215, device=dev, compute_dtype=args.dtype)
     tr = TrainerDiffusion(vae, unet, DDIMNoiseScheduler(**SCHED_KW))
 
     rgb = (0.18215 * torch.randn(B, 4, L, L, generator=torch.Generator().manual_seed(1234 + rank))).to(dev)
@@ -380,7 +418,7 @@ def main():
 
     # ---- the one collective of the path, timed on its own: all-gather of the final latents [B,4,L,L] fp32 per rank ----
     allgather_us = None
-    if world > 1:
+    if world > 1 and args.full:
         gathered = torch.empty((B * world, 4, L, L), device=dev, dtype=torch.float32)
         for _ in range(3):
             dist.all_gather_into_tensor(gathered, lat.contiguous())
@@ -398,7 +436,7 @@ def main():
     # ---- images/s: 50-step DDIM + all-gather of latents + seg-VAE decode to logits ----
     images_per_s = None
     postprocess = None
-    if not args.no_images:
+    if args.full and not args.no_images:
         sync_all()
         t1 = time.perf_counter()
         s50 = DDIMNoiseScheduler(**SCHED_KW)
@@ -434,7 +472,7 @@ def main():
 
     # ---- RGB image encoder (once per image, before the loop) ----
     image_encoder = None
-    if rank == 0 and not args.no_images:
+    if rank == 0 and args.full and not args.no_images:
         from ldmseg_amd.models import GeneralVAEImage
         isd = weights.generate(weights.vae_image_schema(), seed=11, norm_keys=weights.VAE_IMAGE_NORM_KEYS)
         enc = GeneralVAEImage(isd, device=dev, compute_dtype=args.dtype)
@@ -497,7 +535,7 @@ def main():
 
     # ---- side measurements (rank 0, single GPU): the other BASELINE configs and the fp32 parity mode ----
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         def timed(tr_, Bx, Lx, k, fn=None):
             rgbx = (0.18215 * torch.randn(Bx, 4, Lx, Lx, generator=torch.Generator().manual_seed(99))).to(dev)
             def go(n):
@@ -563,7 +601,7 @@ def main():
     # ---- same-box yardstick: the graph the reference executes (oracle/unet.py) run by torch-ROCm eager on this GPU, in a
     # child process (its 5 GB of weights and the SDPA / MIOpen workspaces stay out of this one), outside the timed region
     torch_ref = None
-    if rank == 0 and world == 1 and not args.no_torch_reference and (B, L) == (8, 64):
+    if rank == 0 and world == 1 and args.full and not args.no_torch_reference and (B, L) == (8, 64):
         import subprocess
         try:
             r_ = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "yardstick.py"), "--whole-only", "--fast", "--batch", str(B),
@@ -574,7 +612,7 @@ def main():
             torch_ref = {"error": repr(e)[:300]}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         del unet, vae
         cpu = cpu_baseline(usd)
 

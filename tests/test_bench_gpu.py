@@ -19,7 +19,7 @@ def run_bench(nproc, extra_env, port, extra_args=()):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--profile-steps", "0",
+           "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras", "--profile-steps", "0",
            *extra_args]
     return subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
 
@@ -103,3 +103,32 @@ def test_direct_form_refuses_rccl_without_enough_devices():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                        capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode != 0 and "visible devices" in r.stderr
+
+
+def test_plain_run_times_one_region_and_dumps_what_a_full_run_dumps(tmp_path):
+    """A run without --full does set-up, warm-up, ONE timed region and --dump-outputs, and nothing else: the side
+    measurements' keys are null.  Its dumped latents are those of a --full run with three timed regions, bit for bit (every
+    region samples the same seeded inputs)."""
+    def bench(*extra):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", *extra]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    out = bench("--dump-outputs", str(tmp_path / "plain"))
+    assert out["metric"] == "denoising-steps/sec" and out["unit"] == "image-steps/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "bf16" and out["steps"] == 2 and out["warmup"] == 1 and out["finite"] is True
+    assert out["value"] == pytest.approx(8 * 2 / (2 * out["ms_per_step"] * 1e-3), rel=1e-9)
+    assert out["timed_regions"]["n"] == 1 and out["timed_regions"]["ms_per_step"][0] == pytest.approx(out["ms_per_step"], rel=1e-3)
+    for k in ("allgather_latents", "images_per_s_50step_ddim_incl_decode", "roofline", "postprocess_8f1", "image_encoder_8f2",
+              "other_configs", "cpu_baseline", "torch_rocm_reference"):
+        assert out[k] is None, k
+    assert "gpu_over_cpu" not in out
+    full = bench("--full", "--no-cpu-baseline", "--no-extras", "--no-torch-reference", "--no-images", "--profile-steps", "0",
+                 "--dump-outputs", str(tmp_path / "full"))
+    assert full["timed_regions"]["n"] == 3
+    a, b = np.load(tmp_path / "plain" / "latents.npy"), np.load(tmp_path / "full" / "latents.npy")
+    assert a.shape == (8, 4, 64, 64) and np.isfinite(a).all()
+    assert np.array_equal(a, b)

@@ -114,3 +114,17 @@ def test_bench_dump_outputs_float32_within_the_size_limit(tmp_path, monkeypatch)
         assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= bench.DUMP_LIMIT_BYTES
     s1, s2 = np.load(tmp_path / "s1" / "latents.npy"), np.load(tmp_path / "s2" / "latents.npy")
     assert np.array_equal(s1, s2) and np.isin(s1, a).all()
+
+
+def test_bench_weights_drawn_on_threads_equal_the_serial_draw():
+    """bench.generate_weights draws the state dict on a thread pool: same keys, order, dtypes and values as
+    weights.generate (every tensor has its own key-seeded generator), norm keys included."""
+    import bench
+    from ldmseg_amd import weights
+    unet = dict(list(weights.unet_schema(12, False).items())[:48])
+    for schema, seed, norm_keys in ((unet, 0, ()), (weights.vae_schema(), 7, weights.VAE_NORM_KEYS)):
+        a = bench.generate_weights(schema, seed=seed, norm_keys=norm_keys)
+        b = weights.generate(schema, seed=seed, norm_keys=norm_keys)
+        assert list(a) == list(b)
+        for k in b:
+            assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and torch.equal(a[k], b[k]), k

@@ -3,7 +3,7 @@
 for rep in 1 2; do
   for lib in "$@"; do
     if [ "$lib" = "HEAD" ]; then unset LDMSEG_HIP_LIB; else export LDMSEG_HIP_LIB=$GRAFT_REPO_ROOT/$lib; fi
-    python bench.py --no-cpu-baseline --no-extras --no-images --steps 30 --warmup 3 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-extras --no-images --steps 30 --warmup 3 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 f=d['roofline']['families_ms_per_step']

@@ -68,7 +68,7 @@ try:
     out = {"kernel": "igemm_kernel (all instantiations) + mlp_fused_kernel + proj_ln_qkv_kernel + conv_out_tail_kernel", "launches": n_f,
            "fetch_bytes_per_launch": 2 * 1024 * kib_f / n_f, "write_bytes_per_launch": 1024 * kib_w / n_w,
            "hbm_bytes_per_launch": 2 * 1024 * kib_f / n_f + 1024 * kib_w / n_w, "csrc_sha": sha,
-           "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --steps 3 --warmup 1 "
+           "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --full --steps 3 --warmup 1 "
                      "--no-cpu-baseline --no-images --no-extras --profile-steps 0`; FETCH_SIZE (KiB) doubled per MI355X_MICROARCH.md "
                      "(HBM section: gfx950 tallies 128-B requests at 64 B); WRITE_SIZE uncalibrated; Infinity-Cache hits are counted",
            "source": [f"profiles/{tag}_pmc_fetch.txt", f"profiles/{tag}_pmc_write.txt"]}
