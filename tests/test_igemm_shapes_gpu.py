@@ -23,7 +23,8 @@ pytestmark = pytest.mark.gpu
 F32, BF16 = 0, 1
 X3W = 3     # operator dtype 3: fp32 tensors, split-bf16 products, weights as hi | lo planes - what a bf16x3 handle runs
 # (batch, latent size): the measured launch table (csrc/igemm_tuned.inc) has entries - instantiation x K-slice count - for
-# exactly these three; every other shape goes through the rules that the same lists exercise
+# exactly these three; every other shape goes through the rules that the same lists exercise (tests/test_offgrid_shapes_gpu.py runs
+# the helpers below at configurations off the power-of-two grid, where those rules fall the other way)
 CONFIGS = [(8, 64), (16, 64), (4, 128)]
 CFG_IDS = [f"b{b}l{l}" for b, l in CONFIGS]
 # compute modes of the forward: "bf16fp8" = bf16 with UNet.set_attention_fp8() (BASELINE configs[4]); it runs what bf16 runs
@@ -34,8 +35,8 @@ SEEN = {(c, m): set() for c in CONFIGS for m in MODES}
 
 
 @contextlib.contextmanager
-def recorded(L, cfg, *modes):
-    """dispatch log on (every family) around the body; every name it logged is added to SEEN[(cfg, mode)] of each mode given"""
+def recorded(L, seen, cfg, *modes):
+    """dispatch log on (every family) around the body; every name it logged is added to seen[(cfg, mode)] of each mode given"""
     L.igemm_log(L.LOG_ALL)
     try:
         yield
@@ -44,7 +45,7 @@ def recorded(L, cfg, *modes):
     finally:
         L.igemm_log(False)
     for m in modes:
-        SEEN[(cfg, m)] |= names
+        seen[(cfg, m)] |= names
 
 
 @pytest.fixture(scope="module")
@@ -139,6 +140,10 @@ SHAPES = [
 @pytest.mark.parametrize("cfg", CONFIGS, ids=CFG_IDS)
 @pytest.mark.parametrize("case", SHAPES)
 def test_unet_layer_shape_vs_oracle(L, dt, cfg, case):
+    check_layer_shape(L, SEEN, dt, cfg, case)
+
+
+def check_layer_shape(L, seen, dt, cfg, case):
     H, Ci, Ci2, Co, k, stride, up, geglu, use_res, use_rb = case
     B, lat = cfg
     H = H * lat // 64
@@ -165,7 +170,7 @@ def test_unet_layer_shape_vs_oracle(L, dt, cfg, case):
         ref = ref + (bf16_round(res) if dt == BF16 else res)
     out = torch.empty(ref.shape, device="cuda")
     dx, dx2, dw, db, dres, drb = dev(x), dev(x2), dev(w), dev(b), dev(res), dev(rb)
-    with recorded(L, cfg, MODE[dt]):
+    with recorded(L, seen, cfg, MODE[dt]):
         r = L.lib().ldmseg_op_igemm(P(dx), P(dx2), P(dw), P(db), P(dres), P(drb), B, Ci, Ci2, H, H, Co, k, stride, up, geglu,
                                     0, 0, dt, P(out), None)
         assert r == 0, L.lib().ldmseg_last_error()
@@ -176,7 +181,7 @@ def test_unet_layer_shape_vs_oracle(L, dt, cfg, case):
     if dt == F32:
         # bf16x3: the same unrounded reference, the bound of the split-bf16 operator tests (test_ops_gpu X3_CASES)
         out3 = torch.empty(ref.shape, device="cuda")
-        with recorded(L, cfg, "bf16x3"):
+        with recorded(L, seen, cfg, "bf16x3"):
             r = L.lib().ldmseg_op_igemm(P(dx), P(dx2), P(dw), P(db), P(dres), P(drb), B, Ci, Ci2, H, H, Co, k, stride, up, geglu,
                                         0, 0, X3W, P(out3), None)
             assert r == 0, L.lib().ldmseg_last_error()
@@ -192,7 +197,7 @@ def test_unet_layer_shape_vs_oracle(L, dt, cfg, case):
         out2 = torch.empty(ref.shape, device="cuda")
         try:
             assert lib.ldmseg_debug_set(23, 0) == 0
-            with recorded(L, cfg, MODE[dt]):
+            with recorded(L, seen, cfg, MODE[dt]):
                 assert lib.ldmseg_op_igemm(P(dx), P(dx2), P(dw), P(db), P(dres), P(drb), B, Ci, Ci2, H, H, Co, k, stride, up, geglu,
                                            0, 0, dt, P(out2), None) == 0
             name2 = L.igemm_last_kernel()
@@ -212,6 +217,10 @@ LN_SHAPES = [   # (M at B = 8 / L = 64, K = C, N, geglu): norm1 -> q|k|v and nor
 @pytest.mark.parametrize("cfg", CONFIGS, ids=CFG_IDS)
 @pytest.mark.parametrize("M,K,N,geglu", LN_SHAPES)
 def test_unet_layernorm_folded_gemm_vs_oracle(L, dt, cfg, M, K, N, geglu):
+    check_layernorm_folded_gemm(L, SEEN, dt, cfg, M, K, N, geglu)
+
+
+def check_layernorm_folded_gemm(L, seen, dt, cfg, M, K, N, geglu):
     """LayerNorm -> Linear / GEGLU of the transformer blocks as the engine runs them: one statistics pass, then the GEMM
     on the un-normalised tokens with gamma folded into the weights and rstd*(acc - mean*c1) + c2 in the epilogue (its own
     template instantiations, ',ln').  Reference: F.layer_norm + F.linear (+ GEGLU); the tokens carry a large common offset
@@ -231,7 +240,7 @@ def test_unet_layernorm_folded_gemm_vs_oracle(L, dt, cfg, M, K, N, geglu):
         y = a * F.gelu(gate)
     out = torch.empty(y.shape, device="cuda")
     dx, dg, db, dw, dbias = dev(x), dev(gamma), dev(beta), dev(w), dev(b)
-    with recorded(L, cfg, MODE[dt]):
+    with recorded(L, seen, cfg, MODE[dt]):
         assert L.lib().ldmseg_op_ln_linear(P(dx), P(dg), P(db), P(dw), P(dbias), M, K, N, 1e-5, geglu, dt, P(out), None) == 0
     name = L.igemm_last_kernel()
     assert ",ln" in name
@@ -240,7 +249,7 @@ def test_unet_layernorm_folded_gemm_vs_oracle(L, dt, cfg, M, K, N, geglu):
     assert e < (1.5e-2 if dt == BF16 else 1e-4), name
     if dt == F32:       # bf16x3 (weight planes); bound of the split-bf16 LayerNorm-fold operator test (test_ops_gpu)
         out3 = torch.empty(y.shape, device="cuda")
-        with recorded(L, cfg, "bf16x3"):
+        with recorded(L, seen, cfg, "bf16x3"):
             assert L.lib().ldmseg_op_ln_linear(P(dx), P(dg), P(db), P(dw), P(dbias), M, K, N, 1e-5, geglu, X3W, P(out3), None) == 0
         name3 = L.igemm_last_kernel()
         assert ",ln" in name3 and ",x3w>" in name3, name3
@@ -251,7 +260,12 @@ def test_unet_layernorm_folded_gemm_vs_oracle(L, dt, cfg, M, K, N, geglu):
 @pytest.mark.parametrize("dt", [BF16, F32])
 @pytest.mark.parametrize("cfg", CONFIGS, ids=CFG_IDS)
 def test_conv_out_shape_vs_oracle(L, dt, cfg):
-    """conv_out: 320 -> 4 channels at the full latent resolution, written straight to fp32 NCHW (EPI_NCHW_F32, the narrow-N tile)."""
+    check_conv_out_shape(L, SEEN, dt, cfg)
+
+
+def check_conv_out_shape(L, seen, dt, cfg, tail=True):
+    """conv_out: 320 -> 4 channels at the full latent resolution, written straight to fp32 NCHW (EPI_NCHW_F32, the narrow-N tile).
+    tail: the shape has the step-tail kernel (conv_out_tail_ok), so the bf16 forward runs conv_out through it."""
     B, lat = cfg
     g = torch.Generator().manual_seed(4)
     x = torch.randn(B, 320, lat, lat, generator=g)
@@ -261,18 +275,18 @@ def test_conv_out_shape_vs_oracle(L, dt, cfg):
     ref = F.conv2d(xr, wr, b, padding=1)
     out = torch.empty(ref.shape, device="cuda")
     dx, dw, db = dev(x), dev(w), dev(b)
-    with recorded(L, cfg, MODE[dt]):
+    with recorded(L, seen, cfg, MODE[dt]):
         assert L.lib().ldmseg_op_conv2d(P(dx), None, P(dw), P(db), B, 320, 0, lat, lat, 4, 3, 1, 0, dt, P(out), None) == 0
     assert rel_err(out, ref) < (1e-3 if dt == BF16 else 1e-4)
     if dt == F32:           # bf16x3 (dtype 3: weight planes, what the handles hold), same unrounded reference
         out3 = torch.empty(ref.shape, device="cuda")
-        with recorded(L, cfg, "bf16x3"):
+        with recorded(L, seen, cfg, "bf16x3"):
             assert L.lib().ldmseg_op_conv2d(P(dx), None, P(dw), P(db), B, 320, 0, lat, lat, 4, 3, 1, 0, X3W, P(out3), None) == 0
         assert ",x3w>" in L.igemm_last_kernel(), L.igemm_last_kernel()
         assert rel_err(out3, ref) < 1e-4, rel_err(out3, ref)
-    if dt == BF16:          # the bf16 forward runs conv_out as the halo-resident stencil of tail.hip
+    if dt == BF16 and tail:     # the bf16 forward runs conv_out as the halo-resident stencil of tail.hip
         out2 = torch.empty(ref.shape, device="cuda")
-        with recorded(L, cfg, "bf16"):
+        with recorded(L, seen, cfg, "bf16"):
             assert L.lib().ldmseg_op_conv_out_tail(P(dx), P(dw), P(db), B, lat, lat, P(out2), 0, 0, None, 0, 0, 1.0, None, None, None,
                                                    None, None, None, 0.0, 0.0, None, None) == 0
         assert rel_err(out2, ref) < 1e-3
@@ -291,6 +305,10 @@ XT_SHAPES = [
 @pytest.mark.parametrize("cfg", CONFIGS, ids=CFG_IDS)
 @pytest.mark.parametrize("case", XT_SHAPES)
 def test_resnet_tail_one_launch_vs_oracle(L, cfg, case):
+    check_resnet_tail_one_launch(L, SEEN, cfg, case)
+
+
+def check_resnet_tail_one_launch(L, seen, cfg, case):
     """F.conv2d(h, w2, b2, padding=1) + F.conv2d(cat([x, skip]), ws, bs) (diffusers ResnetBlock2D: conv2 + conv_shortcut) against the
     engine's single extra-tap launch at the configuration's shapes; records the ',xt' instantiation that ran."""
     import ctypes as C
@@ -309,7 +327,7 @@ def test_resnet_tail_one_launch_vs_oracle(L, cfg, case):
     ref = F.conv2d(bf16_round(h), bf16_round(w2), b2, padding=1) + F.conv2d(bf16_round(xin), bf16_round(ws), bs)
     out = torch.empty(ref.shape, device="cuda")
     dh, dxs, dxs2, dw2, dws, db2, dbs = dev(h), dev(xs), dev(xs2), dev(w2), dev(ws), dev(b2), dev(bs)
-    with recorded(L, cfg, "bf16"):
+    with recorded(L, seen, cfg, "bf16"):
         r = L.lib().ldmseg_op_conv3x3_plus_1x1(P(dh), P(dw2), P(db2), P(dxs), P(dxs2), P(dws), P(dbs), B, Cc, Cs, Cs2, H, H, Cc, 0, BF16,
                                                P(out), 0, None, None)
         assert r == 0, (r, L.lib().ldmseg_last_error())
@@ -320,6 +338,10 @@ def test_resnet_tail_one_launch_vs_oracle(L, cfg, case):
 
 @pytest.mark.parametrize("cfg", CONFIGS, ids=CFG_IDS)
 def test_fused_feed_forward_at_config_shape(L, cfg):
+    check_fused_feed_forward(L, SEEN, cfg)
+
+
+def check_fused_feed_forward(L, seen, cfg):
     """The row-local fused feed-forward kernel (tfuse.hip: LayerNorm_3 -> GEGLU -> ff.net.2 (+h) -> proj_out (+x)) that the
     bf16 forward runs on the 320-channel level, at this configuration's token count M = B * L * L, against torch on the same
     bf16-rounded operands (the arithmetic of oracle/unet.py::transformer)."""
@@ -329,15 +351,19 @@ def test_fused_feed_forward_at_config_shape(L, cfg):
     case = _ff_case(M, 320, 7 + M)
     ref = _ff_ref(*case)
     for mode, name in ((3, "mlp_fused<bf16,proj=1>"), (1, "mlp_fused<bf16,proj=0>")):
-        with recorded(L, cfg, "bf16"):
+        with recorded(L, seen, cfg, "bf16"):
             out, _ = _ff_run(L, case, M, 320, mode)
-        assert name in SEEN[(cfg, "bf16")]
+        assert name in seen[(cfg, "bf16")]
         l2 = float((out.double() - ref.double()).norm() / ref.double().norm())
         assert torch.isfinite(out).all() and l2 < 6e-3 and rel_err(out, ref) < 3e-2, (cfg, mode, l2)
 
 
 @pytest.mark.parametrize("cfg", CONFIGS, ids=CFG_IDS)
 def test_fused_transformer_entry_at_config_shape(L, cfg):
+    check_fused_transformer_entry(L, SEEN, cfg)
+
+
+def check_fused_transformer_entry(L, seen, cfg):
     """The row-local fused entry kernel (tproj.hip: proj_in -> LayerNorm_1 -> q|k|v) that the bf16 forward runs on the
     320-channel level, at this configuration's token count, against torch on the same bf16-rounded operands."""
     from test_ops_gpu import _tin_case, _tin_ref, _tin_run
@@ -345,15 +371,19 @@ def test_fused_transformer_entry_at_config_shape(L, cfg):
     M = B * lat * lat
     case = _tin_case(M, 320, 11 + M)
     href, qref = _tin_ref(*case)
-    with recorded(L, cfg, "bf16"):
+    with recorded(L, seen, cfg, "bf16"):
         h, qkv, _ = _tin_run(L, case, M, 320, 1)
-    assert "proj_ln_qkv<bf16>" in SEEN[(cfg, "bf16")]
+    assert "proj_ln_qkv<bf16>" in seen[(cfg, "bf16")]
     l2 = lambda a, b: float((a.double() - b.double()).norm() / b.double().norm())
     assert torch.isfinite(qkv).all() and l2(h, href) < 3e-3 and l2(qkv, qref) < 6e-3, (cfg, l2(h, href), l2(qkv, qref))
 
 
 @pytest.mark.parametrize("cfg", CONFIGS, ids=CFG_IDS)
 def test_fused_transformer_entry_with_groupnorm_at_config_shape(L, cfg):
+    check_fused_transformer_entry_with_groupnorm(L, SEEN, cfg)
+
+
+def check_fused_transformer_entry_with_groupnorm(L, seen, cfg):
     """The same kernel with the transformer's GroupNorm folded in (statistics pass + apply sweep on the LDS tile: what the bf16
     forward launches since round 5), at this configuration's image count and map size, against torch GroupNorm -> proj_in ->
     LayerNorm_1 -> q|k|v on the bf16-rounded operands."""
@@ -368,9 +398,9 @@ def test_fused_transformer_entry_with_groupnorm_at_config_shape(L, cfg):
     gb = 0.3 * torch.randn(320, generator=g)
     xn = F.group_norm(bf16_round(x).permute(0, 2, 1).reshape(B, 320, HW, 1), 32, gg, gb, 1e-6).reshape(B, 320, HW).permute(0, 2, 1)
     href, qref = _tin_ref(xn.reshape(M, 320), *case[1:])
-    with recorded(L, cfg, "bf16"):
+    with recorded(L, seen, cfg, "bf16"):
         h, qkv, _ = _gtin_run(L, x.reshape(M, 320), gg, gb, B, 1, case, M, 320, 1)
-    assert "proj_ln_qkv<bf16,gn>" in SEEN[(cfg, "bf16")]
+    assert "proj_ln_qkv<bf16,gn>" in seen[(cfg, "bf16")]
     l2 = lambda a, b: float((a.double() - b.double()).norm() / b.double().norm())
     assert torch.isfinite(qkv).all() and l2(h, href) < 4e-3 and l2(qkv, qref) < 7e-3, (cfg, l2(h, href), l2(qkv, qref))
 
@@ -392,6 +422,10 @@ GN_SHAPES = [
 @pytest.mark.parametrize("cfg", CONFIGS, ids=CFG_IDS)
 @pytest.mark.parametrize("case", GN_SHAPES)
 def test_unet_groupnorm_shape_vs_oracle(L, dt, cfg, case):
+    check_groupnorm_shape(L, SEEN, dt, cfg, case)
+
+
+def check_groupnorm_shape(L, seen, dt, cfg, case):
     """F.group_norm(cat([x, x2], 1), 32) (+ SiLU) in fp64 on the storage-rounded input against ldmseg_op_groupnorm at the
     configuration's (B, C, C2, H x W): the kernel form the launcher picks there (gn_group / gn_coop / gn_one / gn_fused / gn_small /
     gn_partial + gn_apply: chosen from B * groups, the map size and the CU count) is the one the forward runs.  Two launches, bit
@@ -413,7 +447,7 @@ def test_unet_groupnorm_shape_vs_oracle(L, dt, cfg, case):
         ref = F.silu(ref)
     outs = [torch.empty(B, Cc + C2, HW, device="cuda") for _ in range(2)]
     dx, dx2, dg, db = dev(x), dev(x2), dev(gamma), dev(beta)
-    with recorded(L, cfg, *(("bf16",) if dt == BF16 else ("fp32", "bf16x3"))):
+    with recorded(L, seen, cfg, *(("bf16",) if dt == BF16 else ("fp32", "bf16x3"))):
         for o in outs:
             assert L.lib().ldmseg_op_groupnorm(P(dx), P(dx2), P(dg), P(db), B, Cc, C2, HW, eps, silu, dt, P(o), None) == 0
     assert torch.isfinite(outs[0]).all()
@@ -433,6 +467,10 @@ CONV_GN_SHAPES = [
 @pytest.mark.parametrize("dt", [BF16, F32])
 @pytest.mark.parametrize("cfg", CONFIGS, ids=CFG_IDS)
 def test_conv_groupnorm_fused_finish_at_config_shapes(L, dt, cfg):
+    assert check_conv_groupnorm_fused_finish(L, SEEN, dt, cfg) >= 1, cfg
+
+
+def check_conv_groupnorm_fused_finish(L, seen, dt, cfg):
     """ldmseg_op_conv_groupnorm at every resnet conv1 -> norm2 shape of the configuration, with the K-slice count the engine plans
     there (read from the plain conv launch), against F.conv2d + time-embedding row + F.group_norm + SiLU in fp64 on the rounded
     operands.  Shapes the engine does not K-slice (one slice planned) or has no fused form for (-4) are skipped over; at least one shape per configuration is
@@ -461,7 +499,7 @@ def test_conv_groupnorm_fused_finish_at_config_shapes(L, dt, cfg):
         h = F.conv2d(rnd(x).double(), rnd(w).double(), b.double(), padding=1) + rb.double()[:, :, None, None]
         ref = F.silu(F.group_norm(h, 32, gamma.double(), beta.double(), 1e-5))
         out = torch.empty(ref.shape, device="cuda")
-        with recorded(L, cfg, *(("bf16",) if dt == BF16 else ("fp32", "bf16x3"))):
+        with recorded(L, seen, cfg, *(("bf16",) if dt == BF16 else ("fp32", "bf16x3"))):
             r = L.lib().ldmseg_op_conv_groupnorm(P(dx), P(dw), P(db), P(drb), P(dg), P(dbe), B, Ci, H, H, Co, 1e-5, 1, splits, dt,
                                                  P(out), None)
             if r == -4:         # no finish-GroupNorm instantiation for the shape (finish_groupnorm_ok): the engine keeps conv and norm apart
@@ -470,7 +508,7 @@ def test_conv_groupnorm_fused_finish_at_config_shapes(L, dt, cfg):
         fused += 1
         assert torch.isfinite(out).all()
         assert rel_err(out, ref) < (8e-3 if dt == BF16 else 2e-4), (cfg, H, Ci, Co, splits)
-    assert fused >= 1, cfg
+    return fused
 
 
 # ---- self-attention: every (map side at L = 64, C) level of the UNet, 8 heads (head dim 40 / 80 / 160 / 160)
@@ -511,6 +549,10 @@ def _attn_case(B, N, Cc, seed):
 @pytest.mark.parametrize("cfg", CONFIGS, ids=CFG_IDS)
 @pytest.mark.parametrize("level", ATTN_LEVELS)
 def test_unet_attention_level_vs_oracle(L, mode, cfg, level):
+    check_attention_level(L, SEEN, mode, cfg, level)
+
+
+def check_attention_level(L, seen, mode, cfg, level):
     """ldmseg_op_attention at the configuration's (B, N = H x W, C) of every transformer level, in the operator dtype the forward
     launches for the mode (the 4- / 8-wave forms are chosen from B * heads * ceil(N / 256), head dim 160 goes to attention.hip):
     the first and last image against fp64 on the storage-rounded input, on sampled query rows.  Bounds of test_attention /
@@ -522,7 +564,7 @@ def test_unet_attention_level_vs_oracle(L, mode, cfg, level):
     qkv = _attn_case(B, N, Cc, N + Cc + B)
     out = torch.empty(B, N, Cc, device="cuda")
     dq = dev(qkv)
-    with recorded(L, cfg, mode):
+    with recorded(L, seen, cfg, mode):
         assert L.lib().ldmseg_op_attention(P(dq), B, N, Cc, 8, ATTN_DT[mode], P(out), None) == 0, L.lib().ldmseg_last_error()
     assert torch.isfinite(out).all()
     src = bf16_round(qkv) if mode == "bf16" else qkv
@@ -535,6 +577,10 @@ def test_unet_attention_level_vs_oracle(L, mode, cfg, level):
 
 @pytest.mark.parametrize("cfg", CONFIGS, ids=CFG_IDS)
 def test_unet_attention_fp8_level_vs_oracle(L, cfg):
+    check_attention_fp8_level(L, SEEN, cfg)
+
+
+def check_attention_fp8_level(L, seen, cfg):
     """ldmseg_op_attention_fp8 at the head-dim-40 level of the configuration (the only one a bf16 forward with set_attention_fp8()
     takes to the fp8 path: N >= 4096 on whole 128-key tiles): first and last image against fp64 on the same e4m3-quantised
     operands and on the unquantised ones.  Bounds of test_attention_fp8_path (test_ops_gpu)."""
@@ -547,7 +593,7 @@ def test_unet_attention_fp8_level_vs_oracle(L, cfg):
     qkv[:, :, :Cc] *= 1.5
     out = torch.empty(B, N, Cc, device="cuda")
     dq = dev(qkv)
-    with recorded(L, cfg, "bf16fp8"):
+    with recorded(L, seen, cfg, "bf16fp8"):
         assert L.lib().ldmseg_op_attention_fp8(P(dq), B, N, Cc, 8, P(out), 0, None, None) == 0
     assert torch.isfinite(out).all()
     # (N <= 4096: every query row, so that the max-norm is taken over the same population as in test_attention_fp8_path)
@@ -563,6 +609,8 @@ def test_unet_attention_fp8_level_vs_oracle(L, cfg):
         l2 = float((o.double() - ref).norm() / ref.norm())
         print(f"fp8 attention {cfg} image {b}: vs quantised operands {e_same:.3e}, vs unquantised {e_total:.3e}, rel-L2 {l2:.3e}")
         assert e_same < 4e-2 and e_total < 0.2 and l2 < 0.1, (cfg, b, e_same, e_total, l2)
+
+
 GN_FAMILY = ("gn_", "finish_gn<")
 ATTN_FAMILY = ("attn", "kv_to_")
 
@@ -571,10 +619,16 @@ ATTN_FAMILY = ("attn", "kv_to_")
 @pytest.mark.parametrize("mode,dt", [("bf16", BF16), ("fp32", F32), ("bf16x3", X3W), ("bf16fp8", BF16)])
 @pytest.mark.parametrize("cfg", CONFIGS, ids=CFG_IDS)
 def test_every_forward_instantiation_is_oracle_tested(L, unet_sd, cfg, mode, dt):
+    check_every_forward_instantiation(L, SEEN, unet_sd, cfg, mode, dt)
+
+
+def check_every_forward_instantiation(L, seen, unet_sd, cfg, mode, dt, fp8_level=None):
     """Run a forward of the configuration (BASELINE configs[1] / [3] / [4]) in the compute mode with the dispatch log on: every
     kernel it launches - igemm instantiation (tile shape, wave layout, ring depth, K-sliced or not, split-bf16 marker), GroupNorm /
     LayerNorm-statistics / attention form with its template arguments, fused kernels - must be one that a per-op test above has
-    just compared with the oracle AT THIS CONFIGURATION'S shapes and in this mode.  bf16fp8 = bf16 with set_attention_fp8()."""
+    just compared with the oracle AT THIS CONFIGURATION'S shapes and in this mode.  bf16fp8 = bf16 with set_attention_fp8().
+    fp8_level: whether a bf16fp8 forward must / must not launch an fp8 attention kernel (None: must from 4096 tokens up, the
+    tuned configurations' rule).  Returns the names the forward launched."""
     from ldmseg_amd.models import UNet
     B, lat = cfg
     u = UNet(unet_sd, in_channels=12, device="cuda:0", compute_dtype="bf16" if mode == "bf16fp8" else mode)
@@ -597,9 +651,12 @@ def test_every_forward_instantiation_is_oracle_tested(L, unet_sd, cfg, mode, dt)
     assert fam["gn"] and fam["attn"], (cfg, mode, sorted(used))
     if mode == "bf16x3":
         assert all(",x3w>" in n for n in fam["igemm"]), fam["igemm"]      # every GEMM of the mode on the split-bf16 K loop
-    if mode == "bf16fp8" and lat * lat >= 4096:
-        assert any(n.startswith(("attn_mx<", "attn_fp8<")) for n in fam["attn"]), fam["attn"]
-    tested = SEEN[(cfg, mode)] | (SEEN[(cfg, "bf16")] if mode == "bf16fp8" else set())
+    if fp8_level is None:
+        fp8_level = True if lat * lat >= 4096 else None
+    if mode == "bf16fp8" and fp8_level is not None:
+        assert any(n.startswith(("attn_mx<", "attn_fp8<")) for n in fam["attn"]) == fp8_level, fam["attn"]
+    tested = seen[(cfg, mode)] | (seen[(cfg, "bf16")] if mode == "bf16fp8" else set())
     missing = used - tested
     assert not missing, (f"{cfg} {mode}: forward kernels without a per-op oracle test: {sorted(missing)}; "
                          f"tested: {sorted(tested)}")
+    return used
