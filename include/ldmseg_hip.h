@@ -105,8 +105,8 @@ int ldmseg_unet_forward_parts(ldmseg_unet* h, const float* latents, const float*
                               void* stream);
 /* UNet.forward(sample, timestep, encoder_hidden_states=ctx).sample of a cross-attention handle (unet.py:281-436 with
  * attn2 kept).  ctx: [B, S, ctx_dim] fp32 on the device, 1 <= S <= 4096 (77 CLIP text tokens, 257 CLIP-L/14 patch features,
- * 1 projected image embedding); ctx_dim = 768, or 1024 when the handle holds encoder_hid_proj (applied once per call,
- * unet.py:319-320).  The context's keys / values for all 16 transformers are computed once per call into the workspace
+ * 1 projected image embedding - the last two are what ldmseg_clip_vision_describe / _forward below produce); ctx_dim = 768,
+ * or 1024 when the handle holds encoder_hid_proj (applied once per call, unet.py:319-320).  The context's keys / values for all 16 transformers are computed once per call into the workspace
  * (planned for the last S / ctx_dim used: a call with another context shape re-plans and may synchronise).  LDMSEG_E_ARG on a
  * handle without cross-attention; the plain ldmseg_unet_forward / _forward_parts return LDMSEG_E_ARG on a cross handle. */
 int ldmseg_unet_forward_ctx(ldmseg_unet* h, const float* x, const int64_t* t_dev, int t_count, int64_t t_host, int B, int L,
@@ -234,6 +234,45 @@ int64_t ldmseg_vae_image_num_params(const ldmseg_vae_image* h);
  * (mean | logvar before the clamp); feed ldmseg_vae_posterior for .mode()/.sample() and the scaling factor. */
 int ldmseg_vae_image_encode(ldmseg_vae_image* h, const float* x, float in_mul, float in_add, int B, int H, int W,
                             float* moments, void* stream);
+
+/* ------------------------------------------------------------------ CLIP image encoder (image descriptors)
+ * The image descriptor of image_descriptors = clip_image / clip_image_proj: transformers' CLIPVisionModel /
+ * CLIPVisionModelWithProjection behind MyCLIPVisionModel / MyCLIPVisionModelWithProjection (ldmseg/models/descriptors.py:15-56,
+ * 67-76, called at trainers_ldm_cond.py:1102-1103).  Patch conv (stride = patch, no bias) + class token + position table,
+ * pre_layrnorm, num_layers pre-norm blocks (self-attention with head dim 64, quick-GELU MLP), last_hidden_state WITHOUT the
+ * post-layernorm, pooled = post_layernorm(class row), image_embeds = visual_projection(pooled).  All LayerNorms eps 1e-5.
+ * The arithmetic is transformers' (not vendored by the reference): parity is pinned against tests/clip_vision_ref.py, which
+ * the CPU suite pins against transformers itself. */
+typedef struct ldmseg_clip_vision ldmseg_clip_vision;  /* opaque */
+typedef struct {
+  int32_t hidden_size;        /* 1024; 64 * num_heads, at most 1280 (the widest row the LayerNorm statistics kernel serves in fp32) */
+  int32_t intermediate_size;  /* 4096; a multiple of 64 */
+  int32_t num_layers;         /* 24 */
+  int32_t num_heads;          /* 16; hidden_size / num_heads must be 64 */
+  int32_t image_size;         /* 224; a multiple of patch_size */
+  int32_t patch_size;         /* 14 */
+  int32_t projection_dim;     /* 768, or 0: no visual_projection (clip_image) */
+  int32_t compute_dtype;      /* LDMSEG_F32 | LDMSEG_BF16 | LDMSEG_BF16X3 */
+  int32_t device;
+} ldmseg_clip_vision_cfg;
+/* keys: CLIPVisionModel.state_dict() without the `vision_model.` prefix - embeddings.{class_embedding, patch_embedding.weight,
+ * position_embedding.weight}, pre_layrnorm.{weight,bias} (sic), encoder.layers.{i}.{layer_norm1, self_attn.{q,k,v,out}_proj,
+ * layer_norm2, mlp.fc1, mlp.fc2}.{weight,bias}, post_layernorm.{weight,bias} - plus visual_projection.weight when
+ * projection_dim > 0 (embeddings.position_ids is ignored).  LDMSEG_E_SHAPE for a configuration the kernels do not serve. */
+int ldmseg_clip_vision_create(const ldmseg_clip_vision_cfg* cfg, int n_weights, const char* const* names,
+                              const void* const* dev_ptrs, const int64_t* numels, ldmseg_clip_vision** out);
+void ldmseg_clip_vision_destroy(ldmseg_clip_vision* h);
+int64_t ldmseg_clip_vision_num_params(const ldmseg_clip_vision* h);
+/* CLIPVisionModel(pixel_values).last_hidden_state -> last_hidden [B, T, hidden] (T = (image/patch)^2 + 1) and
+ * CLIPVisionModelWithProjection(pixel_values).image_embeds -> image_embeds [B, projection_dim]; pixel_values [B,3,S,S] fp32,
+ * already resized and normalised.  Either output may be NULL; image_embeds on a handle without projection: LDMSEG_E_ARG. */
+int ldmseg_clip_vision_forward(ldmseg_clip_vision* h, const float* pixel_values, int B, float* last_hidden, float* image_embeds,
+                               void* stream);
+/* The same from raw images rgb [B,3,H,W] in [0,1], any H, W >= 1: norm_resize_images (trainers_ldm_cond.py:663-675) -
+ * F.interpolate(rgb, (S,S), mode='bilinear', align_corners=False) without antialias, then (x - mean) / std per channel - runs
+ * inside the kernel that writes the patch rows. */
+int ldmseg_clip_vision_describe(ldmseg_clip_vision* h, const float* rgb, int B, int H, int W, const float mean[3],
+                                const float std[3], float* last_hidden, float* image_embeds, void* stream);
 
 /* ---- scheduler: ldmseg/schedulers/ddim_scheduler.py --------------------------------------- */
 /* DDIMNoiseScheduler.step (:218-269), elementwise over n floats.  The four coefficients are

@@ -97,9 +97,22 @@ int ldmseg_op_conv_groupnorm(const float* x, const float* w, const float* bias, 
                              float* out, void* stream);
 /* F.linear(F.layer_norm(x, (K,), gamma, beta, eps), w, bias) - GEGLU on top when geglu=1 - the way the engine runs
  * norm1 -> to_q|k|v and norm3 -> ff.net.0.proj (diffusers BasicTransformerBlock): one statistics pass over x, then the GEMM on
- * the un-normalised x with gamma folded into the weights and rstd*(acc - mean*c1) + c2 in the epilogue. */
+ * the un-normalised x with gamma folded into the weights and rstd*(acc - mean*c1) + c2 in the epilogue.  Without GEGLU, an N
+ * that is no multiple of 160 is padded with zero weight rows to the next one (the folded instantiations have 160-column tiles;
+ * the CLIP vision executor pads its N = 3072 / 4096 the same way) in every dtype; GEGLU keeps its 128-column tile. */
 int ldmseg_op_ln_linear(const float* x, const float* gamma, const float* beta, const float* w, const float* bias, int M, int K,
                         int N, float eps, int geglu, int dtype, float* out, void* stream);
+/* silu(F.linear(F.layer_norm(x, (K,), gamma, beta, eps), w, bias)) launched the way the CLIP vision executor launches
+ * layer_norm2 -> mlp.fc1 (transformers CLIPMLP with quick_gelu, whose x * sigmoid(1.702 x) the executor obtains from this SiLU
+ * epilogue by scaling fc1 by 1.702 and fc2 by 1 / 1.702): the folded-LayerNorm GEMM with the SiLU flag of the store epilogue. */
+int ldmseg_op_ln_linear_silu(const float* x, const float* gamma, const float* beta, const float* w, const float* bias, int M,
+                             int K, int N, float eps, int dtype, float* out, void* stream);
+/* The front kernel of the CLIP vision executor: F.unfold(x, P, stride=P) rows, k = (channel, dy, dx), of
+ * x = (F.interpolate(img, (S,S), mode='bilinear', align_corners=False) - mean) / std (norm_resize_images, trainers_ldm_cond.py:
+ * 663-675; resample = 0: x = img, already S x S) -> out [B * (S/P)^2][Kpad] fp32, Kpad = 3 P P rounded up to a multiple of 64,
+ * zero beyond 3 P P.  mean / std: host arrays of 3. */
+int ldmseg_op_clip_patch_rows(const float* img, int B, int H, int W, int S, int P, const float* mean, const float* std,
+                              int resample, int dtype, float* out, void* stream);
 /* The tail of a transformer block on [M, C] token rows (diffusers BasicTransformerBlock.ff + Transformer2DModel.proj_out,
  * /root/reference/ldmseg/models/unet.py:401-425):  h2 = h + ff.net.2(GEGLU(ff.net.0.proj(LayerNorm(h))));  out = proj_out(h2) + x.
  * mode 0 = the unfused launches, 1 = row-local fused feed-forward (tfuse.hip) + proj_out GEMM, 3 = all in the fused kernel

@@ -1,5 +1,6 @@
 // Tiled online-softmax ("flash") self-attention for the UNet transformer blocks
-// (8 heads, head dims 40 / 80 / 160, N = H*W tokens) on gfx950 MFMA.
+// (8 heads, head dims 40 / 80 / 160, N = H*W tokens) and the CLIP vision encoder
+// (head dim 64, N = 257 tokens) on gfx950 MFMA.
 //
 // Input is the fused projection qkv [B, N, 3C] (q | k | v, channel = head*d + i,
 // SURVEY App. A); output [B, N, C].  Per workgroup: 4 waves x QF x 16 query rows;
@@ -435,6 +436,7 @@ int dispatch(const void* qkv, void* out, int B, int N, int C, int heads, hipStre
   const bool big = N >= 256 && g_attn_qf1 != 1 && g_attn_qf1 != 3;
   switch (d) {
     case 40: return big ? run<T, 40, 2>(qkv, out, B, N, C, heads, s) : run<T, 40, 1>(qkv, out, B, N, C, heads, s);
+    case 64: return big ? run<T, 64, 2>(qkv, out, B, N, C, heads, s) : run<T, 64, 1>(qkv, out, B, N, C, heads, s);   // CLIP ViT heads
     case 80: return big ? run<T, 80, 2>(qkv, out, B, N, C, heads, s) : run<T, 80, 1>(qkv, out, B, N, C, heads, s);
     case 160: return run<T, 160, 1>(qkv, out, B, N, C, heads, s);
     default: return -2;
@@ -447,6 +449,7 @@ int dispatch_x3(const void* qkv, void* out, int B, int N, int C, int heads, hipS
   const bool big = N >= 256;
   switch (d) {
     case 40: return big ? run<bf16_t, 40, 2, true>(qkv, out, B, N, C, heads, s) : run<bf16_t, 40, 1, true>(qkv, out, B, N, C, heads, s);
+    case 64: return big ? run<bf16_t, 64, 2, true>(qkv, out, B, N, C, heads, s) : run<bf16_t, 64, 1, true>(qkv, out, B, N, C, heads, s);
     case 80: return big ? run<bf16_t, 80, 2, true>(qkv, out, B, N, C, heads, s) : run<bf16_t, 80, 1, true>(qkv, out, B, N, C, heads, s);
     case 160: return run<bf16_t, 160, 1, true>(qkv, out, B, N, C, heads, s);
     default: return -2;

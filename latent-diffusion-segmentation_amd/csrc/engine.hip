@@ -1673,6 +1673,277 @@ int klenc_encode_impl(ldmseg_vae_image* v, const float* x, float mul, float add,
 
 }  // namespace
 
+// =================================================================== CLIP vision encoder
+// transformers CLIPVisionModel(/WithProjection) - the image descriptor of the clip_image / clip_image_proj modes
+// (ldmseg/models/descriptors.py:15-76).  Row-local kernels: clip_vision.hip; every GEMM and the attention: the UNet's kernels.
+struct ClipLayerW { ConvW qkv, out, fc1, fc2; };
+struct ldmseg_clip_vision {
+  ldmseg_clip_vision_cfg cfg{};
+  int dt = DT_BF16;
+  bool x3 = false;
+  DeviceArena arena;
+  Workspace ws;
+  void* ws_mem = nullptr;
+  size_t ws_cap = 0;
+  int64_t nparams = 0;
+  int T = 0, Kpad = 0;          // tokens per image; K of the patch GEMM (3 * patch^2 rounded up to whole 128-byte lines)
+  ConvW patch;
+  float* cls = nullptr;
+  float* pos = nullptr;
+  NormW pre, post;
+  std::vector<ClipLayerW> layers;
+  float* wproj = nullptr;       // visual_projection [projection_dim][hidden] fp32 (GEMV on the B pooled rows)
+  void* cf_sync = nullptr;
+  int plan_B = -1, plan_epoch = -1;
+  size_t plan_persist = 0, plan_scratch = 0;
+  ~ldmseg_clip_vision() {
+    arena.release();
+    if (ws_mem) (void)hipFree(ws_mem);
+    if (cf_sync) (void)hipFree(cf_sync);
+  }
+};
+
+namespace {
+
+constexpr float kQuickGelu = 1.702f;   // quick_gelu(x) = x * sigmoid(1.702 x) = silu(1.702 x) / 1.702
+
+// Build-time scratch of build_ln_linear, shared by all layers of a handle (every use is ordered on the builder's stream)
+struct LnFoldScratch {
+  float* gs = nullptr;    // [K] scale * gamma
+  float* bs = nullptr;    // [K] scale * beta
+  float* pb = nullptr;    // [Nmax] scale * bias, zero in the padding
+  float* wb = nullptr;    // [Nmax][K] beta-weighted rows, only to take their sums
+  int K = 0, Nmax = 0;
+  int reserve(Builder& b, int K_, int Nmax_) {
+    K = K_; Nmax = Nmax_;
+    HIP_TRY(hipMalloc((void**)&gs, (size_t)K * sizeof(float))); b.temps.push_back(gs);
+    HIP_TRY(hipMalloc((void**)&bs, (size_t)K * sizeof(float))); b.temps.push_back(bs);
+    HIP_TRY(hipMalloc((void**)&pb, (size_t)Nmax * sizeof(float))); b.temps.push_back(pb);
+    HIP_TRY(hipMalloc((void**)&wb, (size_t)Nmax * K * sizeof(float))); b.temps.push_back(wb);
+    return 0;
+  }
+};
+
+// out = scale * Linear_i(LayerNorm(x)) for the `prefixes.size()` Linear layers [Nper][K] stacked on N, as ONE folded-LayerNorm
+// launch (IgemmParams::rowstats): W' = scale * gamma (.) W, c1 = rowsum(W'), bias' = scale * (W beta + b).  N is padded with
+// zero rows to the 160-column tile the folded instantiations have.  The LayerNorm's gamma / beta (keys ln_prefix.{weight,bias})
+// are read where the caller's tensors lie: they are needed at build time only.
+int build_ln_linear(Builder& b, LnFoldScratch& sc, const std::string& ln_prefix, const std::vector<std::string>& prefixes, int Nper,
+                    int K, float scale, ConvW* out) {
+  const int dt = b.dt;
+  const int parts = (int)prefixes.size(), Nreal = parts * Nper;
+  const int Npad = (int)rup(Nreal, 160);
+  if (K != sc.K || Npad > sc.Nmax) return fail(LDMSEG_E_SHAPE, "build_ln_linear: scratch too small");
+  out->N = Npad; out->n_valid = Nreal; out->cin_pad = K; out->taps = 1; out->cout = Nreal;
+  const float *gamma, *beta;
+  TRY(b.wm->get(ln_prefix + ".weight", K, &gamma));
+  TRY(b.wm->get(ln_prefix + ".bias", K, &beta));
+  b.nparams += 2 * (int64_t)K;
+  TRY(launch_axpby(gamma, scale, 0.f, sc.gs, K, b.s));
+  TRY(launch_axpby(beta, scale, 0.f, sc.bs, K, b.s));
+  HIP_TRY(hipMemsetAsync(sc.pb, 0, (size_t)Npad * sizeof(float), b.s));
+  TRY(b.arena->alloc(&out->w, (size_t)Npad * K * esize(dt)));
+  b.weights(out->w, (size_t)Npad * K);
+  std::vector<int> map(Npad - (parts - 1) * Nper, -1);
+  for (int r = 0; r < Nper; ++r) map[r] = r;
+  int* dmap;
+  TRY(b.upload_ints(map, &dmap));
+  for (int i = 0; i < parts; ++i) {
+    const float *w, *bias;
+    TRY(b.wm->get(prefixes[i] + ".weight", (int64_t)Nper * K, &w));
+    TRY(b.wm->get(prefixes[i] + ".bias", Nper, &bias));
+    const int rows = i + 1 < parts ? Nper : (int)map.size();
+    TRY(launch_repack_rows_scaled(w, (char*)out->w + (size_t)i * Nper * K * esize(dt), dmap, rows, K, sc.gs, dt, b.s));
+    TRY(launch_repack_rows_scaled(w, (char*)sc.wb + (size_t)i * Nper * K * sizeof(float), dmap, rows, K, sc.bs, DT_F32, b.s));
+    TRY(launch_axpby(bias, scale, 0.f, sc.pb + (size_t)i * Nper, Nper, b.s));
+    b.nparams += (int64_t)Nper * K + Nper;
+  }
+  void *pc1, *pc2;
+  TRY(b.arena->alloc(&pc1, (size_t)Npad * sizeof(float)));
+  TRY(b.arena->alloc(&pc2, (size_t)Npad * sizeof(float)));
+  TRY(launch_rowsum(out->w, nullptr, (float*)pc1, Npad, K, dt, b.s));
+  TRY(launch_rowsum(sc.wb, sc.pb, (float*)pc2, Npad, K, DT_F32, b.s));
+  out->c1 = (float*)pc1;
+  out->bias = (float*)pc2;
+  return 0;
+}
+
+// Linear [N][K] with every weight scaled by `scale` (the bias is not)
+int build_scaled_linear(Builder& b, const std::string& prefix, int N, int K, float scale, ConvW* out) {
+  const int dt = b.dt;
+  const float* w;
+  TRY(b.wm->get(prefix + ".weight", (int64_t)N * K, &w));
+  const int Npad = (int)rup(N, igemm_pick_bn(N, EPI_STORE));
+  out->N = Npad; out->n_valid = N; out->cin_pad = K; out->taps = 1; out->cout = N;
+  float* cs;
+  HIP_TRY(hipMalloc((void**)&cs, (size_t)K * sizeof(float))); b.temps.push_back(cs);
+  {
+    const std::vector<float> hv(K, scale);
+    HIP_TRY(hipMemcpy(cs, hv.data(), (size_t)K * sizeof(float), hipMemcpyHostToDevice));
+  }
+  std::vector<int> map(Npad, -1);
+  for (int r = 0; r < N; ++r) map[r] = r;
+  int* dmap;
+  TRY(b.upload_ints(map, &dmap));
+  TRY(b.arena->alloc(&out->w, (size_t)Npad * K * esize(dt)));
+  TRY(launch_repack_rows_scaled(w, out->w, dmap, Npad, K, cs, dt, b.s));
+  b.weights(out->w, (size_t)Npad * K);
+  b.nparams += (int64_t)N * K;
+  TRY(b.f32_copy(prefix + ".bias", N, &out->bias, Npad));
+  return 0;
+}
+
+int clip_build(ldmseg_clip_vision* v, const WeightMap& wm) {
+  hipStream_t s = nullptr;
+  Builder b{&v->arena, &wm, v->dt, s};
+  b.x3 = v->x3;
+  const ldmseg_clip_vision_cfg& c = v->cfg;
+  const int C = c.hidden_size, I = c.intermediate_size, P = c.patch_size;
+  // patch_embedding [C][3][P][P] is a Linear over k = (channel, dy, dx): [C][3 P P] padded to [C][Kpad]
+  TRY(b.conv("embeddings.patch_embedding", C, 3 * P * P, 1, v->Kpad, &v->patch, false));
+  TRY(b.f32_copy("embeddings.class_embedding", C, &v->cls));
+  TRY(b.f32_copy("embeddings.position_embedding.weight", (int64_t)v->T * C, &v->pos));
+  TRY(b.norm("pre_layrnorm", C, &v->pre));
+  v->layers.resize(c.num_layers);
+  LnFoldScratch sc;
+  TRY(sc.reserve(b, C, (int)rup((size_t)(3 * C > I ? 3 * C : I), 160)));
+  for (int i = 0; i < c.num_layers; ++i) {
+    const std::string p = "encoder.layers." + std::to_string(i) + ".";
+    ClipLayerW& l = v->layers[i];
+    TRY(build_ln_linear(b, sc, p + "layer_norm1", {p + "self_attn.q_proj", p + "self_attn.k_proj", p + "self_attn.v_proj"}, C, C, 1.f, &l.qkv));
+    TRY(b.conv(p + "self_attn.out_proj", C, C, 1, C, &l.out));
+    // quick_gelu on the SiLU epilogue: fc1 scaled by 1.702, fc2's weights by 1 / 1.702
+    TRY(build_ln_linear(b, sc, p + "layer_norm2", {p + "mlp.fc1"}, I, C, kQuickGelu, &l.fc1));
+    TRY(build_scaled_linear(b, p + "mlp.fc2", C, I, 1.f / kQuickGelu, &l.fc2));
+  }
+  TRY(b.norm("post_layernorm", C, &v->post));
+  if (c.projection_dim > 0) TRY(b.f32_copy("visual_projection.weight", (int64_t)c.projection_dim * C, &v->wproj));
+  TRY(b.finish());
+  v->nparams = b.nparams;
+  return 0;
+}
+
+int clip_forward_impl(ldmseg_clip_vision* v, const float* img, int B, int H, int W, const float* mean, const float* std,
+                      int resample, float* last_hidden, float* image_embeds, hipStream_t s, bool dry, size_t scratch_base) {
+  Workspace* ws = &v->ws;
+  ws->begin(dry, scratch_base);
+  Exec ex{ws, v->dt, B, s};
+  ex.cf_sync = v->cf_sync;
+  ex.x3 = v->x3 ? 2 : 0;
+  const ldmseg_clip_vision_cfg& c = v->cfg;
+  const int dt = v->dt, C = c.hidden_size, I = c.intermediate_size, T = v->T, NP = T - 1, M = B * T;
+  const size_t es = esize(dt);
+  Act h;
+  h.C = C; h.H = T; h.W = 1;
+  h.p = ws->persist((size_t)M * C * es);
+  {
+    const size_t m = ws->mark();
+    void* rows = ws->scratch((size_t)B * NP * v->Kpad * es);
+    void* pe = ws->scratch((size_t)B * NP * C * es);
+    {
+      ProfScope ps(4, s, 0, 0, dry);
+      if (!dry) {
+        TRY(ex.ws_ok());
+        TRY(launch_clip_patch_rows(img, rows, B, H, W, c.image_size, c.patch_size, v->Kpad, mean, std, resample, dt, s));
+      }
+    }
+    IgemmParams p;
+    p.src0 = rows; p.C0 = v->Kpad; p.B = B; p.Hi = p.Ho = NP; p.Wi = p.Wo = 1;
+    p.M = B * NP; p.N = v->patch.N; p.n_valid = C; p.W = v->patch.w; p.bias = v->patch.bias;
+    p.out = pe; p.ldo = C;
+    TRY(ex.igemm(p));
+    {
+      ProfScope ps(3, s, 0, 2.0 * M * C * es, dry);
+      if (!dry) TRY(launch_clip_tokens(pe, v->cls, v->pos, v->pre.g, v->pre.b, h.p, B, T, C, 1e-5f, dt, s));
+    }
+    ws->reset(m);
+  }
+  for (const ClipLayerW& l : v->layers) {
+    const size_t m = ws->mark();
+    float* stats = (float*)ws->scratch((size_t)M * 2 * sizeof(float));
+    void* qkv = ws->scratch((size_t)M * 3 * C * es);
+    void* att = ws->scratch((size_t)M * C * es);
+    TRY(ex.rowstats(h, 1e-5f, stats));
+    {
+      IgemmParams p;                                   // layer_norm1 -> q | k | v
+      p.src0 = h.p; p.C0 = C; p.B = B; p.Hi = p.Ho = T; p.Wi = p.Wo = 1;
+      p.M = M; p.N = l.qkv.N; p.n_valid = 3 * C; p.W = l.qkv.w; p.bias = l.qkv.bias;
+      p.rowstats = stats; p.c1 = l.qkv.c1;
+      p.out = qkv; p.ldo = 3 * C;
+      TRY(ex.igemm(p));
+    }
+    {
+      ProfScope ps(1, s, 4.0 * B * (double)T * T * C, 4.0 * M * C * es, dry, "clip N=" + std::to_string(T) + " C=" + std::to_string(C));
+      if (!dry) {
+        TRY(ex.ws_ok());
+        const int r = launch_attention(qkv, att, B, T, C, c.num_heads, ex.x3 ? 2 : dt, s);
+        if (r) return fail(r == -2 ? LDMSEG_E_SHAPE : LDMSEG_E_HIP, "launch_attention failed (head dim 64)");
+      }
+    }
+    {
+      IgemmParams p;                                   // h += out_proj(att)
+      p.src0 = att; p.C0 = C; p.B = B; p.Hi = p.Ho = T; p.Wi = p.Wo = 1;
+      p.M = M; p.N = l.out.N; p.n_valid = C; p.W = l.out.w; p.bias = l.out.bias;
+      p.resid = h.p; p.ldr = C; p.out = h.p; p.ldo = C;
+      TRY(ex.igemm(p));
+    }
+    ws->reset(m);
+    stats = (float*)ws->scratch((size_t)M * 2 * sizeof(float));
+    void* ff = ws->scratch((size_t)M * I * es);
+    TRY(ex.rowstats(h, 1e-5f, stats));
+    {
+      IgemmParams p;                                   // silu(1.702 fc1(layer_norm2(h)))
+      p.src0 = h.p; p.C0 = C; p.B = B; p.Hi = p.Ho = T; p.Wi = p.Wo = 1;
+      p.M = M; p.N = l.fc1.N; p.n_valid = I; p.W = l.fc1.w; p.bias = l.fc1.bias;
+      p.rowstats = stats; p.c1 = l.fc1.c1; p.silu = 1;
+      p.out = ff; p.ldo = I;
+      TRY(ex.igemm(p));
+    }
+    {
+      IgemmParams p;                                   // h += fc2(.) / 1.702
+      p.src0 = ff; p.C0 = I; p.B = B; p.Hi = p.Ho = T; p.Wi = p.Wo = 1;
+      p.M = M; p.N = l.fc2.N; p.n_valid = C; p.W = l.fc2.w; p.bias = l.fc2.bias;
+      p.resid = h.p; p.ldr = C; p.out = h.p; p.ldo = C;
+      TRY(ex.igemm(p));
+    }
+    ws->reset(m);
+  }
+  if (last_hidden) {
+    ProfScope ps(4, s, 0, 0, dry);
+    if (!dry) TRY(launch_clip_rows_to_f32(h.p, last_hidden, (size_t)M * C, dt, s));
+  }
+  if (image_embeds) {
+    float* pooled = (float*)ws->scratch((size_t)B * C * sizeof(float));
+    ProfScope ps(4, s, 0, 0, dry);
+    if (!dry) {
+      TRY(ex.ws_ok());
+      TRY(launch_clip_pooled_ln(h.p, v->post.g, v->post.b, pooled, B, T, C, 1e-5f, dt, s));
+      TRY(launch_small_linear(pooled, v->wproj, nullptr, image_embeds, B, C, c.projection_dim, 0, 0, s));
+    }
+  }
+  return 0;
+}
+
+int clip_forward_checked(ldmseg_clip_vision* v, const float* img, int B, int H, int W, const float* mean, const float* std,
+                         int resample, float* last_hidden, float* image_embeds, hipStream_t s) {
+  if (!v || !img) return fail(LDMSEG_E_ARG, "null argument");
+  if (B < 1 || H < 1 || W < 1 || (long)B * v->T > (1 << 22)) return fail(LDMSEG_E_SHAPE, "B, H, W must be >= 1 (and B * tokens <= 2^22)");
+  if (image_embeds && !v->wproj) return fail(LDMSEG_E_ARG, "image_embeds requested from a handle without visual_projection");
+  // the plan covers both outputs, so that it does not depend on which the caller asked for
+  float* const any = (float*)(uintptr_t)0x1000;
+  if (v->plan_B != B || v->plan_epoch != g_plan_epoch) {
+    TRY(clip_forward_impl(v, img, B, H, W, mean, std, resample, any, v->wproj ? any : nullptr, s, true, 0));
+    v->plan_persist = rup(v->ws.persist_peak, 4096);
+    v->plan_scratch = rup(v->ws.scratch_peak, 4096);
+    v->plan_B = B;
+    v->plan_epoch = g_plan_epoch;
+  }
+  TRY(ensure_ws(&v->ws_mem, &v->ws_cap, &v->ws, v->plan_persist + v->plan_scratch));
+  return clip_forward_impl(v, img, B, H, W, mean, std, resample, last_hidden, image_embeds, s, false, v->plan_persist);
+}
+
+}  // namespace
+
 // =================================================================== C ABI
 extern "C" {
 
@@ -1886,6 +2157,80 @@ int ldmseg_vae_image_encode(ldmseg_vae_image* h, const float* x, float in_mul, f
   const size_t persist = rup(h->ws.persist_peak, 4096), scratch = rup(h->ws.scratch_peak, 4096);
   TRY(ensure_ws(&h->ws_mem, &h->ws_cap, &h->ws, persist + scratch));
   return klenc_encode_impl(h, x, in_mul, in_add, B, H, W, moments, (hipStream_t)stream, false, persist);
+}
+
+int ldmseg_clip_vision_create(const ldmseg_clip_vision_cfg* cfg, int n_weights, const char* const* names,
+                              const void* const* dev_ptrs, const int64_t* numels, ldmseg_clip_vision** out) {
+  g_err.clear();
+  if (!cfg || !out) return fail(LDMSEG_E_ARG, "null argument");
+  if (cfg->compute_dtype != LDMSEG_F32 && cfg->compute_dtype != LDMSEG_BF16 && cfg->compute_dtype != LDMSEG_BF16X3) return fail(LDMSEG_E_ARG, "bad compute_dtype");
+  if (cfg->num_layers < 1 || cfg->projection_dim < 0) return fail(LDMSEG_E_ARG, "num_layers must be >= 1, projection_dim >= 0");
+  if (cfg->num_heads < 1 || cfg->hidden_size != 64 * cfg->num_heads) return fail(LDMSEG_E_SHAPE, "hidden_size / num_heads must be 64 (the head dim the attention kernel is built for here)");
+  // (hidden_size is a multiple of 64 by the line above.  1280: the widest row launch_rowstats serves in fp32, and the widest K the
+  // folded-LayerNorm GEMMs run at in the UNet - one bound for all modes)
+  if (cfg->hidden_size > 1280) return fail(LDMSEG_E_SHAPE, "hidden_size must be at most 1280");
+  if (cfg->intermediate_size < 64 || cfg->intermediate_size % 64 != 0) return fail(LDMSEG_E_SHAPE, "intermediate_size must be a multiple of 64");
+  if (cfg->patch_size < 1 || cfg->image_size < cfg->patch_size || cfg->image_size % cfg->patch_size != 0) return fail(LDMSEG_E_SHAPE, "image_size must be a multiple of patch_size");
+  DeviceGuard dg(cfg->device);
+  TRY(check_arch(cfg->device));
+  WeightMap wm;
+  TRY(make_weight_map(n_weights, names, dev_ptrs, numels, &wm));
+  ldmseg_clip_vision* v = nullptr;
+  try {
+    v = new ldmseg_clip_vision();
+  } catch (...) {
+    return fail(LDMSEG_E_OOM, "host allocation failed");
+  }
+  v->cfg = *cfg;
+  v->dt = cfg->compute_dtype == LDMSEG_BF16 ? DT_BF16 : DT_F32;
+  v->x3 = cfg->compute_dtype == LDMSEG_BF16X3;
+  const int g = cfg->image_size / cfg->patch_size;
+  v->T = g * g + 1;
+  v->Kpad = (int)rup((size_t)3 * cfg->patch_size * cfg->patch_size, 64);
+  int r = 0;
+  try {
+    r = clip_build(v, wm);
+  } catch (...) {
+    r = fail(LDMSEG_E_OOM, "host allocation failed while building the CLIP vision handle");
+  }
+  if (r == 0) r = igemm_warm();
+  if (r == 0) r = alloc_cf_sync(&v->cf_sync);
+  if (r != 0) { delete v; return r; }
+  *out = v;
+  return 0;
+}
+void ldmseg_clip_vision_destroy(ldmseg_clip_vision* h) {
+  if (!h) return;
+  DeviceGuard dg(h->cfg.device);
+  delete h;
+}
+int64_t ldmseg_clip_vision_num_params(const ldmseg_clip_vision* h) { return h ? h->nparams : 0; }
+
+int ldmseg_clip_vision_forward(ldmseg_clip_vision* h, const float* pixel_values, int B, float* last_hidden, float* image_embeds,
+                               void* stream) {
+  g_err.clear();
+  if (!h) return fail(LDMSEG_E_ARG, "null handle");
+  DeviceGuard dg(h->cfg.device);
+  try {
+    return clip_forward_checked(h, pixel_values, B, h->cfg.image_size, h->cfg.image_size, nullptr, nullptr, 0, last_hidden,
+                                image_embeds, (hipStream_t)stream);
+  } catch (...) {
+    return fail(LDMSEG_E_OOM, "host allocation failed");
+  }
+}
+
+int ldmseg_clip_vision_describe(ldmseg_clip_vision* h, const float* rgb, int B, int H, int W, const float mean[3],
+                                const float std[3], float* last_hidden, float* image_embeds, void* stream) {
+  g_err.clear();
+  if (!h || !mean || !std) return fail(LDMSEG_E_ARG, "null argument");
+  for (int c = 0; c < 3; ++c)
+    if (!(std[c] > 0.f)) return fail(LDMSEG_E_ARG, "std must be positive");
+  DeviceGuard dg(h->cfg.device);
+  try {
+    return clip_forward_checked(h, rgb, B, H, W, mean, std, 1, last_hidden, image_embeds, (hipStream_t)stream);
+  } catch (...) {
+    return fail(LDMSEG_E_OOM, "host allocation failed");
+  }
 }
 
 int ldmseg_vae_posterior(const float* moments, const float* noise, float out_scale, int B, int l, float* out,

@@ -283,6 +283,20 @@ int launch_repack_rows_scaled(const float* w, void* out, const int* src_row_dev,
 // out[n] = sum_k W[n][k] (+ add[n]) over a packed [N][K] matrix in `dtype`, fp32 accumulation
 int launch_rowsum(const void* W, const float* add, float* out, int N, int K, int dtype, hipStream_t s);
 
+// CLIP ViT image encoder, row-local kernels (clip_vision.hip)
+// image [B,3,H,W] fp32 -> patch-conv GEMM operand [B * (S/P)^2][Kpad], k = (channel, dy, dx), zero padded from 3 P P to Kpad.
+// resample = 1: bilinear resize to S x S (align_corners=False, no antialias) and (x - mean[c]) / std[c] first (mean / std: host
+// arrays); resample = 0: the image is S x S pixel_values already
+int launch_clip_patch_rows(const float* img, void* rows, int B, int H, int W, int S, int P, int Kpad, const float* mean,
+                           const float* std, int resample, int dtype, hipStream_t s);
+// h[b][t] = LayerNorm((t == 0 ? cls : patch[b][t - 1]) + pos[t]); patch [B][T - 1][C] and h [B][T][C] in the compute dtype
+int launch_clip_tokens(const void* patch, const float* cls, const float* pos, const float* gamma, const float* beta, void* h,
+                       int B, int T, int C, float eps, int dtype, hipStream_t s);
+// out[b] = LayerNorm(h[b][0]) -> fp32 [B][C]
+int launch_clip_pooled_ln(const void* h, const float* gamma, const float* beta, float* out, int B, int T, int C, float eps,
+                          int dtype, hipStream_t s);
+int launch_clip_rows_to_f32(const void* x, float* y, size_t n, int dtype, hipStream_t s);
+
 // fp8 (e4m3) operand path of the bf16 attention for the long-context levels (attention_fp8.hip): head dims 40 / 80 only
 size_t attention_fp8_scratch_bytes(int B, int N, int C, int heads);
 int launch_attention_fp8(const void* qkv, void* kv8_scratch, void* out, int B, int N, int C, int heads, hipStream_t s);

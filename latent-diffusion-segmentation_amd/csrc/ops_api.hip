@@ -638,8 +638,14 @@ int ldmseg_bench_attention(const float* qkv, int B, int N, int C, int heads, int
 // F.linear(F.layer_norm(x, (K,), gamma, beta, eps), w, bias) - or the GEGLU feed-forward half on the normalised input when
 // geglu = 1 - computed the way the engine computes norm1 -> q|k|v and norm3 -> ff.net.0: statistics pass + GEMM on the raw x
 // with the LayerNorm folded into weights and epilogue (IgemmParams::rowstats).  x [M,K], w [N,K], out [M, N or N/2], f32.
-int ldmseg_op_ln_linear(const float* x, const float* gamma, const float* beta, const float* w, const float* bias, int M, int K,
-                        int N, float eps, int geglu, int dtype, float* out, void* stream) {
+}  // extern "C"
+namespace {
+// silu: the SiLU flag of the store epilogue on top (the CLIP vision executor's layer_norm2 -> fc1).  A non-GEGLU N that is no
+// multiple of 160 is padded with zero rows to the 160-column tile of the folded instantiations, in every mode - what the CLIP
+// vision executor does for its N = 3 C and 4 C (before, such an N returned -2 except in the split-bf16 modes, where an
+// N % 128 == 0 took the 128-column plain-loop form).
+int op_ln_linear_impl(const float* x, const float* gamma, const float* beta, const float* w, const float* bias, int M, int K,
+                      int N, float eps, int geglu, int silu, int dtype, float* out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   Temp t;
   const int x3 = dtype == 2 ? 1 : (dtype == 3 ? 2 : 0);   // LDMSEG_BF16X3 (3: weights pre-split into planes)
@@ -648,7 +654,7 @@ int ldmseg_op_ln_linear(const float* x, const float* gamma, const float* beta, c
   void* xp = t.get((size_t)M * K * es(dtype));
   to_dev_dtype(x, xp, (size_t)M * K, dtype, s);
   const int epi = geglu ? EPI_GEGLU : EPI_STORE;
-  const int bn = igemm_pick_bn(N, epi);
+  const int bn = (!geglu && N % 160 != 0) ? 160 : igemm_pick_bn(N, epi);     // (the folded instantiations: 160 columns, GEGLU 128)
   const int Np = rupi(N, bn);
   const int nout = geglu ? N / 2 : N;
   std::vector<int> map(Np);
@@ -675,7 +681,7 @@ int ldmseg_op_ln_linear(const float* x, const float* gamma, const float* beta, c
   IgemmParams p;
   p.src0 = xp; p.C0 = K; p.B = 1; p.Hi = p.Ho = M; p.Wi = p.Wo = 1;
   p.M = M; p.N = Np; p.n_valid = nout; p.W = wp; p.bias = c2; p.rowstats = stats; p.c1 = c1;
-  p.out = op; p.ldo = nout; p.epi = epi;
+  p.out = op; p.ldo = nout; p.epi = epi; p.silu = silu;
   p.x3 = x3;
   if (x3 == 2 && launch_split_planes(wp, (size_t)Np * K, s)) return -3;      // (c1 / c2 above were taken from the fp32 matrix)
   const int sp = igemm_plan_splits(p, dtype);
@@ -683,6 +689,32 @@ int ldmseg_op_ln_linear(const float* x, const float* gamma, const float* beta, c
   const int r = launch_igemm(p, dtype, s);
   if (r) return r;
   from_dev_dtype(op, out, (size_t)M * nout, dtype, s);
+  return 0;
+}
+}  // namespace
+extern "C" {
+int ldmseg_op_ln_linear(const float* x, const float* gamma, const float* beta, const float* w, const float* bias, int M, int K,
+                        int N, float eps, int geglu, int dtype, float* out, void* stream) {
+  return op_ln_linear_impl(x, gamma, beta, w, bias, M, K, N, eps, geglu, 0, dtype, out, stream);
+}
+// silu(F.linear(F.layer_norm(x), w, bias)): layer_norm2 -> mlp.fc1 of the CLIP vision executor (the 1.702 of quick_gelu is the
+// caller's: it passes 1.702 w, 1.702 bias)
+int ldmseg_op_ln_linear_silu(const float* x, const float* gamma, const float* beta, const float* w, const float* bias, int M,
+                             int K, int N, float eps, int dtype, float* out, void* stream) {
+  return op_ln_linear_impl(x, gamma, beta, w, bias, M, K, N, eps, 0, 1, dtype, out, stream);
+}
+// the front kernel of the CLIP vision executor (clip_vision.hip): out [B * (S/P)^2][Kpad] fp32, Kpad = 3 P P rounded up to 64
+int ldmseg_op_clip_patch_rows(const float* img, int B, int H, int W, int S, int P, const float* mean, const float* std,
+                              int resample, int dtype, float* out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (B < 1 || P < 1 || S < P || S % P) return -2;
+  Temp t;
+  const int Kpad = rupi(3 * P * P, 64), G = S / P;
+  const size_t n = (size_t)B * G * G * Kpad;
+  void* rows = t.get(n * es(dtype));
+  const int r = launch_clip_patch_rows(img, rows, B, H, W, S, P, Kpad, mean, std, resample, dtype, s);
+  if (r) return r;
+  from_dev_dtype(rows, out, n, dtype, s);
   return 0;
 }
 

@@ -31,6 +31,12 @@ class VAEImageCfg(C.Structure):
     _fields_ = [("compute_dtype", C.c_int32), ("device", C.c_int32)]
 
 
+class ClipVisionCfg(C.Structure):
+    _fields_ = [("hidden_size", C.c_int32), ("intermediate_size", C.c_int32), ("num_layers", C.c_int32),
+                ("num_heads", C.c_int32), ("image_size", C.c_int32), ("patch_size", C.c_int32),
+                ("projection_dim", C.c_int32), ("compute_dtype", C.c_int32), ("device", C.c_int32)]
+
+
 class SampleCfg(C.Structure):
     _fields_ = [("n_steps", C.c_int32), ("timesteps", C.POINTER(C.c_int64)), ("coef", C.POINTER(C.c_float)),
                 ("prediction_type", C.c_int32), ("clip_sample", C.c_int32), ("self_condition", C.c_int32),
@@ -71,6 +77,11 @@ SIGNATURES = {
     "ldmseg_vae_image_destroy": (None, [_vp]),
     "ldmseg_vae_image_num_params": (_i64, [_vp]),
     "ldmseg_vae_image_encode": (_i, [_vp, _vp, _f, _f, _i, _i, _i, _vp, _vp]),
+    "ldmseg_clip_vision_create": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "ldmseg_clip_vision_destroy": (None, [_vp]),
+    "ldmseg_clip_vision_num_params": (_i64, [_vp]),
+    "ldmseg_clip_vision_forward": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "ldmseg_clip_vision_describe": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _vp]),
     "ldmseg_vae_decode_panoptic": (_i, [_vp, _vp, _f, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _f, _i, _d, _i64, _vp, _vp, _vp, _vp, _vp,
                                         _vp]),
     "ldmseg_panoptic_postprocess": (_i, [_vp, _i, _i, _i, _i, _i, _i, _f, _i, _d, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -98,6 +109,8 @@ SIGNATURES = {
     "ldmseg_op_igemm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ldmseg_op_conv3x3_plus_1x1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, C.POINTER(C.c_float), _vp]),
     "ldmseg_op_ln_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp]),
+    "ldmseg_op_ln_linear_silu": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp]),
+    "ldmseg_op_clip_patch_rows": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _i, _vp, _vp]),
     "ldmseg_op_conv_out_tail": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, C.POINTER(C.c_float), _i, _i, _f, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _f, _f, _vp, _vp]),
     "ldmseg_op_transformer_ff": (_i, [_vp] * 10 + [_i, _i, _f, _i, _i, _vp, _i, C.POINTER(C.c_float), _vp]),

@@ -1,2 +1,3 @@
 from .unet import UNet  # noqa: F401
 from .vae import GeneralVAESeg, GeneralVAEImage, DiagonalGaussianDistribution  # noqa: F401
+from .clip_vision import CLIPVisionDescriptor  # noqa: F401

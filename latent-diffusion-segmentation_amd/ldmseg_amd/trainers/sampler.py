@@ -39,9 +39,10 @@ class TrainerDiffusion(object):
         self.latent_size = latent_size
         self.unet_dtype = torch.float32
         self.weight_dtype = torch.float32
-        # Conditioning models of the cross-attention UNets (:55-127, descriptors.py:66-102): caller-supplied torch modules run
-        # once per batch - an image descriptor model (clip_image / clip_image_proj: returns {'last_feat': [B, D, ...]}) or a
-        # text encoder with its tokenizer (image_descriptors none).  None of them: the UNet runs without a context.
+        # Conditioning models of the cross-attention UNets (:55-127, descriptors.py:66-102), run once per batch: an image
+        # descriptor model (clip_image / clip_image_proj: models.CLIPVisionDescriptor on the library, or any caller-supplied
+        # torch module that returns {'last_feat': [B, D, ...]}) or a caller-supplied text encoder with its tokenizer
+        # (image_descriptors none).  None of them: the UNet runs without a context.
         if textencoder is not None and image_descriptor_model is not None:
             raise ValueError("pass either a text encoder or an image descriptor model, not both (:126-127)")
         if textencoder is not None and tokenizer is None:
@@ -157,9 +158,14 @@ class TrainerDiffusion(object):
         if self.image_descriptor_model is not None:
             if rgb_images is None:
                 raise ValueError("an image descriptor model needs rgb_images")
-            x = self.norm_resize_images(rgb_images.to(self.device))
-            d = self.image_descriptor_model(x.to(self.weight_dtype))['last_feat']
-            d = d.view(d.shape[0], d.shape[1], -1).permute(0, 2, 1)
+            if hasattr(self.image_descriptor_model, "describe"):
+                # the library's own encoder (models/clip_vision.py): resize + normalise run in its front kernel and the
+                # context comes back as [B, S, D]
+                d = self.image_descriptor_model.describe(rgb_images.to(self.device))
+            else:
+                x = self.norm_resize_images(rgb_images.to(self.device))
+                d = self.image_descriptor_model(x.to(self.weight_dtype))['last_feat']
+                d = d.view(d.shape[0], d.shape[1], -1).permute(0, 2, 1)
             ehs = torch.cat([d] * 2).to(torch.float)
             multiplier = 2
         if self.textencoder is not None:

@@ -202,6 +202,51 @@ def vae_image_schema(old_attention_names=True):
 VAE_IMAGE_NORM_KEYS = ("encoder.mid_block.attentions.0.group_norm.weight", "encoder.mid_block.attentions.0.group_norm.bias")
 
 
+def clip_vision_schema(hidden=1024, intermediate=4096, layers=24, heads=16, image=224, patch=14, projection_dim=0):
+    """Ordered key -> shape of transformers' CLIPVisionModel.state_dict() without the ``vision_model.`` prefix (the image
+    descriptor of image_descriptors clip_image, ldmseg/models/descriptors.py:15-56), plus
+    ``visual_projection.weight`` of CLIPVisionModelWithProjection when projection_dim > 0 (clip_image_proj).  The defaults
+    are openai/clip-vit-large-patch14: 303,179,776 parameters, 303,966,208 with projection_dim=768.  ``heads`` does not
+    shape any tensor; it is listed because the configuration needs it."""
+    if hidden % heads or image % patch:
+        raise ValueError("hidden must be a multiple of heads and image a multiple of patch")
+    sd = OrderedDict()
+    sd["embeddings.class_embedding"] = (hidden,)
+    sd["embeddings.patch_embedding.weight"] = (hidden, 3, patch, patch)
+    sd["embeddings.position_embedding.weight"] = ((image // patch) ** 2 + 1, hidden)
+
+    def norm(name):
+        sd[name + ".weight"] = (hidden,)
+        sd[name + ".bias"] = (hidden,)
+
+    def linear(name, co, ci):
+        sd[name + ".weight"] = (co, ci)
+        sd[name + ".bias"] = (co,)
+
+    norm("pre_layrnorm")                                   # (sic: the key of the transformers module)
+    for i in range(layers):
+        p = f"encoder.layers.{i}."
+        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            linear(p + "self_attn." + n, hidden, hidden)
+        norm(p + "layer_norm1")
+        linear(p + "mlp.fc1", intermediate, hidden)
+        linear(p + "mlp.fc2", hidden, intermediate)
+        norm(p + "layer_norm2")
+    norm("post_layernorm")
+    if projection_dim:
+        sd["visual_projection.weight"] = (projection_dim, hidden)
+    return sd
+
+
+def clip_vision_norm_keys(schema):
+    """The LayerNorm tensors of a clip_vision_schema (``norm_keys`` of generate(): their names do not start with 'norm')."""
+    return tuple(k for k in schema if k.split(".")[-2] in ("layer_norm1", "layer_norm2", "pre_layrnorm", "post_layernorm"))
+
+
+CLIP_EMBED_KEYS = ("embeddings.class_embedding", "embeddings.position_embedding.weight")
+CLIP_EMBED_STD = 0.02       # CLIP initialises the class token and the position table at this scale
+
+
 def count_params(schema):
     n = 0
     for shp in schema.values():
@@ -225,7 +270,9 @@ def generate(schema, seed=0, device="cpu", dtype=torch.float32, norm_keys=()):
         g = torch.Generator(device="cpu").manual_seed((zlib.crc32(key.encode()) ^ seed) & 0x7FFFFFFF)
         is_norm = _is_norm(key) or key in norm_keys
         u = torch.rand(shp, generator=g, dtype=torch.float32) * 2 - 1
-        if len(shp) == 1:
+        if key in CLIP_EMBED_KEYS:
+            t = CLIP_EMBED_STD * (3.0 ** 0.5) * u             # uniform with standard deviation 0.02
+        elif len(shp) == 1:
             if is_norm and key.endswith("weight"):
                 t = 1.0 + 0.1 * u
             elif is_norm:

@@ -5,6 +5,7 @@ detectron2 and cannot run here).
 
     python tools/main_ldm_eval.py --images DIR [--panoptic DIR] [--ldm ldmseg.pt --ae ae.pt --vae-image vae.pt]
                                   [--size 512] [--steps 50] [--batch 8] [--dtype bf16]
+                                  [--image-descriptors {remove,clip_image,clip_image_proj}] [--clip-vision clip.pt]
 
 It assembles what main_worker assembles (image VAE encoder, seg-VAE, UNet with the 12-channel conv_in and cross-attention
 removed, DDIM scheduler with base.yaml's noise_scheduler_kwargs), then runs `TrainerDiffusion.compute_pq`:
@@ -47,11 +48,32 @@ def build_trainer(args, device):
         isd = torch.load(args.vae_image, map_location="cpu", weights_only=True)
     else:
         isd = weights.generate(weights.vae_image_schema(), seed=11, norm_keys=weights.VAE_IMAGE_NORM_KEYS)
-    unet = UNet(usd, in_channels=int(usd["conv_in.weight"].shape[1]), device=device, compute_dtype=args.dtype)
+    # image_descriptors (tools/configs/base/base.yaml, trainers_ldm_cond.py:55-127): remove = the UNet without cross-attention;
+    # clip_image = CLIP-L/14 patch features [B, 257, 1024] through encoder_hid_proj; clip_image_proj = the projected image
+    # embedding [B, 1, 768].  The descriptor runs on the library (models.CLIPVisionDescriptor).
+    cross = args.image_descriptors != "remove"
+    desc = None
+    if cross:
+        from ldmseg_amd.models import CLIPVisionDescriptor
+        proj = args.image_descriptors == "clip_image_proj"
+        if not args.ldm:
+            # the conditioned UNet is the 8-channel one: self-conditioning (12 channels) cannot be combined with the guidance
+            # the descriptor modes run under (multiplier 2)
+            usd = weights.generate(weights.unet_schema(8, True), seed=0)
+            if not proj:
+                usd.update(weights.generate(weights.hid_proj_schema(), seed=12))
+        if args.clip_vision:
+            csd = torch.load(args.clip_vision, map_location="cpu", weights_only=True)
+        else:
+            schema = weights.clip_vision_schema(projection_dim=768 if proj else 0)
+            csd = weights.generate(schema, seed=13, norm_keys=weights.clip_vision_norm_keys(schema))
+        desc = CLIPVisionDescriptor(csd, projection=proj, device=device, compute_dtype=args.dtype)
+    unet = UNet(usd, in_channels=int(usd["conv_in.weight"].shape[1]), device=device, compute_dtype=args.dtype,
+                cross_attention=cross)
     vae = GeneralVAESeg(vsd, scaling_factor=args.scaling_factor, device=device, compute_dtype=args.dtype)
     enc = GeneralVAEImage(isd, scaling_factor=0.18215, device=device, compute_dtype=args.dtype)
     return TrainerDiffusion(vae, unet, DDIMNoiseScheduler(**NOISE_SCHEDULER_KWARGS), vae_image=enc,
-                            latent_size=args.size // 8)
+                            latent_size=args.size // 8, image_descriptor_model=desc)
 
 
 def batches(files, size, batch, panoptic_dir):
@@ -78,6 +100,11 @@ def main():
     ap.add_argument("--scaling-factor", type=float, default=0.18215)      # tools/scripts/eval.sh:11
     ap.add_argument("--seed", type=int, default=42); ap.add_argument("--count-th", type=int, default=512)
     ap.add_argument("--mask-th", type=float, default=0.5); ap.add_argument("--out", default=None)
+    ap.add_argument("--image-descriptors", default="remove", choices=["remove", "clip_image", "clip_image_proj"],
+                    help="conditioning of the UNet's cross-attention (base.yaml image_descriptors); remove = no cross-attention")
+    ap.add_argument("--clip-vision", default=None,
+                    help="torch.save'd state dict of CLIPVisionModel / CLIPVisionModelWithProjection (openai/clip-vit-large-patch14); "
+                         "generated weights without it")
     args = ap.parse_args()
     import torch.distributed as dist
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
