@@ -6,6 +6,8 @@
 // is one K tile; norm parameters, biases and the time-embedding MLP stay fp32.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -209,6 +211,32 @@ struct ConvW {
 };
 struct NormW { float* g = nullptr; float* b = nullptr; int C = 0; };
 
+// What every handle owns: its device and compute mode, the parameter arena, the workspace with its cached plan and the two
+// hand-off regions of its launches.  The four public handle types derive from it.
+struct HandleBase {
+  int device = 0;
+  int dt = DT_BF16;
+  bool x3 = false;      // fp32 storage with split-bf16 GEMM arithmetic (LDMSEG_BF16X3)
+  DeviceArena arena;
+  Workspace ws;
+  void* ws_mem = nullptr;
+  size_t ws_cap = 0;
+  int64_t nparams = 0;
+  void* gn_sync = nullptr;     // cooperative GroupNorm (null: a handle without GroupNorm launches)
+  void* cf_sync = nullptr;     // in-launch split-K finish
+  // plan_workspace: the shape key the sizes below were measured for (plan_key[4] = g_plan_epoch then)
+  int plan_key[5] = {};
+  bool plan_valid = false;
+  size_t plan_persist = 0, plan_scratch = 0;
+  ~HandleBase() {
+    DeviceGuard dg(device);    // (the caller's current device may be another one)
+    arena.release();
+    if (ws_mem) (void)hipFree(ws_mem);
+    if (gn_sync) (void)hipFree(gn_sync);
+    if (cf_sync) (void)hipFree(cf_sync);
+  }
+};
+
 struct Builder {
   DeviceArena* arena;
   const WeightMap* wm;
@@ -218,18 +246,29 @@ struct Builder {
   std::vector<void*> temps;
   bool x3 = false;                                         // LDMSEG_BF16X3 handle: every GEMM weight matrix becomes hi | lo planes at finish()
   std::vector<std::pair<void*, size_t>> x3_w;              // (packed fp32 matrix, floats)
+  void* fold_scratch = nullptr;                            // ln_linear
+  size_t fold_cap = 0;
   void weights(void* w, size_t nfloats) { if (x3 && dt == DT_F32) x3_w.emplace_back(w, nfloats); }
 
-  int f32_copy(const std::string& key, int64_t n, float** out, int64_t pad_to = 0) {
+  int f32_copy(const std::string& key, int64_t n, float** out) {
     const float* src;
     TRY(wm->get(key, n, &src));
-    const int64_t tot = pad_to > n ? pad_to : n;
     void* p;
-    TRY(arena->alloc(&p, tot * sizeof(float)));
-    if (tot > n) HIP_TRY(hipMemsetAsync(p, 0, tot * sizeof(float), s));
+    TRY(arena->alloc(&p, n * sizeof(float)));
     HIP_TRY(hipMemcpyAsync(p, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     *out = (float*)p;
     nparams += n;
+    return 0;
+  }
+  // [Npad] bias of a GEMM: the n values of `key` (null: none), zeros behind them
+  int padded_bias(const std::string* key, int n, int Npad, float** out) {
+    const float* src = nullptr;
+    if (key) TRY(wm->get(*key, n, &src));
+    void* p;
+    TRY(arena->alloc(&p, Npad * sizeof(float)));
+    TRY(launch_padded_bias(src, n, (float*)p, Npad, s));
+    *out = (float*)p;
+    if (key) nparams += n;
     return 0;
   }
   int norm(const std::string& prefix, int C, NormW* out) {
@@ -259,13 +298,37 @@ struct Builder {
       TRY(launch_repack_conv(w, out->w_cm, Co, Ci, k, k, Npad, cin_pad, dt, s, bke(dt)));
     }
     nparams += (int64_t)Co * Ci * k * k;
-    if (has_bias) TRY(f32_copy(prefix + ".bias", Co, &out->bias, Npad));
-    else {
-      void* p;
-      TRY(arena->alloc(&p, Npad * sizeof(float)));
-      HIP_TRY(hipMemsetAsync(p, 0, Npad * sizeof(float), s));
-      out->bias = (float*)p;
+    const std::string bkey = prefix + ".bias";
+    return padded_bias(has_bias ? &bkey : nullptr, Co, Npad, &out->bias);
+  }
+  // Linear layers `wkeys` [Nper][K] each (+ `bkeys`, or none), stacked on N, with the LayerNorm (gamma, beta) in front of them
+  // folded in: launch_ln_fold's format.  n_valid: output columns of the launch (half the rows for a GEGLU projection)
+  int ln_linear(const float* gamma, const float* beta, const std::vector<std::string>& wkeys, const std::vector<std::string>& bkeys,
+                int Nper, int K, int Npad, int n_valid, const std::vector<int>* row_map, float scale, ConvW* out) {
+    LnFold f;
+    f.parts = (int)wkeys.size(); f.Nper = Nper; f.K = K; f.Npad = Npad;
+    f.gamma = gamma; f.beta = beta; f.row_map = row_map; f.scale = scale; f.dtype = dt;
+    for (int i = 0; i < f.parts; ++i) {
+      TRY(wm->get(wkeys[i], (int64_t)Nper * K, &f.w[i]));
+      if (!bkeys.empty()) TRY(wm->get(bkeys[i], Nper, &f.bias[i]));
+      nparams += (int64_t)Nper * K + (bkeys.empty() ? 0 : Nper);
     }
+    out->N = Npad; out->n_valid = n_valid; out->cin_pad = K; out->taps = 1; out->cout = n_valid;
+    TRY(arena->alloc(&out->w, (size_t)Npad * K * esize(dt)));
+    weights(out->w, (size_t)Npad * K);
+    // one scratch for the folds of a handle, grown when a larger one comes (every use is ordered on the builder's stream)
+    if (const size_t need = ln_fold_scratch_bytes(f); need > fold_cap) {
+      HIP_TRY(hipMalloc(&fold_scratch, need));
+      temps.push_back(fold_scratch);
+      fold_cap = need;
+    }
+    void *pc1, *pc2;
+    TRY(arena->alloc(&pc1, (size_t)Npad * sizeof(float)));
+    TRY(arena->alloc(&pc2, (size_t)Npad * sizeof(float)));
+    out->c1 = (float*)pc1;
+    out->bias = (float*)pc2;
+    const int r = launch_ln_fold(f, fold_scratch, out->w, out->c1, out->bias, s);
+    if (r) return fail(r == -2 ? LDMSEG_E_SHAPE : LDMSEG_E_HIP, "launch_ln_fold failed");
     return 0;
   }
   int upload_ints(const std::vector<int>& v, int** dev) {
@@ -291,6 +354,14 @@ struct Builder {
 struct Act {
   void* p = nullptr;
   int C = 0, H = 0, W = 0;
+};
+
+// what differs between the Linear launches of Exec::linear
+struct LinearOpt {
+  const float* rowstats = nullptr;   // [M][2] from Exec::rowstats(): the ConvW holds a folded LayerNorm
+  const void* resid = nullptr;       // [M][ldo], may be the output itself
+  int epi = EPI_STORE;
+  int silu = 0;
 };
 
 struct Exec {
@@ -378,6 +449,20 @@ struct Exec {
     p.out = out->p; p.ldo = w.n_valid;
     p.epi = EPI_STORE; p.silu = silu;
     return igemm(p);
+  }
+
+  // Linear over token rows: out[B * Hi * Wi][ldo] = src[.][K] w^T + bias.  (Hi, Wi) is the row geometry of the launch: the map of a
+  // UNet level, (tokens, 1) elsewhere.  A folded LayerNorm (o.rowstats) reads its row sums from the ConvW.
+  int linear(const ConvW& w, const void* src, int K, int Hi, int Wi, void* out, int ldo, const LinearOpt& o = {}) {
+    // (the callers size `out` by ldo, the kernel stores w.n_valid columns)
+    if (K != w.cin_pad || w.taps != 1 || ldo != w.n_valid || (o.rowstats && !w.c1)) return fail(LDMSEG_E_SHAPE, "linear: shape mismatch");
+    IgemmParams g;
+    g.src0 = src; g.C0 = K; g.B = B; g.Hi = g.Ho = Hi; g.Wi = g.Wo = Wi;
+    g.M = B * Hi * Wi; g.N = w.N; g.n_valid = w.n_valid; g.W = w.w; g.bias = w.bias;
+    if (o.rowstats) { g.rowstats = o.rowstats; g.c1 = w.c1; }
+    if (o.resid) { g.resid = o.resid; g.ldr = ldo; }
+    g.out = out; g.ldo = ldo; g.epi = o.epi; g.silu = o.silu;
+    return igemm(g);
   }
 
   // resnet tail: out = conv2(h) + conv_shortcut(cat([x, x2])) as one launch (ResnetW::conv2x); false = the launch has no
@@ -504,6 +589,16 @@ struct Exec {
   }
 };
 
+// the executor of one (dry or real) pass over a handle's workspace
+Exec make_exec(HandleBase& h, int B, hipStream_t s, bool dry, size_t scratch_base) {
+  h.ws.begin(dry, scratch_base);
+  Exec ex{&h.ws, h.dt, B, s};
+  ex.gn_sync = h.gn_sync;
+  ex.cf_sync = h.cf_sync;
+  ex.x3 = h.x3 ? 2 : 0;          // (2: the handle's weights are hi | lo planes, Builder::finish)
+  return ex;
+}
+
 // ------------------------------------------------------------------ UNet
 constexpr int kBlockOut[4] = {320, 640, 1280, 1280};
 constexpr int kTimeDim = 1280;
@@ -535,16 +630,8 @@ constexpr int kTransformers = 16;
 
 }  // namespace
 
-struct ldmseg_unet {
+struct ldmseg_unet : HandleBase {
   ldmseg_unet_cfg cfg{};
-  int dt = DT_BF16;
-  bool x3 = false;      // fp32 storage with split-bf16 GEMM arithmetic (LDMSEG_BF16X3)
-  DeviceArena arena;
-  Workspace ws;
-  void* ws_mem = nullptr;
-  size_t ws_cap = 0;
-  int64_t nparams = 0;
-
   float *te1_w = nullptr, *te1_b = nullptr, *te2_w = nullptr, *te2_b = nullptr;
   float *tproj_w = nullptr, *tproj_b = nullptr;
   int temb_total = 0;
@@ -559,12 +646,9 @@ struct ldmseg_unet {
   int ctx_S = 77, ctx_dim = kCrossDim; // shape the workspace is planned for (last call's; 77 text tokens before any call)
   bool ctx_kv_ready = false;           // ldmseg_sample_loop_guided: the context's K|V is already in the workspace (first step made it)
   const void* ctx_kv_base = nullptr;   // workspace base that K|V lives in
-  int plan_S = 0, plan_cdim = 0;
   float* guide_buf = nullptr;          // guided loop: [2B,4,L,L] latents | [2B,4,L,L] rgb latents
   size_t guide_elems = 0;
   // sampler state
-  int plan_B = 0, plan_L = 0, plan_epoch = -1;
-  size_t plan_persist = 0, plan_scratch = 0;
   int attn_fp8_min_tokens = 0;   // > 0: bf16 mode runs attention levels with N >= this many tokens on the fp8 operand path
   float* cond = nullptr;   // [B,4,L,L] self-conditioning channel
   float* eps = nullptr;
@@ -574,8 +658,6 @@ struct ldmseg_unet {
   void* temb_buf = nullptr;            // [steps] int64 timesteps | sinusoid | two MLP activations | [steps][temb_total] rows
   int temb_cap = 0;                    // steps the buffer holds
   const float* temb_override = nullptr;   // non-null while the loop runs a forward: this step's row (broadcast over the batch)
-  void* gn_sync = nullptr;
-  void* cf_sync = nullptr;
   // fused step tail (tail.hip): the sampling loop parks the scheduler step here before a forward; the forward's conv_out
   // launch carries it out (tail_done) and leaves the next forward's packed input in place (xin_ready)
   const StepTail* tail_req = nullptr;
@@ -590,14 +672,11 @@ struct ldmseg_unet {
   const void* xin_ptr = nullptr;       // where the tail wrote that input: the next forward skips its pack only if its own xin IS this buffer
 
   ~ldmseg_unet() {
-    arena.release();
-    if (ws_mem) (void)hipFree(ws_mem);
+    DeviceGuard dg(device);
     if (cond) (void)hipFree(cond);
     if (eps) (void)hipFree(eps);
     if (temb_buf) (void)hipFree(temb_buf);
     if (gn_diag_host) (void)hipHostFree(gn_diag_host);
-    if (gn_sync) (void)hipFree(gn_sync);
-    if (cf_sync) (void)hipFree(cf_sync);
     if (guide_buf) (void)hipFree(guide_buf);
   }
 };
@@ -635,32 +714,7 @@ int build_resnet(Builder& b, const std::string& p, int cin, int cout, int* temb_
 int build_attn2(Builder& b, const std::string& tb, int C, TransformerW* t) {
   const int dt = b.dt;
   TRY(b.norm(tb + "norm2", C, &t->ln2));
-  {
-    ConvW& q = t->q2;
-    const int Np = (int)rup(C, igemm_pick_bn(C, EPI_STORE));
-    q.N = Np; q.n_valid = C; q.cin_pad = C; q.taps = 1; q.cout = C;
-    std::vector<int> map(Np);
-    for (int r = 0; r < Np; ++r) map[r] = r < C ? r : -1;
-    int* dmap;
-    TRY(b.upload_ints(map, &dmap));
-    const float* w;
-    TRY(b.wm->get(tb + "attn2.to_q.weight", (int64_t)C * C, &w));
-    TRY(b.arena->alloc(&q.w, (size_t)Np * C * esize(dt)));
-    b.weights(q.w, (size_t)Np * C);
-    TRY(launch_repack_rows_scaled(w, q.w, dmap, Np, C, t->ln2.g, dt, b.s));
-    void* tmp;
-    HIP_TRY(hipMalloc(&tmp, (size_t)Np * C * sizeof(float)));
-    b.temps.push_back(tmp);
-    TRY(launch_repack_rows_scaled(w, tmp, dmap, Np, C, t->ln2.b, DT_F32, b.s));
-    void *pc1, *pc2;
-    TRY(b.arena->alloc(&pc1, (size_t)Np * sizeof(float)));
-    TRY(b.arena->alloc(&pc2, (size_t)Np * sizeof(float)));
-    TRY(launch_rowsum(q.w, nullptr, (float*)pc1, Np, C, dt, b.s));
-    TRY(launch_rowsum(tmp, nullptr, (float*)pc2, Np, C, DT_F32, b.s));
-    q.c1 = (float*)pc1;
-    q.bias = (float*)pc2;
-    b.nparams += (int64_t)C * C;
-  }
+  TRY(b.ln_linear(t->ln2.g, t->ln2.b, {tb + "attn2.to_q.weight"}, {}, C, C, (int)rup(C, igemm_pick_bn(C, EPI_STORE)), C, nullptr, 0.f, &t->q2));
   {
     ConvW& k = t->kv2;
     const int Np = (int)rup(2 * C, igemm_pick_bn(2 * C, EPI_STORE));
@@ -677,10 +731,7 @@ int build_attn2(Builder& b, const std::string& tb, int C, TransformerW* t) {
     // rows [0, C) <- to_k, [C, 2C) <- to_v, the padding rows behind them zero (map -1)
     TRY(launch_repack_rows(wk, k.w, dmap, C, kCrossDim, dt, b.s));
     TRY(launch_repack_rows(wv, (char*)k.w + (size_t)C * kCrossDim * esize(dt), dmap, Np - C, kCrossDim, dt, b.s));
-    void* pb;
-    TRY(b.arena->alloc(&pb, (size_t)Np * sizeof(float)));
-    HIP_TRY(hipMemsetAsync(pb, 0, (size_t)Np * sizeof(float), b.s));
-    k.bias = (float*)pb;
+    TRY(b.padded_bias(nullptr, 0, Np, &k.bias));
     b.nparams += (int64_t)2 * C * kCrossDim;
   }
   TRY(b.conv(tb + "attn2.to_out.0", C, C, 1, C, &t->out2));
@@ -694,71 +745,16 @@ int build_transformer(Builder& b, const std::string& p, int C, TransformerW* t, 
   TRY(b.conv(p + "proj_in", C, C, 1, C, &t->proj_in));
   const std::string tb = p + "transformer_blocks.0.";
   TRY(b.norm(tb + "norm1", C, &t->ln1));
-  // fused q|k|v projection, no bias, with norm1 (LayerNorm) folded in: W' = gamma (.) W, c1 = rowsum(W'), bias = W beta
-  {
-    ConvW& q = t->qkv;
-    q.N = 3 * C; q.n_valid = 3 * C; q.cin_pad = C; q.taps = 1; q.cout = 3 * C;
-    TRY(b.arena->alloc(&q.w, (size_t)3 * C * C * esize(dt)));
-    b.weights(q.w, (size_t)3 * C * C);
-    std::vector<int> ident(C);
-    for (int r = 0; r < C; ++r) ident[r] = r;
-    int* dident;
-    TRY(b.upload_ints(ident, &dident));
-    void* tmp;
-    HIP_TRY(hipMalloc(&tmp, (size_t)3 * C * C * sizeof(float)));
-    b.temps.push_back(tmp);
-    const char* names[3] = {"attn1.to_q.weight", "attn1.to_k.weight", "attn1.to_v.weight"};
-    for (int i = 0; i < 3; ++i) {
-      const float* w;
-      TRY(b.wm->get(tb + names[i], (int64_t)C * C, &w));
-      TRY(launch_repack_rows_scaled(w, (char*)q.w + (size_t)i * C * C * esize(dt), dident, C, C, t->ln1.g, dt, b.s));
-      TRY(launch_repack_rows_scaled(w, (char*)tmp + (size_t)i * C * C * sizeof(float), dident, C, C, t->ln1.b, DT_F32, b.s));
-      b.nparams += (int64_t)C * C;
-    }
-    void *pc1, *pc2;
-    TRY(b.arena->alloc(&pc1, (size_t)3 * C * sizeof(float)));
-    TRY(b.arena->alloc(&pc2, (size_t)3 * C * sizeof(float)));
-    TRY(launch_rowsum(q.w, nullptr, (float*)pc1, 3 * C, C, dt, b.s));
-    TRY(launch_rowsum(tmp, nullptr, (float*)pc2, 3 * C, C, DT_F32, b.s));
-    q.c1 = (float*)pc1;
-    q.bias = (float*)pc2;
-  }
+  // fused q|k|v projection, no bias, with norm1 (LayerNorm) folded in
+  TRY(b.ln_linear(t->ln1.g, t->ln1.b, {tb + "attn1.to_q.weight", tb + "attn1.to_k.weight", tb + "attn1.to_v.weight"}, {}, C, C, 3 * C, 3 * C,
+                  nullptr, 0.f, &t->qkv));
   TRY(b.conv(tb + "attn1.to_out.0", C, C, 1, C, &t->attn_out));
   if (cross) TRY(build_attn2(b, tb, C, t));
   TRY(b.norm(tb + "norm3", C, &t->ln3));
-  // GEGLU projection [8C, C]: rows interleaved in 16-row (a | gate) pairs so one lane owns both halves
+  // GEGLU projection [8C, C]: rows interleaved in 16-row (a | gate) pairs so one lane owns both halves; norm3 folded in
   {
-    ConvW& f = t->ff1;
-    const int N = 8 * C;
-    f.N = N; f.n_valid = 4 * C; f.cin_pad = C; f.taps = 1; f.cout = 4 * C;
-    std::vector<int> map(N);
-    for (int r = 0; r < N; ++r) {
-      const int blk = r / 32, w = r % 32;
-      map[r] = (w < 16) ? blk * 16 + w : 4 * C + blk * 16 + (w - 16);
-    }
-    int* dmap;
-    TRY(b.upload_ints(map, &dmap));
-    const float *w, *bias;
-    TRY(b.wm->get(tb + "ff.net.0.proj.weight", (int64_t)N * C, &w));
-    TRY(b.wm->get(tb + "ff.net.0.proj.bias", N, &bias));
-    // norm3 (LayerNorm) folded in: W' = gamma (.) W in the packed row order, c1 = rowsum(W'), bias = W beta + b
-    TRY(b.arena->alloc(&f.w, (size_t)N * C * esize(dt)));
-    b.weights(f.w, (size_t)N * C);
-    TRY(launch_repack_rows_scaled(w, f.w, dmap, N, C, t->ln3.g, dt, b.s));
-    void* tmp;
-    HIP_TRY(hipMalloc(&tmp, (size_t)N * C * sizeof(float)));
-    b.temps.push_back(tmp);
-    TRY(launch_repack_rows_scaled(w, tmp, dmap, N, C, t->ln3.b, DT_F32, b.s));
-    void *pb, *pc1, *pc2;
-    TRY(b.arena->alloc(&pb, N * sizeof(float)));
-    TRY(launch_repack_rows(bias, pb, dmap, N, 1, DT_F32, b.s));
-    TRY(b.arena->alloc(&pc1, N * sizeof(float)));
-    TRY(b.arena->alloc(&pc2, N * sizeof(float)));
-    TRY(launch_rowsum(f.w, nullptr, (float*)pc1, N, C, dt, b.s));
-    TRY(launch_rowsum(tmp, (const float*)pb, (float*)pc2, N, C, DT_F32, b.s));
-    f.c1 = (float*)pc1;
-    f.bias = (float*)pc2;
-    b.nparams += (int64_t)N * C + N;
+    const std::vector<int> map = geglu_row_map(4 * C);
+    TRY(b.ln_linear(t->ln3.g, t->ln3.b, {tb + "ff.net.0.proj.weight"}, {tb + "ff.net.0.proj.bias"}, 8 * C, C, 8 * C, 4 * C, &map, 0.f, &t->ff1));
   }
   TRY(b.conv(tb + "ff.net.2", C, 4 * C, 1, 4 * C, &t->ff2));
   TRY(b.conv(p + "proj_out", C, C, 1, C, &t->proj_out));
@@ -951,12 +947,7 @@ int run_transformer(Exec& ex, const TransformerW& t, const Act& x, Act* out, con
     float* stats = (float*)ws->scratch((size_t)M * 2 * sizeof(float));
     TRY(ex.rowstats(h, 1e-5f, stats));
     qkv = ex.new_act(3 * C, x.H, x.W, false);
-    IgemmParams p;
-    p.src0 = h.p; p.C0 = C; p.B = ex.B; p.Hi = p.Ho = x.H; p.Wi = p.Wo = x.W;
-    p.M = M; p.N = t.qkv.N; p.n_valid = 3 * C; p.W = t.qkv.w; p.bias = t.qkv.bias;
-    p.rowstats = stats; p.c1 = t.qkv.c1;
-    p.out = qkv.p; p.ldo = 3 * C;
-    TRY(ex.igemm(p));
+    TRY(ex.linear(t.qkv, h.p, C, x.H, x.W, qkv.p, 3 * C, {stats}));
   }
   att = ex.new_act(C, x.H, x.W, false);
   {
@@ -977,28 +968,14 @@ int run_transformer(Exec& ex, const TransformerW& t, const Act& x, Act* out, con
       TRY(launch_attention(qkv.p, att.p, ex.B, N, C, 8, ex.x3 ? 2 : ex.dt, ex.s));   // 2 = fp32 tensors, split-bf16 products
     }
   }
-  // h = to_out(att) + h  (in place on h)
-  {
-    IgemmParams p;
-    p.src0 = att.p; p.C0 = C; p.B = ex.B; p.Hi = p.Ho = x.H; p.Wi = p.Wo = x.W;
-    p.M = M; p.N = t.attn_out.N; p.n_valid = C; p.W = t.attn_out.w; p.bias = t.attn_out.bias;
-    p.resid = h.p; p.ldr = C; p.out = h.p; p.ldo = C;
-    TRY(ex.igemm(p));
-  }
+  TRY(ex.linear(t.attn_out, att.p, C, x.H, x.W, h.p, C, {nullptr, h.p}));      // h = to_out(att) + h  (in place on h)
   if (kv_ctx) {
     // h = to_out(attn2(norm2(h), ctx)) + h: norm2 folded into to_q (one statistics pass over h), the cross-attention core on the
     // context's K|V, to_out in place on h.  (The fused 320-channel entry and the fp8 path stay attn1-only.)
     float* st2 = (float*)ws->scratch((size_t)M * 2 * sizeof(float));
     TRY(ex.rowstats(h, 1e-5f, st2));
     Act q2 = ex.new_act(C, x.H, x.W, false);
-    {
-      IgemmParams p;
-      p.src0 = h.p; p.C0 = C; p.B = ex.B; p.Hi = p.Ho = x.H; p.Wi = p.Wo = x.W;
-      p.M = M; p.N = t.q2.N; p.n_valid = C; p.W = t.q2.w; p.bias = t.q2.bias;
-      p.rowstats = st2; p.c1 = t.q2.c1;
-      p.out = q2.p; p.ldo = C;
-      TRY(ex.igemm(p));
-    }
+    TRY(ex.linear(t.q2, h.p, C, x.H, x.W, q2.p, C, {st2}));
     Act a2 = ex.new_act(C, x.H, x.W, false);
     {
       ProfScope ps(1, ex.s, 4.0 * ex.B * (double)N * S * C, 2.0 * M * C * esize(ex.dt), ex.dry(),
@@ -1009,13 +986,7 @@ int run_transformer(Exec& ex, const TransformerW& t, const Act& x, Act* out, con
         if (r) return fail(r == -2 ? LDMSEG_E_SHAPE : LDMSEG_E_HIP, "launch_attention_cross failed");
       }
     }
-    {
-      IgemmParams p;
-      p.src0 = a2.p; p.C0 = C; p.B = ex.B; p.Hi = p.Ho = x.H; p.Wi = p.Wo = x.W;
-      p.M = M; p.N = t.out2.N; p.n_valid = C; p.W = t.out2.w; p.bias = t.out2.bias;
-      p.resid = h.p; p.ldr = C; p.out = h.p; p.ldo = C;
-      TRY(ex.igemm(p));
-    }
+    TRY(ex.linear(t.out2, a2.p, C, x.H, x.W, h.p, C, {nullptr, h.p}));
   }
   if (t.mlp_stream && mlp_fused_ok(C, ex.dt)) {
     // 320-channel level: norm3 -> GEGLU -> ff.net.2 (+h) [-> proj_out (+x)] in one row-local launch (tfuse.hip); the [M, 4C]
@@ -1040,27 +1011,14 @@ int run_transformer(Exec& ex, const TransformerW& t, const Act& x, Act* out, con
   float* stats = (float*)ws->scratch((size_t)M * 2 * sizeof(float));
   TRY(ex.rowstats(h, 1e-5f, stats));          // norm3, folded into the GEGLU GEMM the same way
   ff = ex.new_act(4 * C, x.H, x.W, false);
-  {
-    IgemmParams p;
-    p.src0 = h.p; p.C0 = C; p.B = ex.B; p.Hi = p.Ho = x.H; p.Wi = p.Wo = x.W;
-    p.M = M; p.N = t.ff1.N; p.n_valid = 4 * C; p.W = t.ff1.w; p.bias = t.ff1.bias;
-    p.rowstats = stats; p.c1 = t.ff1.c1;
-    p.out = ff.p; p.ldo = 4 * C; p.epi = EPI_GEGLU;
-    TRY(ex.igemm(p));
-  }
+  TRY(ex.linear(t.ff1, h.p, C, x.H, x.W, ff.p, 4 * C, {stats, nullptr, EPI_GEGLU}));
   if (t.ffp.w && g_ffp_mode) {
     // out = proj_out(h + ff.net.2(g)) + x as one Linear over torch.cat([g, h], -1) (TransformerW::ffp)
     TRY(ex.conv(t.ffp, ff, &h, out, 1, 0, true, nullptr, 0, &x));
     ws->reset(m);
     return 0;
   }
-  {
-    IgemmParams p;
-    p.src0 = ff.p; p.C0 = 4 * C; p.B = ex.B; p.Hi = p.Ho = x.H; p.Wi = p.Wo = x.W;
-    p.M = M; p.N = t.ff2.N; p.n_valid = C; p.W = t.ff2.w; p.bias = t.ff2.bias;
-    p.resid = h.p; p.ldr = C; p.out = h.p; p.ldo = C;
-    TRY(ex.igemm(p));
-  }
+  TRY(ex.linear(t.ff2, ff.p, 4 * C, x.H, x.W, h.p, C, {nullptr, h.p}));
   TRY(ex.conv(t.proj_out, h, nullptr, out, 1, 0, true, nullptr, 0, &x));
   ws->reset(m);
   return 0;
@@ -1074,12 +1032,8 @@ int unet_forward_impl(ldmseg_unet* u, const float* a, int Ca, const float* b, in
   if (Ca + Cb + Cc != u->cfg.in_channels) return fail(LDMSEG_E_SHAPE, "input channel count != in_channels");
   if (t_dev && t_count != 1 && t_count != B) return fail(LDMSEG_E_ARG, "t_count must be 1 or B");
   Workspace* ws = &u->ws;
-  ws->begin(dry, scratch_base);
-  Exec ex{ws, u->dt, B, s};
+  Exec ex = make_exec(*u, B, s, dry, scratch_base);
   ex.attn_fp8_min_tokens = u->attn_fp8_min_tokens;
-  ex.gn_sync = u->gn_sync;
-  ex.cf_sync = u->cf_sync;
-  ex.x3 = u->x3 ? 2 : 0;          // (2: the handle's weights are hi | lo planes, Builder::finish)
   ex.gn_poll_us = u->gn_backoff_calls > 0 ? 2 : -1;
   const int dt = u->dt;
 
@@ -1135,11 +1089,7 @@ int unet_forward_impl(ldmseg_unet* u, const float* a, int Ca, const float* b, in
       }
       for (int k = 0; k < kTransformers; ++k) {
         const ConvW& w = tw[k]->kv2;
-        IgemmParams p;
-        p.src0 = c.p; p.C0 = kCrossDim; p.B = B; p.Hi = p.Ho = S; p.Wi = p.Wo = 1;
-        p.M = B * S; p.N = w.N; p.n_valid = w.n_valid; p.W = w.w; p.bias = w.bias;
-        p.out = const_cast<void*>(kv_ctx[k]); p.ldo = w.n_valid;
-        TRY(ex.igemm(p));
+        TRY(ex.linear(w, c.p, kCrossDim, S, 1, const_cast<void*>(kv_ctx[k]), w.n_valid));
       }
       ws->reset(m0);
       if (!dry) u->ctx_kv_base = ws->base;
@@ -1240,41 +1190,59 @@ int unet_forward_impl(ldmseg_unet* u, const float* a, int Ca, const float* b, in
   return 0;
 }
 
-int ensure_ws(void** mem, size_t* cap, Workspace* ws, size_t need) {
-  if (need <= *cap) return 0;
-  if (*mem) {
+int ensure_ws(HandleBase& h, size_t need) {
+  if (need <= h.ws_cap) return 0;
+  if (h.ws_mem) {
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipFree(*mem));
-    *mem = nullptr;
-    *cap = 0;
+    HIP_TRY(hipFree(h.ws_mem));
+    h.ws_mem = nullptr;
+    h.ws_cap = 0;
   }
-  if (hipMalloc(mem, need) != hipSuccess) return fail(LDMSEG_E_OOM, "workspace hipMalloc failed (" + std::to_string(need) + " bytes)");
-  *cap = need;
-  ws->base = (char*)*mem;
-  ws->cap = need;
+  if (hipMalloc(&h.ws_mem, need) != hipSuccess) return fail(LDMSEG_E_OOM, "workspace hipMalloc failed (" + std::to_string(need) + " bytes)");
+  h.ws_cap = need;
+  h.ws.base = (char*)h.ws_mem;
+  h.ws.cap = need;
   return 0;
+}
+
+// Measure a pass (impl(dry = true, 0)) and make the workspace large enough for it.  key: up to four shape numbers the dry run depends
+// on besides the handle itself - the plan is then kept until they or g_plan_epoch change; null = measure on every call.
+using PlanKey = std::array<int, 4>;
+template <typename Impl>
+int plan_workspace(HandleBase& h, const PlanKey* key, Impl&& impl) {
+  int k[5] = {0, 0, 0, 0, g_plan_epoch};
+  if (key) std::copy(key->begin(), key->end(), k);
+  if (!key || !h.plan_valid || !std::equal(k, k + 5, h.plan_key)) {
+    h.plan_valid = false;
+    TRY(impl(true, (size_t)0));
+    h.plan_persist = rup(h.ws.persist_peak, 4096);
+    h.plan_scratch = rup(h.ws.scratch_peak, 4096);
+    std::copy(k, k + 5, h.plan_key);
+    h.plan_valid = key != nullptr;
+  }
+  return ensure_ws(h, h.plan_persist + h.plan_scratch);
+}
+// ... and run it.  A host allocation failure inside a pass (labels, the skip stack) ends here, not in the caller's C frame.
+template <typename Impl>
+int plan_and_run(HandleBase& h, const PlanKey* key, Impl&& impl) {
+  try {
+    TRY(plan_workspace(h, key, impl));
+    return impl(false, h.plan_persist);
+  } catch (...) {
+    return fail(LDMSEG_E_OOM, "host allocation failed");
+  }
 }
 
 int unet_forward_checked(ldmseg_unet* u, const float* a, int Ca, const float* b, int Cb, const float* c, int Cc,
                          const int64_t* t_dev, int t_count, int64_t t_host, int B, int L, float* out, hipStream_t s) {
-  // measure (cached per shape), (re)allocate, run
-  if (u->plan_B != B || u->plan_L != L || u->plan_epoch != g_plan_epoch || u->plan_S != u->ctx_S || u->plan_cdim != u->ctx_dim) {
-    TRY(unet_forward_impl(u, a, Ca, b, Cb, c, Cc, t_dev, t_count, t_host, B, L, out, s, true, 0));
-    u->plan_persist = rup(u->ws.persist_peak, 4096);
-    u->plan_scratch = rup(u->ws.scratch_peak, 4096);
-    u->plan_B = B;
-    u->plan_L = L;
-    u->plan_epoch = g_plan_epoch;
-    u->plan_S = u->ctx_S;
-    u->plan_cdim = u->ctx_dim;
-  }
-  {
-    const void* before = u->ws_mem;
-    const size_t cap_before = u->ws_cap;
-    TRY(ensure_ws(&u->ws_mem, &u->ws_cap, &u->ws, u->plan_persist + u->plan_scratch));
-    if (u->ws_mem != before || u->ws_cap != cap_before) { u->xin_ready = false; u->xin_ptr = nullptr; }   // (a new arena may reuse the old address)
-  }
-  return unet_forward_impl(u, a, Ca, b, Cb, c, Cc, t_dev, t_count, t_host, B, L, out, s, false, u->plan_persist);
+  const PlanKey key{B, L, u->ctx_S, u->ctx_dim};
+  const void* before = u->ws_mem;
+  const size_t cap_before = u->ws_cap;
+  return plan_and_run(*u, &key, [&](bool dry, size_t scratch_base) {
+    // (the workspace moved or grew: a new arena may reuse the old address, so the tail's hand-over is void either way)
+    if (!dry && (u->ws_mem != before || u->ws_cap != cap_before)) { u->xin_ready = false; u->xin_ptr = nullptr; }
+    return unet_forward_impl(u, a, Ca, b, Cb, c, Cc, t_dev, t_count, t_host, B, L, out, s, dry, scratch_base);
+  });
 }
 
 int check_arch(int device) {
@@ -1291,18 +1259,44 @@ int make_weight_map(int n, const char* const* names, const void* const* ptrs, co
   return 0;
 }
 
+// *_create of every handle type: the argument checks all share, `check(cfg)` for the type's own, then the handle on cfg->device:
+// parameters (build), the GEMM launcher's per-device state and the hand-off regions.  Nothing is left behind on an error.
+template <typename H, typename Cfg, typename Check>
+int create_handle(const Cfg* cfg, int n_weights, const char* const* names, const void* const* dev_ptrs, const int64_t* numels,
+                  Check&& check, int (*build)(H*, const WeightMap&), bool needs_gn_sync, H** out) {
+  g_err.clear();
+  if (!cfg || !out) return fail(LDMSEG_E_ARG, "null argument");
+  if (cfg->compute_dtype != LDMSEG_F32 && cfg->compute_dtype != LDMSEG_BF16 && cfg->compute_dtype != LDMSEG_BF16X3) return fail(LDMSEG_E_ARG, "bad compute_dtype");
+  TRY(check(*cfg));
+  DeviceGuard dg(cfg->device);
+  TRY(check_arch(cfg->device));
+  H* h = nullptr;
+  int r = 0;
+  try {
+    WeightMap wm;
+    TRY(make_weight_map(n_weights, names, dev_ptrs, numels, &wm));
+    h = new H();
+    h->cfg = *cfg;
+    h->device = cfg->device;
+    h->dt = cfg->compute_dtype == LDMSEG_BF16 ? DT_BF16 : DT_F32;
+    h->x3 = cfg->compute_dtype == LDMSEG_BF16X3;
+    r = build(h, wm);
+  } catch (...) {
+    r = fail(LDMSEG_E_OOM, "host allocation failed while building the handle");
+  }
+  if (r == 0) r = igemm_warm();
+  if (r == 0 && needs_gn_sync) r = alloc_gn_sync(&h->gn_sync);
+  if (r == 0) r = alloc_cf_sync(&h->cf_sync);
+  if (r != 0) { delete h; return r; }
+  *out = h;
+  return 0;
+}
+
 }  // namespace
 
 // =================================================================== seg-VAE
-struct ldmseg_vae {
+struct ldmseg_vae : HandleBase {
   ldmseg_vae_cfg cfg{};
-  int dt = DT_BF16;
-  bool x3 = false;      // fp32 storage with split-bf16 GEMM arithmetic (LDMSEG_BF16X3)
-  DeviceArena arena;
-  Workspace ws;
-  void* ws_mem = nullptr;
-  size_t ws_cap = 0;
-  int64_t nparams = 0;
   // encoder
   ConvW enc[10];          // encoder.{0,2,3,5,6,8,9,11,15} in order (9 used)
   NormW enc_gn;
@@ -1311,14 +1305,6 @@ struct ldmseg_vae {
   ConvW dec_in, dec_out;
   ConvW convt[4];
   NormW ln[4], dec_gn;
-  void* gn_sync = nullptr;
-  void* cf_sync = nullptr;
-  ~ldmseg_vae() {
-    arena.release();
-    if (ws_mem) (void)hipFree(ws_mem);
-    if (gn_sync) (void)hipFree(gn_sync);
-    if (cf_sync) (void)hipFree(cf_sync);
-  }
 };
 
 namespace {
@@ -1393,11 +1379,7 @@ struct PanopticOut {
 int vae_decode_impl(ldmseg_vae* v, const float* z, float z_scale, int B, int L, int interpolate, float* logits,
                     hipStream_t s, bool dry, size_t scratch_base, const ArgmaxOut* am = nullptr, const PanopticOut* po = nullptr) {
   Workspace* ws = &v->ws;
-  ws->begin(dry, scratch_base);
-  Exec ex{ws, v->dt, B, s};
-  ex.gn_sync = v->gn_sync;
-  ex.cf_sync = v->cf_sync;
-  ex.x3 = v->x3 ? 2 : 0;
+  Exec ex = make_exec(*v, B, s, dry, scratch_base);
   const int dt = v->dt;
   const ldmseg_vae_cfg& c = v->cfg;
   Act zin = ex.new_act(bke(dt), L, L, true);
@@ -1462,11 +1444,7 @@ int vae_decode_impl(ldmseg_vae* v, const float* z, float z_scale, int B, int L, 
 int vae_encode_impl(ldmseg_vae* v, const float* x, float mul, float add, int B, int H, float* moments, hipStream_t s,
                     bool dry, size_t scratch_base) {
   Workspace* ws = &v->ws;
-  ws->begin(dry, scratch_base);
-  Exec ex{ws, v->dt, B, s};
-  ex.gn_sync = v->gn_sync;
-  ex.cf_sync = v->cf_sync;
-  ex.x3 = v->x3 ? 2 : 0;
+  Exec ex = make_exec(*v, B, s, dry, scratch_base);
   const int dt = v->dt;
   const ldmseg_vae_cfg& c = v->cfg;
   Act xin = ex.new_act(bke(dt), H, H, true);
@@ -1496,29 +1474,14 @@ int vae_encode_impl(ldmseg_vae* v, const float* x, float mul, float add, int B, 
 }  // namespace
 
 // =================================================================== image VAE encoder (AutoencoderKL, SD-1.x)
-struct ldmseg_vae_image {
+struct ldmseg_vae_image : HandleBase {
   ldmseg_vae_image_cfg cfg{};
-  int dt = DT_BF16;
-  bool x3 = false;      // fp32 storage with split-bf16 GEMM arithmetic (LDMSEG_BF16X3)
-  DeviceArena arena;
-  Workspace ws;
-  void* ws_mem = nullptr;
-  size_t ws_cap = 0;
-  int64_t nparams = 0;
   ConvW conv_in, downs[3], conv_out, quant;
   ResnetW down[4][2], mid[2];
   NormW attn_gn, norm_out;
   ConvW q, k, proj;
   void* wv = nullptr;       // value projection [512][512], used as the X operand of the V^T GEMM
   float* bv = nullptr;
-  void* gn_sync = nullptr;
-  void* cf_sync = nullptr;
-  ~ldmseg_vae_image() {
-    arena.release();
-    if (ws_mem) (void)hipFree(ws_mem);
-    if (gn_sync) (void)hipFree(gn_sync);
-    if (cf_sync) (void)hipFree(cf_sync);
-  }
 };
 
 namespace {
@@ -1640,11 +1603,7 @@ int klenc_attention(Exec& ex, const ldmseg_vae_image* v, const Act& x, Act* out)
 int klenc_encode_impl(ldmseg_vae_image* v, const float* x, float mul, float add, int B, int H, int W, float* moments,
                       hipStream_t s, bool dry, size_t scratch_base) {
   Workspace* ws = &v->ws;
-  ws->begin(dry, scratch_base);
-  Exec ex{ws, v->dt, B, s};
-  ex.gn_sync = v->gn_sync;
-  ex.cf_sync = v->cf_sync;
-  ex.x3 = v->x3 ? 2 : 0;
+  Exec ex = make_exec(*v, B, s, dry, scratch_base);
   const int dt = v->dt;
   Act xin = ex.new_act(bke(dt), H, W, true);
   {
@@ -1677,15 +1636,8 @@ int klenc_encode_impl(ldmseg_vae_image* v, const float* x, float mul, float add,
 // transformers CLIPVisionModel(/WithProjection) - the image descriptor of the clip_image / clip_image_proj modes
 // (ldmseg/models/descriptors.py:15-76).  Row-local kernels: clip_vision.hip; every GEMM and the attention: the UNet's kernels.
 struct ClipLayerW { ConvW qkv, out, fc1, fc2; };
-struct ldmseg_clip_vision {
+struct ldmseg_clip_vision : HandleBase {
   ldmseg_clip_vision_cfg cfg{};
-  int dt = DT_BF16;
-  bool x3 = false;
-  DeviceArena arena;
-  Workspace ws;
-  void* ws_mem = nullptr;
-  size_t ws_cap = 0;
-  int64_t nparams = 0;
   int T = 0, Kpad = 0;          // tokens per image; K of the patch GEMM (3 * patch^2 rounded up to whole 128-byte lines)
   ConvW patch;
   float* cls = nullptr;
@@ -1693,80 +1645,11 @@ struct ldmseg_clip_vision {
   NormW pre, post;
   std::vector<ClipLayerW> layers;
   float* wproj = nullptr;       // visual_projection [projection_dim][hidden] fp32 (GEMV on the B pooled rows)
-  void* cf_sync = nullptr;
-  int plan_B = -1, plan_epoch = -1;
-  size_t plan_persist = 0, plan_scratch = 0;
-  ~ldmseg_clip_vision() {
-    arena.release();
-    if (ws_mem) (void)hipFree(ws_mem);
-    if (cf_sync) (void)hipFree(cf_sync);
-  }
 };
 
 namespace {
 
 constexpr float kQuickGelu = 1.702f;   // quick_gelu(x) = x * sigmoid(1.702 x) = silu(1.702 x) / 1.702
-
-// Build-time scratch of build_ln_linear, shared by all layers of a handle (every use is ordered on the builder's stream)
-struct LnFoldScratch {
-  float* gs = nullptr;    // [K] scale * gamma
-  float* bs = nullptr;    // [K] scale * beta
-  float* pb = nullptr;    // [Nmax] scale * bias, zero in the padding
-  float* wb = nullptr;    // [Nmax][K] beta-weighted rows, only to take their sums
-  int K = 0, Nmax = 0;
-  int reserve(Builder& b, int K_, int Nmax_) {
-    K = K_; Nmax = Nmax_;
-    HIP_TRY(hipMalloc((void**)&gs, (size_t)K * sizeof(float))); b.temps.push_back(gs);
-    HIP_TRY(hipMalloc((void**)&bs, (size_t)K * sizeof(float))); b.temps.push_back(bs);
-    HIP_TRY(hipMalloc((void**)&pb, (size_t)Nmax * sizeof(float))); b.temps.push_back(pb);
-    HIP_TRY(hipMalloc((void**)&wb, (size_t)Nmax * K * sizeof(float))); b.temps.push_back(wb);
-    return 0;
-  }
-};
-
-// out = scale * Linear_i(LayerNorm(x)) for the `prefixes.size()` Linear layers [Nper][K] stacked on N, as ONE folded-LayerNorm
-// launch (IgemmParams::rowstats): W' = scale * gamma (.) W, c1 = rowsum(W'), bias' = scale * (W beta + b).  N is padded with
-// zero rows to the 160-column tile the folded instantiations have.  The LayerNorm's gamma / beta (keys ln_prefix.{weight,bias})
-// are read where the caller's tensors lie: they are needed at build time only.
-int build_ln_linear(Builder& b, LnFoldScratch& sc, const std::string& ln_prefix, const std::vector<std::string>& prefixes, int Nper,
-                    int K, float scale, ConvW* out) {
-  const int dt = b.dt;
-  const int parts = (int)prefixes.size(), Nreal = parts * Nper;
-  const int Npad = (int)rup(Nreal, 160);
-  if (K != sc.K || Npad > sc.Nmax) return fail(LDMSEG_E_SHAPE, "build_ln_linear: scratch too small");
-  out->N = Npad; out->n_valid = Nreal; out->cin_pad = K; out->taps = 1; out->cout = Nreal;
-  const float *gamma, *beta;
-  TRY(b.wm->get(ln_prefix + ".weight", K, &gamma));
-  TRY(b.wm->get(ln_prefix + ".bias", K, &beta));
-  b.nparams += 2 * (int64_t)K;
-  TRY(launch_axpby(gamma, scale, 0.f, sc.gs, K, b.s));
-  TRY(launch_axpby(beta, scale, 0.f, sc.bs, K, b.s));
-  HIP_TRY(hipMemsetAsync(sc.pb, 0, (size_t)Npad * sizeof(float), b.s));
-  TRY(b.arena->alloc(&out->w, (size_t)Npad * K * esize(dt)));
-  b.weights(out->w, (size_t)Npad * K);
-  std::vector<int> map(Npad - (parts - 1) * Nper, -1);
-  for (int r = 0; r < Nper; ++r) map[r] = r;
-  int* dmap;
-  TRY(b.upload_ints(map, &dmap));
-  for (int i = 0; i < parts; ++i) {
-    const float *w, *bias;
-    TRY(b.wm->get(prefixes[i] + ".weight", (int64_t)Nper * K, &w));
-    TRY(b.wm->get(prefixes[i] + ".bias", Nper, &bias));
-    const int rows = i + 1 < parts ? Nper : (int)map.size();
-    TRY(launch_repack_rows_scaled(w, (char*)out->w + (size_t)i * Nper * K * esize(dt), dmap, rows, K, sc.gs, dt, b.s));
-    TRY(launch_repack_rows_scaled(w, (char*)sc.wb + (size_t)i * Nper * K * sizeof(float), dmap, rows, K, sc.bs, DT_F32, b.s));
-    TRY(launch_axpby(bias, scale, 0.f, sc.pb + (size_t)i * Nper, Nper, b.s));
-    b.nparams += (int64_t)Nper * K + Nper;
-  }
-  void *pc1, *pc2;
-  TRY(b.arena->alloc(&pc1, (size_t)Npad * sizeof(float)));
-  TRY(b.arena->alloc(&pc2, (size_t)Npad * sizeof(float)));
-  TRY(launch_rowsum(out->w, nullptr, (float*)pc1, Npad, K, dt, b.s));
-  TRY(launch_rowsum(sc.wb, sc.pb, (float*)pc2, Npad, K, DT_F32, b.s));
-  out->c1 = (float*)pc1;
-  out->bias = (float*)pc2;
-  return 0;
-}
 
 // Linear [N][K] with every weight scaled by `scale` (the bias is not)
 int build_scaled_linear(Builder& b, const std::string& prefix, int N, int K, float scale, ConvW* out) {
@@ -1789,8 +1672,8 @@ int build_scaled_linear(Builder& b, const std::string& prefix, int N, int K, flo
   TRY(launch_repack_rows_scaled(w, out->w, dmap, Npad, K, cs, dt, b.s));
   b.weights(out->w, (size_t)Npad * K);
   b.nparams += (int64_t)N * K;
-  TRY(b.f32_copy(prefix + ".bias", N, &out->bias, Npad));
-  return 0;
+  const std::string bkey = prefix + ".bias";
+  return b.padded_bias(&bkey, N, Npad, &out->bias);
 }
 
 int clip_build(ldmseg_clip_vision* v, const WeightMap& wm) {
@@ -1799,21 +1682,33 @@ int clip_build(ldmseg_clip_vision* v, const WeightMap& wm) {
   b.x3 = v->x3;
   const ldmseg_clip_vision_cfg& c = v->cfg;
   const int C = c.hidden_size, I = c.intermediate_size, P = c.patch_size;
+  v->T = (c.image_size / P) * (c.image_size / P) + 1;
+  v->Kpad = (int)rup((size_t)3 * P * P, 64);
   // patch_embedding [C][3][P][P] is a Linear over k = (channel, dy, dx): [C][3 P P] padded to [C][Kpad]
   TRY(b.conv("embeddings.patch_embedding", C, 3 * P * P, 1, v->Kpad, &v->patch, false));
   TRY(b.f32_copy("embeddings.class_embedding", C, &v->cls));
   TRY(b.f32_copy("embeddings.position_embedding.weight", (int64_t)v->T * C, &v->pos));
   TRY(b.norm("pre_layrnorm", C, &v->pre));
   v->layers.resize(c.num_layers);
-  LnFoldScratch sc;
-  TRY(sc.reserve(b, C, (int)rup((size_t)(3 * C > I ? 3 * C : I), 160)));
+  // out = scale * Linear(LayerNorm(x)) as one folded-LayerNorm launch, N padded with zero rows to the 160-column tile the folded
+  // instantiations have.  The LayerNorm's gamma / beta are read where the caller's tensors lie: they are needed at build time only.
+  auto ln_linear = [&](const std::string& ln, const std::vector<std::string>& lin, int Nper, float scale, ConvW* out) -> int {
+    const float *gamma, *beta;
+    TRY(wm.get(ln + ".weight", C, &gamma));
+    TRY(wm.get(ln + ".bias", C, &beta));
+    b.nparams += 2 * (int64_t)C;
+    std::vector<std::string> wk, bk;
+    for (const std::string& l : lin) { wk.push_back(l + ".weight"); bk.push_back(l + ".bias"); }
+    const int Nreal = (int)lin.size() * Nper;
+    return b.ln_linear(gamma, beta, wk, bk, Nper, C, (int)rup(Nreal, 160), Nreal, nullptr, scale, out);
+  };
   for (int i = 0; i < c.num_layers; ++i) {
     const std::string p = "encoder.layers." + std::to_string(i) + ".";
     ClipLayerW& l = v->layers[i];
-    TRY(build_ln_linear(b, sc, p + "layer_norm1", {p + "self_attn.q_proj", p + "self_attn.k_proj", p + "self_attn.v_proj"}, C, C, 1.f, &l.qkv));
+    TRY(ln_linear(p + "layer_norm1", {p + "self_attn.q_proj", p + "self_attn.k_proj", p + "self_attn.v_proj"}, C, 1.f, &l.qkv));
     TRY(b.conv(p + "self_attn.out_proj", C, C, 1, C, &l.out));
     // quick_gelu on the SiLU epilogue: fc1 scaled by 1.702, fc2's weights by 1 / 1.702
-    TRY(build_ln_linear(b, sc, p + "layer_norm2", {p + "mlp.fc1"}, I, C, kQuickGelu, &l.fc1));
+    TRY(ln_linear(p + "layer_norm2", {p + "mlp.fc1"}, I, kQuickGelu, &l.fc1));
     TRY(build_scaled_linear(b, p + "mlp.fc2", C, I, 1.f / kQuickGelu, &l.fc2));
   }
   TRY(b.norm("post_layernorm", C, &v->post));
@@ -1826,10 +1721,7 @@ int clip_build(ldmseg_clip_vision* v, const WeightMap& wm) {
 int clip_forward_impl(ldmseg_clip_vision* v, const float* img, int B, int H, int W, const float* mean, const float* std,
                       int resample, float* last_hidden, float* image_embeds, hipStream_t s, bool dry, size_t scratch_base) {
   Workspace* ws = &v->ws;
-  ws->begin(dry, scratch_base);
-  Exec ex{ws, v->dt, B, s};
-  ex.cf_sync = v->cf_sync;
-  ex.x3 = v->x3 ? 2 : 0;
+  Exec ex = make_exec(*v, B, s, dry, scratch_base);
   const ldmseg_clip_vision_cfg& c = v->cfg;
   const int dt = v->dt, C = c.hidden_size, I = c.intermediate_size, T = v->T, NP = T - 1, M = B * T;
   const size_t es = esize(dt);
@@ -1847,11 +1739,7 @@ int clip_forward_impl(ldmseg_clip_vision* v, const float* img, int B, int H, int
         TRY(launch_clip_patch_rows(img, rows, B, H, W, c.image_size, c.patch_size, v->Kpad, mean, std, resample, dt, s));
       }
     }
-    IgemmParams p;
-    p.src0 = rows; p.C0 = v->Kpad; p.B = B; p.Hi = p.Ho = NP; p.Wi = p.Wo = 1;
-    p.M = B * NP; p.N = v->patch.N; p.n_valid = C; p.W = v->patch.w; p.bias = v->patch.bias;
-    p.out = pe; p.ldo = C;
-    TRY(ex.igemm(p));
+    TRY(ex.linear(v->patch, rows, v->Kpad, NP, 1, pe, C));
     {
       ProfScope ps(3, s, 0, 2.0 * M * C * es, dry);
       if (!dry) TRY(launch_clip_tokens(pe, v->cls, v->pos, v->pre.g, v->pre.b, h.p, B, T, C, 1e-5f, dt, s));
@@ -1864,14 +1752,7 @@ int clip_forward_impl(ldmseg_clip_vision* v, const float* img, int B, int H, int
     void* qkv = ws->scratch((size_t)M * 3 * C * es);
     void* att = ws->scratch((size_t)M * C * es);
     TRY(ex.rowstats(h, 1e-5f, stats));
-    {
-      IgemmParams p;                                   // layer_norm1 -> q | k | v
-      p.src0 = h.p; p.C0 = C; p.B = B; p.Hi = p.Ho = T; p.Wi = p.Wo = 1;
-      p.M = M; p.N = l.qkv.N; p.n_valid = 3 * C; p.W = l.qkv.w; p.bias = l.qkv.bias;
-      p.rowstats = stats; p.c1 = l.qkv.c1;
-      p.out = qkv; p.ldo = 3 * C;
-      TRY(ex.igemm(p));
-    }
+    TRY(ex.linear(l.qkv, h.p, C, T, 1, qkv, 3 * C, {stats}));                       // layer_norm1 -> q | k | v
     {
       ProfScope ps(1, s, 4.0 * B * (double)T * T * C, 4.0 * M * C * es, dry, "clip N=" + std::to_string(T) + " C=" + std::to_string(C));
       if (!dry) {
@@ -1880,32 +1761,13 @@ int clip_forward_impl(ldmseg_clip_vision* v, const float* img, int B, int H, int
         if (r) return fail(r == -2 ? LDMSEG_E_SHAPE : LDMSEG_E_HIP, "launch_attention failed (head dim 64)");
       }
     }
-    {
-      IgemmParams p;                                   // h += out_proj(att)
-      p.src0 = att; p.C0 = C; p.B = B; p.Hi = p.Ho = T; p.Wi = p.Wo = 1;
-      p.M = M; p.N = l.out.N; p.n_valid = C; p.W = l.out.w; p.bias = l.out.bias;
-      p.resid = h.p; p.ldr = C; p.out = h.p; p.ldo = C;
-      TRY(ex.igemm(p));
-    }
+    TRY(ex.linear(l.out, att, C, T, 1, h.p, C, {nullptr, h.p}));                    // h += out_proj(att)
     ws->reset(m);
     stats = (float*)ws->scratch((size_t)M * 2 * sizeof(float));
     void* ff = ws->scratch((size_t)M * I * es);
     TRY(ex.rowstats(h, 1e-5f, stats));
-    {
-      IgemmParams p;                                   // silu(1.702 fc1(layer_norm2(h)))
-      p.src0 = h.p; p.C0 = C; p.B = B; p.Hi = p.Ho = T; p.Wi = p.Wo = 1;
-      p.M = M; p.N = l.fc1.N; p.n_valid = I; p.W = l.fc1.w; p.bias = l.fc1.bias;
-      p.rowstats = stats; p.c1 = l.fc1.c1; p.silu = 1;
-      p.out = ff; p.ldo = I;
-      TRY(ex.igemm(p));
-    }
-    {
-      IgemmParams p;                                   // h += fc2(.) / 1.702
-      p.src0 = ff; p.C0 = I; p.B = B; p.Hi = p.Ho = T; p.Wi = p.Wo = 1;
-      p.M = M; p.N = l.fc2.N; p.n_valid = C; p.W = l.fc2.w; p.bias = l.fc2.bias;
-      p.resid = h.p; p.ldr = C; p.out = h.p; p.ldo = C;
-      TRY(ex.igemm(p));
-    }
+    TRY(ex.linear(l.fc1, h.p, C, T, 1, ff, I, {stats, nullptr, EPI_STORE, 1}));     // silu(1.702 fc1(layer_norm2(h)))
+    TRY(ex.linear(l.fc2, ff, I, T, 1, h.p, C, {nullptr, h.p}));                      // h += fc2(.) / 1.702
     ws->reset(m);
   }
   if (last_hidden) {
@@ -1931,15 +1793,11 @@ int clip_forward_checked(ldmseg_clip_vision* v, const float* img, int B, int H, 
   if (image_embeds && !v->wproj) return fail(LDMSEG_E_ARG, "image_embeds requested from a handle without visual_projection");
   // the plan covers both outputs, so that it does not depend on which the caller asked for
   float* const any = (float*)(uintptr_t)0x1000;
-  if (v->plan_B != B || v->plan_epoch != g_plan_epoch) {
-    TRY(clip_forward_impl(v, img, B, H, W, mean, std, resample, any, v->wproj ? any : nullptr, s, true, 0));
-    v->plan_persist = rup(v->ws.persist_peak, 4096);
-    v->plan_scratch = rup(v->ws.scratch_peak, 4096);
-    v->plan_B = B;
-    v->plan_epoch = g_plan_epoch;
-  }
-  TRY(ensure_ws(&v->ws_mem, &v->ws_cap, &v->ws, v->plan_persist + v->plan_scratch));
-  return clip_forward_impl(v, img, B, H, W, mean, std, resample, last_hidden, image_embeds, s, false, v->plan_persist);
+  const PlanKey key{B};
+  return plan_and_run(*v, &key, [&](bool dry, size_t scratch_base) {
+    return clip_forward_impl(v, img, B, H, W, mean, std, resample, dry ? any : last_hidden, dry ? (v->wproj ? any : nullptr) : image_embeds, s,
+                             dry, scratch_base);
+  });
 }
 
 }  // namespace
@@ -1952,26 +1810,12 @@ const char* ldmseg_version(void) { return "ldmseg_hip 0.1 (gfx950)"; }
 
 int ldmseg_unet_create(const ldmseg_unet_cfg* cfg, int n_weights, const char* const* names,
                        const void* const* dev_ptrs, const int64_t* numels, ldmseg_unet** out) {
-  g_err.clear();
-  if (!cfg || !out) return fail(LDMSEG_E_ARG, "null argument");
-  if (cfg->cross_attention != 0 && cfg->cross_attention != 1) return fail(LDMSEG_E_ARG, "cross_attention must be 0 or 1");
-  if (cfg->compute_dtype != LDMSEG_F32 && cfg->compute_dtype != LDMSEG_BF16 && cfg->compute_dtype != LDMSEG_BF16X3) return fail(LDMSEG_E_ARG, "bad compute_dtype");
-  if (cfg->in_channels != 4 && cfg->in_channels != 8 && cfg->in_channels != 12) return fail(LDMSEG_E_ARG, "in_channels must be 4, 8 or 12");
-  DeviceGuard dg(cfg->device);
-  TRY(check_arch(cfg->device));
-  WeightMap wm;
-  TRY(make_weight_map(n_weights, names, dev_ptrs, numels, &wm));
-  ldmseg_unet* u = new ldmseg_unet();
-  u->cfg = *cfg;
-  u->dt = cfg->compute_dtype == LDMSEG_BF16 ? DT_BF16 : DT_F32;
-  u->x3 = cfg->compute_dtype == LDMSEG_BF16X3;
-  int r = unet_build(u, wm);
-  if (r == 0) r = igemm_warm();
-  if (r == 0) r = alloc_gn_sync(&u->gn_sync);
-  if (r == 0) r = alloc_cf_sync(&u->cf_sync);
-  if (r != 0) { delete u; return r; }
-  *out = u;
-  return 0;
+  auto check = [](const ldmseg_unet_cfg& c) {
+    if (c.cross_attention != 0 && c.cross_attention != 1) return fail(LDMSEG_E_ARG, "cross_attention must be 0 or 1");
+    if (c.in_channels != 4 && c.in_channels != 8 && c.in_channels != 12) return fail(LDMSEG_E_ARG, "in_channels must be 4, 8 or 12");
+    return 0;
+  };
+  return create_handle(cfg, n_weights, names, dev_ptrs, numels, check, unet_build, true, out);
 }
 
 void ldmseg_unet_destroy(ldmseg_unet* h) { delete h; }
@@ -2039,25 +1883,11 @@ int ldmseg_unet_forward_ctx(ldmseg_unet* h, const float* x, const int64_t* t_dev
 
 int ldmseg_vae_create(const ldmseg_vae_cfg* cfg, int n_weights, const char* const* names, const void* const* dev_ptrs,
                       const int64_t* numels, ldmseg_vae** out) {
-  g_err.clear();
-  if (!cfg || !out) return fail(LDMSEG_E_ARG, "null argument");
-  if (cfg->compute_dtype != LDMSEG_F32 && cfg->compute_dtype != LDMSEG_BF16 && cfg->compute_dtype != LDMSEG_BF16X3) return fail(LDMSEG_E_ARG, "bad compute_dtype");
-  if (cfg->num_latents != 2 || cfg->norm_num_groups != 32) return fail(LDMSEG_E_ARG, "only the gaussian parametrization with 32 groups is supported");
-  DeviceGuard dg(cfg->device);
-  TRY(check_arch(cfg->device));
-  WeightMap wm;
-  TRY(make_weight_map(n_weights, names, dev_ptrs, numels, &wm));
-  ldmseg_vae* v = new ldmseg_vae();
-  v->cfg = *cfg;
-  v->dt = cfg->compute_dtype == LDMSEG_BF16 ? DT_BF16 : DT_F32;
-  v->x3 = cfg->compute_dtype == LDMSEG_BF16X3;
-  int r = vae_build(v, wm);
-  if (r == 0) r = igemm_warm();
-  if (r == 0) r = alloc_gn_sync(&v->gn_sync);
-  if (r == 0) r = alloc_cf_sync(&v->cf_sync);
-  if (r != 0) { delete v; return r; }
-  *out = v;
-  return 0;
+  auto check = [](const ldmseg_vae_cfg& c) {
+    if (c.num_latents != 2 || c.norm_num_groups != 32) return fail(LDMSEG_E_ARG, "only the gaussian parametrization with 32 groups is supported");
+    return 0;
+  };
+  return create_handle(cfg, n_weights, names, dev_ptrs, numels, check, vae_build, true, out);
 }
 void ldmseg_vae_destroy(ldmseg_vae* h) { delete h; }
 int64_t ldmseg_vae_num_params(const ldmseg_vae* h) { return h ? h->nparams : 0; }
@@ -2068,10 +1898,9 @@ int ldmseg_vae_decode(ldmseg_vae* h, const float* z, float z_scale, int B, int L
   if (!h || !z || !logits) return fail(LDMSEG_E_ARG, "null argument");
   DeviceGuard dg(h->cfg.device);
   if (B < 1 || L < 1) return fail(LDMSEG_E_SHAPE, "bad B/L");
-  TRY(vae_decode_impl(h, z, z_scale, B, L, interpolate, logits, (hipStream_t)stream, true, 0));
-  const size_t persist = rup(h->ws.persist_peak, 4096), scratch = rup(h->ws.scratch_peak, 4096);
-  TRY(ensure_ws(&h->ws_mem, &h->ws_cap, &h->ws, persist + scratch));
-  return vae_decode_impl(h, z, z_scale, B, L, interpolate, logits, (hipStream_t)stream, false, persist);
+  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
+    return vae_decode_impl(h, z, z_scale, B, L, interpolate, logits, (hipStream_t)stream, dry, scratch_base);
+  });
 }
 
 int ldmseg_vae_decode_argmax(ldmseg_vae* h, const float* z, float z_scale, int B, int L, float mask_th, int64_t ignore_label,
@@ -2082,10 +1911,9 @@ int ldmseg_vae_decode_argmax(ldmseg_vae* h, const float* z, float z_scale, int B
   if (B < 1 || L < 1) return fail(LDMSEG_E_SHAPE, "bad B/L");
   if (h->cfg.num_upscalers != 2) return fail(LDMSEG_E_ARG, "the fused tail assumes interpolation_factor 2 (num_upscalers 2)");
   ArgmaxOut am{ids, max_prob, mask_th, ignore_label};
-  TRY(vae_decode_impl(h, z, z_scale, B, L, 1, nullptr, (hipStream_t)stream, true, 0, &am));
-  const size_t persist = rup(h->ws.persist_peak, 4096), scratch = rup(h->ws.scratch_peak, 4096);
-  TRY(ensure_ws(&h->ws_mem, &h->ws_cap, &h->ws, persist + scratch));
-  return vae_decode_impl(h, z, z_scale, B, L, 1, nullptr, (hipStream_t)stream, false, persist, &am);
+  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
+    return vae_decode_impl(h, z, z_scale, B, L, 1, nullptr, (hipStream_t)stream, dry, scratch_base, &am);
+  });
 }
 
 int ldmseg_vae_decode_panoptic(ldmseg_vae* h, const float* z, float z_scale, int B, int L, int in_h, int in_w,
@@ -2105,10 +1933,9 @@ int ldmseg_vae_decode_panoptic(ldmseg_vae* h, const float* z, float z_scale, int
   po.threshold_output = threshold_output; po.threshold_mode = threshold_mode; po.mask_th = mask_th; po.count_th = count_th;
   po.overlap_th = overlap_th; po.ignore_label = ignore_label;
   po.labels = labels; po.panoptic = panoptic; po.keep = keep; po.counts = counts; po.mask_counts = mask_counts;
-  TRY(vae_decode_impl(h, z, z_scale, B, L, 1, nullptr, (hipStream_t)stream, true, 0, nullptr, &po));
-  const size_t persist = rup(h->ws.persist_peak, 4096), scratch = rup(h->ws.scratch_peak, 4096);
-  TRY(ensure_ws(&h->ws_mem, &h->ws_cap, &h->ws, persist + scratch));
-  return vae_decode_impl(h, z, z_scale, B, L, 1, nullptr, (hipStream_t)stream, false, persist, nullptr, &po);
+  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
+    return vae_decode_impl(h, z, z_scale, B, L, 1, nullptr, (hipStream_t)stream, dry, scratch_base, nullptr, &po);
+  });
 }
 
 int ldmseg_vae_encode(ldmseg_vae* h, const float* x, float in_mul, float in_add, int B, int H, float* moments,
@@ -2117,32 +1944,14 @@ int ldmseg_vae_encode(ldmseg_vae* h, const float* x, float in_mul, float in_add,
   if (!h || !x || !moments) return fail(LDMSEG_E_ARG, "null argument");
   DeviceGuard dg(h->cfg.device);
   if (B < 1 || H < 8 || H % 8) return fail(LDMSEG_E_SHAPE, "H must be a multiple of 8");
-  TRY(vae_encode_impl(h, x, in_mul, in_add, B, H, moments, (hipStream_t)stream, true, 0));
-  const size_t persist = rup(h->ws.persist_peak, 4096), scratch = rup(h->ws.scratch_peak, 4096);
-  TRY(ensure_ws(&h->ws_mem, &h->ws_cap, &h->ws, persist + scratch));
-  return vae_encode_impl(h, x, in_mul, in_add, B, H, moments, (hipStream_t)stream, false, persist);
+  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
+    return vae_encode_impl(h, x, in_mul, in_add, B, H, moments, (hipStream_t)stream, dry, scratch_base);
+  });
 }
 
 int ldmseg_vae_image_create(const ldmseg_vae_image_cfg* cfg, int n_weights, const char* const* names,
                             const void* const* dev_ptrs, const int64_t* numels, ldmseg_vae_image** out) {
-  g_err.clear();
-  if (!cfg || !out) return fail(LDMSEG_E_ARG, "null argument");
-  if (cfg->compute_dtype != LDMSEG_F32 && cfg->compute_dtype != LDMSEG_BF16 && cfg->compute_dtype != LDMSEG_BF16X3) return fail(LDMSEG_E_ARG, "bad compute_dtype");
-  DeviceGuard dg(cfg->device);
-  TRY(check_arch(cfg->device));
-  WeightMap wm;
-  TRY(make_weight_map(n_weights, names, dev_ptrs, numels, &wm));
-  ldmseg_vae_image* v = new ldmseg_vae_image();
-  v->cfg = *cfg;
-  v->dt = cfg->compute_dtype == LDMSEG_BF16 ? DT_BF16 : DT_F32;
-  v->x3 = cfg->compute_dtype == LDMSEG_BF16X3;
-  int r = klenc_build(v, wm);
-  if (r == 0) r = igemm_warm();
-  if (r == 0) r = alloc_gn_sync(&v->gn_sync);
-  if (r == 0) r = alloc_cf_sync(&v->cf_sync);
-  if (r != 0) { delete v; return r; }
-  *out = v;
-  return 0;
+  return create_handle(cfg, n_weights, names, dev_ptrs, numels, [](const ldmseg_vae_image_cfg&) { return 0; }, klenc_build, true, out);
 }
 void ldmseg_vae_image_destroy(ldmseg_vae_image* h) { delete h; }
 int64_t ldmseg_vae_image_num_params(const ldmseg_vae_image* h) { return h ? h->nparams : 0; }
@@ -2153,57 +1962,26 @@ int ldmseg_vae_image_encode(ldmseg_vae_image* h, const float* x, float in_mul, f
   if (!h || !x || !moments) return fail(LDMSEG_E_ARG, "null argument");
   DeviceGuard dg(h->cfg.device);
   if (B < 1 || H < 8 || W < 8 || H % 8 || W % 8) return fail(LDMSEG_E_SHAPE, "H and W must be multiples of 8");
-  TRY(klenc_encode_impl(h, x, in_mul, in_add, B, H, W, moments, (hipStream_t)stream, true, 0));
-  const size_t persist = rup(h->ws.persist_peak, 4096), scratch = rup(h->ws.scratch_peak, 4096);
-  TRY(ensure_ws(&h->ws_mem, &h->ws_cap, &h->ws, persist + scratch));
-  return klenc_encode_impl(h, x, in_mul, in_add, B, H, W, moments, (hipStream_t)stream, false, persist);
+  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
+    return klenc_encode_impl(h, x, in_mul, in_add, B, H, W, moments, (hipStream_t)stream, dry, scratch_base);
+  });
 }
 
 int ldmseg_clip_vision_create(const ldmseg_clip_vision_cfg* cfg, int n_weights, const char* const* names,
                               const void* const* dev_ptrs, const int64_t* numels, ldmseg_clip_vision** out) {
-  g_err.clear();
-  if (!cfg || !out) return fail(LDMSEG_E_ARG, "null argument");
-  if (cfg->compute_dtype != LDMSEG_F32 && cfg->compute_dtype != LDMSEG_BF16 && cfg->compute_dtype != LDMSEG_BF16X3) return fail(LDMSEG_E_ARG, "bad compute_dtype");
-  if (cfg->num_layers < 1 || cfg->projection_dim < 0) return fail(LDMSEG_E_ARG, "num_layers must be >= 1, projection_dim >= 0");
-  if (cfg->num_heads < 1 || cfg->hidden_size != 64 * cfg->num_heads) return fail(LDMSEG_E_SHAPE, "hidden_size / num_heads must be 64 (the head dim the attention kernel is built for here)");
-  // (hidden_size is a multiple of 64 by the line above.  1280: the widest row launch_rowstats serves in fp32, and the widest K the
-  // folded-LayerNorm GEMMs run at in the UNet - one bound for all modes)
-  if (cfg->hidden_size > 1280) return fail(LDMSEG_E_SHAPE, "hidden_size must be at most 1280");
-  if (cfg->intermediate_size < 64 || cfg->intermediate_size % 64 != 0) return fail(LDMSEG_E_SHAPE, "intermediate_size must be a multiple of 64");
-  if (cfg->patch_size < 1 || cfg->image_size < cfg->patch_size || cfg->image_size % cfg->patch_size != 0) return fail(LDMSEG_E_SHAPE, "image_size must be a multiple of patch_size");
-  DeviceGuard dg(cfg->device);
-  TRY(check_arch(cfg->device));
-  WeightMap wm;
-  TRY(make_weight_map(n_weights, names, dev_ptrs, numels, &wm));
-  ldmseg_clip_vision* v = nullptr;
-  try {
-    v = new ldmseg_clip_vision();
-  } catch (...) {
-    return fail(LDMSEG_E_OOM, "host allocation failed");
-  }
-  v->cfg = *cfg;
-  v->dt = cfg->compute_dtype == LDMSEG_BF16 ? DT_BF16 : DT_F32;
-  v->x3 = cfg->compute_dtype == LDMSEG_BF16X3;
-  const int g = cfg->image_size / cfg->patch_size;
-  v->T = g * g + 1;
-  v->Kpad = (int)rup((size_t)3 * cfg->patch_size * cfg->patch_size, 64);
-  int r = 0;
-  try {
-    r = clip_build(v, wm);
-  } catch (...) {
-    r = fail(LDMSEG_E_OOM, "host allocation failed while building the CLIP vision handle");
-  }
-  if (r == 0) r = igemm_warm();
-  if (r == 0) r = alloc_cf_sync(&v->cf_sync);
-  if (r != 0) { delete v; return r; }
-  *out = v;
-  return 0;
+  auto check = [](const ldmseg_clip_vision_cfg& c) {
+    if (c.num_layers < 1 || c.projection_dim < 0) return fail(LDMSEG_E_ARG, "num_layers must be >= 1, projection_dim >= 0");
+    if (c.num_heads < 1 || c.hidden_size != 64 * c.num_heads) return fail(LDMSEG_E_SHAPE, "hidden_size / num_heads must be 64 (the head dim the attention kernel is built for here)");
+    // (hidden_size is a multiple of 64 by the line above.  1280: the widest row launch_rowstats serves in fp32, and the widest K the
+    // folded-LayerNorm GEMMs run at in the UNet - one bound for all modes)
+    if (c.hidden_size > 1280) return fail(LDMSEG_E_SHAPE, "hidden_size must be at most 1280");
+    if (c.intermediate_size < 64 || c.intermediate_size % 64 != 0) return fail(LDMSEG_E_SHAPE, "intermediate_size must be a multiple of 64");
+    if (c.patch_size < 1 || c.image_size < c.patch_size || c.image_size % c.patch_size != 0) return fail(LDMSEG_E_SHAPE, "image_size must be a multiple of patch_size");
+    return 0;
+  };
+  return create_handle(cfg, n_weights, names, dev_ptrs, numels, check, clip_build, false, out);    // (no GroupNorm in a ViT)
 }
-void ldmseg_clip_vision_destroy(ldmseg_clip_vision* h) {
-  if (!h) return;
-  DeviceGuard dg(h->cfg.device);
-  delete h;
-}
+void ldmseg_clip_vision_destroy(ldmseg_clip_vision* h) { delete h; }
 int64_t ldmseg_clip_vision_num_params(const ldmseg_clip_vision* h) { return h ? h->nparams : 0; }
 
 int ldmseg_clip_vision_forward(ldmseg_clip_vision* h, const float* pixel_values, int B, float* last_hidden, float* image_embeds,
@@ -2211,12 +1989,8 @@ int ldmseg_clip_vision_forward(ldmseg_clip_vision* h, const float* pixel_values,
   g_err.clear();
   if (!h) return fail(LDMSEG_E_ARG, "null handle");
   DeviceGuard dg(h->cfg.device);
-  try {
-    return clip_forward_checked(h, pixel_values, B, h->cfg.image_size, h->cfg.image_size, nullptr, nullptr, 0, last_hidden,
-                                image_embeds, (hipStream_t)stream);
-  } catch (...) {
-    return fail(LDMSEG_E_OOM, "host allocation failed");
-  }
+  return clip_forward_checked(h, pixel_values, B, h->cfg.image_size, h->cfg.image_size, nullptr, nullptr, 0, last_hidden, image_embeds,
+                              (hipStream_t)stream);
 }
 
 int ldmseg_clip_vision_describe(ldmseg_clip_vision* h, const float* rgb, int B, int H, int W, const float mean[3],
@@ -2226,11 +2000,7 @@ int ldmseg_clip_vision_describe(ldmseg_clip_vision* h, const float* rgb, int B, 
   for (int c = 0; c < 3; ++c)
     if (!(std[c] > 0.f)) return fail(LDMSEG_E_ARG, "std must be positive");
   DeviceGuard dg(h->cfg.device);
-  try {
-    return clip_forward_checked(h, rgb, B, H, W, mean, std, 1, last_hidden, image_embeds, (hipStream_t)stream);
-  } catch (...) {
-    return fail(LDMSEG_E_OOM, "host allocation failed");
-  }
+  return clip_forward_checked(h, rgb, B, H, W, mean, std, 1, last_hidden, image_embeds, (hipStream_t)stream);
 }
 
 int ldmseg_vae_posterior(const float* moments, const float* noise, float out_scale, int B, int l, float* out,
@@ -2334,7 +2104,7 @@ int ldmseg_unet_set_attention_fp8(ldmseg_unet* h, int min_tokens) {
   if (!h || min_tokens < 0) return fail(LDMSEG_E_ARG, "bad argument");
   if (min_tokens > 0 && h->dt != DT_BF16) return fail(LDMSEG_E_ARG, "the fp8 attention path belongs to the bf16 perf mode");
   h->attn_fp8_min_tokens = min_tokens;
-  h->plan_B = h->plan_L = 0;          // the workspace plan depends on it
+  h->plan_valid = false;              // the workspace plan depends on it
   return 0;
 }
 
@@ -2344,17 +2114,10 @@ int ldmseg_unet_reserve(ldmseg_unet* h, int B, int L) {
   if (B < 1 || L < 8 || L % 8 != 0) return fail(LDMSEG_E_SHAPE, "L must be a positive multiple of 8, B >= 1");
   DeviceGuard dg(h->cfg.device);
   const int ci = h->cfg.in_channels;
-  if (h->plan_B != B || h->plan_L != L || h->plan_epoch != g_plan_epoch || h->plan_S != h->ctx_S || h->plan_cdim != h->ctx_dim) {
-    TRY(unet_forward_impl(h, nullptr, ci, nullptr, 0, nullptr, 0, nullptr, 1, 0, B, L, nullptr, nullptr, true, 0));
-    h->plan_persist = rup(h->ws.persist_peak, 4096);
-    h->plan_scratch = rup(h->ws.scratch_peak, 4096);
-    h->plan_B = B;
-    h->plan_L = L;
-    h->plan_epoch = g_plan_epoch;
-    h->plan_S = h->ctx_S;
-    h->plan_cdim = h->ctx_dim;
-  }
-  TRY(ensure_ws(&h->ws_mem, &h->ws_cap, &h->ws, h->plan_persist + h->plan_scratch));
+  const PlanKey key{B, L, h->ctx_S, h->ctx_dim};
+  TRY(plan_workspace(*h, &key, [&](bool dry, size_t scratch_base) {
+    return unet_forward_impl(h, nullptr, ci, nullptr, 0, nullptr, 0, nullptr, 1, 0, B, L, nullptr, nullptr, dry, scratch_base);
+  }));
   TRY(loop_reserve(h, (size_t)B * 4 * L * L));
   TRY(temb_reserve(h, 64));
   TRY(igemm_warm());

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
 namespace ldmseg {
 
@@ -282,6 +283,35 @@ int launch_repack_rows_scaled(const float* w, void* out, const int* src_row_dev,
                               int dtype, hipStream_t s);
 // out[n] = sum_k W[n][k] (+ add[n]) over a packed [N][K] matrix in `dtype`, fp32 accumulation
 int launch_rowsum(const void* W, const float* add, float* out, int N, int K, int dtype, hipStream_t s);
+
+// Weight formats of the GEMM epilogues, made once here for the handles (engine.hip) and the operator entry points (ops_api.hip).
+// Source rows of the packed [2 nout][K] GEGLU projection (EPI_GEGLU): 32-row blocks of 16 value rows | their 16 gate rows, so that
+// one lane owns both halves of an output column.  Row r of the packed matrix is row map[r] of ff.net.0.proj ([value | gate]).
+std::vector<int> geglu_row_map(int nout);
+// dst[0, n) = src (null: nothing), dst[n, Npad) = 0: the bias of a GEMM whose N is padded to its tile
+int launch_padded_bias(const float* src, int n, float* dst, int Npad, hipStream_t s);
+// A LayerNorm folded into the `parts` Linear layers [Nper][K] behind it, stacked on N (IgemmParams::rowstats / c1):
+//   W' = gamma (.) W in the packed row order, c1 = rowsum(W') of the matrix as stored in `dtype`, bias' = W beta + b.
+// All pointers are device memory, fp32 unless said otherwise.
+struct LnFold {
+  int parts = 1;
+  const float* w[3] = {};             // [Nper][K] each
+  const float* bias[3] = {};          // [Nper] each, or all null
+  int Nper = 0, K = 0;
+  int Npad = 0;                       // rows of W', c1 and bias' (>= parts * Nper)
+  const float* gamma = nullptr;       // [K]
+  const float* beta = nullptr;        // [K]
+  // packed row -> row of w[0] (-1: a zero row), Npad entries: a one-part fold in another row order (geglu_row_map).  Null: the parts
+  // in order and zero rows behind them
+  const std::vector<int>* row_map = nullptr;
+  // 0: the tensors as they are.  Else W', bias' (not c1's definition) carry this factor: gamma, beta and the biases are scaled by it
+  // first (launch_axpby), also where it is 1 - the CLIP encoder's q|k|v has always been built that way
+  float scale = 0.f;
+  int dtype = DT_BF16;                // of W'
+};
+size_t ln_fold_scratch_bytes(const LnFold& f);   // build-time scratch of launch_ln_fold (the beta-weighted rows, the row map ...)
+// Launches are ordered on `s`; `scratch` may be reused by a later call on the same stream.  W' is [Npad][K] in f.dtype.
+int launch_ln_fold(const LnFold& f, void* scratch, void* W, float* c1, float* bias, hipStream_t s);
 
 // CLIP ViT image encoder, row-local kernels (clip_vision.hip)
 // image [B,3,H,W] fp32 -> patch-conv GEMM operand [B * (S/P)^2][Kpad], k = (channel, dy, dx), zero padded from 3 P P to Kpad.

@@ -397,6 +397,77 @@ int launch_rowsum(const void* W, const float* add, float* out, int N, int K, int
   return ok();
 }
 
+std::vector<int> geglu_row_map(int nout) {
+  std::vector<int> map(2 * (size_t)nout);
+  for (int r = 0; r < 2 * nout; ++r) {
+    const int blk = r / 32, q = r % 32;
+    map[r] = q < 16 ? blk * 16 + q : nout + blk * 16 + (q - 16);
+  }
+  return map;
+}
+
+int launch_padded_bias(const float* src, int n, float* dst, int Npad, hipStream_t s) {
+  if (hipMemsetAsync(dst, 0, (size_t)Npad * sizeof(float), s) != hipSuccess) return -3;
+  if (src && hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return -3;
+  return 0;
+}
+
+namespace {
+// launch_ln_fold's scratch: row map | scaled gamma | scaled beta | packed biases | beta-weighted rows
+struct LnFoldLayout {
+  size_t map_rows, gs, bs, pb, wb, total;
+  explicit LnFoldLayout(const LnFold& f) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    map_rows = f.row_map ? f.row_map->size() : (size_t)(f.Npad - (f.parts - 1) * f.Nper);
+    gs = up(map_rows * sizeof(int));
+    bs = gs + up((size_t)f.K * sizeof(float));
+    pb = bs + up((size_t)f.K * sizeof(float));
+    wb = pb + up((size_t)f.Npad * sizeof(float));
+    total = wb + (size_t)f.Npad * f.K * sizeof(float);
+  }
+};
+}  // namespace
+
+size_t ln_fold_scratch_bytes(const LnFold& f) { return LnFoldLayout(f).total; }
+
+int launch_ln_fold(const LnFold& f, void* scratch, void* W, float* c1, float* bias, hipStream_t s) {
+  const LnFoldLayout l(f);
+  if (f.parts < 1 || f.parts > 3 || f.Npad < f.parts * f.Nper || (f.row_map && (f.parts != 1 || (int)l.map_rows != f.Npad))) return -2;
+  int* map = (int*)scratch;
+  float* gs = (float*)((char*)scratch + l.gs);
+  float* bs = (float*)((char*)scratch + l.bs);
+  float* pb = (float*)((char*)scratch + l.pb);
+  float* wb = (float*)((char*)scratch + l.wb);
+  std::vector<int> rows;
+  if (!f.row_map) {
+    rows.assign(l.map_rows, -1);
+    for (int r = 0; r < f.Nper; ++r) rows[r] = r;
+  }
+  if (hipMemcpyAsync(map, (f.row_map ? *f.row_map : rows).data(), l.map_rows * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return -3;
+  const float *gamma = f.gamma, *beta = f.beta;
+  const bool has_bias = f.bias[0] != nullptr;
+  if (f.scale != 0.f) {
+    if (int r = launch_axpby(f.gamma, f.scale, 0.f, gs, f.K, s)) return r;
+    if (int r = launch_axpby(f.beta, f.scale, 0.f, bs, f.K, s)) return r;
+    gamma = gs; beta = bs;
+    if (has_bias && hipMemsetAsync(pb, 0, (size_t)f.Npad * sizeof(float), s) != hipSuccess) return -3;
+  }
+  const size_t es = f.dtype == DT_BF16 ? 2 : 4;
+  for (int i = 0; i < f.parts; ++i) {
+    // every part but the last takes its Nper rows, the last one the zero rows behind it too
+    const int n = i + 1 < f.parts ? f.Nper : (int)l.map_rows;
+    const size_t at = (size_t)i * f.Nper;
+    if (int r = launch_repack_rows_scaled(f.w[i], (char*)W + at * f.K * es, map, n, f.K, gamma, f.dtype, s)) return r;
+    if (int r = launch_repack_rows_scaled(f.w[i], wb + at * f.K, map, n, f.K, beta, DT_F32, s)) return r;
+    if (!has_bias) continue;
+    if (int r = f.scale != 0.f ? launch_axpby(f.bias[i], f.scale, 0.f, pb + at, f.Nper, s)
+                               : launch_repack_rows(f.bias[i], pb + at, map, n, 1, DT_F32, s)) return r;
+  }
+  // (c1 from the matrix as the GEMM will read it - rounded to bf16 where that is the storage; a bf16x3 handle splits its planes later)
+  if (int r = launch_rowsum(W, nullptr, c1, f.Npad, f.K, f.dtype, s)) return r;
+  return launch_rowsum(wb, has_bias ? pb : nullptr, bias, f.Npad, f.K, DT_F32, s);
+}
+
 int launch_repack_convt2(const float* w, void* out, int Ci, int Co, int dtype, hipStream_t s) {
   const size_t total = (size_t)4 * Co * Ci;
   if (dtype == DT_BF16)

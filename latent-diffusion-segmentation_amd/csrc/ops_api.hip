@@ -60,6 +60,21 @@ struct Temp {
     for (void* p : v) (void)hipFree(p);
   }
 };
+// `warm` untimed calls of fn(i), then `iters` timed ones (i keeps counting) between two HIP events on `s`: microseconds per call
+template <typename F>
+float time_launches(hipStream_t s, int warm, int iters, F fn) {
+  hipEvent_t e0, e1;
+  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+  for (int i = 0; i < warm; ++i) fn(i);
+  (void)hipEventRecord(e0, s);
+  for (int i = 0; i < iters; ++i) fn(warm + i);
+  (void)hipEventRecord(e1, s);
+  (void)hipEventSynchronize(e1);
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  return 1e3f * ms / iters;
+}
 __global__ void fastdiv_probe_kernel(const int* n, int count, FastDiv f, int* q) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < count) q[i] = fd_div(n[i], f);
@@ -68,6 +83,18 @@ inline size_t es(int dt) { return dt == DT_BF16 ? 2 : 4; }
 inline int bke(int dt) { return dt == DT_BF16 ? 64 : 32; }
 inline int rupi(int v, int a) { return (v + a - 1) / a * a; }
 
+// device copy of a host row map
+int* upload_map(Temp& t, const std::vector<int>& map, hipStream_t s) {
+  int* d = (int*)t.get(map.size() * sizeof(int));
+  if (d) (void)hipMemcpyAsync(d, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice, s);
+  return d;
+}
+// zero-padded [Npad] copy of a bias of n values (null: zeros)
+float* padded_bias(Temp& t, const float* bias, int n, int Npad, hipStream_t s) {
+  float* bp = (float*)t.get(Npad * sizeof(float));
+  if (bp) (void)launch_padded_bias(bias, n, bp, Npad, s);
+  return bp;
+}
 int to_dev_dtype(const float* x, void* y, size_t n, int dt, hipStream_t s) {
   int g = (int)((n + 255) / 256); if (g > 4096) g = 4096; if (g < 1) g = 1;
   if (dt == DT_BF16) hipLaunchKernelGGL(convert_rows_kernel<bf16_t>, dim3(g), dim3(256), 0, s, x, (bf16_t*)y, n);
@@ -115,16 +142,13 @@ int ldmseg_op_conv2d(const float* x, const float* x2, const float* w, const floa
   } else {
     // channel-concat weights: [Co][Ci+Ci2][k][k] -> pad each part; do it on the host-free way: two strided repacks
     // (Ci % a == 0 so c0 == Ci; only the second part may be padded)
-    std::vector<int> dummy;
     void* w_cat = t.get((size_t)Co * (c0 + c1) * k * k * sizeof(float));
     (void)hipMemsetAsync(w_cat, 0, (size_t)Co * (c0 + c1) * k * k * sizeof(float), s);
     (void)hipMemcpy2DAsync(w_cat, (size_t)(c0 + c1) * k * k * sizeof(float), w, (size_t)(Ci + Ci2) * k * k * sizeof(float),
                            (size_t)(Ci + Ci2) * k * k * sizeof(float), Co, hipMemcpyDeviceToDevice, s);
     if (launch_repack_conv((const float*)w_cat, wp, Co, c0 + c1, k, k, Np, ct, dtype, s)) return -3;
   }
-  float* bp = (float*)t.get(Np * sizeof(float));
-  (void)hipMemsetAsync(bp, 0, Np * sizeof(float), s);
-  if (bias) (void)hipMemcpyAsync(bp, bias, Co * sizeof(float), hipMemcpyDeviceToDevice, s);
+  float* bp = padded_bias(t, bias, Co, Np, s);
   const int Hl = up ? 2 * H : H, Wl = up ? 2 * W : W;
   const int Ho = (k == 3 && stride == 2) ? (Hl - 1) / 2 + 1 : Hl, Wo = (k == 3 && stride == 2) ? (Wl - 1) / 2 + 1 : Wl;
   IgemmParams p;
@@ -191,22 +215,16 @@ int ldmseg_op_linear(const float* x, const float* w, const float* bias, const fl
   const int bn = igemm_pick_bn(N, epi);
   const int Np = rupi(N, bn);
   void* wp = t.get((size_t)Np * K * es(dtype));
-  float* bp = (float*)t.get(Np * sizeof(float));
-  (void)hipMemsetAsync(bp, 0, Np * sizeof(float), s);
   const int nout = geglu ? N / 2 : N;
+  float* bp = padded_bias(t, geglu ? nullptr : bias, N, Np, s);
   if (geglu) {
-    std::vector<int> map(Np);
-    for (int r = 0; r < Np; ++r) {
-      const int blk = r / 32, q = r % 32;
-      map[r] = (q < 16) ? blk * 16 + q : nout + blk * 16 + (q - 16);
-    }
-    int* dmap = (int*)t.get(Np * sizeof(int));
-    (void)hipMemcpy(dmap, map.data(), Np * sizeof(int), hipMemcpyHostToDevice);
+    std::vector<int> map = geglu_row_map(nout);
+    map.resize(Np, -1);
+    const int* dmap = upload_map(t, map, s);
     if (launch_repack_rows(w, wp, dmap, Np, K, dtype, s)) return -3;
     if (bias && launch_repack_rows(bias, bp, dmap, Np, 1, DT_F32, s)) return -3;
   } else {
     if (launch_repack_conv(w, wp, N, K, 1, 1, Np, K, dtype, s)) return -3;
-    if (bias) (void)hipMemcpyAsync(bp, bias, N * sizeof(float), hipMemcpyDeviceToDevice, s);
   }
   void* rp = nullptr;
   if (resid) { rp = t.get((size_t)M * N * es(dtype)); to_dev_dtype(resid, rp, (size_t)M * N, dtype, s); }
@@ -259,9 +277,7 @@ int ldmseg_op_conv_groupnorm(const float* x, const float* w, const float* bias, 
   const int Np = rupi(Co, bn);
   void* wp = t.get((size_t)Np * 9 * Ci * es(dtype));
   if (launch_repack_conv(w, wp, Co, Ci, 3, 3, Np, Ci, dtype, s)) return -3;
-  float* bp = (float*)t.get(Np * sizeof(float));
-  (void)hipMemsetAsync(bp, 0, Np * sizeof(float), s);
-  if (bias) (void)hipMemcpyAsync(bp, bias, Co * sizeof(float), hipMemcpyDeviceToDevice, s);
+  float* bp = padded_bias(t, bias, Co, Np, s);
   void* op = t.get((size_t)B * H * W * Co * es(dtype));
   IgemmParams p;
   p.src0 = xp; p.C0 = Ci; p.B = B; p.Hi = H; p.Wi = W; p.Ho = H; p.Wo = W; p.taps = 9;
@@ -294,21 +310,9 @@ int ldmseg_bench_groupnorm(const float* gamma, const float* beta, int B, int C, 
   g.src0 = xp; g.C0 = C; g.src1 = x2p; g.C1 = C2; g.B = B; g.HW = HW; g.gamma = gamma; g.beta = beta; g.eps = 1e-5f;
   g.silu = silu; g.out = op; g.nchunk = gn_nchunk(B, HW);
   g.partial = (float*)t.get((size_t)B * g.nchunk * 64 * sizeof(float));
-  for (int i = 0; i < 3; ++i) {
-    const int r = launch_groupnorm(g, dtype, s);
-    if (r) return r;
-  }
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  (void)hipEventRecord(e0, s);
-  for (int i = 0; i < iters; ++i) (void)launch_groupnorm(g, dtype, s);
-  (void)hipEventRecord(e1, s);
-  (void)hipEventSynchronize(e1);
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  *us_per_launch = 1e3f * ms / iters;
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  return 0;
+  int err = 0;
+  *us_per_launch = time_launches(s, 3, iters, [&](int) { if (const int r = launch_groupnorm(g, dtype, s)) err = err ? err : r; });
+  return err;
 }
 
 // The fused evaluation tail (ldmseg_vae_decode_panoptic) on a given 4L decoder output x4 [B,C,H4,W4] f32 NCHW: packs it to
@@ -412,7 +416,6 @@ int ldmseg_op_bilinear2x(const float* x, int B, int C, int H, int W, int dtype, 
 // x [B,Ci,H,W], x2 [B,Ci2,H,W] or NULL, w [Co,Ci+Ci2,k,k], resid [B,Cout,Ho,Wo] or NULL, rowbias [B,Co] or NULL,
 // out [B,Cout,Ho,Wo] with Cout = Co (Co/2 for GEGLU, whose w rows are [value | gate] like ff.net.0.proj).
 static int g_bench_rot = 1, g_bench_ln = 0;
-static inline bool sp_gt1(int sp) { return sp > 1; }
 static int op_igemm_impl(const float* x, const float* x2, const float* w, const float* bias, const float* resid,
                          const float* rowbias, int B, int Ci, int Ci2, int H, int W, int Co, int k, int stride, int up, int geglu,
                          int silu, int splits, int dtype, float* out, void* stream, int time_iters, float* us_per_launch) {
@@ -435,28 +438,21 @@ static int op_igemm_impl(const float* x, const float* x2, const float* w, const 
   const int cout = geglu ? Co / 2 : Co;
   const bool cm = !geglu && igemm_conv_cm(H * W, c0 + c1, Np, k, stride, up, dtype) && (Ci % a) == 0 && (!Ci2 || (Ci2 % a) == 0);   // the engine's rule
   void* wp = t.get((size_t)Np * k * k * ct * es(dtype));
-  float* bp = (float*)t.get(Np * sizeof(float));
-  (void)hipMemsetAsync(bp, 0, Np * sizeof(float), s);
+  float* bp = padded_bias(t, geglu ? nullptr : bias, Co, Np, s);
   if (geglu) {
-    std::vector<int> map(Np);
-    for (int r = 0; r < Np; ++r) {
-      const int blk = r / 32, q = r % 32;
-      map[r] = (q < 16) ? blk * 16 + q : cout + blk * 16 + (q - 16);
-    }
-    int* dmap = (int*)t.get(Np * sizeof(int));
-    (void)hipMemcpy(dmap, map.data(), Np * sizeof(int), hipMemcpyHostToDevice);
+    std::vector<int> map = geglu_row_map(cout);
+    map.resize(Np, -1);
+    const int* dmap = upload_map(t, map, s);
     if (launch_repack_rows(w, wp, dmap, Np, ct, dtype, s)) return -3;
     if (bias && launch_repack_rows(bias, bp, dmap, Np, 1, DT_F32, s)) return -3;
   } else if (!Ci2) {
     if (launch_repack_conv(w, wp, Co, Ci, k, k, Np, c0, dtype, s, cm ? a : 0)) return -3;
-    if (bias) (void)hipMemcpyAsync(bp, bias, Co * sizeof(float), hipMemcpyDeviceToDevice, s);
   } else {
     void* w_cat = t.get((size_t)Co * ct * k * k * sizeof(float));
     (void)hipMemsetAsync(w_cat, 0, (size_t)Co * ct * k * k * sizeof(float), s);
     (void)hipMemcpy2DAsync(w_cat, (size_t)ct * k * k * sizeof(float), w, (size_t)(Ci + Ci2) * k * k * sizeof(float),
                            (size_t)(Ci + Ci2) * k * k * sizeof(float), Co, hipMemcpyDeviceToDevice, s);
     if (launch_repack_conv((const float*)w_cat, wp, Co, ct, k, k, Np, ct, dtype, s, cm ? a : 0)) return -3;
-    if (bias) (void)hipMemcpyAsync(bp, bias, Co * sizeof(float), hipMemcpyDeviceToDevice, s);
   }
   const int Hl = up ? 2 * H : H, Wl = up ? 2 * W : W;
   const int Ho = (k == 3 && stride == 2) ? (Hl - 1) / 2 + 1 : Hl, Wo = (k == 3 && stride == 2) ? (Wl - 1) / 2 + 1 : Wl;
@@ -483,7 +479,7 @@ static int op_igemm_impl(const float* x, const float* x2, const float* w, const 
   p.cf_ctr = op_cf_region();
   int sp = splits > 0 ? splits : igemm_plan_splits(p, dtype);
   if (sp > 1) { p.splits = sp; p.partial = (float*)t.get((size_t)sp * p.M * Np * sizeof(float)); }
-  if (time_iters > 0 && g_bench_ln && !sp_gt1(sp) && !rowbias) {   // time the folded-LayerNorm instantiation (mean 0, rstd 1, c1 0)
+  if (time_iters > 0 && g_bench_ln && sp <= 1 && !rowbias) {   // time the folded-LayerNorm instantiation (mean 0, rstd 1, c1 0)
     float* st = (float*)t.get((size_t)p.M * 2 * sizeof(float));
     float* c1z = (float*)t.get(Np * sizeof(float));
     (void)hipMemsetAsync(c1z, 0, Np * sizeof(float), s);
@@ -507,17 +503,7 @@ static int op_igemm_impl(const float* x, const float* x2, const float* w, const 
       wc.push_back(c);
     }
     rot = (int)wc.size();
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    for (int i = 0; i < 3; ++i) { p.W = wc[i % rot]; (void)launch_igemm(p, dtype, s); }
-    (void)hipEventRecord(e0, s);
-    for (int i = 0; i < time_iters; ++i) { p.W = wc[(i + 3) % rot]; (void)launch_igemm(p, dtype, s); }
-    (void)hipEventRecord(e1, s);
-    (void)hipEventSynchronize(e1);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    *us_per_launch = 1e3f * ms / time_iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    *us_per_launch = time_launches(s, 3, time_iters, [&](int i) { p.W = wc[i % rot]; (void)launch_igemm(p, dtype, s); });
   }
   if (!out) return 0;
   return unpack_nhwc(op, out, B, cout, Ho * Wo, cout, dtype, s);
@@ -547,13 +533,9 @@ int ldmseg_op_conv3x3_plus_1x1(const float* h, const float* w2, const float* b2,
   if (launch_repack_conv(w2, w2p, Co, C, 3, 3, Np, C, dtype, s)) return -3;
   if (launch_repack_conv(ws, wsp, Co, cs, 1, 1, Np, cs, dtype, s)) return -3;
   if (launch_concat_rows(w2p, 9 * C, wsp, cs, wx, Np, dtype, s)) return -3;
-  float* b2p = (float*)t.get(Np * sizeof(float));
-  float* bsp = (float*)t.get(Np * sizeof(float));
+  float* b2p = padded_bias(t, b2, Co, Np, s);
+  float* bsp = padded_bias(t, bs, Co, Np, s);
   float* bx = (float*)t.get(Np * sizeof(float));
-  (void)hipMemsetAsync(b2p, 0, Np * sizeof(float), s);
-  (void)hipMemsetAsync(bsp, 0, Np * sizeof(float), s);
-  if (b2) (void)hipMemcpyAsync(b2p, b2, Co * sizeof(float), hipMemcpyDeviceToDevice, s);
-  if (bs) (void)hipMemcpyAsync(bsp, bs, Co * sizeof(float), hipMemcpyDeviceToDevice, s);
   if (launch_vec_add(b2p, bsp, bx, Np, s)) return -3;
   void* op = t.get((size_t)B * HW * Co * 2);
   IgemmParams p;
@@ -566,18 +548,7 @@ int ldmseg_op_conv3x3_plus_1x1(const float* h, const float* w2, const float* b2,
   if (sp > 1) { p.splits = sp; p.partial = (float*)t.get((size_t)sp * p.M * Np * sizeof(float)); }
   const int r = launch_igemm(p, dtype, s);
   if (r) return r;
-  if (iters > 0 && us_per_launch) {
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, s);
-    for (int i = 0; i < iters; ++i) (void)launch_igemm(p, dtype, s);
-    (void)hipEventRecord(e1, s);
-    (void)hipEventSynchronize(e1);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    *us_per_launch = 1e3f * ms / iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  }
+  if (iters > 0 && us_per_launch) *us_per_launch = time_launches(s, 0, iters, [&](int) { (void)launch_igemm(p, dtype, s); });
   if (!out) return 0;
   return unpack_nhwc(op, out, B, Co, HW, Co, dtype, s);
 }
@@ -618,21 +589,9 @@ int ldmseg_bench_attention(const float* qkv, int B, int N, int C, int heads, int
   void* qp = t.get((size_t)B * N * 3 * C * es(dtype));
   to_dev_dtype(qkv, qp, (size_t)B * N * 3 * C, dtype, s);
   void* op = t.get((size_t)B * N * C * es(dtype));
-  for (int i = 0; i < 3; ++i) {
-    const int r = launch_attention(qp, op, B, N, C, heads, dtype, s);
-    if (r) return r;
-  }
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  (void)hipEventRecord(e0, s);
-  for (int i = 0; i < iters; ++i) (void)launch_attention(qp, op, B, N, C, heads, dtype, s);
-  (void)hipEventRecord(e1, s);
-  (void)hipEventSynchronize(e1);
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  *us_per_launch = 1e3f * ms / iters;
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  return 0;
+  int err = 0;
+  *us_per_launch = time_launches(s, 3, iters, [&](int) { if (const int r = launch_attention(qp, op, B, N, C, heads, dtype, s)) err = err ? err : r; });
+  return err;
 }
 
 // F.linear(F.layer_norm(x, (K,), gamma, beta, eps), w, bias) - or the GEGLU feed-forward half on the normalised input when
@@ -657,24 +616,15 @@ int op_ln_linear_impl(const float* x, const float* gamma, const float* beta, con
   const int bn = (!geglu && N % 160 != 0) ? 160 : igemm_pick_bn(N, epi);     // (the folded instantiations: 160 columns, GEGLU 128)
   const int Np = rupi(N, bn);
   const int nout = geglu ? N / 2 : N;
-  std::vector<int> map(Np);
-  for (int r = 0; r < Np; ++r) {
-    if (geglu) { const int blk = r / 32, q = r % 32; map[r] = (q < 16) ? blk * 16 + q : nout + blk * 16 + (q - 16); }
-    else map[r] = r < N ? r : -1;
-  }
-  int* dmap = (int*)t.get(Np * sizeof(int));
-  (void)hipMemcpy(dmap, map.data(), Np * sizeof(int), hipMemcpyHostToDevice);
+  std::vector<int> map;
+  if (geglu) { map = geglu_row_map(nout); map.resize(Np, -1); }
+  LnFold f;
+  f.w[0] = w; f.bias[0] = bias; f.Nper = N; f.K = K; f.Npad = Np; f.gamma = gamma; f.beta = beta; f.dtype = dtype;
+  if (geglu) f.row_map = &map;
   void* wp = t.get((size_t)Np * K * es(dtype));
-  void* wb = t.get((size_t)Np * K * sizeof(float));
-  float* pb = (float*)t.get(Np * sizeof(float));
   float* c1 = (float*)t.get(Np * sizeof(float));
   float* c2 = (float*)t.get(Np * sizeof(float));
-  (void)hipMemsetAsync(pb, 0, Np * sizeof(float), s);
-  if (launch_repack_rows_scaled(w, wp, dmap, Np, K, gamma, dtype, s)) return -3;
-  if (launch_repack_rows_scaled(w, wb, dmap, Np, K, beta, DT_F32, s)) return -3;
-  if (bias && launch_repack_rows(bias, pb, dmap, Np, 1, DT_F32, s)) return -3;
-  if (launch_rowsum(wp, nullptr, c1, Np, K, dtype, s)) return -3;
-  if (launch_rowsum(wb, pb, c2, Np, K, DT_F32, s)) return -3;
+  if (launch_ln_fold(f, t.get(ln_fold_scratch_bytes(f)), wp, c1, c2, s)) return -3;
   float* stats = (float*)t.get((size_t)M * 2 * sizeof(float));
   if (launch_rowstats(xp, stats, M, K, eps, dtype, s)) return -3;
   void* op = t.get((size_t)M * nout * es(dtype));
@@ -739,23 +689,13 @@ int ldmseg_op_transformer_ff(const float* h, const float* x, const float* gamma,
   void* op = t.get((size_t)M * C * es(dtype));
   to_dev_dtype(h, h0, (size_t)M * C, dtype, s);
   to_dev_dtype(x, xp, (size_t)M * C, dtype, s);
-  std::vector<int> map(N1), ident(C);
-  for (int r = 0; r < N1; ++r) { const int blk = r / 32, q = r % 32; map[r] = (q < 16) ? blk * 16 + q : 4 * C + blk * 16 + (q - 16); }
-  for (int r = 0; r < C; ++r) ident[r] = r;
-  int* dmap = (int*)t.get(N1 * sizeof(int));
-  int* dident = (int*)t.get(C * sizeof(int));
-  (void)hipMemcpy(dmap, map.data(), N1 * sizeof(int), hipMemcpyHostToDevice);
-  (void)hipMemcpy(dident, ident.data(), C * sizeof(int), hipMemcpyHostToDevice);
+  const std::vector<int> map = geglu_row_map(4 * C);
+  LnFold f;
+  f.w[0] = w1; f.bias[0] = b1; f.Nper = N1; f.K = C; f.Npad = N1; f.gamma = gamma; f.beta = beta; f.row_map = &map; f.dtype = dtype;
   void* w1p = t.get((size_t)N1 * C * es(dtype));
-  void* w1b = t.get((size_t)N1 * C * sizeof(float));
-  float* pb = (float*)t.get(N1 * sizeof(float));
   float* c1 = (float*)t.get(N1 * sizeof(float));
   float* c2 = (float*)t.get(N1 * sizeof(float));
-  if (launch_repack_rows_scaled(w1, w1p, dmap, N1, C, gamma, dtype, s)) return -3;
-  if (launch_repack_rows_scaled(w1, w1b, dmap, N1, C, beta, DT_F32, s)) return -3;
-  if (launch_repack_rows(b1, pb, dmap, N1, 1, DT_F32, s)) return -3;
-  if (launch_rowsum(w1p, nullptr, c1, N1, C, dtype, s)) return -3;
-  if (launch_rowsum(w1b, pb, c2, N1, C, DT_F32, s)) return -3;
+  if (launch_ln_fold(f, t.get(ln_fold_scratch_bytes(f)), w1p, c1, c2, s)) return -3;
   void* w2p = t.get((size_t)C * 4 * C * es(dtype));
   void* wpp = t.get((size_t)C * C * es(dtype));
   to_dev_dtype(w2, w2p, (size_t)C * 4 * C, dtype, s);        // Linear weights are already [N][K]
@@ -795,19 +735,7 @@ int ldmseg_op_transformer_ff(const float* h, const float* x, const float* gamma,
     return proj ? 0 : gemm(hp, C, wpp, C, C, bpd, xp, op, EPI_STORE, nullptr, nullptr);
   };
   if (int r = run()) return r;
-  if (time_iters > 0 && us_per_call) {
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    for (int i = 0; i < 2; ++i) (void)run();
-    (void)hipEventRecord(e0, s);
-    for (int i = 0; i < time_iters; ++i) (void)run();
-    (void)hipEventRecord(e1, s);
-    (void)hipEventSynchronize(e1);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    *us_per_call = 1e3f * ms / time_iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  }
+  if (time_iters > 0 && us_per_call) *us_per_call = time_launches(s, 2, time_iters, [&](int) { (void)run(); });
   from_dev_dtype(op, out, (size_t)M * C, dtype, s);
   return 0;
 }
@@ -844,24 +772,15 @@ static int transformer_in_impl(const float* x, const float* gn_gamma, const floa
   void* hp = t.get((size_t)M * C * es(dtype));
   void* qp = t.get((size_t)M * 3 * C * es(dtype));
   to_dev_dtype(x, xp, (size_t)M * C, dtype, s);
-  std::vector<int> ident(C);
-  for (int r = 0; r < C; ++r) ident[r] = r;
-  int* dident = (int*)t.get(C * sizeof(int));
-  (void)hipMemcpy(dident, ident.data(), C * sizeof(int), hipMemcpyHostToDevice);
   void* wpp = t.get((size_t)C * C * es(dtype));
   to_dev_dtype(wp, wpp, (size_t)C * C, dtype, s);
   void* wqkv = t.get((size_t)3 * C * C * es(dtype));
-  void* wb = t.get((size_t)3 * C * C * sizeof(float));
-  const float* ws3[3] = {wq, wk, wv};
-  for (int i = 0; i < 3; ++i) {
-    if (launch_repack_rows_scaled(ws3[i], (char*)wqkv + (size_t)i * C * C * es(dtype), dident, C, C, gamma, dtype, s)) return -3;
-    if (launch_repack_rows_scaled(ws3[i], (char*)wb + (size_t)i * C * C * sizeof(float), dident, C, C, beta, DT_F32, s)) return -3;
-  }
-  float* bias4 = (float*)t.get((size_t)4 * C * sizeof(float));
+  float* bias4 = (float*)t.get((size_t)4 * C * sizeof(float));      // proj_in bias | W_q beta | W_k beta | W_v beta
   float* c1 = (float*)t.get((size_t)3 * C * sizeof(float));
   (void)hipMemcpyAsync(bias4, bp, C * sizeof(float), hipMemcpyDeviceToDevice, s);
-  if (launch_rowsum(wqkv, nullptr, c1, 3 * C, C, dtype, s)) return -3;
-  if (launch_rowsum(wb, nullptr, bias4 + C, 3 * C, C, DT_F32, s)) return -3;
+  LnFold f;
+  f.parts = 3; f.w[0] = wq; f.w[1] = wk; f.w[2] = wv; f.Nper = C; f.K = C; f.Npad = 3 * C; f.gamma = gamma; f.beta = beta; f.dtype = dtype;
+  if (launch_ln_fold(f, t.get(ln_fold_scratch_bytes(f)), wqkv, c1, bias4 + C, s)) return -3;
   void* stream_w = nullptr;
   if (mode != 0) {
     stream_w = t.get(proj_qkv_stream_bytes(C));
@@ -897,19 +816,7 @@ static int transformer_in_impl(const float* x, const float* gn_gamma, const floa
     return launch_proj_qkv_fused(xin, hp, qp, stream_w, bias4, igemm_zero_page(), M, C, eps, nullptr, s);
   };
   if (int r = run()) return r;
-  if (time_iters > 0 && us_per_call) {
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    for (int i = 0; i < 2; ++i) (void)run();
-    (void)hipEventRecord(e0, s);
-    for (int i = 0; i < time_iters; ++i) (void)run();
-    (void)hipEventRecord(e1, s);
-    (void)hipEventSynchronize(e1);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    *us_per_call = 1e3f * ms / time_iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  }
+  if (time_iters > 0 && us_per_call) *us_per_call = time_launches(s, 2, time_iters, [&](int) { (void)run(); });
   from_dev_dtype(hp, h_out, (size_t)M * C, dtype, s);
   from_dev_dtype(qp, qkv_out, (size_t)M * 3 * C, dtype, s);
   return 0;
@@ -946,9 +853,7 @@ int ldmseg_op_conv_out_tail(const float* x, const float* w, const float* bias, i
   if (launch_pack_nchw(x, xp, B, 320, H * W, 320, 1.f, 0.f, DT_BF16, s)) return -3;
   void* wp = t.get((size_t)32 * 9 * 320 * 2);
   if (launch_repack_conv(w, wp, 4, 320, 3, 3, 32, 320, DT_BF16, s)) return -3;
-  float* bp = (float*)t.get(32 * sizeof(float));
-  (void)hipMemsetAsync(bp, 0, 32 * sizeof(float), s);
-  if (bias) (void)hipMemcpyAsync(bp, bias, 4 * sizeof(float), hipMemcpyDeviceToDevice, s);
+  float* bp = padded_bias(t, bias, 4, 32, s);
   if (igemm_warm()) return -3;
   StepTail st;
   st.x = xp; st.w = wp; st.bias = bp; st.zeros = igemm_zero_page(); st.B = B; st.H = H; st.W = W; st.eps_out = eps_out;
@@ -980,17 +885,7 @@ int ldmseg_op_attention_fp8(const float* qkv, int B, int N, int C, int heads, fl
   int r = launch_attention_fp8(qp, kp, op, B, N, C, heads, s);
   if (r) return r;
   if (time_iters > 0 && us_per_launch) {
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    for (int i = 0; i < 2; ++i) (void)launch_attention_fp8(qp, kp, op, B, N, C, heads, s);
-    (void)hipEventRecord(e0, s);
-    for (int i = 0; i < time_iters; ++i) (void)launch_attention_fp8(qp, kp, op, B, N, C, heads, s);
-    (void)hipEventRecord(e1, s);
-    (void)hipEventSynchronize(e1);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    *us_per_launch = 1e3f * ms / time_iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    *us_per_launch = time_launches(s, 2, time_iters, [&](int) { (void)launch_attention_fp8(qp, kp, op, B, N, C, heads, s); });
   }
   if (out) from_dev_dtype(op, out, (size_t)B * N * C, DT_BF16, s);
   return 0;
