@@ -274,6 +274,38 @@ int ldmseg_clip_vision_forward(ldmseg_clip_vision* h, const float* pixel_values,
 int ldmseg_clip_vision_describe(ldmseg_clip_vision* h, const float* rgb, int B, int H, int W, const float mean[3],
                                 const float std[3], float* last_hidden, float* image_embeds, void* stream);
 
+/* ---- CLIP text encoder: the conditioning model of image_descriptors `none` ------------------ */
+/* transformers CLIPTextModel, SD-1.x's text_encoder (loaded at ldmseg/models/descriptors.py:98-103, called on the tokenised
+ * prompts and on the empty prompts at trainers_ldm_cond.py:1108-1119, which read [0] = last_hidden_state).  Token + position
+ * embedding, num_layers pre-norm blocks (CAUSAL self-attention with head dim 64, quick-GELU MLP), final_layer_norm on every
+ * row.  All LayerNorms eps 1e-5; no padding mask (the reference passes none).  pooler_output is not computed: nothing reads
+ * it.  The arithmetic is transformers' (not vendored by the reference): parity is pinned against tests/clip_text_ref.py,
+ * which the CPU suite pins against transformers itself. */
+typedef struct ldmseg_clip_text ldmseg_clip_text;  /* opaque */
+typedef struct {
+  int32_t vocab_size;         /* 49408 */
+  int32_t max_positions;      /* 77 */
+  int32_t hidden_size;        /* 768; 64 * num_heads, at most 1280 */
+  int32_t intermediate_size;  /* 3072; a multiple of 64 */
+  int32_t num_layers;         /* 12 */
+  int32_t num_heads;          /* 12 */
+  int32_t compute_dtype;      /* LDMSEG_F32 | LDMSEG_BF16 | LDMSEG_BF16X3 */
+  int32_t device;
+} ldmseg_clip_text_cfg;
+/* keys: CLIPTextModel.state_dict() without the `text_model.` prefix - embeddings.{token_embedding,position_embedding}.weight,
+ * encoder.layers.{i}.{layer_norm1, self_attn.{q,k,v,out}_proj, layer_norm2, mlp.fc1, mlp.fc2}.{weight,bias},
+ * final_layer_norm.{weight,bias} (embeddings.position_ids is ignored).  Both embedding tables stay fp32 in the handle.
+ * LDMSEG_E_SHAPE for a configuration the kernels do not serve (the limits of the vision handle). */
+int ldmseg_clip_text_create(const ldmseg_clip_text_cfg* cfg, int n_weights, const char* const* names,
+                            const void* const* dev_ptrs, const int64_t* numels, ldmseg_clip_text** out);
+void ldmseg_clip_text_destroy(ldmseg_clip_text* h);
+int64_t ldmseg_clip_text_num_params(const ldmseg_clip_text* h);
+/* CLIPTextModel(input_ids).last_hidden_state -> last_hidden [R, T, hidden] fp32; input_ids_dev: int64 [R, T] on the device,
+ * 1 <= T <= max_positions (LDMSEG_E_SHAPE otherwise).  Ids are clamped to [0, vocab_size) for memory safety only: checking
+ * their range is the caller's job (the Python wrapper raises IndexError).  The workspace is planned per (R, T), grows
+ * lazily and never shrinks. */
+int ldmseg_clip_text_forward(ldmseg_clip_text* h, const int64_t* input_ids_dev, int R, int T, float* last_hidden, void* stream);
+
 /* ---- scheduler: ldmseg/schedulers/ddim_scheduler.py --------------------------------------- */
 /* DDIMNoiseScheduler.step (:218-269), elementwise over n floats.  The four coefficients are
  * the 0-d fp32 values the reference computes on the host (alpha_prod_t**0.5, ...); every

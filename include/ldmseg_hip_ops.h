@@ -36,6 +36,9 @@ int ldmseg_op_layernorm(const float* x, const float* gamma, const float* beta, i
                         int dtype, float* out, void* stream);
 /* diffusers Attention core on fused qkv [B,N,3C] -> [B,N,C] */
 int ldmseg_op_attention(const float* qkv, int B, int N, int C, int heads, int dtype, float* out, void* stream);
+/* the same under a causal mask (key j contributes to query i iff j <= i, built in the kernel from the indices): the attention
+ * of transformers' CLIPTextModel.  Head dim 64 only (C == 64 * heads), any N >= 1; dtype 0 / 1 / 2 */
+int ldmseg_op_attention_causal(const float* qkv, int B, int N, int C, int heads, int dtype, float* out, void* stream);
 /* cross-attention core (diffusers Attention with a context, attn2): q [B,N,C], kv = to_k | to_v of the context [B,S,2C]
  * (channel = head*d + i), heads 8 -> out [B,N,C]; any S >= 1, d = C / heads in {40, 80, 160}; dtype 0 / 1 / 2 */
 int ldmseg_op_attention_cross(const float* q, const float* kv, int B, int N, int S, int C, int heads, int dtype, float* out,
@@ -113,6 +116,13 @@ int ldmseg_op_ln_linear_silu(const float* x, const float* gamma, const float* be
  * zero beyond 3 P P.  mean / std: host arrays of 3. */
 int ldmseg_op_clip_patch_rows(const float* img, int B, int H, int W, int S, int P, const float* mean, const float* std,
                               int resample, int dtype, float* out, void* stream);
+/* the row-local kernels of the CLIP text executor (clip_text.hip).  _tokens: out[r][t] = tok[ids[r][t]] + pos[t], summed in
+ * fp32 and rounded once to `dtype` (ids int64 [R, T], tok [vocab, C], pos [>= T, C], out [R * T, C] fp32 holding the rounded
+ * values).  _final_ln: out = F.layer_norm(x, (C,), gamma, beta, eps) of every row of x [M, C] as stored in `dtype`. */
+int ldmseg_op_clip_text_tokens(const int64_t* ids, const float* tok, const float* pos, int R, int T, int C, int vocab, int dtype,
+                               float* out, void* stream);
+int ldmseg_op_clip_text_final_ln(const float* x, const float* gamma, const float* beta, int M, int C, float eps, int dtype,
+                                 float* out, void* stream);
 /* The tail of a transformer block on [M, C] token rows (diffusers BasicTransformerBlock.ff + Transformer2DModel.proj_out,
  * /root/reference/ldmseg/models/unet.py:401-425):  h2 = h + ff.net.2(GEGLU(ff.net.0.proj(LayerNorm(h))));  out = proj_out(h2) + x.
  * mode 0 = the unfused launches, 1 = row-local fused feed-forward (tfuse.hip) + proj_out GEMM, 3 = all in the fused kernel

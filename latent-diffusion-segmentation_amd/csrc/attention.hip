@@ -1,6 +1,7 @@
 // Tiled online-softmax ("flash") self-attention for the UNet transformer blocks
-// (8 heads, head dims 40 / 80 / 160, N = H*W tokens) and the CLIP vision encoder
-// (head dim 64, N = 257 tokens) on gfx950 MFMA.
+// (8 heads, head dims 40 / 80 / 160, N = H*W tokens), the CLIP vision encoder
+// (head dim 64, N = 257 tokens) and, under a causal mask, the CLIP text encoder
+// (head dim 64, N <= 77 tokens) on gfx950 MFMA.
 //
 // Input is the fused projection qkv [B, N, 3C] (q | k | v, channel = head*d + i,
 // SURVEY App. A); output [B, N, C].  Per workgroup: 4 waves x QF x 16 query rows;
@@ -43,12 +44,19 @@ template <typename T, int D> struct AttnCfg {
 // once per tile when they are committed to the LDS, as two planes of the bf16 layout; Q once per workgroup; the probabilities in
 // registers - and every product block is three MFMAs, Xl.Yh + Xh.Yl + Xh.Yh, with fp32 accumulation: the arithmetic of igemm.hip's
 // x3 path on the bf16 kernel's structure (8 keys per 16-byte chunk, ones row of V^T for the row sums).
-template <typename T, int D, int QF, bool X3 = false>
+// CAUSAL (the CLIP text encoder, QF = 1): key j contributes to query i iff j <= i, the mask built from the indices.  A query block
+// of 64 rows visits key tiles 0 .. qb in ascending order and stops there - the tiles above its diagonal are neither loaded nor
+// multiplied - and only the diagonal tile takes the masked (RAGGED) form.  Scores are set to -inf before the row maximum, so a
+// masked key's probability is exp2(-inf - m) = +0 exactly and its K / V rows cannot reach the output.  Key qb * 64 of the
+// diagonal tile is valid for all 64 rows of the block, so no row ever meets a wholly masked tile and the running maximum is
+// finite from tile 0 on (the exp2(-inf - (-inf)) = NaN trap of the line marked "finite" below).
+template <typename T, int D, int QF, bool X3 = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void attention_kernel(const std::conditional_t<X3, float, T>* __restrict__ qkv,
                                                         std::conditional_t<X3, float, T>* __restrict__ out,
                                                         int N, int C, int heads, float scale_log2e) {
   using IO = std::conditional_t<X3, float, T>;
   static_assert(!X3 || sizeof(T) == 2, "the split-bf16 form runs on the bf16 layout");
+  static_assert(!CAUSAL || QF == 1, "causal: one 64-row query block against 64-key tiles, the diagonal tile is tile qb");
   using Cfg = AttnCfg<T, D>;
   constexpr int PC = Chunk<T>::N;
   constexpr int NCH = BKV * Cfg::DCH;          // real 16-B chunks of one K (or V) tile
@@ -223,7 +231,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const std::conditional_t
     else krow_f[f] = 16 * f + lq;
   }
 
-  const int ntiles = (N + BKV - 1) / BKV;
+  const int ntiles = CAUSAL ? qb + 1 : (N + BKV - 1) / BKV;   // causal: up to the diagonal tile (qb < ceil(N / 64))
   const int nfull = N / BKV;                 // tiles without masked keys
   __syncthreads();
   ATTN_COMMIT(0, kregA, vregA)
@@ -274,12 +282,13 @@ __global__ __launch_bounds__(256) void attention_kernel(const std::conditional_t
             if constexpr (sizeof(T) == 2) kv = kv0 + 32 * (f >> 1) + 8 * lg + r + 4 * (f & 1);
             else kv = kv0 + 16 * f + 4 * lg + r;
             if (kv >= N) z = -INFINITY;
+            if constexpr (CAUSAL) { if (kv > q0 + a * 16 + lq) z = -INFINITY; }
             s[a][f][r] = z;
           }
           tmax = fmaxf(tmax, z);
         }
       tmax = xor32_max(xor16_max(tmax));
-      const float mnew = fmaxf(mrow[a], tmax);   // finite: key kv0 is always valid
+      const float mnew = fmaxf(mrow[a], tmax);   // finite: key kv0 is always valid (causal: kv0 <= qb * 64 <= every row of the block)
       grew |= (mnew > mrow[a]);
       alpha[a] = __builtin_amdgcn_exp2f(mrow[a] - mnew);
       mrow[a] = mnew;
@@ -344,7 +353,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const std::conditional_t
   };
 
   auto run_tile = [&](int t, int st) __attribute__((always_inline)) {
-    if (t < nfull) tile(t * BKV, st, std::false_type{});
+    if (CAUSAL ? t < qb : t < nfull) tile(t * BKV, st, std::false_type{});
     else tile(t * BKV, st, std::true_type{});
   };
   if constexpr (NST == 2) {
@@ -407,13 +416,13 @@ __global__ __launch_bounds__(256) void attention_kernel(const std::conditional_t
   }
 }
 
-template <typename T, int D, int QF, bool X3 = false>
+template <typename T, int D, int QF, bool X3 = false, bool CAUSAL = false>
 int run(const void* qkv, void* out, int B, int N, int C, int heads, hipStream_t s) {
   using Cfg = AttnCfg<T, D>;
   using IO = std::conditional_t<X3, float, T>;
   const size_t stage = (size_t)(Cfg::KS_BYTES + Cfg::VT_BYTES) * (X3 ? 2 : 1);
   const size_t lds = (2 * stage <= 144 * 1024 ? 2 : 1) * stage;
-  auto kern = attention_kernel<T, D, QF, X3>;
+  auto kern = attention_kernel<T, D, QF, X3, CAUSAL>;
   static bool attr_set[64] = {};     // per device: a process may hold handles on several GPUs
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
@@ -423,7 +432,9 @@ int run(const void* qkv, void* out, int B, int N, int C, int heads, hipStream_t 
   }
   const int nqb = (N + 64 * QF - 1) / (64 * QF);
   const float scale_log2e = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
-  LDMSEG_LAUNCH(X3 ? launch_name("attn_x3<%d,%d>", D, QF) : launch_name("attn<%s,%d,%d>", dtype_tag<T>(), D, QF), kern,
+  const std::string name = CAUSAL ? (X3 ? launch_name("attn_causal_x3<%d,%d>", D, QF) : launch_name("attn_causal<%s,%d,%d>", dtype_tag<T>(), D, QF))
+                                  : (X3 ? launch_name("attn_x3<%d,%d>", D, QF) : launch_name("attn<%s,%d,%d>", dtype_tag<T>(), D, QF));
+  LDMSEG_LAUNCH(name, kern,
                 dim3(nqb * heads * B), dim3(256), lds, s, (const IO*)qkv, (IO*)out, N, C, heads, scale_log2e);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -472,6 +483,14 @@ int launch_attention(const void* qkv, void* out, int B, int N, int C, int heads,
     if (r != -100) return r;
   }
   return dtype == DT_BF16 ? dispatch<bf16_t>(qkv, out, B, N, C, heads, s) : dispatch<float>(qkv, out, B, N, C, heads, s);
+}
+
+// causal self-attention (the CLIP text encoder): head dim 64 only, any N >= 1
+int launch_attention_causal(const void* qkv, void* out, int B, int N, int C, int heads, int dtype, hipStream_t s) {
+  if (B < 1 || N < 1 || heads < 1 || C != 64 * heads) return -2;
+  if (dtype == 2) return run<bf16_t, 64, 1, true, true>(qkv, out, B, N, C, heads, s);
+  return dtype == DT_BF16 ? run<bf16_t, 64, 1, false, true>(qkv, out, B, N, C, heads, s)
+                          : run<float, 64, 1, false, true>(qkv, out, B, N, C, heads, s);
 }
 
 }  // namespace ldmseg

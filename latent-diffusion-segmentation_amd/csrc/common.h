@@ -133,6 +133,34 @@ __device__ __forceinline__ float wave64_max(float v) { return xor32_max(xor16_ma
 // all-lanes sum of a wave64, result in every lane
 __device__ __forceinline__ float wave64_sum(float v) { return xor32_sum(xor16_sum(row16_sum(v))); }
 
+// ---- one row per 256-thread block, held in registers (the CLIP encoders' row-local kernels: clip_vision.hip, clip_text.hip)
+// sum over a 256-thread block, result in every thread; `red` holds 4 floats
+__device__ __forceinline__ float block256_sum(float v, float* red) {
+  v = wave64_sum(v);
+  __syncthreads();                                      // (the previous reduction's readers are done)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+constexpr int kClipMaxPer = 8;                          // channels per thread: C <= 2048
+
+// LayerNorm of one row held in registers (fp32 statistics, two-pass centred variance)
+template <int PER>
+__device__ __forceinline__ void row_layernorm(float (&v)[PER], int C, float eps, const float* __restrict__ g,
+                                              const float* __restrict__ b, float* red) {
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < PER; ++i) { const int c = threadIdx.x + i * 256; if (c < C) sum += v[i]; }
+  const float mean = block256_sum(sum, red) / (float)C;
+  float sq = 0.f;
+#pragma unroll
+  for (int i = 0; i < PER; ++i) { const int c = threadIdx.x + i * 256; if (c < C) { const float d = v[i] - mean; sq += d * d; } }
+  const float rstd = rsqrtf(block256_sum(sq, red) / (float)C + eps);
+#pragma unroll
+  for (int i = 0; i < PER; ++i) { const int c = threadIdx.x + i * 256; if (c < C) v[i] = (v[i] - mean) * rstd * g[c] + b[c]; }
+}
+
 // k-th storage element of a 16-byte chunk (k must fold to a constant after unrolling); avoids
 // union/array punning, which hipcc leaves in scratch memory
 template <typename T> __device__ __forceinline__ T chunk_elem(const u32x4 c, int k);

@@ -235,6 +235,9 @@ int launch_layernorm(const void* x, void* y, const float* gamma, const float* be
 // self-attention on fused qkv [B, N, 3C] (q | k | v, channel = head*d + i) -> out [B, N, C]
 // dtype 2 = fp32 tensors with the products as three bf16 MFMAs on hi/lo splits (compute_dtype "bf16x3")
 int launch_attention(const void* qkv, void* out, int B, int N, int C, int heads, int dtype, hipStream_t s);
+// the same with a causal mask built in the kernel (key j contributes to query i iff j <= i; key tiles above a query block's diagonal
+// are skipped): head dim 64 only (C == 64 * heads), any N >= 1 - the CLIP text encoder
+int launch_attention_causal(const void* qkv, void* out, int B, int N, int C, int heads, int dtype, hipStream_t s);
 
 // cross-attention (attention_cross.hip): q [B*N, C], kv = to_k | to_v of the context [B*S, 2C] -> out [B*N, C]; any S >= 1 (keys
 // past S masked), head dims 40 / 80 / 160; dtype 0 / 1 / 2 as launch_attention (every product in fp32 on the VALU)
@@ -326,6 +329,15 @@ int launch_clip_tokens(const void* patch, const float* cls, const float* pos, co
 int launch_clip_pooled_ln(const void* h, const float* gamma, const float* beta, float* out, int B, int T, int C, float eps,
                           int dtype, hipStream_t s);
 int launch_clip_rows_to_f32(const void* x, float* y, size_t n, int dtype, hipStream_t s);
+
+// CLIP text encoder, row-local kernels (clip_text.hip)
+// h[r][t] = tok[ids[r][t]] + pos[t] (fp32 sum, rounded once) -> [R * T][C] in the compute dtype; ids int64 on the device, clamped to
+// [0, vocab) for memory safety only
+int launch_clip_text_tokens(const int64_t* ids, const float* tok, const float* pos, void* h, int R, int T, int C, int vocab,
+                            int dtype, hipStream_t s);
+// out[m] = LayerNorm(h[m]) for every row -> fp32 [M][C] (final_layer_norm; two-pass fp32 statistics)
+int launch_clip_text_final_ln(const void* h, const float* gamma, const float* beta, float* out, int M, int C, float eps, int dtype,
+                              hipStream_t s);
 
 // fp8 (e4m3) operand path of the bf16 attention for the long-context levels (attention_fp8.hip): head dims 40 / 80 only
 size_t attention_fp8_scratch_bytes(int B, int N, int C, int heads);

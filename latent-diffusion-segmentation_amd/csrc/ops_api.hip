@@ -359,6 +359,41 @@ int ldmseg_op_attention(const float* qkv, int B, int N, int C, int heads, int dt
   return 0;
 }
 
+int ldmseg_op_attention_causal(const float* qkv, int B, int N, int C, int heads, int dtype, float* out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (B < 1 || N < 1 || heads < 1 || C != 64 * heads) return -2;
+  Temp t;
+  void* qp = t.get((size_t)B * N * 3 * C * es(dtype));
+  to_dev_dtype(qkv, qp, (size_t)B * N * 3 * C, dtype, s);
+  void* op = t.get((size_t)B * N * C * es(dtype));
+  const int r = launch_attention_causal(qp, op, B, N, C, heads, dtype, s);
+  if (r) return r;
+  from_dev_dtype(op, out, (size_t)B * N * C, dtype, s);
+  return 0;
+}
+
+int ldmseg_op_clip_text_tokens(const int64_t* ids, const float* tok, const float* pos, int R, int T, int C, int vocab, int dtype,
+                               float* out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (R < 1 || T < 1 || C < 1 || vocab < 1) return -2;
+  Temp t;
+  void* hp = t.get((size_t)R * T * C * es(dtype));
+  const int r = launch_clip_text_tokens(ids, tok, pos, hp, R, T, C, vocab, dtype, s);
+  if (r) return r;
+  from_dev_dtype(hp, out, (size_t)R * T * C, dtype, s);
+  return 0;
+}
+
+int ldmseg_op_clip_text_final_ln(const float* x, const float* gamma, const float* beta, int M, int C, float eps, int dtype,
+                                 float* out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (M < 1 || C < 1) return -2;
+  Temp t;
+  void* xp = t.get((size_t)M * C * es(dtype));
+  to_dev_dtype(x, xp, (size_t)M * C, dtype, s);
+  return launch_clip_text_final_ln(xp, gamma, beta, out, M, C, eps, dtype, s);
+}
+
 int ldmseg_op_attention_cross(const float* q, const float* kv, int B, int N, int S, int C, int heads, int dtype, float* out,
                               void* stream) {
   hipStream_t s = (hipStream_t)stream;

@@ -37,6 +37,12 @@ class ClipVisionCfg(C.Structure):
                 ("projection_dim", C.c_int32), ("compute_dtype", C.c_int32), ("device", C.c_int32)]
 
 
+class ClipTextCfg(C.Structure):
+    _fields_ = [("vocab_size", C.c_int32), ("max_positions", C.c_int32), ("hidden_size", C.c_int32),
+                ("intermediate_size", C.c_int32), ("num_layers", C.c_int32), ("num_heads", C.c_int32),
+                ("compute_dtype", C.c_int32), ("device", C.c_int32)]
+
+
 class SampleCfg(C.Structure):
     _fields_ = [("n_steps", C.c_int32), ("timesteps", C.POINTER(C.c_int64)), ("coef", C.POINTER(C.c_float)),
                 ("prediction_type", C.c_int32), ("clip_sample", C.c_int32), ("self_condition", C.c_int32),
@@ -82,6 +88,10 @@ SIGNATURES = {
     "ldmseg_clip_vision_num_params": (_i64, [_vp]),
     "ldmseg_clip_vision_forward": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "ldmseg_clip_vision_describe": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _vp]),
+    "ldmseg_clip_text_create": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "ldmseg_clip_text_destroy": (None, [_vp]),
+    "ldmseg_clip_text_num_params": (_i64, [_vp]),
+    "ldmseg_clip_text_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ldmseg_vae_decode_panoptic": (_i, [_vp, _vp, _f, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _f, _i, _d, _i64, _vp, _vp, _vp, _vp, _vp,
                                         _vp]),
     "ldmseg_panoptic_postprocess": (_i, [_vp, _i, _i, _i, _i, _i, _i, _f, _i, _d, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -101,6 +111,9 @@ SIGNATURES = {
     "ldmseg_op_groupnorm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp]),
     "ldmseg_op_layernorm": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _i, _vp, _vp]),
     "ldmseg_op_attention": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ldmseg_op_attention_causal": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ldmseg_op_clip_text_tokens": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ldmseg_op_clip_text_final_ln": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp]),
     "ldmseg_op_attention_cross": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ldmseg_op_attention_fp8": (_i, [_vp, _i, _i, _i, _i, _vp, _i, C.POINTER(C.c_float), _vp]),
     "ldmseg_op_convt2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -243,8 +243,44 @@ def clip_vision_norm_keys(schema):
     return tuple(k for k in schema if k.split(".")[-2] in ("layer_norm1", "layer_norm2", "pre_layrnorm", "post_layernorm"))
 
 
-CLIP_EMBED_KEYS = ("embeddings.class_embedding", "embeddings.position_embedding.weight")
-CLIP_EMBED_STD = 0.02       # CLIP initialises the class token and the position table at this scale
+def clip_text_schema(vocab=49408, hidden=768, intermediate=3072, layers=12, heads=12, positions=77):
+    """Ordered key -> shape of transformers' CLIPTextModel.state_dict() without the ``text_model.`` prefix (SD-1.x's
+    text_encoder, the conditioning model of image_descriptors none, ldmseg/models/descriptors.py:98-103).  The defaults are
+    openai/clip-vit-large-patch14's text tower: 123,060,480 parameters in 196 tensors.  ``heads`` does not shape any tensor;
+    it is listed because the configuration needs it."""
+    if hidden % heads:
+        raise ValueError("hidden must be a multiple of heads")
+    sd = OrderedDict()
+    sd["embeddings.token_embedding.weight"] = (vocab, hidden)
+    sd["embeddings.position_embedding.weight"] = (positions, hidden)
+
+    def norm(name):
+        sd[name + ".weight"] = (hidden,)
+        sd[name + ".bias"] = (hidden,)
+
+    def linear(name, co, ci):
+        sd[name + ".weight"] = (co, ci)
+        sd[name + ".bias"] = (co,)
+
+    for i in range(layers):
+        p = f"encoder.layers.{i}."
+        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            linear(p + "self_attn." + n, hidden, hidden)
+        norm(p + "layer_norm1")
+        linear(p + "mlp.fc1", intermediate, hidden)
+        linear(p + "mlp.fc2", hidden, intermediate)
+        norm(p + "layer_norm2")
+    norm("final_layer_norm")
+    return sd
+
+
+def clip_text_norm_keys(schema):
+    """The LayerNorm tensors of a clip_text_schema (``norm_keys`` of generate())."""
+    return tuple(k for k in schema if k.split(".")[-2] in ("layer_norm1", "layer_norm2", "final_layer_norm"))
+
+
+CLIP_EMBED_KEYS = ("embeddings.class_embedding", "embeddings.position_embedding.weight", "embeddings.token_embedding.weight")
+CLIP_EMBED_STD = 0.02       # CLIP initialises the class token, the position table and the token table at this scale
 
 
 def count_params(schema):
