@@ -150,6 +150,12 @@ int ldmseg_bench_attention(const float* qkv, int B, int N, int C, int heads, int
 /* "igemm<dtype,BM,BN,WM,WN,NST,PIPE,LDR> splits=S grid=G": template instantiation and plan of the most recent igemm
  * launch of this process - lets a parity test assert WHICH kernel it just compared with the oracle. */
 int ldmseg_igemm_last_kernel(char* buf, int n);
+/* The same string for a launch that is only described - what ldmseg_igemm_last_kernel would report after it, under the current
+ * ldmseg_debug_set state, on a device of `cus` compute units.  No device is touched.  desc: 17 ints, M, N, C0, C1, C2, C3, taps,
+ * stride, up, up4, cm, epi (0 store, 1 GEGLU), lnf (a LayerNorm is folded), x3, splits (0 = planned the way the engines plan the
+ * K slices), no_finish, region (the caller has a counter region for the in-launch finish).  dtype 0 fp32, 1 bf16, 2 / 3 = fp32
+ * with x3 = 1 / 2 as the operators take it.  Returns 0, or -2 when the library has no such launch. */
+int ldmseg_op_igemm_plan(const int* desc, int dtype, int cus, char* buf, int n);
 /* enable=1 clears and starts a log of the DISTINCT igemm instantiations launched ("igemm<...>" + "/splitk" for K-sliced
  * launches; ",x3" / ",x3w" for split-bf16 products) and of the fused GEMM kernels; enable=2 logs every kernel of the UNet
  * forward path (split-K finish, GroupNorm, LayerNorm statistics, attention too), each named with its template arguments and

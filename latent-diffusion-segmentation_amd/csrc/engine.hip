@@ -2501,8 +2501,7 @@ int ldmseg_debug_get(int key) {
 // "igemm<bf16,BM,BN,WM,WN,NST,PIPE,LDR>[/splitk] splits=S grid=G" of the most recent igemm launch
 int ldmseg_igemm_last_kernel(char* buf, int n) {
   if (!buf || n < 1) return LDMSEG_E_ARG;
-  const IgemmDispatch d = igemm_last_dispatch();
-  std::snprintf(buf, (size_t)n, "%s splits=%d grid=%d", igemm_dispatch_name(d).c_str(), d.splits, d.grid);
+  std::snprintf(buf, (size_t)n, "%s", igemm_dispatch_line(igemm_last_dispatch()).c_str());
   return 0;
 }
 int ldmseg_igemm_log(int enable) { igemm_log_enable(enable); return 0; }

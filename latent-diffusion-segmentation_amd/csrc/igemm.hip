@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "igemm_plan.h"
 #include "kernels.h"
 
 namespace ldmseg {
@@ -1228,7 +1229,6 @@ const void* zero_page() {
   return z[dev];
 }
 
-constexpr int kDefaultPolicy = 61;
 }  // namespace
 std::string igemm_dispatch_name(const IgemmDispatch& d);
 namespace {
@@ -1237,55 +1237,27 @@ std::set<std::string> g_log;   // distinct instantiations launched while logging
 IgemmDispatch g_last{};   // what the last launch_igemm on this thread's process ran (parity tests assert on it)
 int g_dbg = 0;       // ablation flags (profiling experiments only)
 void* g_tsbuf = nullptr;   // s_memtime stamp buffer (LDMSEG_IGEMM_ABLATE builds)
-int g_big = kDefaultPolicy;      // bit0: 8-wave 256-row tiles with a 3-stage ring (-0.15 ms per forward, on);
-                     // bit1: 4-stage ring, one workgroup per CU, for mid-size grids (+0.5 ms, off)
-                     // bit2: lone 64-row 4-stage tiles; bit3: pipelined K loop on the 256-row tiles; bit4: 8-wave 128-row
-                     // tiles (+ loader waves on long K); bit5: loader waves on the 256-row tiles (long K / GEGLU)
+IgemmKnobs g_knobs;        // the igemm_set_* / ldmseg_debug_set state the chooser reads (igemm_plan.h)
 
-int g_force_cfg = -1;            // tools/tune_igemm.py: run every launch with this entry of the instantiation list
-int g_cf_mode = 5;               // igemm_set_cf_mode (debug key 23)
-int g_cm_mode = -1;              // igemm_set_cm_mode
-
-// Launch table measured on the MI355X (tools/tune_igemm.py): launch shape -> entry of the instantiation list in run_cfg()
-// + number of K slices.  Shapes that are not listed (other batch sizes, other models) use the rules in dispatch() /
-// igemm_plan_splits(); so does every launch while a non-default tile policy is set (tests, ablations).
-struct TunedEntry { int dtype, M, N, K, taps, stride, up, epi, lnf, cfg, splits; };
-const TunedEntry kTuned[] = {
-#include "igemm_tuned.inc"
-    {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}};
-
-int g_table_override = -1;       // igemm_set_table_override (debug key 24)
-const TunedEntry* tuned_lookup(const IgemmParams& p, int dtype) {
-  if (g_big != kDefaultPolicy || g_force_cfg >= 0) return nullptr;
-  if (g_table_override >= 0 && p.epi == EPI_STORE && !p.rowstats) {     // tuning: every plain-store launch as if the table held this entry
-    static thread_local TunedEntry e;
-    e = TunedEntry{dtype, p.M, p.N, 0, p.taps, p.stride, p.up, p.epi, 0, g_table_override & 0xff, (g_table_override >> 8) & 0xff};
-    if (e.splits < 1) e.splits = 1;
-    return &e;
-  }
-  const int K = p.taps * (p.C0 + p.C1), lnf = p.rowstats ? 1 : 0;
-  for (const TunedEntry* e = kTuned; e->dtype >= 0; ++e)
-    if (e->M == p.M && e->N == p.N && e->K == K && e->dtype == dtype && e->taps == p.taps && e->stride == p.stride &&
-        e->up == p.up && e->epi == p.epi && e->lnf == lnf)
-      return e;
-  return nullptr;
+IgemmLaunchDesc describe(const IgemmParams& p) {
+  return {p.M, p.N, p.C0, p.C1, p.C2, p.C3, p.taps, p.stride, p.up, p.up4, p.cm, p.epi, p.rowstats ? 1 : 0, p.x3, p.splits, p.no_finish, p.cf_ctr ? 1 : 0};
 }
 
-// the instantiations that exist with the in-launch finish: bf16, the four tile forms K-sliced launches of the UNet run on
-template <typename T, int BM, int BN, int WM, int WN, int NST, bool PIPE, int LDR, bool LNF, bool CM, bool XT, bool UP4>
-constexpr bool cf_instantiated() {
-  if (sizeof(T) != 2 || BN != 160 || LNF || CM) return false;
-  const bool c0 = BM == 256 && WM == 4 && WN == 2 && NST == 3 && PIPE && LDR == 4;      // entry 0 of the instantiation list
-  const bool c3 = BM == 128 && WM == 2 && WN == 2 && NST == 4 && PIPE && LDR == 4;      // entry 3
-  const bool c4 = BM == 128 && WM == 4 && WN == 2 && NST == 3 && PIPE && LDR == 0;      // entry 4
-  const bool c10 = BM == 64 && WM == 2 && WN == 2 && NST == 4 && PIPE && LDR == 4;      // entry 10
-  if (UP4) return c0 && !XT;
-  if (XT) return c0 || c3 || c4;
-  return c0 || c3 || c4 || c10;
+// the split-K finish every kernel of the family shares (p.splits > 1, slabs written; p as run() filled it)
+template <typename T>
+int launch_finish(const IgemmParams& p, hipStream_t s) {
+  const int nq = p.n_valid >> 2;
+  const int gx = (nq + 63) / 64;
+  int gy = (p.M + 3) / 4;
+  if (gy > 2048 / gx) gy = 2048 / gx > 0 ? 2048 / gx : 1;
+  LDMSEG_LAUNCH(launch_name("splitk_finish<%s>", dtype_tag<T>()), splitk_finish_kernel<T>, dim3(gx, gy), dim3(256), 0, s, p);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
 }
-template <typename T, int BM, int BN, int WM, int WN, int NST = 2, bool PIPE = false, int LDR = 0, bool LNF = false, bool CM = false, bool XT = false,
-          bool UP4 = false>
-int run(const IgemmParams& pin, hipStream_t s) {
+
+// One instantiation, launched as the chooser planned it (d): what is left here needs the device.  CF: it has the twin with the
+// in-launch finish.
+template <typename T, int BM, int BN, int WM, int WN, int NST, bool PIPE, int LDR, bool LNF, bool CM, bool XT, bool UP4, bool CF>
+int run(const IgemmDispatch& d, const IgemmParams& pin, hipStream_t s) {
   IgemmParams p = pin;
   p.dbg = g_dbg;
   p.ts = (unsigned long long*)g_tsbuf;
@@ -1296,264 +1268,68 @@ int run(const IgemmParams& pin, hipStream_t s) {
   p.fd_wo = fastdiv_make(p.Wo);
   p.fd_nt = fastdiv_make(nt);
   p.fd_ntiles = fastdiv_make(mt * nt);
-  p.fd_nsplit = fastdiv_make(p.splits > 1 ? p.splits : 1);
+  p.fd_nsplit = fastdiv_make(d.splits);
   p.fd_mphase = fastdiv_make(p.up4 ? p.M / 4 : 1);
   p.fd_tpt = fastdiv_make(CM ? 9 : (p.C0 + p.C1) / (int)(kRowBytes / sizeof(T)));   // CM: K tiles per channel tile
-  const int nwork = mt * nt * (p.splits > 1 ? p.splits : 1);
-  // persistent grid: as many workgroups as fit on the chip at once (2 per CU for the 4-wave tiles,
-  // 1 per CU for the 8-wave ones); each walks nwork / grid items
-  int resident = num_cus() * ((WM * WN == 4 && NST == 2 && LDR == 0) ? 2 : 1);
-  const int grid_x = nwork < resident ? nwork : resident;
   const size_t lds = (size_t)NST * (BM + BN) * kRowBytes +
                      (epi_stage_dedicated<BM, BN, WM, WN>() ? epi_stage_bytes<BM, BN, WM, WN>() : 0);
   auto kern = igemm_kernel<T, BM, BN, WM, WN, NST, PIPE, LDR, LNF, CM, XT, UP4>;
-  constexpr bool kHasCf = cf_instantiated<T, BM, BN, WM, WN, NST, PIPE, LDR, LNF, CM, XT, UP4>();
   static bool attr_set[kMaxDev] = {};
   const int dev = cur_dev();
   if (!attr_set[dev]) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if constexpr (kHasCf)
+    if constexpr (CF)
       (void)hipFuncSetAttribute((const void*)igemm_kernel<T, BM, BN, WM, WN, NST, PIPE, LDR, LNF, CM, XT, UP4, true>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set[dev] = true;
   }
-  // Cooperative finish inside the launch: every (tile, K slice) item has a workgroup of its own and all of them fit on the chip
-  // together (one per CU is what every instantiation can hold), the slab set is addressable through one buffer descriptor,
-  // the tile's counters fit the caller's region.  Otherwise: slabs + the finish kernel.
-  p.cf = 0;
-  // (measured per launch shape, tools/cf_bench.py: the in-launch finish wins 2-4 % on the 256-row tiles with 2-4 slices and loses
-  // 2-20 % on the 128-row tiles with 8 - the serial chain drain -> ticket -> poll -> read costs what boundary + finish launch do;
-  // mode bit 3 takes it on every tile form that has the instantiation)
-  if (kHasCf && (BM == 256 || (g_cf_mode & 8)) && p.splits > 1 && p.splits <= 32 && !p.no_finish && p.cf_ctr && (g_cf_mode & 1) && nwork == grid_x && nwork <= num_cus() &&
-      (size_t)p.splits * p.M * p.N * sizeof(float) < ((size_t)1 << 31) && (size_t)(2 * mt * nt + 2) * 8 <= igemm_cf_bytes()) {
-    p.cf = 1;
-    p.cf_diag = (int)(igemm_cf_bytes() / 8) - 1;
+  p.cf = d.cf;
+  if (p.cf) {
+    p.cf_diag = (int)(kIgemmCfBytes / 8) - 1;
     p.cf_bytes = (unsigned)((size_t)p.splits * p.M * p.N * sizeof(float));
-    const int us = (g_cf_mode >> 8) & 0xffff;
-    p.cf_poll_ticks = (g_cf_mode & 2) ? 0 : (us ? us : 200) * 100;
+    p.cf_poll_ticks = d.cf_poll;
   }
-  g_last = IgemmDispatch{(int)sizeof(T) == 2 ? DT_BF16 : DT_F32, BM, BN, WM, WN, NST, PIPE ? 1 : 0, LDR,
-                         p.splits > 1 ? p.splits : 1, grid_x, LNF ? 1 : 0, CM ? 1 : 0, p.cf, XT ? 1 : 0, UP4 ? 1 : 0,
-                         sizeof(T) == 4 ? p.x3 : 0};
-  if constexpr (kHasCf) {
+  g_last = d;
+  const dim3 grid(d.grid), block((WM * WN + LDR) * 64);
+  if constexpr (CF) {
     if (p.cf) {
-      LDMSEG_LAUNCH_GEMM(igemm_dispatch_name(g_last), (igemm_kernel<T, BM, BN, WM, WN, NST, PIPE, LDR, LNF, CM, XT, UP4, true>), dim3(grid_x),
-                         dim3((WM * WN + LDR) * 64), lds, s, p);
+      LDMSEG_LAUNCH_GEMM(igemm_dispatch_name(d), (igemm_kernel<T, BM, BN, WM, WN, NST, PIPE, LDR, LNF, CM, XT, UP4, true>), grid, block, lds, s, p);
       return hipGetLastError() == hipSuccess ? 0 : -3;
     }
   }
-  LDMSEG_LAUNCH_GEMM(igemm_dispatch_name(g_last), kern, dim3(grid_x), dim3((WM * WN + LDR) * 64), lds, s, p);
-  if (p.splits > 1 && !p.no_finish) {
-    const int nq = p.n_valid >> 2;
-    const int gx = (nq + 63) / 64;
-    int gy = (p.M + 3) / 4;
-    if (gy > 2048 / gx) gy = 2048 / gx > 0 ? 2048 / gx : 1;
-    LDMSEG_LAUNCH(launch_name("splitk_finish<%s>", dtype_tag<T>()), splitk_finish_kernel<T>, dim3(gx, gy), dim3(256), 0, s, p);
-  }
+  LDMSEG_LAUNCH_GEMM(igemm_dispatch_name(d), kern, grid, block, lds, s, p);
+  if (p.splits > 1 && !p.no_finish) return launch_finish<T>(p, s);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-// 8-wave 128-row tile, one workgroup per CU (3-stage ring, pipelined K loop): the mid-size grids
-// (16x16 / 32x32 feature maps) where 128-row tiles x K slices give about one work item per CU.  Versus
-// two co-resident 64-row workgroups it stages 36% fewer operand bytes per FLOP through the LDS DMA.
-inline bool mid8_ok(long t128, int splits) {
-  const long items = t128 * (splits > 1 ? splits : 1);
-  return (g_big & 16) && items >= 160 && items <= 2 * (long)num_cus();
-}
-
-// The instantiation list the launch table indexes (BN and the LayerNorm fold follow from the launch): -2 = not in the list.
-//   0  256 rows, 8 compute + 4 loader waves      3  128 rows, 4 compute + 4 loader waves, 4-stage ring
-//   1  256 rows, 8 waves, pipelined K loop       4  128 rows, 8 waves, pipelined K loop
-//   2  256 rows, 8 waves, plain K loop           5  128 rows, 4 waves, 4-stage ring (one workgroup per CU)
-//   6  64 rows, 4 waves, 4-stage ring            7  64 rows, 4 waves, two workgroups per CU
-//   8  128 rows, 4 waves, two workgroups per CU  9  64 rows, 8 waves (16 x 80 wave tiles), 4-stage ring
-//   10 / 11  64 rows, 4 compute (32 x 80 wave tiles) + 4 loader waves, 4- / 3-stage ring: the M = 512 .. 2048 1x1 launches.
-//      (entry 9 re-reads the W fragments in each of its four wave rows - 98 KB of fragment reads per K tile against 56 KB here -
-//      and its compute waves issue the LDS-DMA themselves: phase ablation of M = 2048, N = K = 1280 showed DMA issue, fragment
-//      reads + MFMA, epilogue and launch skeleton ADDING UP, 4 + 5 + 2 + 5 us; with loader waves 17.0 -> 13.6 us)
-constexpr int kNumCfg = 12;
-template <typename T, int BN, bool LNF>
-int run_cfg(int cfg, const IgemmParams& p, hipStream_t s) {
-  switch (cfg) {
-    case 0: return run<T, 256, BN, 4, 2, 3, true, 4, LNF>(p, s);
-    case 1: return run<T, 256, BN, 4, 2, 3, true, 0, LNF>(p, s);
-    case 4: return run<T, 128, BN, 4, 2, 3, true, 0, LNF>(p, s);
-    case 6: return run<T, 64, BN, 2, 2, 4, false, 0, LNF>(p, s);
-    case 7: return run<T, 64, BN, 2, 2, 2, false, 0, LNF>(p, s);
-    case 8: return run<T, 128, BN, 2, 2, 2, false, 0, LNF>(p, s);
-    default: break;
-  }
-  if constexpr (!LNF) {
-    if (cfg == 9) return run<T, 64, BN, 4, 2, 4>(p, s);
-    if (cfg == 10) return run<T, 64, BN, 2, 2, 4, true, 4>(p, s);
-    if (cfg == 11) return run<T, 64, BN, 2, 2, 3, true, 4>(p, s);
-    switch (cfg) {
-      case 2: return run<T, 256, BN, 4, 2, 3, false>(p, s);
-      case 3: return run<T, 128, BN, 2, 2, 4, true, 4>(p, s);
-      case 5: return run<T, 128, BN, 2, 2, 4>(p, s);
-      default: break;
-    }
-  }
-  return -2;
-}
-template <typename T>
-int run_cfg_any(int cfg, const IgemmParams& p, hipStream_t s) {
-  const bool geglu = p.epi == EPI_GEGLU;
-  const int bn = geglu ? 128 : (p.N % 160 == 0 ? 160 : (p.N % 128 == 0 ? 128 : 0));
-  if (p.rowstats) return bn == 160 ? run_cfg<T, 160, true>(cfg, p, s) : bn == 128 ? run_cfg<T, 128, true>(cfg, p, s) : -2;
-  return bn == 160 ? run_cfg<T, 160, false>(cfg, p, s) : bn == 128 ? run_cfg<T, 128, false>(cfg, p, s) : -2;
-}
-
-// Launches with a folded LayerNorm (norm1 -> q|k|v, norm3 -> GEGLU: K = C <= 1280, N a multiple of 160 or GEGLU's 128):
-// the same tile rules as dispatch() below, restricted to the instantiations those shapes can reach.
-template <typename T>
-int dispatch_ln(const IgemmParams& p, hipStream_t s) {
-  const bool geglu = p.epi == EPI_GEGLU;
-  if (!geglu && p.N % 160 != 0) return -2;
-  const int bn = geglu ? 128 : 160;
-  const long t256 = (long)((p.M + 255) / 256) * (p.N / bn);
-  const long t128 = (long)((p.M + 127) / 128) * (p.N / bn);
-  const long t64 = (long)((p.M + 63) / 64) * (p.N / bn);
-  if (t256 >= 240) {
-    if (geglu) return (g_big & 32) && sizeof(T) == 2 ? run<T, 256, 128, 4, 2, 3, true, 4, true>(p, s) : run<T, 256, 128, 4, 2, 3, true, 0, true>(p, s);
-    return run<T, 256, 160, 4, 2, 3, true, 0, true>(p, s);
-  }
-  if (!geglu && mid8_ok(t128, 1)) return run<T, 128, 160, 4, 2, 3, true, 0, true>(p, s);
-  if (t64 <= num_cus()) return geglu ? run<T, 64, 128, 2, 2, 4, false, 0, true>(p, s) : run<T, 64, 160, 2, 2, 4, false, 0, true>(p, s);
-  return geglu ? run<T, 64, 128, 2, 2, 2, false, 0, true>(p, s) : run<T, 64, 160, 2, 2, 2, false, 0, true>(p, s);
-}
-
-int g_xt_mode = 1;               // igemm_set_xt_mode (debug key 19): 0 = engines keep conv_shortcut as a launch of its own
-
-// conv2 + conv_shortcut of a resnet as one launch (IgemmParams::src2 ...): the three tile forms the UNet's resnet convs use.
-// The launch table is consulted with the 3x3 part's K (tuned_lookup ignores the extra tap), so the launch inherits the entry
-// of the conv it extends.
-template <typename T>
-int dispatch_xt(const IgemmParams& p, hipStream_t s) {
-  if constexpr (sizeof(T) == 2) {
-    if (p.N % 160 != 0) return -2;
-    int cfg = -1;
-    if (const TunedEntry* e = tuned_lookup(p, DT_BF16)) cfg = e->cfg;
-    if (cfg != 0 && cfg != 3 && cfg != 4) {
-      const int sp = p.splits > 1 ? p.splits : 1;
-      const long t256 = (long)((p.M + 255) / 256) * (p.N / 160), t128 = (long)((p.M + 127) / 128) * (p.N / 160);
-      const int nk_slice = ((p.taps * (p.C0 + p.C1) + p.C2 + p.C3) / 64) / sp;
-      if (t256 >= 240) cfg = 0;
-      else if (mid8_ok(t128, sp)) cfg = nk_slice >= 40 ? 3 : 4;
-      else cfg = t256 * sp >= 160 ? 0 : 3;
-    }
-    if (cfg == 0) return run<T, 256, 160, 4, 2, 3, true, 4, false, false, true>(p, s);
-    if (cfg == 3) return run<T, 128, 160, 2, 2, 4, true, 4, false, false, true>(p, s);
-    return run<T, 128, 160, 4, 2, 3, true, 0, false, false, true>(p, s);
-  }
-  return -2;
-}
-
-// the split-K finish every kernel of the family shares (p.splits > 1, slabs written)
-template <typename T>
-int launch_finish(const IgemmParams& pin, hipStream_t s) {
-  IgemmParams p = pin;
-  p.fd_hwo = fastdiv_make(p.Ho * p.Wo);
-  p.fd_wo = fastdiv_make(p.Wo);
-  p.fd_mphase = fastdiv_make(p.up4 ? p.M / 4 : 1);
-  const int nq = p.n_valid >> 2;
-  const int gx = (nq + 63) / 64;
-  int gy = (p.M + 3) / 4;
-  if (gy > 2048 / gx) gy = 2048 / gx > 0 ? 2048 / gx : 1;
-  LDMSEG_LAUNCH(launch_name("splitk_finish<%s>", dtype_tag<T>()), splitk_finish_kernel<T>, dim3(gx, gy), dim3(256), 0, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-template <typename T>
-int dispatch(const IgemmParams& p, hipStream_t s) {
-  if (p.up4) {                 // one tile form: 256 x 160 with loader waves (every up4 launch is >= 240 work items, K >= 20 tiles)
-    if constexpr (sizeof(T) == 2) return run<T, 256, 160, 4, 2, 3, true, 4, false, false, false, true>(p, s);
+// One line of LDMSEG_IGEMM_FORMS (igemm_plan.h) in one dtype on one N tile: the instantiations the line says exist, nothing else.
+template <typename T, int BM, int BN, int WM, int WN, int NST, bool PIPE, int LDR, bool LN, bool XT, bool UP4, bool CM, bool CF>
+int launch_form(const IgemmDispatch& d, const IgemmParams& p, hipStream_t s) {
+  constexpr bool var = sizeof(T) == 2 && BN == 160;        // the variants and the CF twin: bf16, 160 columns, no LayerNorm
+  if (d.cm || d.xt || d.up4) {
+    if constexpr (var && CM) { if (d.cm && !d.lnf) return run<T, BM, BN, WM, WN, NST, PIPE, LDR, false, true, false, false, false>(d, p, s); }
+    if constexpr (var && XT) { if (d.xt && !d.lnf) return run<T, BM, BN, WM, WN, NST, PIPE, LDR, false, false, true, false, CF>(d, p, s); }
+    if constexpr (var && UP4) { if (d.up4 && !d.lnf) return run<T, BM, BN, WM, WN, NST, PIPE, LDR, false, false, false, true, CF>(d, p, s); }
     return -2;
   }
-  if (p.C2 > 0) return dispatch_xt<T>(p, s);
-  if (p.cm) {   // channel-major 3x3 conv: one instantiation (the 256-row loader-wave tile the large maps use anyway), bf16 only
-    if constexpr (sizeof(T) == 2) {
-      if (!p.rowstats && p.epi == EPI_STORE && p.N % 160 == 0) return run<T, 256, 160, 4, 2, 3, true, 4, false, true>(p, s);
-    }
-    return -2;
-  }
-  {
-    int cfg = g_force_cfg;
-    if (cfg < 0 && !p.x3) {
-      if (const TunedEntry* e = tuned_lookup(p, sizeof(T) == 2 ? DT_BF16 : DT_F32)) cfg = e->cfg;
-    }
-    if (cfg >= 0 && !p.x3) {
-      const int r = run_cfg_any<T>(cfg, p, s);
-      if (r != -2 || g_force_cfg >= 0) return r;     // a forced entry that does not exist for this launch is an error
-    }
-  }
-  if constexpr (sizeof(T) == 4) {
-    // split-bf16 mode: the arithmetic lives in the plain K loop only, so these launches take the plain-loop instantiations
-    if (p.x3) {
-      // Tile choice: fp32 operands double the bytes staged per MAC, so these launches are bound by the L2 -> LDS path before the
-      // split's VALU work: the largest tile wins even where its 64 x 80 wave tiles spill 17-19 VGPRs in this loop (measured:
-      // 36.8 ms per B = 8 / L = 64 forward with the large tiles against 41.0 ms with spill-free 64-row tiles)
-      const int bnx = (p.epi == EPI_GEGLU) ? 128 : (p.N % 160 == 0 ? 160 : (p.N % 128 == 0 ? 128 : (p.N % 64 == 0 ? 64 : 32)));
-      const int sp = p.splits > 1 ? p.splits : 1;
-      const long t256 = (long)((p.M + 255) / 256) * (p.N / bnx) * sp, t128 = (long)((p.M + 127) / 128) * (p.N / bnx) * sp;
-      const long t64 = (long)((p.M + 63) / 64) * (p.N / bnx) * sp;
-      if (bnx == 64) return run<T, 128, 64, 4, 1>(p, s);
-      if (bnx == 32) return run<T, 128, 32, 4, 1>(p, s);
-      if (p.rowstats) {
-        if (t128 >= 400) return bnx == 160 ? run<T, 128, 160, 2, 2, 2, false, 0, true>(p, s) : run<T, 128, 128, 2, 2, 2, false, 0, true>(p, s);
-        if (t64 <= num_cus()) return bnx == 160 ? run<T, 64, 160, 2, 2, 4, false, 0, true>(p, s) : run<T, 64, 128, 2, 2, 4, false, 0, true>(p, s);
-        return bnx == 160 ? run<T, 64, 160, 2, 2, 2, false, 0, true>(p, s) : run<T, 64, 128, 2, 2, 2, false, 0, true>(p, s);
-      }
-      if (t256 >= 240) return bnx == 160 ? run<T, 256, 160, 4, 2, 3, false>(p, s) : run<T, 256, 128, 4, 2, 3, false>(p, s);
-      if (t128 >= 400) return bnx == 160 ? run<T, 128, 160, 2, 2>(p, s) : run<T, 128, 128, 2, 2>(p, s);
-      if (t64 <= num_cus()) return bnx == 160 ? run<T, 64, 160, 2, 2, 4>(p, s) : run<T, 64, 128, 2, 2, 4>(p, s);
-      return bnx == 160 ? run<T, 64, 160, 2, 2>(p, s) : run<T, 64, 128, 2, 2>(p, s);
-    }
-  }
-  if (p.rowstats) return dispatch_ln<T>(p, s);
-  const int bn = (p.epi == EPI_GEGLU) ? 128 : (p.N % 160 == 0 ? 160 : (p.N % 128 == 0 ? 128 : (p.N % 64 == 0 ? 64 : 32)));
-  // fewer than ~1.5 workgroups per CU with 128-row tiles: halve the M tile (2 co-resident
-  // workgroups per CU are what hides the per-K-tile barrier)
-  const bool small = (long)((p.M + 127) / 128) * (p.N / bn) < 400;
-  // plenty of rows: 256-row tiles / 8 waves cut the operand bytes staged per FLOP (the K loop is
-  // bound by global->LDS traffic, not by MFMA issue) as long as every CU still gets a workgroup
-  // (the global->LDS path tops out near 12 TB/s chip-wide, i.e. needs ~70 KB in flight per CU).
-  // One workgroup per CU then has to keep two tiles in flight itself: a 3-stage ring.
-  const long t256 = (long)((p.M + 255) / 256) * (p.N / bn);
-  const long t128 = (long)((p.M + 127) / 128) * (p.N / bn);
-  const bool big = (g_big & 1) && t256 >= 240;
-  // 128-row tiles that cannot put two workgroups on every CU: deeper ring, one workgroup per CU
-  const bool deep = (g_big & 2) && !big && t128 >= 200 && t128 < 400;
-  // at most one workgroup per CU anyway: the DMA round trip (~1.1 us) is then hidden only by the
-  // workgroup's own ring, so run it four stages deep instead of two
-  const bool mid8 = !big && bn >= 128 && p.epi != EPI_GEGLU && mid8_ok(t128, p.splits);
-  // long K slices: 4 compute waves (64x80 each) + 4 loader waves, 4-stage ring - measured 3-15 % faster than the 8-wave
-  // form on the >= 45-tile conv launches of the 16x16 / 32x32 maps and slower on short K (policy bit 1 turns it off)
-  if (mid8 && !(g_big & 2) && (p.taps * (p.C0 + p.C1) / (int)(kRowBytes / sizeof(T))) / (p.splits > 1 ? p.splits : 1) >= 40)
-    return bn == 160 ? run<T, 128, 160, 2, 2, 4, true, 4>(p, s) : run<T, 128, 128, 2, 2, 4, true, 4>(p, s);
-  if (mid8) return bn == 160 ? run<T, 128, 160, 4, 2, 3, true>(p, s) : run<T, 128, 128, 4, 2, 3, true>(p, s);
-  // 256-row tiles with four extra loader waves (12-wave workgroups): issuing an LDS-DMA instruction parks the issuing wave
-  // for 60-185 cycles (MI355X_MICROARCH.md), which in the 8-wave form comes straight out of the MFMA stream.  Measured on the
-  // B = 8, L = 64 layer shapes (tools/kbench.py): 3x3 convs with K >= 2880 5-17 % faster, GEGLU 5-10 %, K <= 960 GEMMs 5-13 %
-  // slower (prologue / epilogue bound: the loader waves only add barrier participants) -> long K slices and GEGLU only.
-  const int nk_slice = (p.taps * (p.C0 + p.C1) / (int)(kRowBytes / sizeof(T))) / (p.splits > 1 ? p.splits : 1);
-  const bool ldr_big = (g_big & 32) && sizeof(T) == 2 && (nk_slice >= 24 || p.epi == EPI_GEGLU);   // (the fp32 instantiation spills)
-  const long t64 = (long)((p.M + 63) / 64) * (p.N / bn) * (p.splits > 1 ? p.splits : 1);
-  const bool lone = (g_big & 4) && small && !big && !deep && t64 <= num_cus();
-  switch (bn) {
-    case 160:
-      if (big && ldr_big) return run<T, 256, 160, 4, 2, 3, true, 4>(p, s);
-      return big ? ((g_big & 8) ? run<T, 256, 160, 4, 2, 3, true>(p, s) : run<T, 256, 160, 4, 2, 3, false>(p, s)) : deep ? run<T, 128, 160, 2, 2, 4>(p, s)
-                 : lone ? run<T, 64, 160, 2, 2, 4>(p, s)
-                 : small ? run<T, 64, 160, 2, 2>(p, s) : run<T, 128, 160, 2, 2>(p, s);
-    case 128:
-      if (big && ldr_big) return run<T, 256, 128, 4, 2, 3, true, 4>(p, s);
-      return big ? ((g_big & 8) ? run<T, 256, 128, 4, 2, 3, true>(p, s) : run<T, 256, 128, 4, 2, 3, false>(p, s)) : deep ? run<T, 128, 128, 2, 2, 4>(p, s)
-                 : lone ? run<T, 64, 128, 2, 2, 4>(p, s)
-                 : small ? run<T, 64, 128, 2, 2>(p, s) : run<T, 128, 128, 2, 2>(p, s);
-    case 64: return run<T, 128, 64, 4, 1>(p, s);
-    default: return run<T, 128, 32, 4, 1>(p, s);
-  }
+  if constexpr (LN) { if (d.lnf) return run<T, BM, BN, WM, WN, NST, PIPE, LDR, true, false, false, false, false>(d, p, s); }
+  return d.lnf ? -2 : run<T, BM, BN, WM, WN, NST, PIPE, LDR, false, false, false, false, CF && var>(d, p, s);
+}
+
+// The chosen dispatch -> its line of the table, there its N tile and dtype; -2: the library has no such instantiation.
+int launch_tile(const IgemmDispatch& d, const IgemmParams& p, hipStream_t s) {
+#define LDMSEG_IGEMM_ON(BN, BM, WM, WN, NST, PIPE, LDR, ...)                                                       \
+  (d.dtype == DT_BF16 ? launch_form<bf16_t, BM, BN, WM, WN, NST, PIPE, LDR, __VA_ARGS__>(d, p, s)                   \
+                      : launch_form<float, BM, BN, WM, WN, NST, PIPE, LDR, __VA_ARGS__>(d, p, s))
+#define LDMSEG_IGEMM_LAUNCH_ROW(BM, WM, WN, NST, PIPE, LDR, WIDE, ...)                                             \
+  if (d.bm == BM && d.wm == WM && d.wn == WN && d.nst == NST && d.pipe == (PIPE ? 1 : 0) && d.ldr == LDR)           \
+    return d.bn == (WIDE ? 160 : 64)   ? LDMSEG_IGEMM_ON((WIDE ? 160 : 64), BM, WM, WN, NST, PIPE, LDR, __VA_ARGS__)  \
+           : d.bn == (WIDE ? 128 : 32) ? LDMSEG_IGEMM_ON((WIDE ? 128 : 32), BM, WM, WN, NST, PIPE, LDR, __VA_ARGS__)  \
+                                       : -2;
+  LDMSEG_IGEMM_FORMS(LDMSEG_IGEMM_LAUNCH_ROW)
+#undef LDMSEG_IGEMM_LAUNCH_ROW
+#undef LDMSEG_IGEMM_ON
+  return -2;
 }
 
 }  // namespace
@@ -1563,11 +1339,15 @@ int dispatch(const IgemmParams& p, hipStream_t s) {
 int igemm_warm() { return zero_page() ? 0 : -3; }
 const void* igemm_zero_page() { return zero_page(); }
 void igemm_set_tsbuf(void* b) { g_tsbuf = b; }
-void igemm_force_cfg(int cfg) { g_force_cfg = cfg; }
-void igemm_set_dbg(int f) { g_dbg = f & 0xff; g_big = (f >> 8) & 63; }   // bits 8-13 select the tile policy
-int igemm_get_dbg() { return (g_big << 8) | g_dbg; }
+void igemm_force_cfg(int cfg) { g_knobs.force_cfg = cfg; }
+void igemm_set_dbg(int f) { g_dbg = f & 0xff; g_knobs.policy = (f >> 8) & 63; }   // bits 8-13 select the tile policy
+int igemm_get_dbg() { return (g_knobs.policy << 8) | g_dbg; }
 int igemm_default_dbg() { return kDefaultPolicy << 8; }
 IgemmDispatch igemm_last_dispatch() { return g_last; }
+// the dispatch name + plan: what ldmseg_igemm_last_kernel and ldmseg_op_igemm_plan report
+std::string igemm_dispatch_line(const IgemmDispatch& d) {
+  return igemm_dispatch_name(d) + " splits=" + std::to_string(d.splits) + " grid=" + std::to_string(d.grid);
+}
 // "igemm<dtype,BM,BN,WM,WN,NST,PIPE,LDR>" + "/splitk" when the launch ran K slices (partial epilogue + finish kernel); the
 // split-bf16 K loop of an fp32 instantiation is marked ",x3" (hi / lo split of both operands in registers) or ",x3w" (W read as
 // pre-split hi | lo planes)
@@ -1595,6 +1375,7 @@ std::string igemm_log_read() {
   return out;
 }
 
+// (pads weights by the REAL N, so its rule is its own: igemm_n_tile sees the padded N)
 int igemm_pick_bn(int n_real, int epi) {
   if (epi == EPI_GEGLU) return 128;
   if (n_real % 160 == 0) return 160;
@@ -1603,56 +1384,27 @@ int igemm_pick_bn(int n_real, int epi) {
   return 32;
 }
 
-// Split-K plan for grids that would leave most of the 256 CUs idle (the 8x8 / 16x16 feature maps):
-// returns the number of K slices (1 = no split).  Mirrors dispatch()'s tile choice.
-int igemm_plan_splits(const IgemmParams& p, int dtype) {
-  if (p.epi != EPI_STORE || p.rowstats) return 1;
-  if (p.up4) {                 // 256-row tiles: K slices until every CU has a work item, at least 10 K tiles per slice
-    const long t256 = (long)(p.M / 256) * (p.N / 160);
-    const int nk0 = 4 * (p.C0 + p.C1) / 64;
-    int sp = t256 >= 240 ? 1 : (int)((num_cus() + t256 / 2) / t256);
-    if (sp > nk0 / 10) sp = nk0 / 10;
-    if (sp > 8) sp = 8;
-    return sp < 2 ? 1 : sp;
-  }
-  if (const TunedEntry* e = tuned_lookup(p, dtype)) return e->splits;
-  const int bke = dtype == DT_BF16 ? 64 : 32;
-  const int bn = p.N % 160 == 0 ? 160 : (p.N % 128 == 0 ? 128 : (p.N % 64 == 0 ? 64 : 32));
-  const long tiles128 = (long)((p.M + 127) / 128) * (p.N / bn);
-  const int nk0 = p.taps * (p.C0 + p.C1) / bke;
-  if ((g_big & 16) && bn >= 128 && tiles128 < 200 && ((long)((p.M + 255) / 256) * (p.N / bn)) < 240) {
-    // 128-row 8-wave tiles: aim at one work item per CU, at least 10 K tiles per slice (a 20-tile
-    // K=1280 GEMM measured faster unsplit on 64-row tiles than split in two plus the finish pass)
-    int sp = (int)((num_cus() + tiles128 / 2) / tiles128);
-    if (sp > nk0 / 10) sp = nk0 / 10;
-    if (nk0 < 32) sp = 1;
-    if (sp > 16) sp = 16;
-    if (sp >= 2 && mid8_ok(tiles128, sp)) return sp;
-  }
-  const int bm = (bn >= 128 && tiles128 < 400) ? 64 : 128;
-  const long blocks = (long)((p.M + bm - 1) / bm) * (p.N / bn);
-  const int nk = p.taps * (p.C0 + p.C1) / bke;
-  if (blocks >= 400 || nk < 24) return 1;
-  int splits = (int)((512 + blocks - 1) / blocks);
-  if (splits > nk / 12) splits = nk / 12;
-  if (splits > 16) splits = 16;
-  return splits < 2 ? 1 : splits;
+int igemm_plan_splits(const IgemmParams& p, int dtype) { return igemm_plan_splits_pure(describe(p), dtype, g_knobs, num_cus()); }
+
+// What launch_igemm would run for this description under the current knobs on a device of `cus` CUs - without touching one.
+// splits <= 0: K slices planned as the engines plan them.  0 and *d, or -2.
+int igemm_plan(const IgemmLaunchDesc& desc, int dtype, int cus, IgemmDispatch* d) {
+  IgemmLaunchDesc q = desc;
+  if (q.splits <= 0) q.splits = igemm_plan_splits_pure(q, dtype, g_knobs, cus);
+  return igemm_choose(q, dtype, g_knobs, cus, d);
 }
 
-size_t igemm_cf_bytes() { return 64 << 10; }
-void igemm_set_cf_mode(int mode) { g_cf_mode = mode; }
-void igemm_set_table_override(int v) { g_table_override = v; }
-int igemm_get_cf_mode() { return g_cf_mode; }
+size_t igemm_cf_bytes() { return kIgemmCfBytes; }
+void igemm_set_cf_mode(int mode) { g_knobs.cf_mode = mode; }
+void igemm_set_table_override(int v) { g_knobs.table_override = v; }
+int igemm_get_cf_mode() { return g_knobs.cf_mode; }
 size_t igemm_partial_bytes(const IgemmParams& p) {
   return p.splits > 1 ? (size_t)p.splits * p.M * p.N * sizeof(float) : 0;
 }
 
-int g_up4_mode = 1;
-void igemm_set_up4_mode(int on) { g_up4_mode = on ? 1 : 0; }
-int igemm_get_up4_mode() { return g_up4_mode; }
-bool igemm_up4_ok(int B, int H, int W, int C, int N, int dtype) {
-  return g_up4_mode && dtype == DT_BF16 && C % 64 == 0 && N % 160 == 0 && ((long)B * H * W) % 256 == 0 && g_big == kDefaultPolicy && g_force_cfg < 0;
-}
+void igemm_set_up4_mode(int on) { g_knobs.up4_mode = on ? 1 : 0; }
+int igemm_get_up4_mode() { return g_knobs.up4_mode; }
+bool igemm_up4_ok(int B, int H, int W, int C, int N, int dtype) { return igemm_up4_ok_pure(g_knobs, (long)B * H * W, C, N, dtype); }
 namespace {
 // OIHW fp32 3x3 -> [phase = 2 py + px][Npad][tap = 2 a + b][Cipad]: the taps of the 3x3 window that fall on the same source pixel of
 // the low-resolution map, summed in fp32.  Row group a of phase py: py = 0 -> {ky 0}, {ky 1, 2}; py = 1 -> {ky 0, 1}, {ky 2}.
@@ -1722,12 +1474,10 @@ int launch_pack_up4(const float* w, void* out, int Co, int Ci, int Npad, int Cip
   else hipLaunchKernelGGL(pack_up4_kernel<float>, dim3(g), dim3(256), 0, s, w, (float*)out, Co, Ci, Npad, Cipad);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
-void igemm_set_xt_mode(int on) { g_xt_mode = on ? 1 : 0; }
-int igemm_get_xt_mode() { return g_xt_mode; }
+void igemm_set_xt_mode(int on) { g_knobs.xt_mode = on ? 1 : 0; }   // 0 = engines keep conv_shortcut as a launch of its own
+int igemm_get_xt_mode() { return g_knobs.xt_mode; }
 bool igemm_xt_ok(const IgemmParams& p, int dtype) {
-  return g_xt_mode && dtype == DT_BF16 && p.C2 > 0 && p.src2 && p.C2 % 64 == 0 && p.C3 % 64 == 0 && (p.C3 == 0 || p.src3) && p.taps == 9 && p.stride == 1 &&
-         !p.up && !p.cm && (p.pad < 0 || p.pad == 1) && p.N % 160 == 0 && p.epi == EPI_STORE && !p.rowstats && g_big == kDefaultPolicy &&
-         g_force_cfg < 0;
+  return igemm_xt_ok_pure(describe(p), dtype, g_knobs) && p.src2 && (p.C3 == 0 || p.src3) && (p.pad < 0 || p.pad == 1);
 }
 
 namespace {
@@ -1783,29 +1533,21 @@ int launch_concat_rows(const void* a, int K1, const void* b, int K2, void* out, 
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-void igemm_set_cm_mode(int mode) { g_cm_mode = mode < -1 || mode > 1 ? -1 : mode; }
-int igemm_get_cm_mode() { return g_cm_mode; }
-bool igemm_conv_cm(int hw, int ctot, int n, int k, int stride, int up, int dtype) {
-  if (k != 3 || stride != 1 || up || g_cm_mode == 0 || dtype != DT_BF16 || n % 160 != 0) return false;   // (what dispatch() can run)
-  return g_cm_mode == 1 || (hw >= 4096 && ctot >= 640);
-}
+void igemm_set_cm_mode(int mode) { g_knobs.cm_mode = mode < -1 || mode > 1 ? -1 : mode; }
+int igemm_get_cm_mode() { return g_knobs.cm_mode; }
+bool igemm_conv_cm(int hw, int ctot, int n, int k, int stride, int up, int dtype) { return igemm_conv_cm_pure(g_knobs, hw, ctot, n, k, stride, up, dtype); }
 
 int launch_igemm(const IgemmParams& p, int dtype, hipStream_t s) {
-  const int bke = dtype == DT_BF16 ? 64 : 32;
-  if (p.M <= 0 || p.N <= 0 || p.N % 32 != 0) return -2;
-  if (p.C0 % bke != 0 || p.C1 % bke != 0 || (p.C0 + p.C1) == 0) return -2;
-  if (p.up4) {
-    if (dtype != DT_BF16 || p.taps != 4 || p.stride != 1 || p.up || p.cm || p.C2 || p.epi != EPI_STORE || p.rowstats || p.resid || p.rowbias ||
-        p.N % 160 != 0 || p.M % 1024 != 0 || p.M != 4 * p.B * p.Ho * p.Wo || p.Hi != p.Ho || p.Wi != p.Wo)
-      return -2;
-  } else if (p.taps != 1 && p.taps != 9) return -2;
-  if (p.cm && (p.taps != 9 || p.stride != 1 || p.up || (p.pad >= 0 && p.pad != 1))) return -2;
+  // the checks on pointers and map geometry; igemm_choose makes the ones the description carries (igemm_desc_ok)
+  if (p.up4 && (p.resid || p.rowbias || p.M != 4 * p.B * p.Ho * p.Wo || p.Hi != p.Ho || p.Wi != p.Wo)) return -2;
+  if (p.cm && p.pad >= 0 && p.pad != 1) return -2;
   if (p.n_valid % 4 != 0 && p.epi != EPI_NCHW_F32) return -2;
-  if (p.epi == EPI_GEGLU && p.N % 128 != 0) return -2;
-  if (p.splits > 1 && (p.epi != EPI_STORE || p.partial == nullptr)) return -2;
-  if (p.rowstats && (!p.c1 || p.rowbias || p.splits > 1 || (p.epi != EPI_STORE && p.epi != EPI_GEGLU))) return -2;
+  if (p.splits > 1 && p.partial == nullptr) return -2;
+  if (p.rowstats && (!p.c1 || p.rowbias)) return -2;
   if ((p.C2 > 0 || p.C3 > 0) && !igemm_xt_ok(p, dtype)) return -2;
-  return dtype == DT_BF16 ? dispatch<bf16_t>(p, s) : dispatch<float>(p, s);
+  IgemmDispatch d;
+  if (const int r = igemm_choose(describe(p), dtype, g_knobs, num_cus(), &d)) return r;
+  return launch_tile(d, p, s);
 }
 
 }  // namespace ldmseg

@@ -8,17 +8,9 @@
 #include <string>
 #include <vector>
 
+#include "igemm_types.h"   // DType, Epilogue, IgemmDispatch, IgemmLaunchDesc
+
 namespace ldmseg {
-
-enum DType : int { DT_F32 = 0, DT_BF16 = 1 };
-
-enum Epilogue : int {
-  EPI_STORE = 0,   // out[m][n] = acc + bias (+rowbias) (+resid), optional SiLU
-  EPI_GEGLU = 1,   // packed (a,g) 16-column interleave -> out[m][n/2] = a*gelu(g)
-  EPI_NCHW_F32 = 2,  // out is float NCHW [B][n_valid][Ho*Wo]  (conv_out, VAE heads)
-  EPI_CONVT2 = 3,  // ConvTranspose2d k2s2: n = tap*Cout + co scattered to (2y+dy,2x+dx)
-  EPI_ROWS_F32 = 4,  // out is float row-major [M][ldo] whatever the compute dtype (attention scores of the image VAE)
-};
 
 // Exact n / d for 0 <= n < 2^31 by one v_mul_hi_u32 and a shift (Granlund-Montgomery: s = ceil(log2 d),
 // M = ceil(2^(31+s) / d) < 2^32, q = (n * M) >> (31 + s)).  A runtime integer division is a ~40-instruction VALU sequence
@@ -155,11 +147,11 @@ int launch_concat_rows(const void* a, int K1, const void* b, int K2, void* out, 
 void igemm_force_cfg(int cfg);   // tuning tool: >= 0 runs every launch with that entry of the instantiation list, -1 = off
 int igemm_get_dbg();       // current (policy << 8) | ablation flags
 int igemm_default_dbg();   // the shipped value
-// template instantiation + plan of the most recent launch_igemm (test introspection)
-// cf: the K slices were finished inside the launch; x3: IgemmParams::x3 (1 = split-bf16 in the K loop, 2 = W holds hi | lo planes)
-struct IgemmDispatch { int dtype, bm, bn, wm, wn, nst, pipe, ldr, splits, grid, lnf, cm, cf, xt, up4, x3; };
+// template instantiation + plan of the most recent launch_igemm (test introspection), and of a launch that is only described
 IgemmDispatch igemm_last_dispatch();
+int igemm_plan(const IgemmLaunchDesc& desc, int dtype, int cus, IgemmDispatch* d);
 std::string igemm_dispatch_name(const IgemmDispatch& d);
+std::string igemm_dispatch_line(const IgemmDispatch& d);   // name + " splits=S grid=G"
 // the dispatch log: level 0 = off; 1 = the GEMM family (igemm instantiations, the fused GEMM kernels of tfuse / tproj / tail);
 // 2 = every kernel of the forward path (+ split-K finish, GroupNorm, LayerNorm statistics, attention).  Enabling clears it.
 void igemm_log_enable(int level);

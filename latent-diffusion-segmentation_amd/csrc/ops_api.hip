@@ -4,7 +4,9 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../../include/ldmseg_hip.h"
@@ -586,6 +588,19 @@ int ldmseg_op_conv3x3_plus_1x1(const float* h, const float* w2, const float* b2,
   if (iters > 0 && us_per_launch) *us_per_launch = time_launches(s, 0, iters, [&](int) { (void)launch_igemm(p, dtype, s); });
   if (!out) return 0;
   return unpack_nhwc(op, out, B, Co, HW, Co, dtype, s);
+}
+
+// the dispatch string of a described launch (igemm_plan: the chooser under the current knobs; no device)
+int ldmseg_op_igemm_plan(const int* desc, int dtype, int cus, char* buf, int n) {
+  if (!desc || !buf || n < 1 || cus < 1 || dtype < 0 || dtype > 3) return -2;
+  IgemmLaunchDesc q;
+  static_assert(sizeof q == 17 * sizeof(int), "ldmseg_op_igemm_plan takes the fields of IgemmLaunchDesc in order");
+  std::memcpy(&q, desc, sizeof q);
+  if (dtype >= 2) { q.x3 = dtype - 1; dtype = DT_F32; }
+  IgemmDispatch d;
+  if (const int r = igemm_plan(q, dtype, cus, &d)) return r;
+  std::snprintf(buf, (size_t)n, "%s", igemm_dispatch_line(d).c_str());
+  return 0;
 }
 
 // q[i] = n[i] / d through the multiply-shift divisor the kernels use (FastDiv, kernels.h): exactness test hook

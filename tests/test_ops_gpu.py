@@ -1402,3 +1402,81 @@ def test_upsampler_conv_as_phase_convs(L, case):
         lib.ldmseg_debug_set(21, 1)
     assert rel_err(out9, ref) < 8e-3
     assert float((out - out9).norm() / out9.norm()) < 6e-3          # two roundings of the same convolution
+
+
+# ---- the chooser's answer for a described launch is what the launch runs (csrc/igemm_plan.h, ldmseg_op_igemm_plan) ----
+def _plan_pairs(cus):
+    """(label, below, at): two 1x1 launches, the smallest that sit one tile to either side of one comparison of igemm_choose, so
+    the two run different instantiations (or K slices).  A launch is (operator, M, K, N, geglu, splits, dtype, tile policy);
+    splits = 1 keeps the slice planner out of a tile-count case, 0 lets it plan; policy None = the shipped one."""
+    X3W = 3
+
+    def rows(label, bm, t0, t1, op="igemm", K=64, N=160, geglu=0, splits=(1, 1), dt=BF16, pol=None):
+        return (label, (op, t0 * bm, K, N, geglu, splits[0], dt, pol), (op, t1 * bm, K, N, geglu, splits[1], dt, pol))
+
+    def klen(label, M, N, nk0, nk1):
+        return (label, ("igemm", M, nk0 * 64, N, 0, 1, BF16, None), ("igemm", M, nk1 * 64, N, 0, 1, BF16, None))
+
+    return [
+        ("N tile 160 | 128", ("igemm", 128, 64, 160, 0, 1, BF16, None), ("igemm", 128, 64, 128, 0, 1, BF16, None)),   # K of one K tile
+        ("N tile 128 | 64", ("igemm", 128, 64, 128, 0, 1, BF16, None), ("igemm", 128, 64, 64, 0, 1, BF16, None)),
+        ("N tile 64 | 32", ("igemm", 128, 64, 64, 0, 1, BF16, None), ("igemm", 128, 64, 32, 0, 1, BF16, None)),
+        rows("240 tiles of 256 rows", 256, 239, 240),
+        rows("... under GEGLU (loader waves)", 256, 239, 240, N=128, geglu=1),
+        # 400 tiles of 128 rows: GEGLU, which the 8-wave 128-row window below does not take
+        rows("400 tiles of 128 rows", 128, 399, 400, N=128, geglu=1),
+        # 200 .. 400 tiles of 128 rows on the deeper ring: policy bit 1, without the 8-wave 128-row tiles (bit 4)
+        rows("200 tiles of 128 rows (policy 3)", 128, 199, 200, pol=3),
+        rows("400 tiles of 128 rows (policy 3)", 128, 399, 400, pol=3),
+        rows("the CU count in 64-row tiles", 64, cus, cus + 1),
+        rows("160 items of 128 rows", 128, 159, 160, K=128),
+        rows("... as 80 tiles x 2 slices", 128, 79, 80, K=128, splits=(2, 2)),
+        rows("2 CUs items of 128 rows", 128, cus, cus + 1, K=128, splits=(2, 2)),
+        klen("24 K tiles per slice (256 rows)", 30 * 256, 1280, 23, 24),
+        klen("40 K tiles per slice (128 rows)", 40 * 128, 640, 39, 40),
+        rows("slice planner: 200 tiles of 128 rows", 128, 199, 200, K=2048, splits=(0, 0)),
+        # the folded-LayerNorm rule's own comparisons (a 2 CUs window end is out of reach: 240 tiles of 256 rows come first)
+        rows("LayerNorm: 240 tiles of 256 rows", 256, 239, 240, op="ln"),
+        rows("LayerNorm: 160 tiles of 128 rows", 128, 159, 160, op="ln"),
+        rows("LayerNorm: the CU count in 64-row tiles", 64, cus, cus + 1, op="ln"),
+        # the split-bf16 rule's own (fp32 operands: K of one K tile is 32)
+        rows("x3: 240 tiles of 256 rows", 256, 239, 240, K=32, dt=X3W),
+        rows("x3: 400 tiles of 128 rows", 128, 399, 400, K=32, dt=X3W),
+        rows("x3: the CU count in 64-row tiles", 64, cus, cus + 1, K=32, dt=X3W),
+    ]
+
+
+def test_igemm_plan_equals_launch(L, tile_policy):
+    """ldmseg_op_igemm_plan, given the device's CU count, names the instantiation, K slices and grid that the launch then runs -
+    at shapes to either side of every threshold of the chooser, and the two sides of each threshold run different things (zero
+    operands: only the decision is compared)"""
+    from igemm_desc import desc_igemm, desc_ln_linear, plan
+    lib = L.lib()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    pairs = _plan_pairs(cus)
+    cases = [c for _, a, b in pairs for c in (a, b)]
+    big = max(max(M * K, K * N) for _, M, K, N, _, _, _, _ in cases)
+    assert big * 4 <= 256 << 20
+    z = torch.zeros(big, device="cuda")
+    out = torch.empty(max(M * N for _, M, _, N, _, _, _, _ in cases), device="cuda")
+
+    def launch(label, case):
+        op, M, K, N, geglu, splits, dt, pol = case
+        tile_policy(lib.ldmseg_debug_get(-1) >> 8 if pol is None else pol)
+        knobs = None if pol is None else {1: pol << 8}
+        if op == "ln":
+            desc = desc_ln_linear(M, K, N, 0)
+            r = lib.ldmseg_op_ln_linear(P(z), P(z), P(z), P(z), P(z), M, K, N, 1e-5, 0, dt, P(out), None)
+        else:
+            desc = desc_igemm(1, K, 0, M, 1, N, 1, 1, 0, geglu, splits, BF16 if dt == BF16 else F32, knobs)
+            r = lib.ldmseg_op_igemm(P(z), None, P(z), P(z), None, None, 1, K, 0, M, 1, N, 1, 1, 0, geglu, 0, splits, dt, P(out), None)
+        assert r == 0, (label, case, lib.ldmseg_last_error())
+        ran = L.igemm_last_kernel()
+        assert plan(lib, desc, dt, cus) == (0, ran), (label, case)
+        return ran
+
+    for label, a, b in pairs:
+        below, at = launch(label, a), launch(label, b)
+        print(f"{label:42s} {below}  |  {at}")
+        assert below != at, (label, below)         # the pair does straddle its comparison
+    torch.cuda.synchronize()
