@@ -415,7 +415,7 @@ int ldmseg_profile_dump(const char* path);
  * key 24 = tuning: every plain-store igemm launch runs entry (v & 0xff) of the instantiation list with (v >> 8) K slices as if the
  * launch table held that entry (-1 = off; unlike key 5 the extra-tap / phase-conv routes stay). */
 int ldmseg_debug_set(int key, int value);
-/* current value of a knob (keys 1, 9, 12, 14, 15, 16, 19, 20, 21, 22, 23); key -1 = the shipped default of key 1.  Tests restore through this, never a literal.
+/* current value of a knob (keys 1, 8, 9, 11, 12, 14, 15, 16, 19, 20, 21, 22, 23); key -1 = the shipped default of key 1.  Tests restore through this, never a literal.
  * key 10 = number of cooperative-GroupNorm workgroups that took the self-computing path in ldmseg_op_* launches so far. */
 int ldmseg_debug_get(int key);
 

@@ -156,6 +156,13 @@ int ldmseg_igemm_last_kernel(char* buf, int n);
  * K slices), no_finish, region (the caller has a counter region for the in-launch finish).  dtype 0 fp32, 1 bf16, 2 / 3 = fp32
  * with x3 = 1 / 2 as the operators take it.  Returns 0, or -2 when the library has no such launch. */
 int ldmseg_op_igemm_plan(const int* desc, int dtype, int cus, char* buf, int n);
+/* What ldmseg_op_groupnorm would launch for (B, C + C2 channels in `groups` groups, HW pixels) on a device with `cus` compute units,
+ * under the current debug knobs (keys 8, 10, 11); needs no device.  region_ok: a hand-off region for the cooperative kernel
+ * exists.  buf receives the dispatch-log names joined by " + " and " splits=S grid=GXxGY block=T" (two launches:
+ * grid=GXxGY+GXxGY).  Returns 0, or -2 where ldmseg_op_groupnorm returns -2.  ldmseg_op_conv_groupnorm_plan: the finish +
+ * GroupNorm launch of ldmseg_op_conv_groupnorm over Co channels; -4 where that returns -4. */
+int ldmseg_op_groupnorm_plan(int B, int C, int C2, int HW, int groups, int dtype, int cus, int region_ok, char* buf, int n);
+int ldmseg_op_conv_groupnorm_plan(int B, int Co, int HW, int dtype, char* buf, int n);
 /* enable=1 clears and starts a log of the DISTINCT igemm instantiations launched ("igemm<...>" + "/splitk" for K-sliced
  * launches; ",x3" / ",x3w" for split-bf16 products) and of the fused GEMM kernels; enable=2 logs every kernel of the UNet
  * forward path (split-K finish, GroupNorm, LayerNorm statistics, attention too), each named with its template arguments and

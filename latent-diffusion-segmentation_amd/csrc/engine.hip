@@ -2453,9 +2453,8 @@ int ldmseg_debug_set(int key, int value) {
   if (key == 8) { groupnorm_set_variant(value); ++g_plan_epoch; return 0; }   // (bit 3 changes which scratch conv_groupnorm plans)
   if (key == 9) { igemm_set_cm_mode(value); ++g_plan_epoch; return 0; }   // K order of 3x3 conv launches: -1 rule, 0 tap-major, 1 channel-major
   // cooperative GroupNorm hand-off: 10 = mode (1: every workgroup computes its partners' records itself), 11 = poll bound in us
-  static int gn_mode = 0, gn_poll = 100;
-  if (key == 10) { gn_mode = value; groupnorm_set_coop(gn_mode, gn_poll); return 0; }
-  if (key == 11) { gn_poll = value; groupnorm_set_coop(gn_mode, gn_poll); return 0; }
+  if (key == 10) { groupnorm_set_coop(value, groupnorm_knob(11)); return 0; }
+  if (key == 11) { groupnorm_set_coop(groupnorm_knob(10), value); return 0; }
   if (key == 12) { mlp_fused_set_mode(value); ++g_plan_epoch; return 0; }   // transformer feed-forward fusion: bit 0 MLP, bit 1 + proj_out
   if (key == 13) { mlp_fused_set_dbg(value); return 0; }                    // bit 8: no start-chunk rotation (bits 0-7: ablate builds)
   // 14: step tail.  bit 0: dedicated conv_out kernel (bf16); bit 1: scheduler step in its epilogue.  (The implicit-GEMM
@@ -2484,6 +2483,7 @@ int ldmseg_debug_set(int key, int value) {
 int ldmseg_debug_get(int key) {
   if (key == 1) return igemm_get_dbg();
   if (key == -1) return igemm_default_dbg();     // the shipped value of key 1
+  if (key == 8 || key == 11) return groupnorm_knob(key);
   if (key == 9) return igemm_get_cm_mode();
   if (key == 12) return mlp_fused_get_mode();
   if (key == 14) return step_tail_get_mode();

@@ -1208,6 +1208,7 @@ int cur_dev() {
   return dev;
 }
 
+}  // namespace
 int num_cus() {
   static int n[kMaxDev] = {};
   const int dev = cur_dev();
@@ -1218,6 +1219,7 @@ int num_cus() {
   }
   return n[dev];
 }
+namespace {
 
 const void* zero_page() {
   static void* z[kMaxDev] = {};

@@ -105,6 +105,7 @@ struct IgemmParams {
 int launch_igemm(const IgemmParams& p, int dtype, hipStream_t s);
 size_t igemm_partial_bytes(const IgemmParams& p);
 int igemm_warm();   // per-device lazy state (zero page) created now instead of inside the first launch
+int num_cus();      // compute units of the current device
 int igemm_plan_splits(const IgemmParams& p, int dtype);
 // cooperative split-K finish inside the igemm launch (IgemmParams::cf_ctr).  Region size; debug key 23: bit 0 = on for the 256-row
 // tile forms (default, with bit 2: engine.hip conv_groupnorm), bit 3 = on for every tile form with the instantiation, bit 1 = zero-length poll (every workgroup that is not
@@ -218,7 +219,13 @@ int launch_groupnorm_stats(const GNParams& p, int dtype, hipStream_t s);
 // eps, silu, out.  finish_groupnorm_ok: whether the shape has an instantiation (otherwise: igemm's finish + launch_groupnorm).
 bool finish_groupnorm_ok(int B, int HW, int C, int dtype);
 int launch_finish_groupnorm(const IgemmParams& ip, const GNParams& g, int dtype, hipStream_t s);
-void groupnorm_set_variant(int v);   // tuning knob: bit0 = no cooperative one-pass kernel (64x64 maps on the two-launch path)
+void groupnorm_set_variant(int v);   // tuning knob (debug key 8): the kGn* bits of gn_plan.h
+int groupnorm_knob(int key);         // current value of debug key 8 (variant), 10 (mode) or 11 (poll bound in us)
+// what launch_groupnorm / launch_finish_groupnorm would run under the current knobs (gn_plan.h; no device): 0 and *pl, -2, -4
+struct GnDesc;
+struct GnPlan;
+int groupnorm_plan(const GnDesc& q, int cus, bool region_ok, GnPlan* pl);
+int finish_groupnorm_plan(int B, int HW, int C, int dtype, GnPlan* pl);
 
 // LayerNorm over the last dim of [M][C] (+ optional SiLU) - also LayerNorm2d in NHWC
 int launch_layernorm(const void* x, void* y, const float* gamma, const float* beta, int M, int C,

@@ -14,6 +14,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "gn_plan.h"
 #include "kernels.h"
 
 namespace ldmseg {
@@ -25,17 +26,7 @@ __device__ unsigned long long g_gn_ts[8192 * 8];
 #else
 #define GNSTAMP(slot)
 #endif
-int num_cus_gn() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-constexpr int kMaxIter = 4;   // ceil(nvec / 256) supported (C*sizeof(T)/16 <= 1024)
+constexpr int kMaxIter = kGnMaxIter;   // ceil(nvec / 256) supported (C*sizeof(T)/16 <= 1024)
 
 template <typename T>
 __device__ __forceinline__ uint4 load_cat(const GNParams& p, int b, int pix, int v) {
@@ -1221,7 +1212,7 @@ __global__ __launch_bounds__(NT) void gn_coop_kernel(const GNParams p, int GB) {
 // Every handle (UNet, seg-VAE, image VAE) owns one region, allocated at *_create: its launches are ordered by its stream,
 // so consecutive norms - and replays of a captured graph - draw consecutive generations on it.  Launches that do not come
 // from a handle (the ldmseg_op_* test surface) take a region of a small per-device ring under a mutex.
-constexpr int kGnMaxSlabs = 2048, kGnRing = 16;
+constexpr int kGnRing = 16;
 constexpr size_t kGnCtrWords = kGnMaxSlabs, kGnRecWords = (size_t)kGnMaxSlabs * 8 * 8;
 constexpr size_t kGnRegionWords = kGnCtrWords + kGnRecWords + 8;
 void gn_bind_region(GNParams& p, unsigned long long* base) {
@@ -1233,21 +1224,28 @@ std::mutex g_gn_mu;
 unsigned long long* g_gn_ring[64] = {};
 hipStream_t g_gn_ring_stream[64][kGnRing] = {};
 int g_gn_ring_used[64] = {};
-// One region per (device, stream): launches of one stream are ordered, so consecutive norms draw consecutive generations
-// on their region exactly like a handle's do; two streams never share one (round 4 handed the regions out round-robin,
-// so that two cooperative launches in flight on different streams could meet on one region after the ring wrapped and
-// read each other's records - ADVICE r04).  More distinct streams than regions: null, the caller takes the two-launch path.
-unsigned long long* gn_ring_region(hipStream_t s, int* dev_out = nullptr) {
+// the current device's ring, allocated and zeroed on first use (g_gn_mu held); null: out of memory
+unsigned long long* gn_ring_locked(int* dev_out) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (dev_out) *dev_out = dev;
-  std::lock_guard<std::mutex> lk(g_gn_mu);
+  *dev_out = dev;
   if (!g_gn_ring[dev]) {
     void* q = nullptr;
     if (hipMalloc(&q, kGnRegionWords * kGnRing * sizeof(unsigned long long)) != hipSuccess) return nullptr;
     (void)hipMemset(q, 0, kGnRegionWords * kGnRing * sizeof(unsigned long long));
     g_gn_ring[dev] = (unsigned long long*)q;
   }
+  return g_gn_ring[dev];
+}
+// One region per (device, stream): launches of one stream are ordered, so consecutive norms draw consecutive generations
+// on their region exactly like a handle's do; two streams never share one (round 4 handed the regions out round-robin,
+// so that two cooperative launches in flight on different streams could meet on one region after the ring wrapped and
+// read each other's records - ADVICE r04).  More distinct streams than regions: null, the caller takes the two-launch path.
+unsigned long long* gn_ring_region(hipStream_t s) {
+  std::lock_guard<std::mutex> lk(g_gn_mu);
+  int dev = 0;
+  unsigned long long* ring = gn_ring_locked(&dev);
+  if (!ring) return nullptr;
   int idx = -1;
   for (int i = 0; i < g_gn_ring_used[dev]; ++i)
     if (g_gn_ring_stream[dev][i] == s) { idx = i; break; }
@@ -1256,20 +1254,17 @@ unsigned long long* gn_ring_region(hipStream_t s, int* dev_out = nullptr) {
     idx = g_gn_ring_used[dev]++;
     g_gn_ring_stream[dev][idx] = s;
   }
-  return g_gn_ring[dev] + (size_t)idx * kGnRegionWords;
+  return ring + (size_t)idx * kGnRegionWords;
 }
 
-int g_gn_coop_mode = 0;     // 1: every cooperative workgroup computes its partners' records itself (tests of the cold path)
-int g_gn_poll_us = 100;     // bound of the partner poll
-
-int g_gn_variant = 0;   // tuning knob (ldmseg_debug_set key 8): bit0 = no cooperative kernel (64x64 maps on the two-launch path)
+GnKnobs g_gn_knobs;     // debug keys 8, 10, 11 (groupnorm_set_variant / groupnorm_set_coop): what the chooser and the launcher read
 
 // One workgroup per (image, group), the whole slice in the registers of 512 threads (round 6; bf16, one source): no hand-off between
 // workgroups at all - gn_coop_kernel's S splits of an (image, group block) exchange partial statistics through memory (~3 us of a
 // 12 us launch at 32x32 x 640) - and the tensor is still read once and written once.  The price is that a group's channels are not
 // 16-byte aligned, so the slice moves in 8-byte pieces (cpg % 4 == 0) of partial cache lines.  The 4-byte prototype
 // (tools/ubench/gn_group.hip, B = 8): 8.8 against 12.0 us at 32x32 x 640 (20 dwords per thread), but 20.5 against 16.6 us at 64x64 x 320
-// (40 dwords per thread of 4-byte accesses: TA-bound) and far worse beyond - hence the rule in run_gn; the 8-byte form shipped here
+// (40 dwords per thread of 4-byte accesses: TA-bound) and far worse beyond - hence the rule in gn_choose; the 8-byte form shipped here
 // measures 7.5 us on the first shape.  torch.cat([x0, x1], 1) inputs: an access lies in one source (C0 % 4 == 0), chosen per access.
 // Block b -> image b % B, group b / B: with block b on XCD b % 8 (observed, speed only) all groups of an image share one L2, so every
 // line is fetched into and written back from one L2.  Statistics: two passes over the registers (mean, then centred squares), fixed
@@ -1356,146 +1351,73 @@ __global__ __launch_bounds__(512) void gn_group_kernel(const GNParams p, int upp
   }
 }
 
+// A plan as launches: the derived GNParams fields, then the form's kernel - the only place that names the template arguments
+// of the GroupNorm kernels.  ip: the split-K launch whose slabs finish_gn sums (GN_FINISH only).
+template <typename T>
+int launch_gn_plan(const GnPlan& pl, GNParams p, hipStream_t s, const IgemmParams* ip = nullptr) {
+  constexpr int DT = Elem<T>::kDType;
+  p.cpg = pl.cpg; p.vx = pl.vx; p.ty = pl.ty; p.per = pl.per; p.splits = pl.splits; p.inv_n = pl.inv_n;
+  p.fd_cpg = fastdiv_make(pl.div_cpg); p.fd_vx = fastdiv_make(pl.div_vx); p.fd_aux = fastdiv_make(pl.div_aux);
+  const dim3 grid(pl.grid_x, pl.grid_y), block(pl.block);
+  const int GB = pl.GB;
+#define LDMSEG_GN(KERNEL, ...) LDMSEG_LAUNCH(gn_plan_name(pl, DT), KERNEL, grid, block, 0, s, p, ##__VA_ARGS__)
+#define LDMSEG_FGN(MV) LDMSEG_GN((finish_gn_kernel<T, MV>), GB, ip->partial, ip->splits, ip->N, (long)ip->M * ip->N, ip->bias, ip->rowbias, ip->rb_stride)
+  switch (pl.form) {
+    case GN_GROUP: {
+      const int upp = pl.cpg / 4;                                   // 8-byte accesses per pixel
+      if (pl.NV == 10) LDMSEG_GN((gn_group_kernel<10, 2>), upp, 512 / upp, 512 % upp);
+      else LDMSEG_GN((gn_group_kernel<20, 2>), upp, 512 / upp, 512 % upp);
+      break;
+    }
+    case GN_COOP: LDMSEG_GN((gn_coop_kernel<T, kGnCoopMaxV, kGnCoopThreads>), GB); break;
+    case GN_ONE:
+      if (pl.MAXV == 2) LDMSEG_GN((gn_one_kernel<T, 2>), GB);
+      else if (pl.MAXV == 6) LDMSEG_GN((gn_one_kernel<T, 6>), GB);
+      else LDMSEG_GN((gn_one_kernel<T, 12>), GB);
+      break;
+    case GN_FUSED: LDMSEG_GN((gn_fused_kernel<T, kGnFusedMaxV>), GB); break;
+    case GN_SMALL: LDMSEG_GN((gn_small_kernel<T, 12>)); break;
+    case GN_FINISH:
+      if (pl.MAXV == 2) LDMSEG_FGN(2);
+      else if (pl.MAXV == 6) LDMSEG_FGN(6);
+      else LDMSEG_FGN(12);
+      break;
+    case GN_TWO_LAUNCH:
+    case GN_STATS:
+      LDMSEG_GN(gn_partial_kernel<T>);
+      if (pl.form == GN_TWO_LAUNCH)
+        LDMSEG_LAUNCH(gn_plan_name(pl, DT, 1), gn_apply_kernel<T>, dim3(pl.grid2_x, pl.grid2_y), block, 0, s, p);
+      break;
+    default: return -2;
+  }
+#undef LDMSEG_FGN
+#undef LDMSEG_GN
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+GnDesc gn_describe(const GNParams& p, int dtype) { return {p.B, p.HW, p.C0, p.C1, p.groups, p.nchunk, dtype}; }
+
 template <typename T>
 int run_gn(const GNParams& pin, hipStream_t s) {
-  constexpr int PC = Chunk<T>::N;
+  const GnDesc q = gn_describe(pin, Elem<T>::kDType);
   GNParams p = pin;
-  const int C = p.C0 + p.C1;
-  if (p.groups < 1 || C % p.groups != 0 || C % PC != 0 || p.C0 % PC != 0 || p.groups > 64) return -2;
-  p.cpg = C / p.groups;
-  p.fd_cpg = fastdiv_make(p.cpg);
-  p.inv_n = 1.0 / ((double)p.HW * p.cpg);
-  // a 16-B vector may span at most two groups: cpg >= PC, or exactly two whole groups per vector
-  // (128 channels in bf16: cpg 4, PC 8 - the image VAE's first level)
-  if (C / p.groups < PC && 2 * (C / p.groups) != PC) return -2;
-  if (C / PC > 256 * kMaxIter) return -2;
-  auto try_coop = [&]() -> int {   // returns 1 when the shape is not eligible
-    // cooperative one-pass kernel: the maps the register-resident kernel above cannot hold (64x64 and up)
-    constexpr int NTC = 512, MAXVC = 21;
-    const int cpg = C / p.groups;
-    for (int GB = 1; GB <= 4; GB *= 2) {
-      if ((GB * cpg) % PC != 0 || p.groups % GB != 0 || cpg < PC || cpg % 2 != 0) continue;
-      const int vpp = GB * cpg / PC;
-      if (vpp > 64) continue;
-      const int ppi = NTC / vpp;
-      const int slabs = p.B * (p.groups / GB);
-      if (slabs > kGnMaxSlabs) continue;
-      // splits: enough workgroups for every CU, as few as the registers allow
-      int S = 1;
-      while (S < 8 && ((p.HW + S - 1) / S + ppi - 1) / ppi > MAXVC) S *= 2;
-      while (S < 8 && slabs * S * 2 <= num_cus_gn() && p.HW / (2 * S) >= ppi) S *= 2;
-      if (((p.HW + S - 1) / S + ppi - 1) / ppi > MAXVC) continue;
-      if (slabs * S > num_cus_gn()) continue;                     // every workgroup must be resident: one per CU (8 waves at ~200 registers)
-      unsigned long long* region = (unsigned long long*)p.sync_region;
-      if (!region) {
-        region = gn_ring_region(s);
-        if (!region) break;                                         // no region for this stream: the two-launch path below
-      }
+  GnPlan pl;
+  if (const int r = gn_choose(q, g_gn_knobs, num_cus(), true, &pl)) return r;
+  if (pl.form == GN_COOP) {
+    unsigned long long* region = p.sync_region ? (unsigned long long*)p.sync_region : gn_ring_region(s);
+    if (!region) {                                                  // no region for this stream: the rule without the cooperative kernel
+      if (const int r = gn_choose(q, g_gn_knobs, num_cus(), false, &pl)) return r;
+    } else {
       gn_bind_region(p, region);
-      p.splits = S;
-      p.coop_mode = g_gn_coop_mode;
-      p.poll_ticks = (p.poll_us >= 0 ? p.poll_us : g_gn_poll_us) * 100;   // wall_clock64: 100 MHz
+      p.coop_mode = g_gn_knobs.coop_mode;
+      p.poll_ticks = (p.poll_us >= 0 ? p.poll_us : g_gn_knobs.poll_us) * 100;   // wall_clock64: 100 MHz
       // a handle that is backing off (its own short bound) does not count what that bound makes it miss: the counter then only
       // says what FULL-bound launches met, which is what the back-off decision wants to know (with every fallback
       // counted, 256 of them under the 2 us bound re-armed the back-off on every call and the full bound was never tried again)
       if (p.poll_us >= 0) p.sync_diag = nullptr;
-      p.per = (p.HW + S - 1) / S;
-      p.ty = ppi;
-      p.fd_aux = fastdiv_make(vpp);
-      p.fd_vx = fastdiv_make(S);
-      p.fd_cpg = fastdiv_make(p.groups / GB);
-      LDMSEG_LAUNCH(launch_name("gn_coop<%s,%d,%d,GB=%d>", dtype_tag<T>(), MAXVC, NTC, GB), (gn_coop_kernel<T, MAXVC, NTC>), dim3(slabs * S), dim3(NTC), 0, s, p, GB);
-      return hipGetLastError() == hipSuccess ? 0 : -3;
-    }
-    p.fd_cpg = fastdiv_make(p.cpg);
-    return 1;
-  };
-  // round 6: one workgroup per (image, group) with the slice in registers where that slice is small enough for 8-byte pieces to win
-  // (<= 40 dwords per thread and channels per group a multiple of 4; measured at B = 8, kbench gn: 32x32 x 640 12.0 -> 7.5 us (11 norms of a
-  // forward), 32x32 x (640+640) 15.5 -> 12.0, 16x16 x 640 6.1 -> 4.4, 16x16 x 1280 6.4 -> 5.2, 16x16 x (1280+1280) 9.3 -> 6.9, 16x16 x
-  // (1280+640) 10.4 -> 7.5; 8x8 maps level with gn_one_kernel and left there; whole forward -0.07 ms; tuning bit 5 switches it off)
-  if constexpr (sizeof(T) == 2) {
-    const long acc8 = (long)p.HW * (p.cpg / 4);                     // 8-byte accesses per (image, group) slice
-    constexpr int nv_max = 20;
-    if (!(g_gn_variant & 33) && p.HW >= 256 && p.cpg % 4 == 0 && p.cpg <= 128 && p.C0 % 4 == 0 && p.C1 % 4 == 0 && acc8 <= 512L * nv_max &&
-        (long)p.B * p.groups >= 128) {
-      const int upp = p.cpg / 4;                                    // 8-byte accesses per pixel
-      if (acc8 <= 512 * 10) LDMSEG_LAUNCH("gn_group<bf16,10,2>", (gn_group_kernel<10, 2>), dim3(p.B * p.groups), dim3(512), 0, s, p, upp, 512 / upp, 512 % upp);
-      else LDMSEG_LAUNCH("gn_group<bf16,20,2>", (gn_group_kernel<20, 2>), dim3(p.B * p.groups), dim3(512), 0, s, p, upp, 512 / upp, 512 % upp);
-      return hipGetLastError() == hipSuccess ? 0 : -3;
     }
   }
-  // the cooperative kernel first from 32x32 maps up (measured at B = 8: 32x32 x 640 13.9 -> 11.7 us, 32x32 x 1920 29.1 -> 18.8 us,
-  // 64x64 x 320 22.9 -> 16.3 us against the paths below); tuning bit1 extends it to the 16x16 maps
-  const int coop_min_hw = (g_gn_variant & 2) ? 256 : 1024;
-  if (!(g_gn_variant & 1) && p.HW >= coop_min_hw) {
-    const int r = try_coop();
-    if (r <= 0) return r;
-  }
-  {
-    // single-launch register-resident kernel: GB = 1 or 2 groups per workgroup forming whole 16-byte vectors
-    constexpr int MAXV = 22;
-    const int cpg = C / p.groups;
-    for (int GB = 1; GB <= 2; ++GB) {
-      if ((GB * cpg) % PC != 0 || p.groups % GB != 0) continue;
-      const int vpp = GB * cpg / PC;
-      if (vpp > 64) continue;
-      const int ppi = 256 / vpp;
-      if ((p.HW + ppi - 1) / ppi > MAXV) continue;
-      if ((long)p.B * (p.groups / GB) < 96) continue;          // too few workgroups to fill the chip
-      p.ty = ppi;
-      p.fd_aux = fastdiv_make(vpp);
-      const dim3 grid(p.groups / GB, p.B), grid1((p.groups / GB) * p.B);
-      const int nv = (p.HW + ppi - 1) / ppi;
-      if (!(g_gn_variant & 4) && nv <= 12) {                   // shipped: one reduction, one barrier (gn_one_kernel); measured at
-        // B = 8: 8x8 x 1280 6.2 -> 4.1 us, 16x16 x 1280 7.9 -> 6.9 us; with more than 12 vectors per thread the two-pass kernel
-        // below is the faster one (16x16 x 1920: 10.2 against 11.4 us)
-        if (nv <= 2) LDMSEG_LAUNCH(launch_name("gn_one<%s,2,GB=%d>", dtype_tag<T>(), GB), (gn_one_kernel<T, 2>), grid1, dim3(256), 0, s, p, GB);
-        else if (nv <= 6) LDMSEG_LAUNCH(launch_name("gn_one<%s,6,GB=%d>", dtype_tag<T>(), GB), (gn_one_kernel<T, 6>), grid1, dim3(256), 0, s, p, GB);
-        else LDMSEG_LAUNCH(launch_name("gn_one<%s,12,GB=%d>", dtype_tag<T>(), GB), (gn_one_kernel<T, 12>), grid1, dim3(256), 0, s, p, GB);
-        return hipGetLastError() == hipSuccess ? 0 : -3;
-      }
-      if (p.HW <= 64 && vpp < 10) continue;                    // 8x8 maps with short runs: gn_small measured faster (8.0 vs 9.7 us)
-      LDMSEG_LAUNCH(launch_name("gn_fused<%s,%d,GB=%d>", dtype_tag<T>(), MAXV, GB), (gn_fused_kernel<T, MAXV>), grid, dim3(256), 0, s, p, GB);
-      return hipGetLastError() == hipSuccess ? 0 : -3;
-    }
-  }
-  if (!(g_gn_variant & 1) && p.HW >= 2048) {
-    const int r = try_coop();
-    if (r <= 0) return r;
-  }
-  {
-    constexpr int EPU = 4 / (int)sizeof(T);
-    const int cpg = C / p.groups;
-    const long nunits = (long)p.HW * (cpg / EPU);
-    // measured: wins for the 8x8 maps (16 -> 9 us), loses from 16x16 up (its 4-byte strided loads)
-    if (cpg % EPU == 0 && p.C0 % EPU == 0 && nunits <= 256 * 12 && (long)p.B * p.groups >= 128) {
-      p.fd_aux = fastdiv_make(cpg / EPU);
-      LDMSEG_LAUNCH(launch_name("gn_small<%s,12>", dtype_tag<T>()), (gn_small_kernel<T, 12>), dim3(p.groups, p.B), dim3(256), 0, s, p);
-      return hipGetLastError() == hipSuccess ? 0 : -3;
-    }
-  }
-  const int nvec = C / PC;
-  p.vx = nvec < 256 ? nvec : 256;
-  p.ty = 256 / p.vx;
-  p.fd_vx = fastdiv_make(p.vx);
-  // the two-launch path combines statistics with 8 lanes per group in a 256-thread workgroup (32 groups) and keeps
-  // at most 128 chunk partials per lane set (gn_reduce_stats: MAXP = 16 x 8 lanes)
-  if (p.nchunk < 1 || p.nchunk > 128 || p.groups > 32) return -2;
-  p.per = (p.HW + p.nchunk - 1) / p.nchunk;
-  LDMSEG_LAUNCH(launch_name("gn_partial<%s>", dtype_tag<T>()), gn_partial_kernel<T>, dim3(p.nchunk, p.B), dim3(256), 0, s, p);
-  // pixel chunks: >= 4 pixels per thread row, ~2048 workgroups in total
-  const int ty = p.ty;
-  // 16 pixels per thread row (4 unrolled trips) on the big maps, down to 4 when that would leave fewer than ~512
-  // workgroups on the chip (every workgroup re-reduces the image's partials first, so fewer and fatter is better)
-  int blocks = (p.HW + 16 * ty - 1) / (16 * ty);
-  const int want = max(1, 512 / p.B);
-  if (blocks < want) blocks = min(want, (p.HW + 4 * ty - 1) / (4 * ty));
-  const int cap = max(1, 1024 / p.B);
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  LDMSEG_LAUNCH(launch_name("gn_apply<%s>", dtype_tag<T>()), gn_apply_kernel<T>, dim3(blocks, p.B), dim3(256), 0, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_gn_plan<T>(pl, p, s);
 }
 
 template <typename T>
@@ -1540,7 +1462,7 @@ int run_rowstats(const void* x, float* stats, int M, int C, float eps, hipStream
       if (blocks > 4096) blocks = 4096;
       return dim3(blocks < 1 ? 1 : blocks);
     };
-    if (!(g_gn_variant & 16)) {       // (tuning bit 4: the one-row-per-wave kernel below)
+    if (!(g_gn_knobs.variant & kGnRowstats1)) {       // (the one-row-per-wave kernel below)
       if (nvec <= 40) { LDMSEG_LAUNCH(launch_name("rowstats<%s,8,%d>", dtype_tag<T>(), RPW), (rowstats_kernel<T, 8, RPW>), grid_rows(8 * RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
       if (nvec <= 80) { LDMSEG_LAUNCH(launch_name("rowstats<%s,16,%d>", dtype_tag<T>(), RPW), (rowstats_kernel<T, 16, RPW>), grid_rows(4 * RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
       if (nvec <= 160) { LDMSEG_LAUNCH(launch_name("rowstats<%s,32,%d>", dtype_tag<T>(), RPW), (rowstats_kernel<T, 32, RPW>), grid_rows(2 * RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
@@ -1563,20 +1485,16 @@ int launch_rowstats(const void* x, float* stats, int M, int C, float eps, int dt
   return dtype == DT_BF16 ? run_rowstats<bf16_t>(x, stats, M, C, eps, s) : run_rowstats<float>(x, stats, M, C, eps, s);
 }
 
-int gn_nchunk(int B, int HW) {
-  // ~512-1024 workgroups in total, at least 8 pixels per chunk
-  int n = 768 / (B > 0 ? B : 1);
-  if (n < 1) n = 1;
-  if (n > 128) n = 128;
-  while (n > 1 && HW / n < 8) n >>= 1;
-  return n;
-}
+int gn_nchunk(int B, int HW) { return gn_nchunk_pure(B, HW); }
 
-void groupnorm_set_variant(int v) { g_gn_variant = v; }
+void groupnorm_set_variant(int v) { g_gn_knobs.variant = v; }
 void groupnorm_set_coop(int mode, int poll_us) {
-  g_gn_coop_mode = mode == 1 ? 1 : 0;
-  g_gn_poll_us = poll_us < 0 ? 100 : (poll_us > 1000000 ? 1000000 : poll_us);
+  g_gn_knobs.coop_mode = mode == 1 ? 1 : 0;
+  g_gn_knobs.poll_us = poll_us < 0 ? 100 : (poll_us > 1000000 ? 1000000 : poll_us);
 }
+int groupnorm_knob(int key) { return key == 8 ? g_gn_knobs.variant : key == 10 ? g_gn_knobs.coop_mode : g_gn_knobs.poll_us; }
+int groupnorm_plan(const GnDesc& q, int cus, bool region_ok, GnPlan* pl) { return gn_choose(q, g_gn_knobs, cus, region_ok, pl); }
+int finish_groupnorm_plan(int B, int HW, int C, int dtype, GnPlan* pl) { return gn_finish_choose(B, HW, C, dtype, g_gn_knobs, pl); }
 size_t gn_sync_bytes() { return kGnRegionWords * sizeof(unsigned long long); }
 int gn_sync_init(void* region, hipStream_t s) {
   return hipMemsetAsync(region, 0, gn_sync_bytes(), s) == hipSuccess ? 0 : -3;
@@ -1584,14 +1502,7 @@ int gn_sync_init(void* region, hipStream_t s) {
 int gn_warm() {
   std::lock_guard<std::mutex> lk(g_gn_mu);
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!g_gn_ring[dev]) {
-    void* q = nullptr;
-    if (hipMalloc(&q, kGnRegionWords * kGnRing * sizeof(unsigned long long)) != hipSuccess) return -3;
-    (void)hipMemset(q, 0, kGnRegionWords * kGnRing * sizeof(unsigned long long));
-    g_gn_ring[dev] = (unsigned long long*)q;
-  }
-  return 0;
+  return gn_ring_locked(&dev) ? 0 : -3;
 }
 const void* gn_sync_diag_ptr(const void* region) {
   return region ? (const void*)((const unsigned long long*)region + kGnCtrWords + kGnRecWords) : nullptr;
@@ -1619,73 +1530,30 @@ int launch_groupnorm(const GNParams& p, int dtype, hipStream_t s) {
 }
 
 namespace {
-// group block / pixels per trip / vectors per thread of the finish + GroupNorm kernel; false: no instantiation
-template <typename T>
-bool finish_gn_plan(int B, int HW, int C, int* GBo, int* vppo, int* ppio, int* nvo) {
-  constexpr int PC = Chunk<T>::N;
-  if (C % 32 != 0) return false;
-  const int cpg = C / 32;
-  for (int GB = 1; GB <= 2; ++GB) {
-    if ((GB * cpg) % PC != 0 || 32 % GB != 0) continue;
-    const int vpp = GB * cpg / PC;
-    if (vpp > 64) continue;
-    const int ppi = 256 / vpp;
-    const int nv = (HW + ppi - 1) / ppi;
-    if (nv > 12) continue;
-    if ((long)B * (32 / GB) < 96) continue;
-    *GBo = GB; *vppo = vpp; *ppio = ppi; *nvo = nv;
-    return true;
-  }
-  return false;
-}
 template <typename T>
 int run_finish_gn(const IgemmParams& ip, GNParams p, hipStream_t s) {
-  int GB, vpp, ppi, nv;
-  if (!finish_gn_plan<T>(p.B, p.HW, p.C0, &GB, &vpp, &ppi, &nv)) return -2;
+  GnKnobs k = g_gn_knobs;
+  k.variant &= ~kGnSplitFinish;             // (the engine asked finish_groupnorm_ok; a launch that is asked for runs)
+  GnPlan pl;
+  if (gn_finish_choose(p.B, p.HW, p.C0, Elem<T>::kDType, k, &pl)) return -2;
   if (ip.splits < 2 || !ip.partial || !ip.bias || ip.n_valid != p.C0 || ip.M != p.B * p.HW || p.C1 != 0) return -2;
   p.groups = 32;
-  p.cpg = p.C0 / 32;
-  p.inv_n = 1.0 / ((double)p.HW * p.cpg);
-  p.ty = ppi;
-  p.fd_aux = fastdiv_make(vpp);
-  const dim3 grid((32 / GB) * p.B);
-  const long slab = (long)ip.M * ip.N;
-#define LDMSEG_FGN(MV) LDMSEG_LAUNCH(launch_name("finish_gn<%s,%d,GB=%d>", dtype_tag<T>(), MV, GB), (finish_gn_kernel<T, MV>), grid, dim3(256), 0, s, p, GB, ip.partial, ip.splits, ip.N, slab, \
-                                          ip.bias, ip.rowbias, ip.rb_stride)
-  if (nv <= 2) LDMSEG_FGN(2);
-  else if (nv <= 6) LDMSEG_FGN(6);
-  else LDMSEG_FGN(12);
-#undef LDMSEG_FGN
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-}  // namespace
-
-bool finish_groupnorm_ok(int B, int HW, int C, int dtype) {
-  int a, b, c, d;
-  if (g_gn_variant & 8) return false;       // tuning bit 3: keep finish and norm apart
-  return dtype == DT_BF16 ? finish_gn_plan<bf16_t>(B, HW, C, &a, &b, &c, &d) : finish_gn_plan<float>(B, HW, C, &a, &b, &c, &d);
+  return launch_gn_plan<T>(pl, p, s, &ip);
 }
 // Statistics half of the two-launch path on its own (round 5): partial[b][chunk][group] = {mean, M2} over `per` = ceil(HW / nchunk)
 // pixels per chunk, nothing else is written.  The consumer (tproj.hip: the transformer's norm folded into the fused entry) combines
 // the chunks and applies the affine to its own rows.
 template <typename T>
-int run_gn_stats(const GNParams& pin, hipStream_t s) {
-  constexpr int PC = Chunk<T>::N;
-  GNParams p = pin;
-  const int C = p.C0 + p.C1;
-  if (p.groups < 1 || C % p.groups != 0 || C % PC != 0 || p.C0 % PC != 0 || p.groups > 32 || !p.partial) return -2;
-  p.cpg = C / p.groups;
-  p.fd_cpg = fastdiv_make(p.cpg);
-  if (p.cpg < PC && 2 * p.cpg != PC) return -2;
-  if (C / PC > 256 * kMaxIter) return -2;
-  const int nvec = C / PC;
-  p.vx = nvec < 256 ? nvec : 256;
-  p.ty = 256 / p.vx;
-  p.fd_vx = fastdiv_make(p.vx);
-  if (p.nchunk < 1 || p.nchunk > 128) return -2;
-  p.per = (p.HW + p.nchunk - 1) / p.nchunk;
-  LDMSEG_LAUNCH(launch_name("gn_partial<%s>", dtype_tag<T>()), gn_partial_kernel<T>, dim3(p.nchunk, p.B), dim3(256), 0, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+int run_gn_stats(const GNParams& p, hipStream_t s) {
+  GnPlan pl;
+  if (!p.partial || gn_stats_choose(gn_describe(p, Elem<T>::kDType), &pl)) return -2;
+  return launch_gn_plan<T>(pl, p, s);
+}
+}  // namespace
+
+bool finish_groupnorm_ok(int B, int HW, int C, int dtype) {
+  GnPlan pl;
+  return gn_finish_choose(B, HW, C, dtype, g_gn_knobs, &pl) == 0;
 }
 int launch_groupnorm_stats(const GNParams& p, int dtype, hipStream_t s) {
   return dtype == DT_BF16 ? run_gn_stats<bf16_t>(p, s) : run_gn_stats<float>(p, s);

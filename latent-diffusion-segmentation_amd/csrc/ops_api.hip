@@ -11,6 +11,7 @@
 
 #include "../../include/ldmseg_hip.h"
 #include "common.h"
+#include "gn_plan.h"
 #include "kernels.h"
 
 using namespace ldmseg;
@@ -293,6 +294,23 @@ int ldmseg_op_conv_groupnorm(const float* x, const float* w, const float* bias, 
   r = launch_finish_groupnorm(p, g, dtype, s);
   if (r) return r;
   return unpack_nhwc(op, out, B, Co, H * W, Co, dtype, s);
+}
+
+// The dispatch string of a described GroupNorm launch (gn_plan.h: the chooser under the current knobs; no device): the
+// dispatch-log names joined by " + ", then " splits=S grid=GXxGY block=T" (two launches: grid=GXxGY+GXxGY); -2 where ldmseg_op_groupnorm returns -2.
+// ldmseg_op_conv_groupnorm_plan: the finish + GroupNorm launch of ldmseg_op_conv_groupnorm; -4 where that returns -4.
+static int gn_plan_out(int r, const GnPlan& pl, int dtype, char* buf, int n) {
+  if (!buf || n < 1) return -2;
+  if (r == 0) std::snprintf(buf, (size_t)n, "%s", gn_plan_line(pl, dtype).c_str());
+  return r;
+}
+int ldmseg_op_groupnorm_plan(int B, int C, int C2, int HW, int groups, int dtype, int cus, int region_ok, char* buf, int n) {
+  GnPlan pl;
+  return gn_plan_out(groupnorm_plan(GnDesc{B, HW, C, C2, groups, gn_nchunk(B, HW), dtype}, cus, region_ok != 0, &pl), pl, dtype, buf, n);
+}
+int ldmseg_op_conv_groupnorm_plan(int B, int Co, int HW, int dtype, char* buf, int n) {
+  GnPlan pl;
+  return gn_plan_out(finish_groupnorm_plan(B, HW, Co, dtype, &pl), pl, dtype, buf, n);
 }
 
 // timing of one GroupNorm launch shape the way the engine launches it (tools/kbench.py gn): average microseconds over

@@ -138,6 +138,8 @@ SIGNATURES = {
     "ldmseg_bench_groupnorm": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), _vp]),
     "ldmseg_igemm_last_kernel": (_i, [C.c_char_p, _i]),
     "ldmseg_op_igemm_plan": (_i, [C.POINTER(_i), _i, _i, C.c_char_p, _i]),
+    "ldmseg_op_groupnorm_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i]),
+    "ldmseg_op_conv_groupnorm_plan": (_i, [_i, _i, _i, _i, C.c_char_p, _i]),
     "ldmseg_op_fastdiv": (_i, [_vp, _i, _i, _vp, _vp]),
     "ldmseg_igemm_log": (_i, [_i]),
     "ldmseg_igemm_log_read": (_i, [C.c_char_p, _i]),

@@ -405,6 +405,71 @@ def test_groupnorm_cooperative_without_partners(L, dt, case):
         lib.ldmseg_debug_set(8, 0)
 
 
+def _gn_fixture():
+    import json
+    import os
+    from conftest import GOLDEN
+    return json.load(open(os.path.join(GOLDEN, "gn_dispatch.json")))
+
+
+def _gn_plan_cases():
+    import gn_cases as G
+    return G.digest_cases() + G.CONV_DIGEST_CASES
+
+
+@pytest.mark.parametrize("case", _gn_plan_cases(), ids=lambda c: "-".join(map(str, c)))
+def test_groupnorm_plan_equals_launch(L, case):
+    """ldmseg_op_groupnorm_plan / ldmseg_op_conv_groupnorm_plan, given the device's CU count, name what the launch then logs, and
+    the launch writes the bytes it wrote before the chooser was factored out of the launcher (tests/golden/gn_dispatch.json:
+    SHA-256 of the fp32 output on the closed-form inputs of tests/gn_cases.py, recorded on an MI355X).  The kernels are
+    deterministic and their code is unchanged, so the same bytes mean the same grid, splits and pixels per trip: another split count
+    or trip length changes the order of the reduction.  Cases (B, C, C2, HW, dtype, key 8): every form, the cooperative one at 1, 2,
+    4 and 8 splits, and shapes one step to either side of the rule's comparisons; (B, Ci, H, Co, K slices, dtype): conv + finish."""
+    import gn_cases as G
+    lib = L.lib()
+    fx = _gn_fixture()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert cus == fx["cus"], "the digests belong to the recording's CU count"
+    conv = case in G.CONV_DIGEST_CASES
+    want = {tuple(r[:-1]): r[-1] for r in fx["conv_digests" if conv else "digests"]}
+    L.igemm_log(L.LOG_ALL)
+    try:
+        lib.ldmseg_debug_set(8, 0 if conv else case[5])
+        r, digest = (G.run_conv_digest_case if conv else G.run_digest_case)(lib, case)
+        names = sorted(n for n in L.igemm_log_read() if n.startswith(G.GN_FAMILY))
+        pr, line = G.conv_plan(lib, case[0], case[3], case[2] ** 2, case[5]) if conv else G.plan(lib, *case[:5], cus)
+    finally:
+        lib.ldmseg_debug_set(8, 0)
+        L.igemm_log(False)
+    print(case, line)
+    assert (r, pr) == (0, 0) and names == sorted(G.plan_names(line)), (case, names, line)
+    assert digest == want[case], (case, line)
+
+
+def test_groupnorm_plan_cases_straddle_the_rule(L):
+    """the cases above reach every form and the cooperative one at 1, 2, 4 and 8 splits, hold at most 2^22 elements, and the two
+    shapes of each pair - one step to either side of one comparison of the rule - plan different launches"""
+    import gn_cases as G
+    lib = L.lib()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert all(B * (c + c2) * hw <= 1 << 22 for B, c, c2, hw, _, _ in G.digest_cases())
+    lines = {}
+    try:
+        for case in G.digest_cases():
+            lib.ldmseg_debug_set(8, case[5])
+            r, lines[case] = G.plan(lib, *case[:5], cus)
+            assert r == 0, case
+    finally:
+        lib.ldmseg_debug_set(8, 0)
+    splits = {(ln.split("<")[0], int(ln.split("splits=")[1].split()[0])) for ln in lines.values()}
+    assert {("gn_coop", s) for s in (1, 2, 4, 8)} <= splits
+    assert {"gn_group", "gn_coop", "gn_one", "gn_fused", "gn_small", "gn_partial"} == {f for f, _ in splits}
+    forms = [G.conv_plan(lib, B, Co, H * H, dt)[1].split(",GB")[0] for B, _, H, Co, _, dt in G.CONV_DIGEST_CASES]
+    assert {f.split(",")[1] for f in forms} == {"2", "6", "12"} and all(f.startswith("finish_gn<") for f in forms)
+    for a, b in G.PAIRS:
+        assert lines[a].split(" grid=")[0] != lines[b].split(" grid=")[0], (a, lines[a], b, lines[b])
+
+
 @pytest.mark.parametrize("dt", [F32, BF16])
 @pytest.mark.parametrize("M,Cc,eps,silu", [(77, 320, 1e-5, 0), (64, 640, 1e-5, 0), (33, 1280, 1e-5, 0), (50, 256, 1e-6, 1)])
 def test_layernorm(L, dt, M, Cc, eps, silu):
