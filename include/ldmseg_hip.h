@@ -208,6 +208,37 @@ int ldmseg_vae_encode(ldmseg_vae* h, const float* x, float in_mul, float in_add,
  * out[B,4,l,l] = (mean + exp(0.5*clamp(logvar,-30,20))*noise) * out_scale; noise NULL -> mode(). */
 int ldmseg_vae_posterior(const float* moments, const float* noise, float out_scale, int B, int l, float* out,
                          void* stream);
+/* ---- stage-1 (seg-VAE reconstruction) evaluation: TrainerAE.compute_metrics(['miou', 'pq']), trainers_ae.py:546-803 ---- */
+/* SemsegMeter.update(pred, gt) (ldmseg/evaluations/semseg_evaluation.py:24-33) on n int64 (pred, gt) pairs on the device.
+ * counts int64 [3][num_classes] = (tp | fp | fn) is ADDED to, never reset: per pixel with gt != ignore_index,
+ *   pred == gt, 0 <= gt < K: tp[gt] += 1;  pred != gt, 0 <= gt < K: fn[gt] += 1;  pred != gt, 0 <= pred < K: fp[pred] += 1
+ * (the three masked sums of :31-33 read per pixel).  num_classes <= 256.  One launch, no host synchronisation. */
+int ldmseg_semseg_meter_update(const int64_t* pred, const int64_t* gt, int64_t n, int num_classes, int64_t ignore_index,
+                               int64_t* counts, void* stream);
+/* The tail of TrainerAE.compute_miou (trainers_ae.py:754-761) fused behind the decoder, without the [B,128,out_h,out_w]
+ * fp32 logits: decode(z * z_scale, interpolate=False) (vae.py:267-271) -> F.interpolate(size=(out_h, out_w), bilinear,
+ * align_corners=True) (:754) -> argmax (:755) -> pred = ignore_label where max softmax prob < mask_th (:757-760; mask_th < 0
+ * disables it) -> SemsegMeter.update(pred, targets) (:761) into counts as in ldmseg_semseg_meter_update.
+ *   targets [B,out_h,out_w] int64 device or NULL;  preds [B,out_h,out_w] int64 device or NULL;  counts [3][num_classes] or NULL
+ * (targets and counts are used together: with either NULL no counter is touched). */
+int ldmseg_vae_decode_semseg(ldmseg_vae* h, const float* z, float z_scale, int B, int L, int out_h, int out_w, float mask_th,
+                             int64_t ignore_label, const int64_t* targets, int64_t ignore_index, int num_classes, int64_t* preds,
+                             int64_t* counts, void* stream);
+/* vae_model(images, sample_posterior=False).sample (vae.py:273-307; trainers_ae.py:752) plus that tail in one call:
+ * encode(x * in_mul + in_add) -> posterior mode -> decode(interpolate=False), no scaling factor; x [B,7,H,H], H a multiple of 8.
+ * Moments and latents stay in the handle's workspace, whose plan covers encoder and decoder together. */
+int ldmseg_vae_reconstruct_semseg(ldmseg_vae* h, const float* x, float in_mul, float in_add, int B, int H, int out_h, int out_w,
+                                  float mask_th, int64_t ignore_label, const int64_t* targets, int64_t ignore_index,
+                                  int num_classes, int64_t* preds, int64_t* counts, void* stream);
+/* TrainerAE.compute_pq's per-batch work (trainers_ae.py:611-668) in one call: the same reconstruction chain into the tail of
+ * ldmseg_vae_decode_panoptic (resize to (in_h, in_w) :614-619, crop :626, resize to the original size :629-634, argmax /
+ * max-softmax threshold :637-641, segment filter :648-659) with ONE difference: the overlap mask is logit >= mask_th on the raw
+ * logits (:656), not sigmoid(logit) >= mask_th.  Geometry arrays and outputs as in ldmseg_vae_decode_panoptic. */
+int ldmseg_vae_reconstruct_panoptic(ldmseg_vae* h, const float* x, float in_mul, float in_add, int B, int H, int in_h, int in_w,
+                                    const int32_t* crop_boxes, const int32_t* out_sizes, const int64_t* out_offsets,
+                                    int threshold_output, float mask_th, int count_th, double overlap_th, int64_t ignore_label,
+                                    int32_t* labels, int32_t* panoptic, uint8_t* keep, int32_t* counts, int32_t* mask_counts,
+                                    void* stream);
 int64_t ldmseg_vae_num_params(const ldmseg_vae* h);
 
 /* ---- image VAE encoder: ldmseg/models/vae.py:36-39 GeneralVAEImage(AutoencoderKL), decoder removed

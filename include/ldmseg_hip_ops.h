@@ -63,6 +63,13 @@ int ldmseg_op_panoptic_from_decoder(const float* x4, int B, int C, int H4, int W
                                     int64_t ignore_label, int32_t* labels, int32_t* panoptic, uint8_t* keep, int32_t* counts,
                                     int32_t* mask_counts, float* volume, void* stream);
 
+/* The fused mIoU tail of ldmseg_vae_decode_semseg on a given decoder output x4 [B,C,H4,W4] (f32 NCHW, packed to NHWC `dtype`
+ * first; C <= 256, a multiple of 4 (f32) / 8 (bf16)).  volume (optional, device): the resampled logits [B][C][out_h*out_w] fp32 -
+ * lets a test compare the resampling with F.interpolate(align_corners=True) (trainers_ae.py:754). */
+int ldmseg_op_semseg_from_decoder(const float* x4, int B, int C, int H4, int W4, int dtype, int out_h, int out_w, float mask_th,
+                                  int64_t ignore_label, const int64_t* targets, int64_t ignore_index, int num_classes,
+                                  int64_t* preds, int64_t* counts, float* volume, void* stream);
+
 /* Entry of a transformer on caller-supplied weights: h = x Wp^T + bp (proj_in, /root/reference/ldmseg/models/unet.py:361-373 via
  * diffusers Transformer2DModel), q|k|v = [Wq | Wk | Wv] LayerNorm(h; gamma, beta).  mode 0: unfused launches; 1: the row-local fused
  * kernel (bf16, C = 320, M % 128 == 0).  h_out [M][C], qkv_out [M][3C] fp32.  time_iters > 0 also times the chosen path. */

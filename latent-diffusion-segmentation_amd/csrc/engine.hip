@@ -1374,12 +1374,22 @@ struct PanopticOut {
   int threshold_output = 0, threshold_mode = 0;
   float mask_th = 0.5f; int count_th = 0; double overlap_th = 0.0; int64_t ignore_label = 0;
   int32_t* labels = nullptr; int32_t* panoptic = nullptr; uint8_t* keep = nullptr; int32_t* counts = nullptr; int32_t* mask_counts = nullptr;
+  int mask_rule = 0;       // overlap mask: 0 sigmoid(logit) >= mask_th (trainers_ldm_cond.py:1288,1301), 1 logit >= mask_th (trainers_ae.py:656)
+};
+// fused mIoU tail (ldmseg_vae_decode_semseg / ldmseg_vae_reconstruct_semseg): trainers_ae.py:754-761 + SemsegMeter.update
+struct SemsegOut {
+  int out_h = 0, out_w = 0;
+  float mask_th = -1.f; int64_t ignore_label = 0;
+  const int64_t* targets = nullptr; int64_t ignore_index = 255; int K = 0;
+  int64_t* preds = nullptr; int64_t* counts = nullptr;
 };
 
-int vae_decode_impl(ldmseg_vae* v, const float* z, float z_scale, int B, int L, int interpolate, float* logits,
-                    hipStream_t s, bool dry, size_t scratch_base, const ArgmaxOut* am = nullptr, const PanopticOut* po = nullptr) {
-  Workspace* ws = &v->ws;
-  Exec ex = make_exec(*v, B, s, dry, scratch_base);
+// the decoder on an executor that is already set up (the reconstruct chain runs encoder and decoder on ONE workspace pass)
+int vae_decode_body(Exec& ex, ldmseg_vae* v, const float* z, float z_scale, int L, int interpolate, float* logits,
+                    const ArgmaxOut* am = nullptr, const PanopticOut* po = nullptr, const SemsegOut* so = nullptr) {
+  const int B = ex.B;
+  hipStream_t s = ex.s;
+  const bool dry = ex.dry();
   const int dt = v->dt;
   const ldmseg_vae_cfg& c = v->cfg;
   Act zin = ex.new_act(bke(dt), L, L, true);
@@ -1418,8 +1428,22 @@ int vae_decode_impl(ldmseg_vae* v, const float* z, float z_scale, int B, int L, 
       const int r = launch_panoptic_from_decoder(lo.p, B, H4, W4, c.out_channels, dt, po->in_h, po->in_w, po->boxes, po->sizes,
                                                  po->offsets, po->threshold_output, po->threshold_mode, po->mask_th, po->count_th,
                                                  po->overlap_th, po->ignore_label, po->labels, po->panoptic, po->keep, po->counts,
-                                                 po->mask_counts, s);
+                                                 po->mask_counts, s, nullptr, po->mask_rule);
       if (r == -2) return fail(LDMSEG_E_ARG, "decode_panoptic: bad crop box / output size / class count");
+      TRY(r);
+    }
+  } else if (so) {   // fused mIoU tail: NHWC logits at 4L -> align_corners=True resampling + argmax / threshold + meter counters
+    Act lo = ex.new_act(c.out_channels, H4, W4, false);
+    p.out = lo.p; p.ldo = c.out_channels; p.epi = EPI_STORE;
+    TRY(ex.igemm(p));
+    std::string label;
+    if (g_prof.on && !dry) label = "semseg_tail " + std::to_string(so->out_h) + "x" + std::to_string(so->out_w);
+    ProfScope ps(4, s, 0, (double)B * H4 * W4 * c.out_channels * esize(dt) + (double)B * so->out_h * so->out_w * 16.0, dry, label);
+    if (!dry) {
+      TRY(ex.ws_ok());
+      const int r = launch_semseg_from_decoder(lo.p, B, H4, W4, c.out_channels, dt, so->out_h, so->out_w, so->mask_th, so->ignore_label,
+                                               so->targets, so->ignore_index, so->K, so->preds, so->counts, s);
+      if (r == -2) return fail(LDMSEG_E_ARG, "decode_semseg: bad output size / class count");
       TRY(r);
     }
   } else if (am) {   // fused tail: NHWC logits at 4L -> bilinear x2 + argmax + max-softmax, no logits tensor
@@ -1441,10 +1465,17 @@ int vae_decode_impl(ldmseg_vae* v, const float* z, float z_scale, int B, int L, 
   return 0;
 }
 
-int vae_encode_impl(ldmseg_vae* v, const float* x, float mul, float add, int B, int H, float* moments, hipStream_t s,
-                    bool dry, size_t scratch_base) {
-  Workspace* ws = &v->ws;
+int vae_decode_impl(ldmseg_vae* v, const float* z, float z_scale, int B, int L, int interpolate, float* logits,
+                    hipStream_t s, bool dry, size_t scratch_base, const ArgmaxOut* am = nullptr, const PanopticOut* po = nullptr,
+                    const SemsegOut* so = nullptr) {
   Exec ex = make_exec(*v, B, s, dry, scratch_base);
+  return vae_decode_body(ex, v, z, z_scale, L, interpolate, logits, am, po, so);
+}
+
+int vae_encode_body(Exec& ex, ldmseg_vae* v, const float* x, float mul, float add, int H, float* moments) {
+  const int B = ex.B;
+  hipStream_t s = ex.s;
+  const bool dry = ex.dry();
   const int dt = v->dt;
   const ldmseg_vae_cfg& c = v->cfg;
   Act xin = ex.new_act(bke(dt), H, H, true);
@@ -1469,6 +1500,35 @@ int vae_encode_impl(ldmseg_vae* v, const float* x, float mul, float add, int B, 
   p.W = last.w; p.bias = last.bias; p.out = moments; p.epi = EPI_NCHW_F32;
   TRY(ex.igemm(p));
   return 0;
+}
+
+int vae_encode_impl(ldmseg_vae* v, const float* x, float mul, float add, int B, int H, float* moments, hipStream_t s,
+                    bool dry, size_t scratch_base) {
+  Exec ex = make_exec(*v, B, s, dry, scratch_base);
+  return vae_encode_body(ex, v, x, mul, add, H, moments);
+}
+
+// vae_model(images, sample_posterior=False).sample (vae.py:273-307) behind one workspace plan: encode -> posterior mode -> decode
+// (interpolate=False, no scaling factor) -> the tail `po` / `so`.  Moments [B,8,l,l] and latents [B,4,l,l] (fp32 NCHW, what
+// ldmseg_vae_encode / ldmseg_vae_posterior hand over; the callers refuse latent_channels != 4, which launch_posterior_sample assumes)
+// are persistent regions of the handle's workspace.  The plan is the SUM of both halves' persistent activations and the MAXIMUM of
+// their scratch peaks: the scratch stack is reset between the halves, which is safe because every launch is on the one stream.
+int vae_reconstruct_impl(ldmseg_vae* v, const float* x, float mul, float add, int B, int H, hipStream_t s, bool dry,
+                         size_t scratch_base, const PanopticOut* po, const SemsegOut* so) {
+  Exec ex = make_exec(*v, B, s, dry, scratch_base);
+  const int l = H / 8;
+  float* moments = (float*)v->ws.persist((size_t)B * 8 * l * l * sizeof(float));
+  float* z = (float*)v->ws.persist((size_t)B * 4 * l * l * sizeof(float));
+  TRY(vae_encode_body(ex, v, x, mul, add, H, moments));
+  {
+    ProfScope ps(4, s, 0, 0, dry);
+    if (!dry) {
+      TRY(ex.ws_ok());
+      TRY(launch_posterior_sample(moments, nullptr, z, B, l * l, s));
+    }
+  }
+  v->ws.reset(0);      // the decoder reuses the encoder's scratch (same stream: the encoder's launches are ordered before)
+  return vae_decode_body(ex, v, z, 1.0f, l, 1, nullptr, nullptr, po, so);
 }
 
 }  // namespace
@@ -2017,6 +2077,76 @@ int ldmseg_vae_encode(ldmseg_vae* h, const float* x, float in_mul, float in_add,
   return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
     return vae_encode_impl(h, x, in_mul, in_add, B, H, moments, (hipStream_t)stream, dry, scratch_base);
   });
+}
+
+namespace {
+int semseg_out_check(const ldmseg_vae* h, int out_h, int out_w, const int64_t* targets, int num_classes, const int64_t* counts) {
+  if (out_h < 1 || out_w < 1) return fail(LDMSEG_E_SHAPE, "bad output size");
+  if (h->cfg.out_channels > 256 || h->cfg.out_channels % 8) return fail(LDMSEG_E_ARG, "the fused tail needs out_channels <= 256, a multiple of 8");
+  if (targets && counts && (num_classes < 1 || num_classes > 256)) return fail(LDMSEG_E_ARG, "num_classes must be 1..256");
+  return 0;
+}
+}  // namespace
+
+int ldmseg_vae_decode_semseg(ldmseg_vae* h, const float* z, float z_scale, int B, int L, int out_h, int out_w, float mask_th,
+                             int64_t ignore_label, const int64_t* targets, int64_t ignore_index, int num_classes, int64_t* preds,
+                             int64_t* counts, void* stream) {
+  g_err.clear();
+  if (!h || !z) return fail(LDMSEG_E_ARG, "null argument");
+  if (B < 1 || L < 1) return fail(LDMSEG_E_SHAPE, "bad B/L");
+  TRY(semseg_out_check(h, out_h, out_w, targets, num_classes, counts));
+  DeviceGuard dg(h->cfg.device);
+  SemsegOut so{out_h, out_w, mask_th, ignore_label, targets, ignore_index, num_classes, preds, counts};
+  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
+    return vae_decode_impl(h, z, z_scale, B, L, 0, nullptr, (hipStream_t)stream, dry, scratch_base, nullptr, nullptr, &so);
+  });
+}
+
+int ldmseg_vae_reconstruct_semseg(ldmseg_vae* h, const float* x, float in_mul, float in_add, int B, int H, int out_h, int out_w,
+                                  float mask_th, int64_t ignore_label, const int64_t* targets, int64_t ignore_index,
+                                  int num_classes, int64_t* preds, int64_t* counts, void* stream) {
+  g_err.clear();
+  if (!h || !x) return fail(LDMSEG_E_ARG, "null argument");
+  if (B < 1 || H < 8 || H % 8) return fail(LDMSEG_E_SHAPE, "H must be a multiple of 8");
+  if (h->cfg.latent_channels != 4) return fail(LDMSEG_E_ARG, "the reconstruct chain assumes 4 latent channels");
+  TRY(semseg_out_check(h, out_h, out_w, targets, num_classes, counts));
+  DeviceGuard dg(h->cfg.device);
+  SemsegOut so{out_h, out_w, mask_th, ignore_label, targets, ignore_index, num_classes, preds, counts};
+  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
+    return vae_reconstruct_impl(h, x, in_mul, in_add, B, H, (hipStream_t)stream, dry, scratch_base, nullptr, &so);
+  });
+}
+
+int ldmseg_vae_reconstruct_panoptic(ldmseg_vae* h, const float* x, float in_mul, float in_add, int B, int H, int in_h, int in_w,
+                                    const int32_t* crop_boxes, const int32_t* out_sizes, const int64_t* out_offsets,
+                                    int threshold_output, float mask_th, int count_th, double overlap_th, int64_t ignore_label,
+                                    int32_t* labels, int32_t* panoptic, uint8_t* keep, int32_t* counts, int32_t* mask_counts,
+                                    void* stream) {
+  g_err.clear();
+  if (!h || !x || !out_sizes || !out_offsets || !labels || !panoptic || !keep || !counts || !mask_counts)
+    return fail(LDMSEG_E_ARG, "null argument");
+  if (B < 1 || H < 8 || H % 8 || in_h < 1 || in_w < 1) return fail(LDMSEG_E_SHAPE, "bad B/H/input size");
+  if (h->cfg.latent_channels != 4) return fail(LDMSEG_E_ARG, "the reconstruct chain assumes 4 latent channels");
+  if (h->cfg.num_upscalers != 2) return fail(LDMSEG_E_ARG, "the fused tail assumes interpolation_factor 2 (num_upscalers 2)");
+  DeviceGuard dg(h->cfg.device);
+  PanopticOut po;
+  po.in_h = in_h; po.in_w = in_w; po.boxes = crop_boxes; po.sizes = out_sizes; po.offsets = out_offsets;
+  po.threshold_output = threshold_output; po.threshold_mode = 0; po.mask_th = mask_th; po.count_th = count_th;
+  po.overlap_th = overlap_th; po.ignore_label = ignore_label;
+  po.labels = labels; po.panoptic = panoptic; po.keep = keep; po.counts = counts; po.mask_counts = mask_counts;
+  po.mask_rule = 1;
+  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
+    return vae_reconstruct_impl(h, x, in_mul, in_add, B, H, (hipStream_t)stream, dry, scratch_base, &po, nullptr);
+  });
+}
+
+int ldmseg_semseg_meter_update(const int64_t* pred, const int64_t* gt, int64_t n, int num_classes, int64_t ignore_index,
+                               int64_t* counts, void* stream) {
+  g_err.clear();
+  if (!counts || n < 0 || (n > 0 && (!pred || !gt))) return fail(LDMSEG_E_ARG, "null argument");
+  if (num_classes < 1 || num_classes > 256) return fail(LDMSEG_E_ARG, "num_classes must be 1..256");
+  TRY(launch_semseg_meter(pred, gt, (size_t)n, num_classes, ignore_index, counts, (hipStream_t)stream));
+  return 0;
 }
 
 int ldmseg_vae_image_create(const ldmseg_vae_image_cfg* cfg, int n_weights, const char* const* names,

@@ -428,7 +428,15 @@ int launch_panoptic_from_decoder(const void* x4, int B, int H4, int W4, int C, i
                                  const int32_t* boxes_host, const int32_t* sizes_host, const int64_t* offsets_host,
                                  int threshold_output, int threshold_mode, float mask_th, int count_th, double overlap_th,
                                  int64_t ignore_label, int32_t* labels, int32_t* panoptic, uint8_t* keep, int32_t* counts,
-                                 int32_t* mask_counts, hipStream_t s, float* volume = nullptr);   // volume: test hook, [sum_b C * h_b * w_b] fp32
+                                 int32_t* mask_counts, hipStream_t s, float* volume = nullptr,    // volume: test hook, [sum_b C * h_b * w_b] fp32
+                                 int mask_rule = 0);   // overlap mask: 0 sigmoid(logit) >= mask_th (LDM tail), 1 logit >= mask_th (trainers_ae.py:656)
+// SemsegMeter.update (semseg_evaluation.py:24-33): counts int64 [3][K] (tp | fp | fn) += the rule on n (pred, gt) pairs; K <= 256
+int launch_semseg_meter(const int64_t* pred, const int64_t* gt, size_t n, int K, int64_t ignore_index, int64_t* counts, hipStream_t s);
+// fused mIoU tail on the decoder's 4L NHWC output: align_corners=True bilinear to (oh, ow) -> argmax / max-softmax threshold -> the meter
+// rule against targets [B][oh * ow] (trainers_ae.py:754-761); targets / preds / volume (test hook, [B][C][oh * ow] fp32) may be null
+int launch_semseg_from_decoder(const void* x4, int B, int H4, int W4, int C, int dtype, int oh, int ow, float mask_th,
+                               int64_t ignore_label, const int64_t* targets, int64_t ignore_index, int K, int64_t* preds,
+                               int64_t* counts, hipStream_t s, float* volume = nullptr);
 int launch_bit_encode(const int64_t* ids, float* out, uint8_t* ignore, int B, int n, int HW, int64_t ignore_label,
                       float fill, float mul, float add, hipStream_t s);
 int launch_bit_decode(const float* x, int64_t* out, int B, int n, int HW, hipStream_t s);

@@ -354,6 +354,22 @@ int ldmseg_op_panoptic_from_decoder(const float* x4, int B, int C, int H4, int W
                                       mask_counts, s, volume);
 }
 
+// The fused mIoU tail (ldmseg_vae_decode_semseg) on a given 4L decoder output x4 [B,C,H4,W4] f32 NCHW: packs it to NHWC `dtype`
+// and runs semseg_scan_kernel.  volume (optional) receives the resampled logits [B][C][out_h * out_w] so that the interpolation
+// itself can be compared with F.interpolate(align_corners=True).
+int ldmseg_op_semseg_from_decoder(const float* x4, int B, int C, int H4, int W4, int dtype, int out_h, int out_w, float mask_th,
+                                  int64_t ignore_label, const int64_t* targets, int64_t ignore_index, int num_classes,
+                                  int64_t* preds, int64_t* counts, float* volume, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!x4 || B < 1 || C < 1 || H4 < 1 || W4 < 1) return -2;
+  Temp t;
+  void* xp = t.get((size_t)B * H4 * W4 * C * es(dtype));
+  if (!xp) return -3;
+  if (launch_pack_nchw(x4, xp, B, C, H4 * W4, C, 1.f, 0.f, dtype, s)) return -3;
+  return launch_semseg_from_decoder(xp, B, H4, W4, C, dtype, out_h, out_w, mask_th, ignore_label, targets, ignore_index, num_classes,
+                                    preds, counts, s, volume);
+}
+
 int ldmseg_op_layernorm(const float* x, const float* gamma, const float* beta, int M, int C, float eps, int silu, int dtype,
                         float* out, void* stream) {
   hipStream_t s = (hipStream_t)stream;

@@ -13,6 +13,7 @@
 // Counters are integers accumulated with integer atomics: the result does not depend on the order.
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cstdint>
 
 #include "common.h"
@@ -158,6 +159,7 @@ struct ResampleScanParams {
   int oh, ow;              // output (original image) size
   int threshold_output, threshold_mode;
   float mask_th;
+  int mask_rule;           // overlap mask of class c: 0 sigmoid(logit_c) >= mask_th (trainers_ldm_cond.py:1288,1301), 1 logit_c >= mask_th (trainers_ae.py:656)
   int32_t* labels;         // [oh * ow]
   int32_t* counts;         // [C] of this image
   int32_t* mask_counts;    // [C]
@@ -216,7 +218,7 @@ __global__ __launch_bounds__(256) void resample_scan_kernel(const ResampleScanPa
         ssum += __expf(val - m);
         m2 = fmaxf(m2, val);
       }
-      const bool in_mask = live && (1.0f / (1.0f + expf(-val)) >= p.mask_th);
+      const bool in_mask = live && ((p.mask_rule ? val : 1.0f / (1.0f + expf(-val))) >= p.mask_th);
       const unsigned long long bal = __ballot(in_mask);
       if (lane == 0 && bal) atomicAdd(&s_msk[c + e], __popcll(bal));
     }
@@ -238,6 +240,128 @@ __global__ __launch_bounds__(256) void resample_scan_kernel(const ResampleScanPa
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Stage-1 (seg-VAE reconstruction) evaluation: SemsegMeter.update (ldmseg/evaluations/semseg_evaluation.py:24-33) and the
+// tail of TrainerAE.compute_miou (trainers_ae.py:754-761) without the [B,C,out_h,out_w] fp32 volume.
+//
+// The meter rule for one pixel with target t != ignore_index and prediction q (the three masked sums of :28-33 read per pixel):
+//   q == t and 0 <= t < K : tp[t] += 1
+//   q != t and 0 <= t < K : fn[t] += 1
+//   q != t and 0 <= q < K : fp[q] += 1
+// Counters live in LDS per workgroup ([3][K] ints, K <= 256) and the non-zero ones are added to the caller's int64 [3][K]
+// (tp | fp | fn) with 64-bit integer atomics: sums of integers, the same in any order.  The global counters are NOT reset.
+__device__ __forceinline__ void meter_pixel(int* s_tp, int* s_fp, int* s_fn, int64_t q, int64_t t, int64_t ignore_index, int K) {
+  if (t == ignore_index) return;
+  const bool t_in = t >= 0 && t < K;
+  if (q == t) {
+    if (t_in) atomicAdd(&s_tp[(int)t], 1);
+  } else {
+    if (t_in) atomicAdd(&s_fn[(int)t], 1);
+    if (q >= 0 && q < K) atomicAdd(&s_fp[(int)q], 1);
+  }
+}
+__device__ __forceinline__ void meter_flush(const int* s_cnt, int K, unsigned long long* counts) {
+  for (int i = threadIdx.x; i < 3 * K; i += blockDim.x)
+    if (s_cnt[i]) atomicAdd(&counts[i], (unsigned long long)s_cnt[i]);
+}
+
+// grid-stride over n (pred, gt) pairs; each workgroup handles fewer than 2^31 pixels (int LDS counters)
+__global__ __launch_bounds__(256) void semseg_meter_kernel(const int64_t* pred, const int64_t* gt, size_t n, int K,
+                                                           int64_t ignore_index, unsigned long long* counts) {
+  __shared__ int s_cnt[3 * kMaxClasses];
+  for (int i = threadIdx.x; i < 3 * K; i += blockDim.x) s_cnt[i] = 0;
+  __syncthreads();
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    meter_pixel(s_cnt, s_cnt + K, s_cnt + 2 * K, pred[i], gt[i], ignore_index, K);
+  __syncthreads();
+  meter_flush(s_cnt, K, counts);
+}
+
+// One thread = one pixel of the (oh, ow) target grid of image blockIdx.y; one bilinear stage with torch's align_corners=True
+// arithmetic (F.interpolate(..., align_corners=True), trainers_ae.py:754): scale = (n_in - 1) / (n_out - 1) (0 when n_out == 1),
+// src = scale * dst in fp32, i0 = (int)src, i1 = min(i0 + 1, n_in - 1), weights (1 - frac, frac).  The C classes are walked in
+// 16-byte chunks of the four corner pixels of the NHWC map.  Reads B * H4 * W4 * C elements of the compute dtype (neighbouring
+// pixels share their corners through L1/L2) + 8 bytes of target per pixel, writes 8 bytes per pixel (optional) and 3 * K counters.
+struct SemsegScanParams {
+  const void* x4;          // [B][H4][W4][C], compute dtype
+  int H4, W4, C;
+  int oh, ow;
+  float mask_th;           // >= 0: pred = ignore_label where the max softmax probability < mask_th (:757-760)
+  int64_t ignore_label;
+  const int64_t* targets;  // [B][oh * ow] or null
+  int64_t ignore_index;
+  int K;
+  int64_t* preds;          // [B][oh * ow] or null
+  unsigned long long* counts;   // [3][K] (tp | fp | fn), accumulated; null when targets is null
+  float* volume;           // test hook: when non-null the resampled logits [B][C][oh * ow] are also written (fp32)
+};
+__device__ __forceinline__ void ac_taps(int o, int n_in, int n_out, int& i0, int& i1, float& w0, float& w1) {
+  const float scale = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f;
+  const float src = scale * (float)o;
+  i0 = (int)src;
+  if (i0 > n_in - 1) i0 = n_in - 1;
+  i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
+  w1 = src - (float)i0;
+  w0 = 1.f - w1;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void semseg_scan_kernel(const SemsegScanParams p) {
+  constexpr int PC = Chunk<T>::N;
+  __shared__ int s_cnt[3 * kMaxClasses];
+  const int K = p.targets ? p.K : 0;
+  for (int i = threadIdx.x; i < 3 * K; i += blockDim.x) s_cnt[i] = 0;
+  __syncthreads();
+  const int b = blockIdx.y;
+  const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+  const int HW = p.oh * p.ow;
+  const bool live = pix < HW;
+  const int oy = live ? pix / p.ow : 0, ox = live ? pix - oy * p.ow : 0;
+  int y0, y1, x0, x1;
+  float wy0, wy1, wx0, wx1;
+  ac_taps(oy, p.H4, p.oh, y0, y1, wy0, wy1);
+  ac_taps(ox, p.W4, p.ow, x0, x1, wx0, wx1);
+  const T* x = (const T*)p.x4 + (size_t)b * p.H4 * p.W4 * p.C;
+  const T* p00 = x + ((size_t)y0 * p.W4 + x0) * p.C;
+  const T* p01 = x + ((size_t)y0 * p.W4 + x1) * p.C;
+  const T* p10 = x + ((size_t)y1 * p.W4 + x0) * p.C;
+  const T* p11 = x + ((size_t)y1 * p.W4 + x1) * p.C;
+  // (a finite start: a logit of -inf in channel 0 then adds exp(-inf) = 0 to the denominator instead of exp(-inf + inf) = NaN)
+  float m = -FLT_MAX, ssum = 0.f;
+  int arg = 0;
+  for (int c = 0; live && c < p.C; c += PC) {      // threads past the last pixel only take part in the counter flush
+    float a[PC], bb[PC], cc[PC], d[PC];
+    Chunk<T>::unpack(*(const uint4*)(p00 + c), a);
+    Chunk<T>::unpack(*(const uint4*)(p01 + c), bb);
+    Chunk<T>::unpack(*(const uint4*)(p10 + c), cc);
+    Chunk<T>::unpack(*(const uint4*)(p11 + c), d);
+#pragma unroll
+    for (int e = 0; e < PC; ++e) {
+      // the expression of torch's upsample_bilinear2d
+      const float v = wy0 * (wx0 * a[e] + wx1 * bb[e]) + wy1 * (wx0 * cc[e] + wx1 * d[e]);
+      if (p.volume) p.volume[((size_t)b * p.C + c + e) * HW + pix] = v;
+      if (v > m) {               // strict: the first maximum wins, like torch.argmax
+        ssum = ssum * __expf(m - v) + 1.f;
+        m = v;
+        arg = c + e;
+      } else {
+        ssum += __expf(v - m);
+      }
+    }
+  }
+  if (live) {
+    int64_t q = arg;
+    if (p.mask_th >= 0.f && 1.f / ssum < p.mask_th) q = p.ignore_label;
+    const size_t o = (size_t)b * HW + pix;
+    if (p.preds) p.preds[o] = q;
+    if (K) meter_pixel(s_cnt, s_cnt + K, s_cnt + 2 * K, q, p.targets[o], p.ignore_index, K);
+  }
+  if (K) {
+    __syncthreads();
+    meter_flush(s_cnt, K, p.counts);
+  }
+}
+
 }  // namespace
 
 // Fused evaluation tail on the decoder's 4L output (see resample_scan_kernel).  boxes [B][4] = (y0, x0, height, width) of the
@@ -247,7 +371,7 @@ int launch_panoptic_from_decoder(const void* x4, int B, int H4, int W4, int C, i
                                  const int32_t* boxes, const int32_t* sizes, const int64_t* offsets, int threshold_output,
                                  int threshold_mode, float mask_th, int count_th, double overlap_th, int64_t ignore_label,
                                  int32_t* labels, int32_t* panoptic, uint8_t* keep, int32_t* counts, int32_t* mask_counts,
-                                 hipStream_t s, float* volume) {
+                                 hipStream_t s, float* volume, int mask_rule) {
   if (C < 1 || C > kMaxClasses || B < 1 || H4 < 1 || W4 < 1 || in_h < 1 || in_w < 1) return -2;
   if (C % (dtype == DT_BF16 ? 8 : 4) != 0) return -2;
   if (hipMemsetAsync(counts, 0, (size_t)B * C * sizeof(int32_t), s) != hipSuccess) return -3;
@@ -261,7 +385,7 @@ int launch_panoptic_from_decoder(const void* x4, int B, int H4, int W4, int C, i
     p.ch = boxes ? boxes[4 * b + 2] : in_h; p.cw = boxes ? boxes[4 * b + 3] : in_w;
     p.oh = sizes[2 * b]; p.ow = sizes[2 * b + 1];
     if (p.y0 < 0 || p.x0 < 0 || p.ch < 1 || p.cw < 1 || p.y0 + p.ch > in_h || p.x0 + p.cw > in_w || p.oh < 1 || p.ow < 1) return -2;
-    p.threshold_output = threshold_output; p.threshold_mode = threshold_mode; p.mask_th = mask_th;
+    p.threshold_output = threshold_output; p.threshold_mode = threshold_mode; p.mask_th = mask_th; p.mask_rule = mask_rule;
     p.labels = labels + offsets[b];
     p.counts = counts + (size_t)b * C;
     p.mask_counts = mask_counts + (size_t)b * C;
@@ -296,6 +420,37 @@ int launch_panoptic_postprocess(const float* logits, int B, int C, int HW, int t
   size_t blocks = (total + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(panoptic_remap_kernel, dim3((unsigned)blocks), dim3(256), 0, s, labels, keep, C, HW, total, panoptic);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// SemsegMeter.update on n (pred, gt) int64 pairs: counts int64 [3][K] += (tp | fp | fn); see semseg_meter_kernel
+int launch_semseg_meter(const int64_t* pred, const int64_t* gt, size_t n, int K, int64_t ignore_index, int64_t* counts, hipStream_t s) {
+  if (K < 1 || K > kMaxClasses) return -2;
+  if (n == 0) return 0;
+  size_t blocks = (n + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  if (n / blocks >= (size_t)1 << 31) return -2;        // (an int LDS counter per workgroup)
+  hipLaunchKernelGGL(semseg_meter_kernel, dim3((unsigned)blocks), dim3(256), 0, s, pred, gt, n, K, ignore_index,
+                     (unsigned long long*)counts);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// Fused mIoU tail on the decoder's 4L NHWC output (see semseg_scan_kernel): one launch, grid (ceil(oh * ow / 256), B)
+int launch_semseg_from_decoder(const void* x4, int B, int H4, int W4, int C, int dtype, int oh, int ow, float mask_th,
+                               int64_t ignore_label, const int64_t* targets, int64_t ignore_index, int K, int64_t* preds,
+                               int64_t* counts, hipStream_t s, float* volume) {
+  if (C < 1 || C > kMaxClasses || B < 1 || B > 65535 || H4 < 1 || W4 < 1 || oh < 1 || ow < 1) return -2;
+  if (C % (dtype == DT_BF16 ? 8 : 4) != 0) return -2;
+  if ((size_t)oh * ow > (size_t)0x7fffff00) return -2;
+  if (!counts) targets = nullptr;                       // nothing to add the rule into
+  if (targets && (K < 1 || K > kMaxClasses)) return -2;
+  SemsegScanParams p;
+  p.x4 = x4; p.H4 = H4; p.W4 = W4; p.C = C; p.oh = oh; p.ow = ow; p.mask_th = mask_th; p.ignore_label = ignore_label;
+  p.targets = targets; p.ignore_index = ignore_index; p.K = K; p.preds = preds; p.counts = (unsigned long long*)counts;
+  p.volume = volume;
+  const dim3 grid((oh * ow + 255) / 256, B);
+  if (dtype == DT_BF16) hipLaunchKernelGGL(semseg_scan_kernel<bf16_t>, grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(semseg_scan_kernel<float>, grid, dim3(256), 0, s, p);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -94,6 +94,11 @@ SIGNATURES = {
     "ldmseg_clip_text_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ldmseg_vae_decode_panoptic": (_i, [_vp, _vp, _f, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _f, _i, _d, _i64, _vp, _vp, _vp, _vp, _vp,
                                         _vp]),
+    "ldmseg_semseg_meter_update": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _vp]),
+    "ldmseg_vae_decode_semseg": (_i, [_vp, _vp, _f, _i, _i, _i, _i, _f, _i64, _vp, _i64, _i, _vp, _vp, _vp]),
+    "ldmseg_vae_reconstruct_semseg": (_i, [_vp, _vp, _f, _f, _i, _i, _i, _i, _f, _i64, _vp, _i64, _i, _vp, _vp, _vp]),
+    "ldmseg_vae_reconstruct_panoptic": (_i, [_vp, _vp, _f, _f, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _d, _i64, _vp, _vp, _vp, _vp,
+                                             _vp, _vp]),
     "ldmseg_panoptic_postprocess": (_i, [_vp, _i, _i, _i, _i, _i, _i, _f, _i, _d, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ldmseg_bit_encode": (_i, [_vp, _i, _i, _i, _i64, _f, _f, _f, _vp, _vp, _vp]),
     "ldmseg_bit_decode": (_i, [_vp, _i, _i, _i, _vp, _vp]),
@@ -134,6 +139,7 @@ SIGNATURES = {
     "ldmseg_bench_attention": (_i, [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), _vp]),
     "ldmseg_op_panoptic_from_decoder": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _f, _i, _d, _i64, _vp, _vp, _vp,
                                              _vp, _vp, _vp, _vp]),
+    "ldmseg_op_semseg_from_decoder": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _f, _i64, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "ldmseg_op_conv_groupnorm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp]),
     "ldmseg_bench_groupnorm": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), _vp]),
     "ldmseg_igemm_last_kernel": (_i, [C.c_char_p, _i]),

@@ -165,18 +165,28 @@ class GeneralVAESeg(object):
         bilinear x2 -> bilinear to `in_size` (H, W) -> crop to `crop_boxes[b]` = (y0, x0, height, width) -> bilinear to
         `out_sizes[b]` = (h, w) -> argmax / thresholds / segment filtering, without the [B,128,H,W] logits.
         Returns a list of (panoptic [h,w] int32 tensor on the GPU (label + 1, 0 = void), kept label list)."""
-        import numpy as np
         z = _lib.require_cuda_f32(z, "z")
         if threshold_mode not in ("max", "topk_diff"):
             raise ValueError(f"unknown threshold_mode {threshold_mode!r}")
         B, _, L, _ = z.shape
+
+        def call(boxes, sizes, offs, labels, pan, keep, counts, mcounts):
+            _lib.check(_lib.lib().ldmseg_vae_decode_panoptic(
+                self._h, _lib.ptr(z), float(z_scale), B, L, int(in_size[0]), int(in_size[1]), boxes, sizes, offs,
+                int(bool(threshold_output)), 1 if threshold_mode == "topk_diff" else 0, float(mask_th), int(count_th),
+                float(overlap_th), int(ignore_label), _lib.ptr(labels), _lib.ptr(pan), _lib.ptr(keep), _lib.ptr(counts),
+                _lib.ptr(mcounts), _lib.stream_ptr(z.device)), "ldmseg_vae_decode_panoptic")
+        return self._panoptic_tail(call, B, z.device, out_sizes, crop_boxes, return_stats)
+
+    def _panoptic_tail(self, call, B, dev, out_sizes, crop_boxes, return_stats):
+        """Host geometry arrays and device outputs of the fused panoptic tail; `call` makes the library call on them."""
+        import numpy as np
         Cn = self.out_channels
         sizes = np.ascontiguousarray(np.asarray(out_sizes, dtype=np.int32).reshape(B, 2))
         boxes = None if crop_boxes is None else np.ascontiguousarray(np.asarray(crop_boxes, dtype=np.int32).reshape(B, 4))
         npix = sizes[:, 0].astype(np.int64) * sizes[:, 1].astype(np.int64)
         offs = np.ascontiguousarray(np.concatenate([[0], np.cumsum(npix)[:-1]]).astype(np.int64))
         total = int(npix.sum())
-        dev = z.device
         labels = torch.empty(total, dtype=torch.int32, device=dev)
         pan = torch.empty(total, dtype=torch.int32, device=dev)
         keep = torch.empty(B, Cn, dtype=torch.uint8, device=dev)
@@ -184,11 +194,7 @@ class GeneralVAESeg(object):
         mcounts = torch.empty(B, Cn, dtype=torch.int32, device=dev)
         vp = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().ldmseg_vae_decode_panoptic(
-                self._h, _lib.ptr(z), float(z_scale), B, L, int(in_size[0]), int(in_size[1]), vp(boxes), vp(sizes), vp(offs),
-                int(bool(threshold_output)), 1 if threshold_mode == "topk_diff" else 0, float(mask_th), int(count_th),
-                float(overlap_th), int(ignore_label), _lib.ptr(labels), _lib.ptr(pan), _lib.ptr(keep), _lib.ptr(counts),
-                _lib.ptr(mcounts), _lib.stream_ptr(dev)), "ldmseg_vae_decode_panoptic")
+            call(vp(boxes), vp(sizes), vp(offs), labels, pan, keep, counts, mcounts)
         keep_h = keep.cpu()
         out = []
         for b in range(B):
@@ -198,6 +204,82 @@ class GeneralVAESeg(object):
             lab = [labels[int(offs[b]):int(offs[b]) + int(npix[b])].view(int(sizes[b, 0]), int(sizes[b, 1])) for b in range(B)]
             return out, {"labels": lab, "counts": counts, "mask_counts": mcounts, "keep": keep}
         return out
+
+    def reconstruct_panoptic(self, x: torch.Tensor, in_size, out_sizes, crop_boxes=None, in_mul: float = 1.0,
+                             in_add: float = 0.0, threshold_output: bool = True, mask_th: float = 0.5, count_th: int = 512,
+                             overlap_th: float = 0.5, ignore_label: int = 0, return_stats: bool = False):
+        """One batch of `TrainerAE.compute_pq` (trainers_ae.py:611-668) in one call: encode(x * in_mul + in_add) -> posterior
+        mode -> decode -> the tail of `decode_panoptic`, with the overlap mask `logit >= mask_th` of :656 (not the sigmoid).
+        x [B,7,H,H]; returns what `decode_panoptic` returns."""
+        x = _lib.require_cuda_f32(x, "x")
+        B, H = self._check_bitmaps(x)
+
+        def call(boxes, sizes, offs, labels, pan, keep, counts, mcounts):
+            _lib.check(_lib.lib().ldmseg_vae_reconstruct_panoptic(
+                self._h, _lib.ptr(x), float(in_mul), float(in_add), B, H, int(in_size[0]), int(in_size[1]), boxes, sizes, offs,
+                int(bool(threshold_output)), float(mask_th), int(count_th), float(overlap_th), int(ignore_label),
+                _lib.ptr(labels), _lib.ptr(pan), _lib.ptr(keep), _lib.ptr(counts), _lib.ptr(mcounts),
+                _lib.stream_ptr(x.device)), "ldmseg_vae_reconstruct_panoptic")
+        return self._panoptic_tail(call, B, x.device, out_sizes, crop_boxes, return_stats)
+
+    def _check_bitmaps(self, x):
+        B, Cin, H, W = x.shape
+        if Cin != self._in_channels or H != W or H % self.downsample_factor:
+            raise ValueError(f"expected [B,{self._in_channels},H,H] with H a multiple of {self.downsample_factor}, got {tuple(x.shape)}")
+        return B, H
+
+    def _semseg_tail(self, B, dev, out_size, targets, counts, num_classes, return_preds):
+        """Arguments of the fused mIoU tail: (out_h, out_w, targets, K, preds, counts) with the tensors checked."""
+        oh, ow = int(out_size[0]), int(out_size[1])
+        if (targets is None) != (counts is None):
+            raise ValueError("targets and counts go together")
+        K = 0
+        if targets is not None:
+            if not targets.is_cuda or not counts.is_cuda:
+                raise RuntimeError("targets and counts must live on the MI355X (no CPU fallback)")
+            targets = targets.to(torch.int64).contiguous()
+            if tuple(targets.shape) != (B, oh, ow):
+                raise ValueError(f"targets must be [{B},{oh},{ow}], got {tuple(targets.shape)}")
+            K = int(num_classes) if num_classes is not None else int(counts.shape[-1])
+            if counts.dtype != torch.int64 or not counts.is_contiguous() or tuple(counts.shape) != (3, K):
+                raise ValueError(f"counts must be a contiguous int64 [3,{K}] tensor")
+        preds = torch.empty((B, oh, ow), device=dev, dtype=torch.int64) if return_preds else None
+        return oh, ow, targets, K, preds
+
+    def decode_semseg(self, z: torch.Tensor, out_size, targets: Optional[torch.Tensor] = None,
+                      counts: Optional[torch.Tensor] = None, z_scale: float = 1.0, mask_th: Optional[float] = None,
+                      ignore_label: int = 0, ignore_index: int = 255, num_classes: Optional[int] = None,
+                      return_preds: bool = True):
+        """The tail of `TrainerAE.compute_miou` (trainers_ae.py:754-761) fused behind the decoder: decode(interpolate=False) ->
+        bilinear to `out_size` with align_corners=True -> argmax (+ max-softmax threshold -> `ignore_label`) -> the
+        `SemsegMeter.update` rule against `targets` [B,h,w], ADDED to `counts` (int64 [3,K] on the GPU, e.g.
+        `SemsegMeter.device_counts`).  Returns predictions [B,h,w] int64 (None with return_preds=False)."""
+        z = _lib.require_cuda_f32(z, "z")
+        B, _, L, _ = z.shape
+        oh, ow, targets, K, preds = self._semseg_tail(B, z.device, out_size, targets, counts, num_classes, return_preds)
+        with torch.cuda.device(z.device):
+            _lib.check(_lib.lib().ldmseg_vae_decode_semseg(
+                self._h, _lib.ptr(z), float(z_scale), B, L, oh, ow, -1.0 if mask_th is None else float(mask_th),
+                int(ignore_label), _lib.ptr(targets), int(ignore_index), K, _lib.ptr(preds), _lib.ptr(counts),
+                _lib.stream_ptr(z.device)), "ldmseg_vae_decode_semseg")
+        return preds
+
+    def reconstruct_semseg(self, x: torch.Tensor, out_size, targets: Optional[torch.Tensor] = None,
+                           counts: Optional[torch.Tensor] = None, in_mul: float = 1.0, in_add: float = 0.0,
+                           mask_th: Optional[float] = None, ignore_label: int = 0, ignore_index: int = 255,
+                           num_classes: Optional[int] = None, return_preds: bool = True):
+        """`vae_model(x, sample_posterior=False).sample` (vae.py:273-307) plus the tail of `decode_semseg` in one library call:
+        encode(x * in_mul + in_add) -> posterior mode -> decode, no scaling factor; moments and latents never leave the
+        handle's workspace and nothing synchronises with the host.  x [B,7,H,H]."""
+        x = _lib.require_cuda_f32(x, "x")
+        B, H = self._check_bitmaps(x)
+        oh, ow, targets, K, preds = self._semseg_tail(B, x.device, out_size, targets, counts, num_classes, return_preds)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().ldmseg_vae_reconstruct_semseg(
+                self._h, _lib.ptr(x), float(in_mul), float(in_add), B, H, oh, ow, -1.0 if mask_th is None else float(mask_th),
+                int(ignore_label), _lib.ptr(targets), int(ignore_index), K, _lib.ptr(preds), _lib.ptr(counts),
+                _lib.stream_ptr(x.device)), "ldmseg_vae_reconstruct_semseg")
+        return preds
 
     def forward(self, sample, sample_posterior: bool = True, return_dict: bool = True,
                 generator: Optional[torch.Generator] = None, rgb_sample=None, valid_mask=None):

@@ -1,1 +1,2 @@
 from .sampler import TrainerDiffusion  # noqa: F401
+from .trainer_ae import TrainerAE  # noqa: F401

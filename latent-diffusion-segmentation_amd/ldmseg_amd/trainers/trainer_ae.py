@@ -1,0 +1,105 @@
+"""Stage-1 evaluation: how well the segmentation VAE reconstructs ground-truth panoptic maps through its latent.
+
+Stands behind the evaluation half of the reference's ldmseg/trainers/trainers_ae.py::TrainerAE
+(`compute_metrics` :546-569, `compute_pq` :580-680, `compute_miou` :728-803) - what `tools/main_ae.py` runs with
+`eval_only` (:189-190).  Training, image dumps and overlays (`save_images`) are not built.
+
+Per batch ONE library call does encode -> posterior mode -> decode -> the metric's tail
+(`GeneralVAESeg.reconstruct_semseg` / `reconstruct_panoptic`); the [B,128,S,S] logits are never materialised and the
+mIoU loop does not synchronise with the host until the score is read.
+"""
+from typing import List, Optional, Union
+
+import torch
+
+from ..evaluations.semseg_evaluation import SemsegMeter
+from .sampler import TrainerDiffusion
+
+METRICS = ("miou", "pq")
+
+
+class TrainerAE(object):
+    def __init__(self, vae_model, num_classes: int = 128, ignore_label: int = 0, mask_th: float = 0.5, count_th: int = 512,
+                 overlap_th: float = 0.5, class_names: Optional[List[str]] = None, device=None):
+        self.vae_model = vae_model
+        self.num_classes = num_classes
+        self.ignore_label = ignore_label
+        self.mask_th = mask_th
+        self.count_th = count_th
+        self.overlap_th = overlap_th
+        self.class_names = class_names if class_names is not None else [str(i) for i in range(num_classes)]
+        self.device = torch.device(device) if device is not None else getattr(vae_model, "device", None)
+
+    def compute_metrics(self, names: Union[List[str], str] = ['miou'], dataloader=None, evaluator=None,
+                        threshold_output: bool = False) -> dict:
+        """:546-569.  `dataloader`: an iterable of batches that can be walked once per metric (a list, a DataLoader) or a
+        callable returning one.  Returns {name: result}."""
+        if isinstance(names, str):
+            names = [names]
+        elif not isinstance(names, list):
+            raise TypeError(f"names must be a metric name or a list of them, got {type(names).__name__}")
+        unknown = [n for n in names if n.lower() not in METRICS]
+        if unknown:
+            raise NotImplementedError(f'Unknown metric {unknown[0]}')
+        out = {}
+        for name in names:
+            dl = dataloader() if callable(dataloader) else dataloader
+            if name.lower() == 'miou':
+                out[name] = self.compute_miou(dl, threshold_output=threshold_output)
+            else:
+                out[name] = self.compute_pq(dl, evaluator, threshold_output=threshold_output)
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized():
+                dist.barrier()
+        return out
+
+    crop_padding = staticmethod(TrainerDiffusion.crop_padding)          # :571-577
+
+    @torch.no_grad()
+    def compute_miou(self, dataloader, threshold_output: bool = False) -> dict:
+        """:728-803 over batches {'image_semseg': [B,7,S,S] bit maps in [0,1], 'semseg': [B,h,w] int64 targets}.  Like the
+        reference, an approximation: predictions are compared at the targets' size, not at the original image size."""
+        meter = SemsegMeter(self.num_classes, self.class_names, has_bg=False, ignore_index=self.ignore_label,
+                            gpu_idx=self.device)
+        for data in dataloader:
+            images = data['image_semseg'].to(self.device, non_blocking=True)
+            targets = data['semseg'].to(self.device, non_blocking=True)
+            # 2 * images - 1 (:747) rides on the encoder's input pack; the tail adds this batch's counters on the device
+            self.vae_model.reconstruct_semseg(images, targets.shape[-2:], targets, meter.device_counts(self.device),
+                                              in_mul=2.0, in_add=-1.0, mask_th=self.mask_th if threshold_output else None,
+                                              ignore_label=self.ignore_label, ignore_index=self.ignore_label,
+                                              return_preds=False)
+        meter.synchronize_between_processes()                            # :799
+        return meter.return_score(verbose=False, name='val set')
+
+    @torch.no_grad()
+    def predict_panoptic(self, images: torch.Tensor, im_sizes, padding_masks: Optional[torch.Tensor] = None,
+                         threshold_output: bool = True, return_stats: bool = False):
+        """One batch of `compute_pq` (:604-668): bit maps [B,7,S,S] in [0,1] on the GPU -> `processed_results`."""
+        sizes = [(int(s[0]), int(s[1])) for s in im_sizes]
+        boxes = TrainerDiffusion.padding_boxes(padding_masks) if padding_masks is not None else None
+        res = self.vae_model.reconstruct_panoptic(
+            images, (images.shape[-2], images.shape[-1]), sizes, boxes, in_mul=2.0, in_add=-1.0,
+            threshold_output=threshold_output, mask_th=self.mask_th, count_th=self.count_th, overlap_th=self.overlap_th,
+            ignore_label=self.ignore_label, return_stats=return_stats)
+        outs, stats = res if return_stats else (res, None)
+        processed = [{"panoptic_seg": (pan, [{"id": int(c) + 1, "category_id": 1, "isthing": True} for c in kept])}
+                     for pan, kept in outs]
+        return (processed, stats) if return_stats else processed
+
+    @torch.no_grad()
+    def compute_pq(self, dataloader, evaluator, threshold_output: bool = True):
+        """:580-680 over batches {'image_semseg': [B,7,S,S], 'mask': [B,S,S] padding masks or None, 'meta': [{'image_file',
+        'image_id', 'im_size': (h, w)}, ...]}.  `evaluator` is a PanopticEvaluatorAgnostic; all ranks must call this (the
+        evaluator gathers).  Returns evaluator.evaluate() (rank 0) / None."""
+        if evaluator is None:
+            raise ValueError("compute_pq needs a PanopticEvaluatorAgnostic")
+        evaluator.reset()
+        for data in dataloader:
+            meta = data['meta']
+            images = data['image_semseg'].to(self.device, non_blocking=True)
+            masks = data.get('mask')
+            masks = masks.to(self.device) if masks is not None else None
+            processed = self.predict_panoptic(images, [x['im_size'] for x in meta], masks, threshold_output)
+            evaluator.process([x['image_file'] for x in meta], [x['image_id'] for x in meta], processed)
+        return evaluator.evaluate()
