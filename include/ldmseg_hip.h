@@ -239,6 +239,30 @@ int ldmseg_vae_reconstruct_panoptic(ldmseg_vae* h, const float* x, float in_mul,
                                     int threshold_output, float mask_th, int count_th, double overlap_th, int64_t ignore_label,
                                     int32_t* labels, int32_t* panoptic, uint8_t* keep, int32_t* counts, int32_t* mask_counts,
                                     void* stream);
+/* ---- device-side panoptic-quality meter: pq_compute_annotations (the restated panopticapi rule) for a batch of map pairs ----
+ * Per image b: the prediction map (int32, label + 1, 0 = void, ids 0..P, P <= 256) at pred + pred_offsets[b] and the ground-truth
+ * map of the same (h_b, w_b) = sizes[b] at pixel gt_offsets[b] of gt, in gt_format 0 (int32 segment ids) or 1 (uint8 RGB
+ * [h,w,3], id = R + 256 G + 65536 B).  keep [B][P] uint8 declares prediction id p where keep[b][p - 1] != 0 (the keep table of
+ * ldmseg_vae_decode_panoptic with C = P).  The annotation's declared segments are slots 0..gt_counts[b]-1 in ASCENDING id order:
+ *   slot_ids   [B][Gpad] int32   ids, 1 .. 2^24 - 1          slot_crowd [B][Gpad] uint8  iscrowd
+ *   slot_area  [B][Gpad] int64   area, or -1 = the counted one (gt_segms[g].setdefault("area", count))
+ *   slot_meta  [B][2]    int32   (gt_counts[b], slot of the LAST crowd segment in annotation order or -1)
+ * with gt_counts[b] <= Gpad <= LDMSEG_PQ_G_MAX.  sizes [B][2], pred_offsets [B], gt_offsets [B], gt_counts [B] are HOST arrays,
+ * everything else lives on the device.  Outputs (device, owned by the caller, (re)initialised by the call):
+ *   inter     [B][Gpad + 2][P + 1] int32  pixel counts; row 0 = VOID, rows 1..G = slots, row G + 1 = painted but not declared
+ *   stats     [B][4] int32  tp, fp, fn, flags: bit 0 a painted prediction id >= 1 is not declared, bit 1 a declared prediction
+ *             id has no pixel, bit 2 a prediction id outside 0..P, bit 3 a segment matched twice or an empty union (only
+ *             annotation areas that contradict the map do that; the slot table cannot hold such a result)
+ *   match_iou [B][Gpad] double  the matched IoU (> 0.5) of the slot, 0.0 elsewhere
+ * A pair (slot g not crowd, declared p) with n = inter[g][p] > 0 matches iff (double)n / (double)(area_pred[p] + area_gt[g] - n -
+ * inter[VOID][p]) > 0.5; fn = unmatched non-crowd slots; fp = unmatched declared p unless (inter[VOID][p] + inter[last crowd][p]) /
+ * area_pred[p] > 0.5.  Integer atomics and IEEE double divisions only: the result is exact and order-independent.
+ * B + 1 launches, no host synchronisation, no allocation. */
+#define LDMSEG_PQ_G_MAX 256
+int ldmseg_pq_match(const int32_t* pred, const void* gt, int gt_format, int B, const int32_t* sizes, const int64_t* pred_offsets,
+                    const int64_t* gt_offsets, const uint8_t* keep, int P, const int32_t* gt_counts, int Gpad,
+                    const int32_t* slot_ids, const uint8_t* slot_crowd, const int64_t* slot_area, const int32_t* slot_meta,
+                    int32_t* inter, int32_t* stats, double* match_iou, void* stream);
 int64_t ldmseg_vae_num_params(const ldmseg_vae* h);
 
 /* ---- image VAE encoder: ldmseg/models/vae.py:36-39 GeneralVAEImage(AutoencoderKL), decoder removed

@@ -2149,6 +2149,26 @@ int ldmseg_semseg_meter_update(const int64_t* pred, const int64_t* gt, int64_t n
   return 0;
 }
 
+int ldmseg_pq_match(const int32_t* pred, const void* gt, int gt_format, int B, const int32_t* sizes, const int64_t* pred_offsets,
+                    const int64_t* gt_offsets, const uint8_t* keep, int P, const int32_t* gt_counts, int Gpad,
+                    const int32_t* slot_ids, const uint8_t* slot_crowd, const int64_t* slot_area, const int32_t* slot_meta,
+                    int32_t* inter, int32_t* stats, double* match_iou, void* stream) {
+  g_err.clear();
+  if (!pred || !gt || !sizes || !pred_offsets || !gt_offsets || !keep || !gt_counts || !slot_ids || !slot_crowd || !slot_area ||
+      !slot_meta || !inter || !stats || !match_iou)
+    return fail(LDMSEG_E_ARG, "null argument");
+  if (B < 1 || P < 1 || P > 256) return fail(LDMSEG_E_ARG, "B >= 1 and P in 1..256");
+  if (Gpad < 1 || Gpad > LDMSEG_PQ_G_MAX) return fail(LDMSEG_E_ARG, "Gpad must be 1..LDMSEG_PQ_G_MAX");
+  if (gt_format != 0 && gt_format != 1) return fail(LDMSEG_E_ARG, "gt_format: 0 int32 ids, 1 uint8 RGB");
+  for (int b = 0; b < B; ++b)
+    if (gt_counts[b] < 0 || gt_counts[b] > Gpad || sizes[2 * b] < 1 || sizes[2 * b + 1] < 1 ||
+        (int64_t)sizes[2 * b] * sizes[2 * b + 1] > (int64_t)0x7fff0000 || pred_offsets[b] < 0 || gt_offsets[b] < 0)
+      return fail(LDMSEG_E_SHAPE, "bad size / offset / declared count of image " + std::to_string(b));
+  TRY(launch_pq_match(pred, gt, gt_format, B, sizes, pred_offsets, gt_offsets, keep, P, gt_counts, Gpad, slot_ids, slot_crowd,
+                      slot_area, slot_meta, inter, stats, match_iou, (hipStream_t)stream));
+  return 0;
+}
+
 int ldmseg_vae_image_create(const ldmseg_vae_image_cfg* cfg, int n_weights, const char* const* names,
                             const void* const* dev_ptrs, const int64_t* numels, ldmseg_vae_image** out) {
   return create_handle(cfg, n_weights, names, dev_ptrs, numels, [](const ldmseg_vae_image_cfg&) { return 0; }, klenc_build, true, out);

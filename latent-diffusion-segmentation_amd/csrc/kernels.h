@@ -437,6 +437,12 @@ int launch_semseg_meter(const int64_t* pred, const int64_t* gt, size_t n, int K,
 int launch_semseg_from_decoder(const void* x4, int B, int H4, int W4, int C, int dtype, int oh, int ow, float mask_th,
                                int64_t ignore_label, const int64_t* targets, int64_t ignore_index, int K, int64_t* preds,
                                int64_t* counts, hipStream_t s, float* volume = nullptr);
+// device-side PQ meter (pq_meter.hip): contingency table + IoU > 0.5 matching of a batch of (ground truth, prediction) map pairs;
+// arguments as ldmseg_pq_match (include/ldmseg_hip.h)
+int launch_pq_match(const int32_t* pred, const void* gt, int gt_format, int B, const int32_t* sizes_host, const int64_t* pred_offsets_host,
+                    const int64_t* gt_offsets_host, const uint8_t* keep, int P, const int32_t* gt_counts_host, int Gpad,
+                    const int32_t* slot_ids, const uint8_t* slot_crowd, const int64_t* slot_area, const int32_t* slot_meta,
+                    int32_t* inter, int32_t* stats, double* match_iou, hipStream_t s);
 int launch_bit_encode(const int64_t* ids, float* out, uint8_t* ignore, int B, int n, int HW, int64_t ignore_label,
                       float fill, float mul, float add, hipStream_t s);
 int launch_bit_decode(const float* x, int64_t* out, int B, int n, int HW, hipStream_t s);

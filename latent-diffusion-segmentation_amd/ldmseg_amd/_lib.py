@@ -95,6 +95,7 @@ SIGNATURES = {
     "ldmseg_vae_decode_panoptic": (_i, [_vp, _vp, _f, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _f, _i, _d, _i64, _vp, _vp, _vp, _vp, _vp,
                                         _vp]),
     "ldmseg_semseg_meter_update": (_i, [_vp, _vp, _i64, _i, _i64, _vp, _vp]),
+    "ldmseg_pq_match": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i] + [_vp] * 8),
     "ldmseg_vae_decode_semseg": (_i, [_vp, _vp, _f, _i, _i, _i, _i, _f, _i64, _vp, _i64, _i, _vp, _vp, _vp]),
     "ldmseg_vae_reconstruct_semseg": (_i, [_vp, _vp, _f, _f, _i, _i, _i, _i, _f, _i64, _vp, _i64, _i, _vp, _vp, _vp]),
     "ldmseg_vae_reconstruct_panoptic": (_i, [_vp, _vp, _f, _f, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _d, _i64, _vp, _vp, _vp, _vp,

@@ -160,11 +160,15 @@ class GeneralVAESeg(object):
 
     def decode_panoptic(self, z: torch.Tensor, in_size, out_sizes, crop_boxes=None, z_scale: float = 1.0,
                         threshold_output: bool = True, threshold_mode: str = "max", mask_th: float = 0.5,
-                        count_th: int = 512, overlap_th: float = 0.5, ignore_label: int = 0, return_stats: bool = False):
+                        count_th: int = 512, overlap_th: float = 0.5, ignore_label: int = 0, return_stats: bool = False,
+                        packed: bool = False):
         """The evaluation tail of `compute_pq` (trainers_ldm_cond.py:1243-1313) fused behind the decoder: decode ->
         bilinear x2 -> bilinear to `in_size` (H, W) -> crop to `crop_boxes[b]` = (y0, x0, height, width) -> bilinear to
         `out_sizes[b]` = (h, w) -> argmax / thresholds / segment filtering, without the [B,128,H,W] logits.
-        Returns a list of (panoptic [h,w] int32 tensor on the GPU (label + 1, 0 = void), kept label list)."""
+        Returns a list of (panoptic [h,w] int32 tensor on the GPU (label + 1, 0 = void), kept label list) - or, with
+        `packed=True`, the device form without the copy of the keep table to the host: {"pan": the flat int32 buffer of all
+        maps, "offsets": int64 [B] first element of image b, "sizes": int32 [B,2], "keep": uint8 [B,C] on the GPU}
+        (what `PanopticEvaluatorAgnostic.process_device` takes)."""
         z = _lib.require_cuda_f32(z, "z")
         if threshold_mode not in ("max", "topk_diff"):
             raise ValueError(f"unknown threshold_mode {threshold_mode!r}")
@@ -176,9 +180,9 @@ class GeneralVAESeg(object):
                 int(bool(threshold_output)), 1 if threshold_mode == "topk_diff" else 0, float(mask_th), int(count_th),
                 float(overlap_th), int(ignore_label), _lib.ptr(labels), _lib.ptr(pan), _lib.ptr(keep), _lib.ptr(counts),
                 _lib.ptr(mcounts), _lib.stream_ptr(z.device)), "ldmseg_vae_decode_panoptic")
-        return self._panoptic_tail(call, B, z.device, out_sizes, crop_boxes, return_stats)
+        return self._panoptic_tail(call, B, z.device, out_sizes, crop_boxes, return_stats, packed)
 
-    def _panoptic_tail(self, call, B, dev, out_sizes, crop_boxes, return_stats):
+    def _panoptic_tail(self, call, B, dev, out_sizes, crop_boxes, return_stats, packed=False):
         """Host geometry arrays and device outputs of the fused panoptic tail; `call` makes the library call on them."""
         import numpy as np
         Cn = self.out_channels
@@ -195,11 +199,14 @@ class GeneralVAESeg(object):
         vp = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
         with torch.cuda.device(dev):
             call(vp(boxes), vp(sizes), vp(offs), labels, pan, keep, counts, mcounts)
-        keep_h = keep.cpu()
-        out = []
-        for b in range(B):
-            o, n = int(offs[b]), int(npix[b])
-            out.append((pan[o:o + n].view(int(sizes[b, 0]), int(sizes[b, 1])), torch.nonzero(keep_h[b]).flatten().tolist()))
+        if packed:
+            out = {"pan": pan, "offsets": offs, "sizes": sizes, "keep": keep}
+        else:
+            keep_h = keep.cpu()
+            out = []
+            for b in range(B):
+                o, n = int(offs[b]), int(npix[b])
+                out.append((pan[o:o + n].view(int(sizes[b, 0]), int(sizes[b, 1])), torch.nonzero(keep_h[b]).flatten().tolist()))
         if return_stats:
             lab = [labels[int(offs[b]):int(offs[b]) + int(npix[b])].view(int(sizes[b, 0]), int(sizes[b, 1])) for b in range(B)]
             return out, {"labels": lab, "counts": counts, "mask_counts": mcounts, "keep": keep}
@@ -207,10 +214,10 @@ class GeneralVAESeg(object):
 
     def reconstruct_panoptic(self, x: torch.Tensor, in_size, out_sizes, crop_boxes=None, in_mul: float = 1.0,
                              in_add: float = 0.0, threshold_output: bool = True, mask_th: float = 0.5, count_th: int = 512,
-                             overlap_th: float = 0.5, ignore_label: int = 0, return_stats: bool = False):
+                             overlap_th: float = 0.5, ignore_label: int = 0, return_stats: bool = False, packed: bool = False):
         """One batch of `TrainerAE.compute_pq` (trainers_ae.py:611-668) in one call: encode(x * in_mul + in_add) -> posterior
         mode -> decode -> the tail of `decode_panoptic`, with the overlap mask `logit >= mask_th` of :656 (not the sigmoid).
-        x [B,7,H,H]; returns what `decode_panoptic` returns."""
+        x [B,7,H,H]; returns what `decode_panoptic` returns (`packed` as there)."""
         x = _lib.require_cuda_f32(x, "x")
         B, H = self._check_bitmaps(x)
 
@@ -220,7 +227,7 @@ class GeneralVAESeg(object):
                 int(bool(threshold_output)), float(mask_th), int(count_th), float(overlap_th), int(ignore_label),
                 _lib.ptr(labels), _lib.ptr(pan), _lib.ptr(keep), _lib.ptr(counts), _lib.ptr(mcounts),
                 _lib.stream_ptr(x.device)), "ldmseg_vae_reconstruct_panoptic")
-        return self._panoptic_tail(call, B, x.device, out_sizes, crop_boxes, return_stats)
+        return self._panoptic_tail(call, B, x.device, out_sizes, crop_boxes, return_stats, packed)
 
     def _check_bitmaps(self, x):
         B, Cin, H, W = x.shape

@@ -406,13 +406,16 @@ class TrainerDiffusion(object):
                          num_inference_steps: int = 50, guidance_scale: float = 7.5, seed: Optional[int] = None,
                          threshold_output: bool = True, threshold_mode: str = "max", scheduler=None, rgb_size: Optional[int] = None,
                          mask_th: float = 0.5, count_th: int = 512, overlap_th: float = 0.5, ignore_label: int = 0,
-                         return_intermediates: bool = False, fused: bool = True, prompts: Optional[List[str]] = None):
+                         return_intermediates: bool = False, fused: bool = True, prompts: Optional[List[str]] = None,
+                         packed: bool = False):
         """One batch of `compute_pq` (:1218-1313): RGB images [B,3,S,S] in [0,1] on the GPU -> `processed_results`
         (per image {"panoptic_seg": (panoptic map at the original size (h, w), segments_info)}).
         Pixels -> image-VAE latents -> DDIM sampling -> seg-VAE decoder -> [bilinear x2 -> bilinear to the input size ->
         crop the padding -> bilinear to (h, w) -> argmax / thresholds / segment filtering].  The bracket runs as ONE fused
         tail behind the decoder (`ldmseg_vae_decode_panoptic`: no [B,128,H,W] logits, no per-image torch interpolation);
-        `fused=False` (and `return_intermediates`) materialises the logits and walks the reference's steps one by one."""
+        `fused=False` (and `return_intermediates`) materialises the logits and walks the reference's steps one by one.
+        `packed=True` (fused tail only) returns the device form of `GeneralVAESeg.decode_panoptic` instead: nothing is copied
+        to the host."""
         import torch.nn.functional as F
         if self.vae_image is None:
             raise ValueError("predict_panoptic needs the image VAE (TrainerDiffusion(..., vae_image=...))")
@@ -427,12 +430,16 @@ class TrainerDiffusion(object):
         latents = self.sample(list(prompts) if prompts is not None else [""] * B, num_inference_steps, guidance_scale, seed,
                               rgb_latents=rgb_latents, scheduler=scheduler, disable_progress_bar=True, rgb_images=rgb_images)
         sizes = [(int(s[0]), int(s[1])) for s in im_sizes]
+        if packed and (not fused or return_intermediates):
+            raise ValueError("packed=True needs the fused tail")
         if fused and not return_intermediates:
             boxes = self.padding_boxes(padding_masks) if padding_masks is not None else None
             outs = self.vae_semseg.decode_panoptic(
                 latents, (rgb_images.shape[-2], rgb_images.shape[-1]), sizes, boxes, z_scale=1.0 / self.vae_semseg.scaling_factor,
                 threshold_output=threshold_output, threshold_mode=threshold_mode, mask_th=mask_th, count_th=count_th,
-                overlap_th=overlap_th, ignore_label=ignore_label)
+                overlap_th=overlap_th, ignore_label=ignore_label, packed=packed)
+            if packed:
+                return outs
             return [{"panoptic_seg": (pan, [{"id": int(c) + 1, "category_id": 1, "isthing": True} for c in kept])}
                     for pan, kept in outs]
         logits = self.decode_latents(latents, return_logits=True)
@@ -459,8 +466,10 @@ class TrainerDiffusion(object):
         """`compute_pq` (:1181-1346) over an iterable of batches shaped like the reference's `collate_fn` output:
         {'image': [B,3,S,S] in [0,1], 'mask': [B,S,S] padding masks or None, 'meta': [{'image_file', 'image_id',
         'im_size': (h, w)}, ...]}.  `evaluator` is a PanopticEvaluatorAgnostic; all ranks must call this (the
-        evaluator gathers).  Returns evaluator.evaluate() (rank 0) / None."""
+        evaluator gathers).  Returns evaluator.evaluate() (rank 0) / None.  An evaluator built with `on_device=True` is fed
+        through `process_device` (maps and keep table stay on the GPU; a batch may bring its ground truth as 'panoptic_gt')."""
         evaluator.reset()
+        on_device = getattr(evaluator, "on_device", False)
         scheduler = self.noise_scheduler
         scheduler.set_timesteps_inference(num_inference_steps=num_inference_steps)
         scheduler.move_timesteps_to(self.device)                                              # :1211-1212
@@ -474,8 +483,11 @@ class TrainerDiffusion(object):
             masks = masks.to(self.device) if masks is not None else None
             processed = self.predict_panoptic(rgb, sizes, masks, num_inference_steps, guidance_scale, seed,
                                               threshold_output, threshold_mode, scheduler=scheduler, prompts=data.get("text"),
-                                              **post_kw)
-            evaluator.process(file_names, image_ids, processed)
+                                              **post_kw, **({"packed": True} if on_device else {}))
+            if on_device:
+                evaluator.process_device(file_names, image_ids, processed, gt_maps=data.get("panoptic_gt"))
+            else:
+                evaluator.process(file_names, image_ids, processed)
             if max_iter is not None and batch_idx > max_iter:                                 # (sic, :1332)
                 break
         return evaluator.evaluate()

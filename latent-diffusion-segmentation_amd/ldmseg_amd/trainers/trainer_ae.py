@@ -74,14 +74,17 @@ class TrainerAE(object):
 
     @torch.no_grad()
     def predict_panoptic(self, images: torch.Tensor, im_sizes, padding_masks: Optional[torch.Tensor] = None,
-                         threshold_output: bool = True, return_stats: bool = False):
-        """One batch of `compute_pq` (:604-668): bit maps [B,7,S,S] in [0,1] on the GPU -> `processed_results`."""
+                         threshold_output: bool = True, return_stats: bool = False, packed: bool = False):
+        """One batch of `compute_pq` (:604-668): bit maps [B,7,S,S] in [0,1] on the GPU -> `processed_results`; with
+        `packed=True` the device form of `GeneralVAESeg.reconstruct_panoptic` (nothing is copied to the host)."""
         sizes = [(int(s[0]), int(s[1])) for s in im_sizes]
         boxes = TrainerDiffusion.padding_boxes(padding_masks) if padding_masks is not None else None
         res = self.vae_model.reconstruct_panoptic(
             images, (images.shape[-2], images.shape[-1]), sizes, boxes, in_mul=2.0, in_add=-1.0,
             threshold_output=threshold_output, mask_th=self.mask_th, count_th=self.count_th, overlap_th=self.overlap_th,
-            ignore_label=self.ignore_label, return_stats=return_stats)
+            ignore_label=self.ignore_label, return_stats=return_stats, packed=packed)
+        if packed:
+            return res
         outs, stats = res if return_stats else (res, None)
         processed = [{"panoptic_seg": (pan, [{"id": int(c) + 1, "category_id": 1, "isthing": True} for c in kept])}
                      for pan, kept in outs]
@@ -91,7 +94,9 @@ class TrainerAE(object):
     def compute_pq(self, dataloader, evaluator, threshold_output: bool = True):
         """:580-680 over batches {'image_semseg': [B,7,S,S], 'mask': [B,S,S] padding masks or None, 'meta': [{'image_file',
         'image_id', 'im_size': (h, w)}, ...]}.  `evaluator` is a PanopticEvaluatorAgnostic; all ranks must call this (the
-        evaluator gathers).  Returns evaluator.evaluate() (rank 0) / None."""
+        evaluator gathers).  Returns evaluator.evaluate() (rank 0) / None.  An evaluator built with `on_device=True` is fed
+        through `process_device`: the maps and the keep table stay on the GPU (a batch may bring its ground truth as
+        'panoptic_gt', one RGB or id map per image)."""
         if evaluator is None:
             raise ValueError("compute_pq needs a PanopticEvaluatorAgnostic")
         evaluator.reset()
@@ -100,6 +105,11 @@ class TrainerAE(object):
             images = data['image_semseg'].to(self.device, non_blocking=True)
             masks = data.get('mask')
             masks = masks.to(self.device) if masks is not None else None
+            if getattr(evaluator, "on_device", False):
+                out = self.predict_panoptic(images, [x['im_size'] for x in meta], masks, threshold_output, packed=True)
+                evaluator.process_device([x['image_file'] for x in meta], [x['image_id'] for x in meta], out,
+                                         gt_maps=data.get('panoptic_gt'))
+                continue
             processed = self.predict_panoptic(images, [x['im_size'] for x in meta], masks, threshold_output)
             evaluator.process([x['image_file'] for x in meta], [x['image_id'] for x in meta], processed)
         return evaluator.evaluate()

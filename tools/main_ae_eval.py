@@ -5,7 +5,7 @@ reconstructs ground-truth panoptic maps through its 4-channel latent.  This is t
 sampler can reach, and the check to run after loading `ae.pt`.
 
     python tools/main_ae_eval.py --panoptic DIR [--ae ae.pt] [--size 512] [--batch 8] [--dtype bf16]
-                                 [--mask-th 0.5] [--count-th 512] [--overlap-th 0.5] [--out DIR]
+                                 [--mask-th 0.5] [--count-th 512] [--overlap-th 0.5] [--out DIR] [--device-pq]
 
 Per image: COCO panoptic PNG -> segment ids -> remapped to random distinct labels in [1, 128) with the background (0) fixed
 (coco.py:320-348, seeded here) -> nearest-neighbour resize of the longer side to --size and zero padding to a square (the
@@ -100,7 +100,8 @@ def evaluate(args, device, files):
         gt_anns.append(gt_from_png(gt_maps[iid], iid, os.path.basename(f)))
     world = dist.get_world_size() if dist.is_initialized() else 1
     gloo = dist.new_group(backend="gloo") if world > 1 else None           # object gather side group (detectron2 comm)
-    ev = PanopticEvaluatorAgnostic(output_dir=args.out, gt_maps=gt_maps, gt_annotations=gt_anns, group=gloo)
+    ev = PanopticEvaluatorAgnostic(output_dir=args.out, gt_maps=gt_maps, gt_annotations=gt_anns, group=gloo,
+                                   on_device=getattr(args, "device_pq", False))
     out = trainer.compute_metrics(["miou", "pq"], lambda: batches(files, args.size, args.batch, device), evaluator=ev,
                                   threshold_output=args.threshold_output)
     return out["miou"], out["pq"], ev
@@ -116,6 +117,8 @@ def main():
     ap.add_argument("--overlap-th", type=float, default=0.5)
     ap.add_argument("--threshold-output", action="store_true", help="max-softmax threshold in both metrics (trainers_ae.py:549)")
     ap.add_argument("--out", default=None, help="folder for the prediction PNGs and the evaluator's predictions.json")
+    ap.add_argument("--device-pq", action="store_true",
+                    help="score PQ on the GPU (PanopticEvaluatorAgnostic.process_device): no map is copied to the host")
     args = ap.parse_args()
     if args.size % 8:
         ap.error("--size must be a multiple of 8")

@@ -105,6 +105,8 @@ def main():
     ap.add_argument("--clip-vision", default=None,
                     help="torch.save'd state dict of CLIPVisionModel / CLIPVisionModelWithProjection (openai/clip-vit-large-patch14); "
                          "generated weights without it")
+    ap.add_argument("--device-pq", action="store_true",
+                    help="score PQ on the GPU (PanopticEvaluatorAgnostic.process_device): no map is copied to the host")
     args = ap.parse_args()
     import torch.distributed as dist
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
@@ -137,7 +139,8 @@ def main():
             print(f"{len(res)} images, segments per image: {[len(r['panoptic_seg'][1]) for r in res]}")
     else:
         gloo = dist.new_group(backend="gloo") if world > 1 else None       # object gather side group (detectron2 comm)
-        ev = PanopticEvaluatorAgnostic(output_dir=args.out, gt_maps=gt_maps, gt_annotations=gt_anns, group=gloo)
+        ev = PanopticEvaluatorAgnostic(output_dir=args.out, gt_maps=gt_maps, gt_annotations=gt_anns, group=gloo,
+                                       on_device=args.device_pq)
         out = trainer.compute_pq(batches(files, args.size, args.batch, args.panoptic), ev, num_inference_steps=args.steps,
                                  seed=args.seed, threshold_output=True, mask_th=args.mask_th, count_th=args.count_th)
         if rank == 0:
