@@ -452,7 +452,8 @@ int ldmseg_profile_dump(const char* path);
  * convert instead of the direct e4m3 byte - attention_mx.hip); key 16 = row-local fusion of the 320-channel transformer entry
  * (proj_in -> LayerNorm_1 -> q|k|v in one launch, tproj.hip; bit 0 on, bit 1 loader block rotation; default 3, 0 = the unfused
  * launches); key 2 values: 0 = shipped rule, 7 = the round-3 rule (attention3.hip at head dim 40), 11..14 = attention4.hip forced
- * (8 / 4 waves, lazily tracked / every-tile maxima); (key 17 was round 5's weight-streaming kernel - measured level with
+ * (8 / 4 waves, lazily tracked / every-tile maxima) - DESIGN 3.2 has every value of keys 2 and 15 as a table, csrc/attn_plan.h is
+ * the rule; (key 17 was round 5's weight-streaming kernel - measured level with
  * igemm_kernel, now a record under tools/experiments/);
  * key 19 = resnet conv2 + conv_shortcut as one launch with an extra centre tap (bf16; default 1, 0 = two launches);
  * key 20 = ff.net.2 and proj_out of the 640- / 1280-channel transformers as one chained Linear over [g | h] (bf16; default 1);

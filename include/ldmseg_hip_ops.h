@@ -170,6 +170,12 @@ int ldmseg_op_igemm_plan(const int* desc, int dtype, int cus, char* buf, int n);
  * GroupNorm launch of ldmseg_op_conv_groupnorm over Co channels; -4 where that returns -4. */
 int ldmseg_op_groupnorm_plan(int B, int C, int C2, int HW, int groups, int dtype, int cus, int region_ok, char* buf, int n);
 int ldmseg_op_conv_groupnorm_plan(int B, int Co, int HW, int dtype, char* buf, int n);
+/* What an attention operator would launch under the current debug keys 2 and 15 (csrc/attn_plan.h; needs no device): kind 0 =
+ * ldmseg_op_attention, 1 = ldmseg_op_attention_causal, 2 = ldmseg_op_attention_fp8 (dtype ignored), 3 = ldmseg_op_attention_cross
+ * over S context rows (S is ignored otherwise).  buf receives, per launch, "name grid=GXxGY block=T" (the fp8 pre-passes and the
+ * cross kernel, on 3-D grids: grid=GXxGYxGZ) with the dispatch-log name, the pre-pass of the fp8 forms first, joined by " + ".
+ * Returns 0, or -2 where the operator returns -2. */
+int ldmseg_op_attention_plan(int kind, int B, int N, int S, int C, int heads, int dtype, char* buf, int n);
 /* enable=1 clears and starts a log of the DISTINCT igemm instantiations launched ("igemm<...>" + "/splitk" for K-sliced
  * launches; ",x3" / ",x3w" for split-bf16 products) and of the fused GEMM kernels; enable=2 logs every kernel of the UNet
  * forward path (split-K finish, GroupNorm, LayerNorm statistics, attention too), each named with its template arguments and

@@ -15,6 +15,7 @@
 // are 8 consecutive keys of the V^T row it multiplies.
 #include <type_traits>
 
+#include "attn_plan.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -417,80 +418,66 @@ __global__ __launch_bounds__(256) void attention_kernel(const std::conditional_t
 }
 
 template <typename T, int D, int QF, bool X3 = false, bool CAUSAL = false>
-int run(const void* qkv, void* out, int B, int N, int C, int heads, hipStream_t s) {
+int run(const AttnPlan& p, const void* qkv, void* out, hipStream_t s) {
   using Cfg = AttnCfg<T, D>;
   using IO = std::conditional_t<X3, float, T>;
   const size_t stage = (size_t)(Cfg::KS_BYTES + Cfg::VT_BYTES) * (X3 ? 2 : 1);
   const size_t lds = (2 * stage <= 144 * 1024 ? 2 : 1) * stage;
+  static_assert(attn_v1_rows(QF) == (256 / 64) * 16 * QF, "4 waves of QF 16-row query fragments each");
   auto kern = attention_kernel<T, D, QF, X3, CAUSAL>;
-  static bool attr_set[64] = {};     // per device: a process may hold handles on several GPUs
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set[dev] = true;
-  }
-  const int nqb = (N + 64 * QF - 1) / (64 * QF);
+  static bool lds_raised[64] = {};
+  raise_lds_limit_once((const void*)kern, lds, lds_raised);
   const float scale_log2e = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
   const std::string name = CAUSAL ? (X3 ? launch_name("attn_causal_x3<%d,%d>", D, QF) : launch_name("attn_causal<%s,%d,%d>", dtype_tag<T>(), D, QF))
                                   : (X3 ? launch_name("attn_x3<%d,%d>", D, QF) : launch_name("attn<%s,%d,%d>", dtype_tag<T>(), D, QF));
   LDMSEG_LAUNCH(name, kern,
-                dim3(nqb * heads * B), dim3(256), lds, s, (const IO*)qkv, (IO*)out, N, C, heads, scale_log2e);
+                dim3(p.grid_x), dim3(p.block), lds, s, (const IO*)qkv, (IO*)out, p.q.N, p.q.C, p.q.heads, scale_log2e);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 int g_attn_qf1 = 0;
 
-template <typename T>
-int dispatch(const void* qkv, void* out, int B, int N, int C, int heads, hipStream_t s) {
-  const int d = C / heads;
-  const bool big = N >= 256 && g_attn_qf1 != 1 && g_attn_qf1 != 3;
-  switch (d) {
-    case 40: return big ? run<T, 40, 2>(qkv, out, B, N, C, heads, s) : run<T, 40, 1>(qkv, out, B, N, C, heads, s);
-    case 64: return big ? run<T, 64, 2>(qkv, out, B, N, C, heads, s) : run<T, 64, 1>(qkv, out, B, N, C, heads, s);   // CLIP ViT heads
-    case 80: return big ? run<T, 80, 2>(qkv, out, B, N, C, heads, s) : run<T, 80, 1>(qkv, out, B, N, C, heads, s);
-    case 160: return run<T, 160, 1>(qkv, out, B, N, C, heads, s);
-    default: return -2;
-  }
-}
-
-// fp32 tensors, split-bf16 products (compute_dtype "bf16x3")
-int dispatch_x3(const void* qkv, void* out, int B, int N, int C, int heads, hipStream_t s) {
-  const int d = C / heads;
-  const bool big = N >= 256;
-  switch (d) {
-    case 40: return big ? run<bf16_t, 40, 2, true>(qkv, out, B, N, C, heads, s) : run<bf16_t, 40, 1, true>(qkv, out, B, N, C, heads, s);
-    case 64: return big ? run<bf16_t, 64, 2, true>(qkv, out, B, N, C, heads, s) : run<bf16_t, 64, 1, true>(qkv, out, B, N, C, heads, s);
-    case 80: return big ? run<bf16_t, 80, 2, true>(qkv, out, B, N, C, heads, s) : run<bf16_t, 80, 1, true>(qkv, out, B, N, C, heads, s);
-    case 160: return run<bf16_t, 160, 1, true>(qkv, out, B, N, C, heads, s);
-    default: return -2;
-  }
+// the instantiations of one element type (T, X3): head dim x query fragments per wave; the causal form at <64, 1> only
+#define ATTN1_INSTANCES(X) X(40, 1) X(40, 2) X(64, 1) X(64, 2) X(80, 1) X(80, 2) X(160, 1)
+template <typename T, bool X3>
+int run_plan(const AttnPlan& p, const void* qkv, void* out, hipStream_t s) {
+  if (p.CAUSAL) return p.D == 64 && p.QF == 1 ? run<T, 64, 1, X3, true>(p, qkv, out, s) : -2;
+#define X(D_, QF_) \
+  if (p.D == D_ && p.QF == QF_) return run<T, D_, QF_, X3>(p, qkv, out, s);
+  ATTN1_INSTANCES(X)
+#undef X
+  return -2;
 }
 
 }  // namespace
 
 void attention_set_qf1(int v) { g_attn_qf1 = v; }
+AttnKnobs attention_knobs() {
+  const int mx = attention_mx_get_mode();
+  return AttnKnobs{g_attn_qf1, mx & 1, (mx >> 4) & 3};
+}
 
-int launch_attention3(const void* qkv, void* out, int B, int N, int C, int heads, int variant, hipStream_t s);   // attention3.hip
+int launch_attn_v1_plan(const AttnPlan& p, const void* qkv, void* out, hipStream_t s) {
+  if (p.form != ATTN_V1) return -2;
+  if (p.X3) return run_plan<bf16_t, true>(p, qkv, out, s);       // fp32 in HBM, three bf16 MFMAs per product block
+  return p.q.dtype == DT_BF16 ? run_plan<bf16_t, false>(p, qkv, out, s) : run_plan<float, false>(p, qkv, out, s);
+}
 
 int launch_attention(const void* qkv, void* out, int B, int N, int C, int heads, int dtype, hipStream_t s) {
-  if (C % heads != 0 || N <= 0) return -2;
-  if (dtype == 2) return dispatch_x3(qkv, out, B, N, C, heads, s);      // LDMSEG_BF16X3: fp32 in HBM, three bf16 MFMAs per product block
-  // bf16 perf mode, head dims 40 / 80: the LDS-DMA + folded-max kernel of attention3.hip (knob value 2 forces this file's
-  // kernel for A/B measurements; 1 = 16 query rows per wave)
-  if (dtype == DT_BF16 && g_attn_qf1 != 2 && g_attn_qf1 != 3) {      // 0, 1, 4..7: variants of attention3.hip
-    const int r = launch_attention3(qkv, out, B, N, C, heads, g_attn_qf1, s);
-    if (r != -100) return r;
+  AttnPlan p;
+  if (attn_choose(AttnDesc{ATTN_KIND_SELF, B, N, 0, C, heads, dtype}, attention_knobs(), &p)) return -2;
+  switch (p.form) {
+    case ATTN_V3: return launch_attn3_plan(p, qkv, out, s);
+    case ATTN_V4: return launch_attn4_plan(p, qkv, out, s);
+    default: return launch_attn_v1_plan(p, qkv, out, s);
   }
-  return dtype == DT_BF16 ? dispatch<bf16_t>(qkv, out, B, N, C, heads, s) : dispatch<float>(qkv, out, B, N, C, heads, s);
 }
 
 // causal self-attention (the CLIP text encoder): head dim 64 only, any N >= 1
 int launch_attention_causal(const void* qkv, void* out, int B, int N, int C, int heads, int dtype, hipStream_t s) {
-  if (B < 1 || N < 1 || heads < 1 || C != 64 * heads) return -2;
-  if (dtype == 2) return run<bf16_t, 64, 1, true, true>(qkv, out, B, N, C, heads, s);
-  return dtype == DT_BF16 ? run<bf16_t, 64, 1, false, true>(qkv, out, B, N, C, heads, s)
-                          : run<float, 64, 1, false, true>(qkv, out, B, N, C, heads, s);
+  AttnPlan p;
+  if (attn_choose(AttnDesc{ATTN_KIND_CAUSAL, B, N, 0, C, heads, dtype}, attention_knobs(), &p)) return -2;
+  return launch_attn_v1_plan(p, qkv, out, s);
 }
 
 }  // namespace ldmseg

@@ -21,6 +21,8 @@
 // accumulation, softmax(q k^T d^-1/2) v per head); tests/test_ops_gpu.py::test_attention* cover both.
 #include <type_traits>
 
+#include "attn_dev.h"
+#include "attn_plan.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -35,27 +37,6 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 // see - an asm v_max3_f32 here read half-written accumulators now and then (wrong maxima -> overflow -> NaN, run-to-run
 // different).  This file is built with -fno-honor-nans so no canonicalising v_max(x, x) is emitted in front.
 __device__ __forceinline__ float max3f(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
-// smallest bf16-representable value >= x (finite x), returned as f32
-__device__ __forceinline__ float bf16_ceil(float x) {
-  const uint32_t u = f32_bits(x);
-  return bits_f32(((u & 0x80000000u) ? u : u + 0xffffu) & 0xffff0000u);
-}
-// LDS-DMA of 64 x 16 B: lane l fetches gsrc(l) + OFF into LDS lds_dst + 16 l.  The instruction's immediate offset is
-// applied to the global AND the LDS address, so M0 carries lds_dst - OFF (callers keep lds_dst >= OFF).
-template <int OFF>
-__device__ __forceinline__ void glds16_off(const void* gsrc, unsigned lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, off offset:%2"
-      :
-      : "v"(gsrc), "s"(lds_dst - OFF), "i"(OFF)
-      : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
 
 template <int D, int NWV = 4> struct A3Cfg {
   static constexpr int DCH = D / 8;                  // data planes per tile and operand (16-byte chunks per row)
@@ -371,62 +352,36 @@ __global__ __launch_bounds__(64 * NWV, WPS) void attn3_kernel(const bf16_t* __re
 }
 
 template <int D, int QF, int WPS, int NST, bool PIPE = false, int LAZY = 1, int NWV = 4>
-int run3(const void* qkv, void* out, int B, int N, int C, int heads, hipStream_t s) {
+int run3(const AttnPlan& p, const void* qkv, void* out, hipStream_t s) {
   using Cfg = A3Cfg<D, NWV>;
+  static_assert(attn_v3_rows(QF, NWV) == 16 * NWV * QF && BKV3 == 64, "NWV waves of QF 16-row query fragments each");
   const size_t lds = (size_t)NST * Cfg::STAGE;
   auto kern = attn3_kernel<D, QF, WPS, NST, PIPE, LAZY, NWV>;
-  static bool attr_set[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set[dev] = true;
-  }
-  const int nqb = (N + 16 * NWV * QF - 1) / (16 * NWV * QF);
+  static bool lds_raised[64] = {};
+  raise_lds_limit_once((const void*)kern, lds, lds_raised);
   const float scale_log2e = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
-  LDMSEG_LAUNCH(launch_name("attn3<%d,%d,%d,%d,%d,%d,%d>", D, QF, WPS, NST, PIPE ? 1 : 0, LAZY, NWV), kern, dim3(nqb * heads * B), dim3(64 * NWV), lds, s, (const bf16_t*)qkv, (bf16_t*)out, N, C, heads, scale_log2e);
+  LDMSEG_LAUNCH(launch_name("attn3<%d,%d,%d,%d,%d,%d,%d>", D, QF, WPS, NST, PIPE ? 1 : 0, LAZY, NWV), kern, dim3(p.grid_x), dim3(p.block), lds, s, (const bf16_t*)qkv, (bf16_t*)out, p.q.N, p.q.C, p.q.heads, scale_log2e);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 }  // namespace
 
-// bf16, head dim 40 or 80; returns -100 when the shape is not handled here (caller falls through to attention.hip)
-int launch_attention4(const void* qkv, void* out, int B, int N, int C, int heads, int variant, hipStream_t s);   // attention4.hip
+// head dim, query fragments per wave, waves per SIMD, ring stages, maxima look period, waves per workgroup
+#define ATTN3_INSTANCES(X)                                                                              \
+  X(40, 1, 4, 3, 1, 4) X(40, 2, 3, 2, 1, 4) X(40, 2, 4, 3, 1, 4) X(40, 2, 3, 3, 1, 4) X(40, 2, 4, 3, 1, 8) \
+  X(40, 2, 4, 3, 4, 8) X(40, 2, 3, 3, 16, 4) X(40, 2, 4, 3, 16, 8)                                       \
+  X(80, 1, 3, 2, 1, 4) X(80, 2, 3, 2, 1, 4) X(80, 1, 2, 3, 1, 4) X(80, 2, 2, 3, 1, 4) X(80, 1, 4, 3, 16, 8) \
+  X(80, 2, 2, 3, 16, 8) X(80, 1, 3, 3, 16, 8) X(80, 2, 2, 3, 16, 4)
 
-int launch_attention3(const void* qkv, void* out, int B, int N, int C, int heads, int variant, hipStream_t s) {
-  const int d = C / heads;
-  // variant: 0 = shipped choice; the others are alternatives kept for A/B measurements and the parity tests
-  // (template arguments: head dim, query fragments per wave, waves per SIMD, ring stages, -, maxima look period, waves per workgroup)
-  if (d == 40) {
-    if (variant == 1) return run3<40, 1, 4, 3>(qkv, out, B, N, C, heads, s);
-    if (variant == 4) return run3<40, 2, 3, 2>(qkv, out, B, N, C, heads, s);
-    if (variant == 5) return run3<40, 2, 4, 3>(qkv, out, B, N, C, heads, s);
-    if (variant == 6) return run3<40, 2, 3, 3>(qkv, out, B, N, C, heads, s);                  // the round-2 kernel: 4 waves, maxima on every tile
-    if (variant == 8) return run3<40, 2, 4, 3, false, 1, 8>(qkv, out, B, N, C, heads, s);     // 8 waves, maxima on every tile
-    if (variant == 9) return run3<40, 2, 4, 3, false, 4, 8>(qkv, out, B, N, C, heads, s);
-    if (variant == 10) return run3<40, 2, 3, 3, false, 16, 4>(qkv, out, B, N, C, heads, s);
-    if (variant >= 11 && variant <= 14) return launch_attention4(qkv, out, B, N, C, heads, variant - 11, s);   // attention4.hip, forced form
-    // 8-wave workgroups: 256 query rows share every K / V tile (half the LDS-DMA instructions per score: issuing one parks
-    // the wave for 60-185 cycles); short sequences keep the 4-wave form (too few workgroups otherwise)
-    const bool big = (long)B * heads * ((N + 255) / 256) >= 256;
-    // shipped (0): the 32x32x16 score-block kernel of attention4.hip (round 4: N = 4096 at B = 8 224 -> 196 us, N = 16384 at B = 4
-    // 1.67 -> 1.49 ms, N = 1000 15.8 -> 14.1 us); 7: this file's kernel under the same rule (the round-3 choice), for A/B
-    if (variant == 0) return launch_attention4(qkv, out, B, N, C, heads, big ? 0 : 2, s);
-    if (big) return run3<40, 2, 4, 3, false, 16, 8>(qkv, out, B, N, C, heads, s);
-    return run3<40, 2, 3, 3, false, 16, 4>(qkv, out, B, N, C, heads, s);
-  }
-  if (d == 80) {
-    if (variant == 1) return run3<80, 1, 3, 2>(qkv, out, B, N, C, heads, s);
-    if (variant == 4) return run3<80, 2, 3, 2>(qkv, out, B, N, C, heads, s);
-    if (variant == 5) return run3<80, 1, 2, 3>(qkv, out, B, N, C, heads, s);
-    if (variant == 6) return run3<80, 2, 2, 3>(qkv, out, B, N, C, heads, s);                  // the round-2 kernel
-    if (variant == 8) return run3<80, 1, 4, 3, false, 16, 8>(qkv, out, B, N, C, heads, s);
-    if (variant == 9) return run3<80, 2, 2, 3, false, 16, 8>(qkv, out, B, N, C, heads, s);
-    if (variant == 10) return run3<80, 1, 3, 3, false, 16, 8>(qkv, out, B, N, C, heads, s);
-    if (variant == 0 && (long)B * heads * ((N + 255) / 256) >= 256) return run3<80, 2, 2, 3, false, 16, 8>(qkv, out, B, N, C, heads, s);
-    return run3<80, 2, 2, 3, false, 16, 4>(qkv, out, B, N, C, heads, s);
-  }
-  return -100;
+// bf16, head dim 40 or 80
+int launch_attn3_plan(const AttnPlan& p, const void* qkv, void* out, hipStream_t s) {
+  if (p.form != ATTN_V3 || p.q.dtype != DT_BF16) return -2;
+#define X(D_, QF_, WPS_, NST_, LAZY_, NWV_)                                                                        \
+  if (p.D == D_ && p.QF == QF_ && p.WPS == WPS_ && p.NST == NST_ && p.LAZY == LAZY_ && p.NWV == NWV_) \
+    return run3<D_, QF_, WPS_, NST_, false, LAZY_, NWV_>(p, qkv, out, s);
+  ATTN3_INSTANCES(X)
+#undef X
+  return -2;
 }
 
 }  // namespace ldmseg

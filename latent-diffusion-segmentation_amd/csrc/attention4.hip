@@ -11,6 +11,8 @@
 // of K, lazily tracked maxima with the exact redo pass, row sums through a ones plane of V.  Same arithmetic contract.
 #include <type_traits>
 
+#include "attn_dev.h"
+#include "attn_plan.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -25,24 +27,6 @@ typedef short s16x4b __attribute__((ext_vector_type(4)));
 typedef float v16f4 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8b __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ float bf16_ceil4(float x) {
-  const uint32_t u = f32_bits(x);
-  return bits_f32(((u & 0x80000000u) ? u : u + 0xffffu) & 0xffff0000u);
-}
-template <int OFF>
-__device__ __forceinline__ void glds16_off4(const void* gsrc, unsigned lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, off offset:%2"
-      :
-      : "v"(gsrc), "s"(lds_dst - OFF), "i"(OFF)
-      : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm4() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
 
 template <int NST, int LAZY, int NWV>
 __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 4 : 3) void attn4_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, int N, int C, int heads,
@@ -93,17 +77,17 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 4 : 3) void attn4_kernel(const
     const unsigned vdst = __builtin_amdgcn_readfirstlane(lds0 + stage * STAGE4 + KBYTES4 + wv * VPS4);
     static_for_n<JMAX>([&](auto jc) __attribute__((always_inline)) {
       constexpr int J = decltype(jc)::value;
-      if (wave + NWV * J < DCH4) glds16_off4<J * NWV * 16>(kp, kdst + J * NWV * KPS4);
-      if (wv + NWV * J < DCH4) glds16_off4<J * NWV * 16>(vp, vdst + J * NWV * VPS4);
+      if (wave + NWV * J < DCH4) glds16_off<J * NWV * 16>(kp, kdst + J * NWV * KPS4);
+      if (wv + NWV * J < DCH4) glds16_off<J * NWV * 16>(vp, vdst + J * NWV * VPS4);
     });
   };
   auto wait_tiles_ahead = [&](int ahead) __attribute__((always_inline)) {
-    if (ahead == 0) { wait_vm4<0>(); return; }
+    if (ahead == 0) { wait_vm<0>(); return; }
     if (my_cnt == 0) return;
-    if (my_cnt == 1) wait_vm4<1>();
-    else if (my_cnt == 2) wait_vm4<2>();
-    else if (my_cnt == 3) wait_vm4<3>();
-    else wait_vm4<4>();
+    if (my_cnt == 1) wait_vm<1>();
+    else if (my_cnt == 2) wait_vm<2>();
+    else if (my_cnt == 3) wait_vm<3>();
+    else wait_vm<4>();
   };
   const int ntiles = (N + BKV4 - 1) / BKV4;
   const int nfull = N / BKV4;
@@ -225,7 +209,7 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 4 : 3) void attn4_kernel(const
       if (__any(need)) {
         float one;
         asm volatile("v_mov_b32 %0, 1.0" : "=v"(one));
-        const float mnew = need ? bf16_ceil4(mrow + tm) : mrow;
+        const float mnew = need ? bf16_ceil(mrow + tm) : mrow;
         const float delta = (mnew - mrow) * one;                   // exact: both are bf16 values
         mrow += delta;
 #pragma unroll
@@ -308,34 +292,30 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 4 : 3) void attn4_kernel(const
 }
 
 template <int NST, int LAZY, int NWV>
-int run4(const void* qkv, void* out, int B, int N, int C, int heads, hipStream_t s) {
+int run4(const AttnPlan& p, const void* qkv, void* out, hipStream_t s) {
+  static_assert(attn_v4_rows(NWV) == 32 * NWV && BKV4 == 64, "32 queries per wave");
   const size_t lds = (size_t)NST * STAGE4;
   auto kern = attn4_kernel<NST, LAZY, NWV>;
-  static bool attr_set[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set[dev] = true;
-  }
-  const int nqb = (N + 32 * NWV - 1) / (32 * NWV);
+  static bool lds_raised[64] = {};
+  raise_lds_limit_once((const void*)kern, lds, lds_raised);
   const float scale_log2e = (1.0f / sqrtf((float)D4)) * 1.4426950408889634f;
-  LDMSEG_LAUNCH(launch_name("attn4<d40,%d,%d,%d>", NST, LAZY, NWV), kern, dim3(nqb * heads * B), dim3(64 * NWV), lds, s, (const bf16_t*)qkv, (bf16_t*)out, N, C, heads, scale_log2e);
+  LDMSEG_LAUNCH(launch_name("attn4<d40,%d,%d,%d>", NST, LAZY, NWV), kern, dim3(p.grid_x), dim3(p.block), lds, s, (const bf16_t*)qkv, (bf16_t*)out, p.q.N, p.q.C, p.q.heads, scale_log2e);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 }  // namespace
 
-// bf16, head dim 40 only.  variant 0: 8-wave workgroups (256 queries share every K / V tile), maxima looked at on tile 0 and every 16th;
-// 1: 8 waves, maxima on every tile; 2 / 3: the same two on 4-wave workgroups (short sequences).  -100: shape not handled here.
-// Two ring stages: with three the 8-wave form needs more than the 128 registers four waves per SIMD leave (17-37 spilled, 1.6x
-// slower); 2 stages measured as fast as 3 / 4 on the 4-wave form.
-int launch_attention4(const void* qkv, void* out, int B, int N, int C, int heads, int variant, hipStream_t s) {
-  if (heads <= 0 || C % heads || C / heads != D4) return -100;
-  if (variant == 1) return run4<2, 1, 8>(qkv, out, B, N, C, heads, s);
-  if (variant == 2) return run4<2, 16, 4>(qkv, out, B, N, C, heads, s);
-  if (variant == 3) return run4<2, 1, 4>(qkv, out, B, N, C, heads, s);
-  return run4<2, 16, 8>(qkv, out, B, N, C, heads, s);
+// bf16, head dim 40 only: 8-wave workgroups (256 queries share every K / V tile) or 4-wave ones (short sequences), maxima looked at
+// on tile 0 and every 16th, or on every tile
+int launch_attn4_plan(const AttnPlan& p, const void* qkv, void* out, hipStream_t s) {
+  if (p.form != ATTN_V4 || p.q.dtype != DT_BF16 || p.D != D4 || p.NST != 2) return -2;
+  switch (p.LAZY * 10 + p.NWV) {
+    case 168: return run4<2, 16, 8>(p, qkv, out, s);
+    case 18: return run4<2, 1, 8>(p, qkv, out, s);
+    case 164: return run4<2, 16, 4>(p, qkv, out, s);
+    case 14: return run4<2, 1, 4>(p, qkv, out, s);
+    default: return -2;
+  }
 }
 
 }  // namespace ldmseg

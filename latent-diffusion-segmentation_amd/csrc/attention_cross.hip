@@ -14,6 +14,7 @@
 // keys past S are masked in the tile loop, so any S >= 1 works without padding.
 #include <hip/hip_runtime.h>
 
+#include "attn_plan.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -119,32 +120,37 @@ __global__ void rows_to_dtype_kernel(const float* __restrict__ x, T* __restrict_
 }
 
 template <typename T, int D>
-int launch_d(const void* q, const void* kv, void* out, int B, int N, int S, int C, int heads, hipStream_t s) {
+int launch_d(const AttnPlan& p, const void* q, const void* kv, void* out, hipStream_t s) {
+  static_assert(kRows == kAttnCrossRows, "attn_plan.h sizes the grid from it");
   const float qscale = 1.4426950408889634f / sqrtf((float)D);
-  dim3 grid((N + kRows - 1) / kRows, heads, B);
-  LDMSEG_LAUNCH(launch_name("attention_cross_kernel<%s,%d>", dtype_tag<T>(), D), (attention_cross_kernel<T, D>), grid,
-                dim3(256), 0, s, (const T*)q, (const T*)kv, (T*)out, N, S, C, qscale);
+  LDMSEG_LAUNCH(launch_name("attention_cross_kernel<%s,%d>", dtype_tag<T>(), D), (attention_cross_kernel<T, D>),
+                dim3(p.grid_x, p.grid_y, p.grid_z), dim3(p.block), 0, s, (const T*)q, (const T*)kv, (T*)out, p.q.N, p.q.S, p.q.C, qscale);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 template <typename T>
-int dispatch(const void* q, const void* kv, void* out, int B, int N, int S, int C, int heads, hipStream_t s) {
-  switch (C / heads) {
-    case 40: return launch_d<T, 40>(q, kv, out, B, N, S, C, heads, s);
-    case 80: return launch_d<T, 80>(q, kv, out, B, N, S, C, heads, s);
-    case 160: return launch_d<T, 160>(q, kv, out, B, N, S, C, heads, s);
+int dispatch(const AttnPlan& p, const void* q, const void* kv, void* out, hipStream_t s) {
+  switch (p.D) {
+    case 40: return launch_d<T, 40>(p, q, kv, out, s);
+    case 80: return launch_d<T, 80>(p, q, kv, out, s);
+    case 160: return launch_d<T, 160>(p, q, kv, out, s);
     default: return -2;
   }
 }
 
 }  // namespace
 
+int launch_attn_cross_plan(const AttnPlan& p, const void* q, const void* kv, void* out, hipStream_t s) {
+  if (p.form != ATTN_CROSS) return -2;
+  return p.q.dtype == DT_BF16 ? dispatch<bf16_t>(p, q, kv, out, s)
+                              : dispatch<float>(p, q, kv, out, s);      // (dtype 2: fp32 tensors of a bf16x3 handle)
+}
+
 int launch_attention_cross(const void* q, const void* kv, void* out, int B, int N, int S, int C, int heads, int dtype,
                            hipStream_t s) {
-  if (B < 1 || N < 1 || S < 1 || heads < 1 || C % heads != 0 || heads > 65535 || B > 65535) return -2;
-  if (dtype == DT_BF16) return dispatch<bf16_t>(q, kv, out, B, N, S, C, heads, s);
-  if (dtype == 0 || dtype == 2) return dispatch<float>(q, kv, out, B, N, S, C, heads, s);   // (2: fp32 tensors of a bf16x3 handle)
-  return -2;
+  AttnPlan p;
+  if (attn_choose(AttnDesc{ATTN_KIND_CROSS, B, N, S, C, heads, dtype}, attention_knobs(), &p)) return -2;
+  return launch_attn_cross_plan(p, q, kv, out, s);
 }
 
 int launch_rows_to_dtype(const float* x, void* y, size_t n, int dtype, hipStream_t s) {

@@ -18,6 +18,8 @@
 // memory side.  Accuracy: P and V carry 3 mantissa bits - see tests/test_ops_gpu.py::test_attention_fp8* for the bound.
 #include <type_traits>
 
+#include "attn_dev.h"
+#include "attn_plan.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -36,20 +38,6 @@ __device__ __forceinline__ uint32_t pack_fp8x4(float a, float b, float c, float 
 }
 __device__ __forceinline__ float fp8_to_f32(uint32_t byte) { return __builtin_amdgcn_cvt_f32_fp8((int)byte, 0); }
 
-template <int OFF>
-__device__ __forceinline__ void glds16_off8(const void* gsrc, unsigned lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, off offset:%2"
-      :
-      : "v"(gsrc), "s"(lds_dst - OFF), "i"(OFF)
-      : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm8() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
 
 // ---- pre-pass: K and V of qkv [B, N, 3C] bf16 -> k8 / v8 [B, H, N, DP] e4m3 with the constant columns ----
 template <int D, int DP>
@@ -139,16 +127,16 @@ __global__ __launch_bounds__(256, WPS) void attn_fp8_kernel(const bf16_t* __rest
     const unsigned vdst = __builtin_amdgcn_readfirstlane(lds0 + stage * Cfg::STAGE + Cfg::NPL * Cfg::PS + wv * Cfg::PS);
     static_for_n<Cfg::JMAX>([&](auto jc) __attribute__((always_inline)) {
       constexpr int J = decltype(jc)::value;
-      if (wave + 4 * J < Cfg::NPL) glds16_off8<J * 64>(kp, kdst + J * 4 * Cfg::PS);
-      if (wv + 4 * J < Cfg::NPL) glds16_off8<J * 64>(vp, vdst + J * 4 * Cfg::PS);
+      if (wave + 4 * J < Cfg::NPL) glds16_off<J * 64>(kp, kdst + J * 4 * Cfg::PS);
+      if (wv + 4 * J < Cfg::NPL) glds16_off<J * 64>(vp, vdst + J * 4 * Cfg::PS);
     });
   };
   auto wait_tiles_ahead = [&](int ahead) __attribute__((always_inline)) {
-    if (ahead == 0) { wait_vm8<0>(); return; }
-    if (my_cnt == 1) wait_vm8<1>();
-    else if (my_cnt == 2) wait_vm8<2>();
-    else if (my_cnt == 3) wait_vm8<3>();
-    else wait_vm8<4>();
+    if (ahead == 0) { wait_vm<0>(); return; }
+    if (my_cnt == 1) wait_vm<1>();
+    else if (my_cnt == 2) wait_vm<2>();
+    else if (my_cnt == 3) wait_vm<3>();
+    else wait_vm<4>();
   };
   const int ntiles = (N + BKV8 - 1) / BKV8;
   const int nfull = N / BKV8;
@@ -340,50 +328,46 @@ __global__ __launch_bounds__(256, WPS) void attn_fp8_kernel(const bf16_t* __rest
 }
 
 template <int D, int QF, int WPS, int NST>
-int run8(const void* qkv, void* kv8, void* out, int B, int N, int C, int heads, hipStream_t s) {
+int run8(const AttnPlan& p, const void* qkv, void* kv8, void* out, hipStream_t s) {
   using Cfg = A8Cfg<D>;
+  static_assert(Cfg::DP == (D == 40 ? kAttnFp8DP40 : kAttnFp8DP80) && attn_v1_rows(QF) == (256 / 64) * 16 * QF && BKV8 == 64,
+                "attn_plan.h sizes the scratch and the grids from these");
+  const int B = p.q.B, N = p.q.N, C = p.q.C, heads = p.q.heads;
   unsigned char* k8 = (unsigned char*)kv8;
-  unsigned char* v8 = k8 + (size_t)B * heads * N * Cfg::DP;
-  {
-    const long per_bh = (long)N * (Cfg::DP / 16) * 2;
-    int bx = (int)((per_bh + 255) / 256);
-    if (bx > 256) bx = 256;
-    LDMSEG_LAUNCH(launch_name("kv_to_fp8<%d,%d>", D, Cfg::DP), (kv_to_fp8_kernel<D, Cfg::DP>), dim3(bx, heads, B), dim3(256), 0, s, (const bf16_t*)qkv, k8, v8, B, N, C, heads);
-  }
+  unsigned char* v8 = k8 + p.scratch_bytes / 2;
+  LDMSEG_LAUNCH(launch_name("kv_to_fp8<%d,%d>", D, Cfg::DP), (kv_to_fp8_kernel<D, Cfg::DP>), dim3(p.pre_grid_x, p.pre_grid_y, p.pre_grid_z), dim3(p.pre_block), 0, s, (const bf16_t*)qkv, k8, v8, B, N, C, heads);
   const size_t lds = (size_t)NST * Cfg::STAGE;
   auto kern = attn_fp8_kernel<D, QF, WPS, NST>;
-  static bool attr_set[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set[dev] = true;
-  }
-  const int nqb = (N + 64 * QF - 1) / (64 * QF);
+  static bool lds_raised[64] = {};
+  raise_lds_limit_once((const void*)kern, lds, lds_raised);
   const float scale_log2e = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
-  LDMSEG_LAUNCH(launch_name("attn_fp8<%d,%d,%d,%d>", D, QF, WPS, NST), kern, dim3(nqb * heads * B), dim3(256), lds, s, (const bf16_t*)qkv, k8, v8, (bf16_t*)out, N, C, heads,
+  LDMSEG_LAUNCH(launch_name("attn_fp8<%d,%d,%d,%d>", D, QF, WPS, NST), kern, dim3(p.grid_x), dim3(p.block), lds, s, (const bf16_t*)qkv, k8, v8, (bf16_t*)out, N, C, heads,
                      scale_log2e);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 }  // namespace
 
-// bytes of the fp8 K/V scratch launch_attention_fp8 needs (0 = head dim not supported by the fp8 path)
+// head dims 40 / 80, unscaled fp8 MFMAs
+int launch_attn_fp8_plan(const AttnPlan& p, const void* qkv, void* kv8, void* out, hipStream_t s) {
+  if (p.form != ATTN_FP8 || p.QF != 2 || p.NST != 3) return -2;
+  if (p.D == 40 && p.WPS == 4) return run8<40, 2, 4, 3>(p, qkv, kv8, out, s);
+  if (p.D == 80 && p.WPS == 2) return run8<80, 2, 2, 3>(p, qkv, kv8, out, s);
+  return -2;
+}
+
+// bytes of the fp8 K/V scratch launch_attention_fp8 needs under the current knobs (0 = head dim not supported by the fp8 path)
 size_t attention_fp8_scratch_bytes(int B, int N, int C, int heads) {
-  const int d = C / heads;
-  if (const size_t mx = attention_mx_scratch_bytes(B, N, C, heads)) return mx;       // head dim 40, whole 128-key tiles: the scaled-MFMA path
-  if (d == 40) return (size_t)2 * B * heads * N * A8Cfg<40>::DP;
-  if (d == 80) return (size_t)2 * B * heads * N * A8Cfg<80>::DP;
-  return 0;
+  AttnPlan p;
+  return attn_choose(AttnDesc{ATTN_KIND_FP8, B, N, 0, C, heads, DT_BF16}, attention_knobs(), &p) ? 0 : p.scratch_bytes;
 }
 
 // qkv bf16 [B, N, 3C] -> out bf16 [B, N, C] with fp8 (e4m3) Q/K/V/P operands; kv8 = scratch of attention_fp8_scratch_bytes
 int launch_attention_fp8(const void* qkv, void* kv8, void* out, int B, int N, int C, int heads, hipStream_t s) {
-  const int d = C / heads;
-  if (attention_mx_ok(N, C, heads)) return launch_attention_mx(qkv, kv8, out, B, N, C, heads, s);   // 2x-rate block-scaled MFMAs (attention_mx.hip)
-  if (d == 40) return run8<40, 2, 4, 3>(qkv, kv8, out, B, N, C, heads, s);
-  if (d == 80) return run8<80, 2, 2, 3>(qkv, kv8, out, B, N, C, heads, s);
-  return -2;
+  AttnPlan p;
+  if (attn_choose(AttnDesc{ATTN_KIND_FP8, B, N, 0, C, heads, DT_BF16}, attention_knobs(), &p)) return -2;
+  return p.form == ATTN_MX ? launch_attn_mx_plan(p, qkv, kv8, out, s)       // 2x-rate block-scaled MFMAs (attention_mx.hip)
+                           : launch_attn_fp8_plan(p, qkv, kv8, out, s);
 }
 
 }  // namespace ldmseg

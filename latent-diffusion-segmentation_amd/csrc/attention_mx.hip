@@ -19,6 +19,7 @@
 // e4m3 range, row sum through a ones row of V^T: as in attention_fp8.hip.
 #include <type_traits>
 
+#include "attn_plan.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -359,6 +360,24 @@ int g_mx_variant = 3;   // bit 0: 8-wave workgroups (256 queries share a K/V til
 float g_mx_pshift = 13.95f;     // FEXP: folded reference = maximum - pshift (byte of the maximum = 8 pshift = 111.6: the -0.4 centres the
                                 // interpolation error; measured optimum of tools/attn8_acc.py, rel-L2 1.2 x the exact-exp form's)
 
+template <int NST, int NW, bool FEXP>
+int run_mx(const AttnPlan& p, const void* qkv, void* kv8, void* out, hipStream_t s) {
+  static_assert(kTile == kAttnMxTile && kKB == kAttnMxKB && kVB == kAttnMxVB && attn_v4_rows(NW) == 32 * NW && kD == 40,
+                "attn_plan.h sizes the scratch and the grids from these");
+  const int N = p.q.N, C = p.q.C, heads = p.q.heads;
+  unsigned char* k8 = (unsigned char*)kv8;
+  unsigned char* v8 = k8 + (size_t)p.q.B * heads * (N / kTile) * kKB;
+  LDMSEG_LAUNCH("kv_to_mx", kv_to_mx_kernel, dim3(p.pre_grid_x, p.pre_grid_y, p.pre_grid_z), dim3(p.pre_block), 0, s, (const bf16_t*)qkv, k8, v8, N, C, heads);
+  const float scale_log2e = (1.0f / sqrtf((float)kD)) * 1.4426950408889634f;
+  const size_t lds = (size_t)NST * kStage;
+  auto kern = attn_mx_kernel<NST, NW, FEXP>;
+  static bool lds_raised[64] = {};
+  raise_lds_limit_once((const void*)kern, lds, lds_raised);
+  LDMSEG_LAUNCH(launch_name("attn_mx<%d,%d,%d>", NST, NW, FEXP ? 1 : 0), kern, dim3(p.grid_x), dim3(p.block), lds, s, (const bf16_t*)qkv, k8, v8, (bf16_t*)out, N, C,
+                     heads, scale_log2e, g_mx_pshift);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
 }  // namespace
 
 void attention_mx_set_mode(int m) {    // bit 0: on / off; bit 8: variant from bits 4-5, bit 9: pshift = 13 + bits 16.. / 1000 (else the defaults)
@@ -367,37 +386,16 @@ void attention_mx_set_mode(int m) {    // bit 0: on / off; bit 8: variant from b
   g_mx_pshift = (m & 0x200) ? 13.0f + (float)((m >> 16) & 0xfff) * 1e-3f : 13.95f;
 }
 int attention_mx_get_mode() { return g_mx_mode | (g_mx_variant << 4); }   // bit 0: on; bits 4-5: variant (bit 5 = direct e4m3 byte)
-bool attention_mx_ok(int N, int C, int heads) { return g_mx_mode && heads > 0 && C / heads == kD && N % kTile == 0 && N >= kTile; }
-size_t attention_mx_scratch_bytes(int B, int N, int C, int heads) {
-  return attention_mx_ok(N, C, heads) ? (size_t)B * heads * (N / kTile) * (kKB + kVB) : 0;
-}
 
-int launch_attention_mx(const void* qkv, void* kv8, void* out, int B, int N, int C, int heads, hipStream_t s) {
-  if (!attention_mx_ok(N, C, heads)) return -2;
-  unsigned char* k8 = (unsigned char*)kv8;
-  unsigned char* v8 = k8 + (size_t)B * heads * (N / kTile) * kKB;
-  LDMSEG_LAUNCH("kv_to_mx", kv_to_mx_kernel, dim3(N / kTile, heads, B), dim3(256), 0, s, (const bf16_t*)qkv, k8, v8, N, C, heads);
-  const float scale_log2e = (1.0f / sqrtf((float)kD)) * 1.4426950408889634f;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  auto go = [&](auto kern, int nst, int nw, bool fexp, bool* attr) {
-    const size_t lds = (size_t)nst * kStage;
-    if (!attr[dev]) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr[dev] = true;
-    }
-    LDMSEG_LAUNCH(launch_name("attn_mx<%d,%d,%d>", nst, nw, fexp ? 1 : 0), kern, dim3((N / (32 * nw)) * heads * B), dim3(64 * nw), lds, s, (const bf16_t*)qkv, k8, v8, (bf16_t*)out, N, C,
-                       heads, scale_log2e, g_mx_pshift);
-  };
-  static bool a0[64] = {}, a1[64] = {}, a2[64] = {}, a3[64] = {};
-  const int variant = (N % 256 == 0) ? g_mx_variant : (g_mx_variant & 2);      // 8-wave workgroups own 256 queries
-  switch (variant) {
-    case 0: go(attn_mx_kernel<3, 4, false>, 3, 4, false, a0); break;
-    case 1: go(attn_mx_kernel<3, 8, false>, 3, 8, false, a1); break;
-    case 2: go(attn_mx_kernel<3, 4, true>, 3, 4, true, a2); break;
-    default: go(attn_mx_kernel<3, 8, true>, 3, 8, true, a3); break;
+// head dim 40, N a multiple of 128 (8-wave workgroups: of 256)
+int launch_attn_mx_plan(const AttnPlan& p, const void* qkv, void* kv8, void* out, hipStream_t s) {
+  if (p.form != ATTN_MX || p.NST != 3 || p.q.N % (32 * p.NWV) != 0) return -2;
+  switch ((p.NWV == 8 ? 1 : 0) | (p.FEXP ? 2 : 0)) {
+    case 0: return run_mx<3, 4, false>(p, qkv, kv8, out, s);
+    case 1: return run_mx<3, 8, false>(p, qkv, kv8, out, s);
+    case 2: return run_mx<3, 4, true>(p, qkv, kv8, out, s);
+    default: return run_mx<3, 8, true>(p, qkv, kv8, out, s);
   }
-  return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 }  // namespace ldmseg

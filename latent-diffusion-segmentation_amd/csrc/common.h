@@ -82,6 +82,17 @@ template <> struct Chunk<bf16_t> {
   }
 };
 
+// Raises the dynamic-LDS limit of one kernel instantiation to `bytes`, once per device (done: the instantiation's own flags; a
+// process may hold handles on several GPUs)
+inline void raise_lds_limit_once(const void* kern, size_t bytes, bool (&done)[64]) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (!done[dev]) {
+    (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    done[dev] = true;
+  }
+}
+
 // compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N-1>{})
 template <int N, typename F>
 __device__ __forceinline__ void static_for_n(F&& f) {

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/ldmseg_hip.h"
+#include "attn_plan.h"
 #include "kernels.h"
 
 using namespace ldmseg;
@@ -954,13 +955,10 @@ int run_transformer(Exec& ex, const TransformerW& t, const Act& x, Act* out, con
     const double d = C / 8.0;
     ProfScope ps(1, ex.s, 4.0 * ex.B * 8 * (double)N * N * d, 4.0 * M * C * esize(ex.dt), ex.dry(),
                  "N=" + std::to_string(N) + " C=" + std::to_string(C));
-    // (only where the fp8 path is the faster one: head dim 40 on whole 128-key tiles = the block-scaled 2x-rate MFMAs.  The
-    // unscaled fp8 kernel that would serve head dim 80 / ragged lengths runs at the bf16 MFMA rate and measured SLOWER than the
-    // bf16 kernel - 222 vs 205 us at d = 80, N = 4096 - so a handle asked for fp8 from 4096 tokens up keeps that level in bf16)
-    const size_t kv8 = (ex.dt == DT_BF16 && ex.attn_fp8_min_tokens > 0 && N >= ex.attn_fp8_min_tokens && attention_mx_ok(N, C, 8))
-                           ? attention_fp8_scratch_bytes(ex.B, N, C, 8) : 0;
-    if (kv8) {                                     // long-context level on the fp8 operand path (BASELINE configs[4])
-      void* scratch = ws->scratch(kv8);
+    AttnPlan fp8;
+    if (attn_self_fp8_level(ex.B, N, C, 8, ex.dt, ex.attn_fp8_min_tokens, attention_knobs(), &fp8)) {
+      // long-context level on the fp8 operand path (BASELINE configs[4])
+      void* scratch = ws->scratch(fp8.scratch_bytes);
       if (!ex.dry()) TRY(ex.ws_ok());
       if (!ex.dry()) TRY(launch_attention_fp8(qkv.p, scratch, att.p, ex.B, N, C, 8, ex.s));
     } else if (!ex.dry()) {

@@ -237,6 +237,18 @@ int launch_attention(const void* qkv, void* out, int B, int N, int C, int heads,
 // the same with a causal mask built in the kernel (key j contributes to query i iff j <= i; key tiles above a query block's diagonal
 // are skipped): head dim 64 only (C == 64 * heads), any N >= 1 - the CLIP text encoder
 int launch_attention_causal(const void* qkv, void* out, int B, int N, int C, int heads, int dtype, hipStream_t s);
+// Every attention launcher describes its launch, asks attn_choose (attn_plan.h: the rule, no device) once under attention_knobs()
+// - debug keys 2 and 15 - and hands the plan to the file that owns the chosen form; launch_attn_*_plan expand the plan's template
+// arguments (-2: no such instantiation).  kv8: scratch of plan.scratch_bytes bytes.
+struct AttnKnobs;
+struct AttnPlan;
+AttnKnobs attention_knobs();
+int launch_attn_v1_plan(const AttnPlan& p, const void* qkv, void* out, hipStream_t s);       // attention.hip
+int launch_attn3_plan(const AttnPlan& p, const void* qkv, void* out, hipStream_t s);         // attention3.hip
+int launch_attn4_plan(const AttnPlan& p, const void* qkv, void* out, hipStream_t s);         // attention4.hip
+int launch_attn_fp8_plan(const AttnPlan& p, const void* qkv, void* kv8, void* out, hipStream_t s);      // attention_fp8.hip
+int launch_attn_mx_plan(const AttnPlan& p, const void* qkv, void* kv8, void* out, hipStream_t s);       // attention_mx.hip
+int launch_attn_cross_plan(const AttnPlan& p, const void* q, const void* kv, void* out, hipStream_t s); // attention_cross.hip
 
 // cross-attention (attention_cross.hip): q [B*N, C], kv = to_k | to_v of the context [B*S, 2C] -> out [B*N, C]; any S >= 1 (keys
 // past S masked), head dims 40 / 80 / 160; dtype 0 / 1 / 2 as launch_attention (every product in fp32 on the VALU)
@@ -342,9 +354,6 @@ int launch_clip_text_final_ln(const void* h, const float* gamma, const float* be
 size_t attention_fp8_scratch_bytes(int B, int N, int C, int heads);
 int launch_attention_fp8(const void* qkv, void* kv8_scratch, void* out, int B, int N, int C, int heads, hipStream_t s);
 // the same on the 2x-rate block-scaled MFMAs (attention_mx.hip): head dim 40, N a multiple of 128; launch_attention_fp8 routes to it
-bool attention_mx_ok(int N, int C, int heads);
-size_t attention_mx_scratch_bytes(int B, int N, int C, int heads);
-int launch_attention_mx(const void* qkv, void* kv8_scratch, void* out, int B, int N, int C, int heads, hipStream_t s);
 void attention_mx_set_mode(int m);          // 0: keep attention_fp8.hip's unscaled MFMAs everywhere (A/B)
 int attention_mx_get_mode();
 

@@ -11,6 +11,7 @@
 
 #include "../../include/ldmseg_hip.h"
 #include "common.h"
+#include "attn_plan.h"
 #include "gn_plan.h"
 #include "kernels.h"
 
@@ -393,6 +394,17 @@ int ldmseg_op_attention(const float* qkv, int B, int N, int C, int heads, int dt
   if (r) return r;
   from_dev_dtype(op, out, (size_t)B * N * C, dtype, s);
   return 0;
+}
+
+// The dispatch string of a described attention launch (attn_plan.h: the chooser under the current debug keys 2 and 15; no
+// device): kind 0 = ldmseg_op_attention, 1 = _causal, 2 = _fp8, 3 = _cross (S: context rows, otherwise ignored); per launch
+// "name grid=.. block=..", the pre-pass of the fp8 forms first, joined by " + ".  -2 where the operator returns -2.
+int ldmseg_op_attention_plan(int kind, int B, int N, int S, int C, int heads, int dtype, char* buf, int n) {
+  if (!buf || n < 1) return -2;
+  AttnPlan pl;
+  const int r = attn_choose(AttnDesc{kind, B, N, S, C, heads, kind == ATTN_KIND_FP8 ? (int)DT_BF16 : dtype}, attention_knobs(), &pl);
+  if (r == 0) std::snprintf(buf, (size_t)n, "%s", attn_plan_line(pl).c_str());
+  return r;
 }
 
 int ldmseg_op_attention_causal(const float* qkv, int B, int N, int C, int heads, int dtype, float* out, void* stream) {

@@ -147,6 +147,7 @@ SIGNATURES = {
     "ldmseg_op_igemm_plan": (_i, [C.POINTER(_i), _i, _i, C.c_char_p, _i]),
     "ldmseg_op_groupnorm_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i]),
     "ldmseg_op_conv_groupnorm_plan": (_i, [_i, _i, _i, _i, C.c_char_p, _i]),
+    "ldmseg_op_attention_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i]),
     "ldmseg_op_fastdiv": (_i, [_vp, _i, _i, _vp, _vp]),
     "ldmseg_igemm_log": (_i, [_i]),
     "ldmseg_igemm_log_read": (_i, [C.c_char_p, _i]),

@@ -662,6 +662,42 @@ def test_attention_lazy_maxima(L, attn_variant, variant, case, Cc):
     assert float((out[0, rows[-1], :d].cpu() - v[0, key, :d]).abs().max()) < 2e-2 * float(v.abs().max())
 
 
+def _attn_fixture():
+    import json
+    import os
+    from conftest import GOLDEN
+    return json.load(open(os.path.join(GOLDEN, "attn_dispatch.json")))
+
+
+def _attn_plan_cases():
+    import attn_cases as A
+    return A.DIGEST_CASES
+
+
+@pytest.mark.parametrize("case", _attn_plan_cases(), ids=lambda c: "-".join(map(str, c)))
+def test_attention_plan_equals_launch(L, case):
+    """ldmseg_op_attention_plan names what the launch of the operator then logs, and the launch writes the bytes it wrote before the
+    rule was factored out of the launchers (tests/golden/attn_dispatch.json: SHA-256 of the fp32 output on the closed-form inputs
+    of tests/attn_cases.py, recorded on an MI355X).  The kernels are deterministic (no atomics, a fixed order inside a workgroup)
+    and their code is unchanged, so the same bytes mean the same instantiation on a grid that covers every query row.  Cases (kind,
+    B, N, S, C, heads, dtype, key 2): every form of the six sources, 4- and 8-wave workgroups, ragged key tiles."""
+    import attn_cases as A
+    lib = L.lib()
+    want = {tuple(r[:-1]): r[-1] for r in _attn_fixture()["digests"]}
+    L.igemm_log(L.LOG_ALL)
+    try:
+        lib.ldmseg_debug_set(2, case[7])
+        r, digest = A.run_case(lib, case)
+        names = sorted(n for n in L.igemm_log_read() if n.startswith(A.ATTN_FAMILY))
+        pr, line = A.plan(lib, *case[:7])
+    finally:
+        lib.ldmseg_debug_set(2, 0)
+        L.igemm_log(False)
+    print(case, line)
+    assert (r, pr) == (0, 0) and names == sorted(A.plan_names(line)), (case, names, line)
+    assert digest == want[tuple(case)], (case, line)
+
+
 def fp8_e4m3_round(t):
     return t.clamp(-448, 448).to(torch.float8_e4m3fn).to(torch.float32)
 
