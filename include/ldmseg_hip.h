@@ -85,7 +85,15 @@ typedef struct {
  * elements.  Unknown keys (e.g. the duplicate `new_conv.*`, unet.py:182,233) are
  * ignored; a missing or mis-sized required key fails with LDMSEG_E_WEIGHT.
  * Replaces: UNet.from_pretrained + remove_cross_attention + modify_encoder +
- * load_state_dict (tools/main_ldm.py:146-168, trainers_ldm_cond.py:1863-1891). */
+ * load_state_dict (tools/main_ldm.py:146-168, trainers_ldm_cond.py:1863-1891).
+ *
+ * Separate image encoder (modify_encoder(separate_encoder=True[, add_adaptor=True]), unet.py:42-63): a state dict that holds
+ * `conv_in_img.weight` makes a separate-encoder handle.  It must then hold conv_in.* and conv_in_img.* with 4 input channels,
+ * `down_blocks_additional.*` (key for key the down_blocks of a UNet without cross-attention) and may hold
+ * `adaptor_layers.{0..3}.{weight,bias}` (3x3, C -> C per level).  cfg.in_channels must be 8 and cfg.cross_attention 0, else
+ * LDMSEG_E_ARG.  Such a handle takes the 8-channel input [segmentation | RGB latents]; conv_in sees the first half, the image
+ * branch the second together with emb(timestep_img), and its 12 outputs are added to the 12 skip connections (unet.py:309-385).
+ * A `separate_conv` checkpoint (conv_in_seg.*) is an ordinary 8-channel conv_in once folded: ldmseg_amd.checkpoint does that. */
 int ldmseg_unet_create(const ldmseg_unet_cfg* cfg, int n_weights, const char* const* names,
                        const void* const* dev_ptrs, const int64_t* numels, ldmseg_unet** out);
 void ldmseg_unet_destroy(ldmseg_unet* h);
@@ -103,6 +111,13 @@ int ldmseg_unet_forward(ldmseg_unet* h, const float* x, const int64_t* t_dev, in
 int ldmseg_unet_forward_parts(ldmseg_unet* h, const float* latents, const float* rgb_latents, const float* cond,
                               const int64_t* t_dev, int t_count, int64_t t_host, int B, int L, float* out,
                               void* stream);
+/* UNet.forward(sample, timestep, None, timestep_img=...).sample (unet.py:281-436): ldmseg_unet_forward with the timestep of the
+ * separate image encoder, given like the timestep itself (timg_dev int64 on the device with timg_count = 1 or B entries, or, NULL,
+ * timg_host); timg_count other than 1 or B is LDMSEG_E_ARG.  ldmseg_unet_forward and ldmseg_unet_forward_parts on a
+ * separate-encoder handle mean timestep_img = 0 (what the reference substitutes for None); all three compute the image branch
+ * inside the call.  On any other handle timestep_img is ignored, as the reference ignores it there. */
+int ldmseg_unet_forward_img(ldmseg_unet* h, const float* x, const int64_t* t_dev, int t_count, int64_t t_host,
+                            const int64_t* timg_dev, int timg_count, int64_t timg_host, int B, int L, float* out, void* stream);
 /* UNet.forward(sample, timestep, encoder_hidden_states=ctx).sample of a cross-attention handle (unet.py:281-436 with
  * attn2 kept).  ctx: [B, S, ctx_dim] fp32 on the device, 1 <= S <= 4096 (77 CLIP text tokens, 257 CLIP-L/14 patch features,
  * 1 projected image embedding - the last two are what ldmseg_clip_vision_describe / _forward below produce); ctx_dim = 768,
@@ -138,7 +153,7 @@ int ldmseg_unet_gn_backoff(ldmseg_unet* h, int32_t* calls_left);
 /* bytes of device workspace a forward at (B, L) needs (allocated lazily, grown never shrunk) */
 size_t ldmseg_unet_workspace_bytes(const ldmseg_unet* h, int B, int L);
 /* number of parameters held (815,556,484 for the 12-channel default; 859,532,484 for an 8-channel cross-attention handle,
- * 860,319,684 with encoder_hid_proj) */
+ * 860,319,684 with encoder_hid_proj; 1,049,661,444 for a separate-encoder handle, 1,083,764,164 with adaptor layers) */
 int64_t ldmseg_unet_num_params(const ldmseg_unet* h);
 
 /* ---- seg-VAE: ldmseg/models/vae.py::GeneralVAESeg (gaussian, num_mid_blocks=0) ------------ */
@@ -397,7 +412,12 @@ typedef struct {
 } ldmseg_sample_cfg;
 /* Runs the whole loop on `stream`: latents [B,4,L,L] holds the initial noise on entry and the
  * final latents on exit (last step = pred_original_sample, :1154-1156).  If all_latents is
- * non-NULL it receives every step's latents [n_steps][B,4,L,L] (return_all_latents). */
+ * non-NULL it receives every step's latents [n_steps][B,4,L,L] (return_all_latents).
+ * Separate-encoder handles: the image branch reads rgb_latents and timestep_img = 0 only (sample() passes no timestep_img,
+ * trainers_ldm_cond.py:1141), so the loop computes its 12 residuals once, in step 0, into handle-owned memory
+ * (B * 6,635,520 * (L/64)^2 elements of the compute dtype's storage, sized by ldmseg_unet_reserve) and every step adds them to
+ * its skip connections in one launch; inpainting included.  Every call computes them again (the caller may have changed
+ * rgb_latents).  ldmseg_debug_set(25, 1) makes every step compute them, the form the reference runs. */
 int ldmseg_sample_loop(ldmseg_unet* h, const ldmseg_sample_cfg* cfg, float* latents, const float* rgb_latents,
                        int B, int L, float* all_latents, void* stream);
 /* The sampling loop of a cross-attention handle with classifier-free guidance (trainers_ldm_cond.py:1098-1160); the plain
@@ -407,7 +427,8 @@ int ldmseg_sample_loop(ldmseg_unet* h, const ldmseg_sample_cfg* cfg, float* late
  *                 (torch's order), and the DDIM step runs on B images (last step: pred_original_sample).
  *   multiplier 1: ctx is [B, S, ctx_dim]; the model output is used as it is (guidance_scale ignored).
  * The context's keys / values are computed once per call (first step).  LDMSEG_E_ARG for self_condition with multiplier 2
- * (the reference fails at step 2 there), for the inpainting fields, and as ldmseg_unet_forward_ctx for the context. */
+ * (the reference fails at step 2 there), for the inpainting fields, on a separate-encoder handle (it has no cross-attention),
+ * and as ldmseg_unet_forward_ctx for the context. */
 int ldmseg_sample_loop_guided(ldmseg_unet* h, const ldmseg_sample_cfg* cfg, float* latents, const float* rgb_latents, int B, int L,
                               const float* ctx, int S, int ctx_dim, int multiplier, float guidance_scale, float* all_latents,
                               void* stream);
@@ -469,9 +490,11 @@ int ldmseg_profile_dump(const char* path);
  * the maps whose convs are not K-sliced), bits 8-23 = poll bound in microseconds (0 = 200); default 5, 0 = slabs + finish launches
  * everywhere.  Bits 0 / 1 / 3 never change a result bit;
  * key 24 = tuning: every plain-store igemm launch runs entry (v & 0xff) of the instantiation list with (v >> 8) K slices as if the
- * launch table held that entry (-1 = off; unlike key 5 the extra-tap / phase-conv routes stay). */
+ * launch table held that entry (-1 = off; unlike key 5 the extra-tap / phase-conv routes stay);
+ * key 25 = separate-encoder handles in ldmseg_sample_loop: 0 (default) the image branch runs once per call, 1 in every step
+ * (the reference's form; results are bit-identical). */
 int ldmseg_debug_set(int key, int value);
-/* current value of a knob (keys 1, 8, 9, 11, 12, 14, 15, 16, 19, 20, 21, 22, 23); key -1 = the shipped default of key 1.  Tests restore through this, never a literal.
+/* current value of a knob (keys 1, 8, 9, 11, 12, 14, 15, 16, 19, 20, 21, 22, 23, 25); key -1 = the shipped default of key 1.  Tests restore through this, never a literal.
  * key 10 = number of cooperative-GroupNorm workgroups that took the self-computing path in ldmseg_op_* launches so far. */
 int ldmseg_debug_get(int key);
 

@@ -31,6 +31,14 @@ int ldmseg_op_chained_ff_out(const float* g, const float* h, const float* x, con
 /* F.group_norm(cat([x,x2],1), 32, gamma, beta, eps) [+SiLU] */
 int ldmseg_op_groupnorm(const float* x, const float* x2, const float* gamma, const float* beta, int B, int C, int C2,
                         int HW, float eps, int silu, int dtype, float* out, void* stream);
+/* out = a + b on n_segs (<= 12) tensors in one launch, as the engine adds the separate image encoder's residuals to the skip
+ * connections (skipadd.hip).  a / b / out: fp32 device arrays holding the segments back to back, each followed by
+ * 8 guard elements (segment k starts at sum_{j<k} (seg_elems[j] + 8)); seg_elems on the HOST.  The operands are converted to the
+ * storage type of `dtype` (0 fp32 | 1 bf16), the guard elements of the staging output are taken from `out` as it comes in, and the
+ * whole staging output - guards included - is converted back into `out`: a guard that changed shows a write past a segment's end.
+ * A segment that does not start 16-byte aligned in the staging buffers (after one of odd length) runs the kernel's
+ * element-wise path. */
+int ldmseg_op_skip_add(const float* a, const float* b, const int64_t* seg_elems, int n_segs, int dtype, float* out, void* stream);
 /* F.layer_norm over the last dim [+SiLU] (also vae.py:309-322 LayerNorm2d in NHWC) */
 int ldmseg_op_layernorm(const float* x, const float* gamma, const float* beta, int M, int C, float eps, int silu,
                         int dtype, float* out, void* stream);

@@ -30,6 +30,7 @@ thread_local std::string g_err;
 int g_plan_epoch = 0;
 int g_gnfold_mode = 1;  // debug key 22: 1 (default) = the GroupNorm in front of a 320-channel transformer as a statistics pass + a sweep inside
                         // proj_ln_qkv (tproj.hip); 0 = a GroupNorm launch of its own; n > 1 = on, with n pixel chunks per image
+int g_sepenc_every_step = 0;   // debug key 25: 1 = ldmseg_sample_loop recomputes the separate image encoder in every step (the reference's form)
 int g_ffp_mode = 1;     // debug key 20: 1 (default) = ff.net.2 and proj_out of the 640- / 1280-channel transformers as one chained Linear
 int fail(int code, const std::string& msg) {
   g_err = msg;
@@ -414,11 +415,12 @@ struct Exec {
   }
 
   // conv3x3 / 1x1 over NHWC `x` (optionally channel-concatenated with `x2`)
+  // dst: the output goes there (memory the caller owns, [B, Ho*Wo, n_valid]) instead of into the workspace
   int conv(const ConvW& w, const Act& x, const Act* x2, Act* out, int stride, int up, bool persist,
-           const float* rowbias, int rb_stride, const Act* resid, int silu = 0, int pad = -1) {
+           const float* rowbias, int rb_stride, const Act* resid, int silu = 0, int pad = -1, void* dst = nullptr) {
     const int ctot = x.C + (x2 ? x2->C : 0);
     if (ctot != w.cin_pad) return fail(LDMSEG_E_SHAPE, "conv: channel mismatch");
-    if (up && w.w_up4 && w.taps == 9 && stride == 1 && !x2 && !resid && !rowbias && !silu && pad < 0 &&
+    if (up && w.w_up4 && w.taps == 9 && stride == 1 && !x2 && !resid && !rowbias && !silu && pad < 0 && !dst &&
         igemm_up4_ok(B, x.H, x.W, x.C, w.N, dt)) {
       // conv3x3(nearest_x2(x)) as four 2x2 phase convs on the low-resolution map: 4 B H W virtual rows, K = 4 C
       *out = new_act(w.n_valid, 2 * x.H, 2 * x.W, persist);
@@ -436,7 +438,8 @@ struct Exec {
     // stride 2: pad 1 both sides (UNet downsample_padding=1) or pad 0 + one zero row/column at the bottom/right
     const int Ho = (w.taps == 9 && stride == 2) ? (pad == 0 ? Hl / 2 : (Hl - 1) / 2 + 1) : Hl;
     const int Wo = (w.taps == 9 && stride == 2) ? (pad == 0 ? Wl / 2 : (Wl - 1) / 2 + 1) : Wl;
-    *out = new_act(w.n_valid, Ho, Wo, persist);
+    if (dst) { out->p = dst; out->C = w.n_valid; out->H = Ho; out->W = Wo; }
+    else *out = new_act(w.n_valid, Ho, Wo, persist);
     IgemmParams p;
     p.src0 = x.p; p.C0 = x.C;
     if (x2) { p.src1 = x2->p; p.C1 = x2->C; }
@@ -671,6 +674,19 @@ struct ldmseg_unet : HandleBase {
   unsigned long long gn_diag_seen = 0;
   int gn_backoff_calls = 0;
   const void* xin_ptr = nullptr;       // where the tail wrote that input: the next forward skips its pack only if its own xin IS this buffer
+  // Separate image encoder (unet.py:42-63, 309-351: separate_encoder, optionally add_adaptor): conv_in_img and a copy of the down blocks
+  // run on the RGB latents with emb(timestep_img); their 12 outputs (through adaptor_layers[block] where the checkpoint has them) are
+  // added to the 12 skip connections.  They depend on the RGB latents and timestep_img only, so a sampling loop computes them once.
+  bool sepenc = false, adaptor = false;
+  ConvW conv_in_img, adapt[4], img_conv[3];
+  ResnetW img_res[4][2];
+  TransformerW img_attn[3][2];
+  float *tproj_img_w = nullptr, *tproj_img_b = nullptr;
+  int temb_img_total = 0;
+  void* img_resid = nullptr;           // the 12 residual tensors back to back (handle-owned: the workspace offsets of a forward do not
+  size_t img_resid_bytes = 0;          // depend on whether the branch ran in it)
+  bool img_keep = false;               // inside ldmseg_sample_loop: residuals computed by a forward stay valid for the forwards after it
+  bool img_ready = false;
 
   ~ldmseg_unet() {
     DeviceGuard dg(device);
@@ -679,6 +695,7 @@ struct ldmseg_unet : HandleBase {
     if (temb_buf) (void)hipFree(temb_buf);
     if (gn_diag_host) (void)hipHostFree(gn_diag_host);
     if (guide_buf) (void)hipFree(guide_buf);
+    if (img_resid) (void)hipFree(img_resid);
   }
 };
 
@@ -806,7 +823,12 @@ int unet_build(ldmseg_unet* u, const WeightMap& wm) {
   b.x3 = u->x3;
   const int cp = bke(u->dt);
   if (u->cfg.in_channels > cp) return fail(LDMSEG_E_ARG, "in_channels too large");
-  TRY(b.conv("conv_in", kBlockOut[0], u->cfg.in_channels, 3, cp, &u->conv_in));
+  u->sepenc = wm.m.count("conv_in_img.weight") != 0;
+  if (u->sepenc && (u->cfg.in_channels != 8 || u->cfg.cross_attention != 0))
+    return fail(LDMSEG_E_ARG, "separate image encoder (conv_in_img.*): in_channels must be 8 and cross_attention 0");
+  // (separate encoder: conv_in sees the 4 segmentation channels of the 8-channel packed input, i.e. zero weights on the RGB columns -
+  // the repack's channel padding - so the main path is the plain 8-channel UNet's launches)
+  TRY(b.conv("conv_in", kBlockOut[0], u->sepenc ? 4 : u->cfg.in_channels, 3, cp, &u->conv_in));
   const bool cross = u->cfg.cross_attention != 0;
   if (cross && wm.m.count("encoder_hid_proj.weight"))       // optional (clip_image descriptors, unet.py:121-122)
     TRY(b.conv("encoder_hid_proj", kCrossDim, kHidProjIn, 1, kHidProjIn, &u->hid_proj));
@@ -864,22 +886,23 @@ int unet_build(ldmseg_unet* u, const WeightMap& wm) {
 
   // all 22 time_emb_proj Linear(1280 -> cout) concatenated: one GEMV per forward
   u->temb_total = temb_off;
+  float *put_w = nullptr, *put_b = nullptr;      // the table `put` fills
+  auto put = [&](const std::string& p, const ResnetW& r) -> int {
+    const float *w, *bias;
+    TRY(wm.get(p + "time_emb_proj.weight", (int64_t)r.cout * kTimeDim, &w));
+    TRY(wm.get(p + "time_emb_proj.bias", r.cout, &bias));
+    HIP_TRY(hipMemcpyAsync(put_w + (size_t)r.temb_off * kTimeDim, w, (size_t)r.cout * kTimeDim * sizeof(float),
+                           hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(put_b + r.temb_off, bias, r.cout * sizeof(float), hipMemcpyDeviceToDevice, s));
+    b.nparams += (int64_t)r.cout * kTimeDim + r.cout;
+    return 0;
+  };
   {
     void *pw, *pb;
     TRY(u->arena.alloc(&pw, (size_t)temb_off * kTimeDim * sizeof(float)));
     TRY(u->arena.alloc(&pb, (size_t)temb_off * sizeof(float)));
-    u->tproj_w = (float*)pw;
-    u->tproj_b = (float*)pb;
-    auto put = [&](const std::string& p, const ResnetW& r) -> int {
-      const float *w, *bias;
-      TRY(wm.get(p + "time_emb_proj.weight", (int64_t)r.cout * kTimeDim, &w));
-      TRY(wm.get(p + "time_emb_proj.bias", r.cout, &bias));
-      HIP_TRY(hipMemcpyAsync(u->tproj_w + (size_t)r.temb_off * kTimeDim, w, (size_t)r.cout * kTimeDim * sizeof(float),
-                             hipMemcpyDeviceToDevice, s));
-      HIP_TRY(hipMemcpyAsync(u->tproj_b + r.temb_off, bias, r.cout * sizeof(float), hipMemcpyDeviceToDevice, s));
-      b.nparams += (int64_t)r.cout * kTimeDim + r.cout;
-      return 0;
-    };
+    put_w = u->tproj_w = (float*)pw;
+    put_b = u->tproj_b = (float*)pb;
     for (int i = 0; i < 4; ++i)
       for (int j = 0; j < 2; ++j)
         TRY(put("down_blocks." + std::to_string(i) + ".resnets." + std::to_string(j) + ".", u->down_res[i][j]));
@@ -888,6 +911,54 @@ int unet_build(ldmseg_unet* u, const WeightMap& wm) {
     for (int i = 0; i < 4; ++i)
       for (int j = 0; j < 3; ++j)
         TRY(put("up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j) + ".", u->up_res[i][j]));
+  }
+  if (u->sepenc) {
+    // conv_in_img reads the RGB half of the same packed 8-channel input: its [320][4][3][3] filters behind four zero input channels
+    {
+      const float *w4, *bias;
+      TRY(wm.get("conv_in_img.weight", (int64_t)kBlockOut[0] * 4 * 9, &w4));
+      TRY(wm.get("conv_in_img.bias", kBlockOut[0], &bias));
+      void* w8;
+      HIP_TRY(hipMalloc(&w8, (size_t)kBlockOut[0] * 8 * 9 * sizeof(float)));
+      b.temps.push_back(w8);
+      HIP_TRY(hipMemsetAsync(w8, 0, (size_t)kBlockOut[0] * 8 * 9 * sizeof(float), s));
+      HIP_TRY(hipMemcpy2DAsync((float*)w8 + 4 * 9, (size_t)8 * 9 * sizeof(float), w4, (size_t)4 * 9 * sizeof(float), (size_t)4 * 9 * sizeof(float),
+                               kBlockOut[0], hipMemcpyDeviceToDevice, s));
+      WeightMap ext;
+      ext.m["conv_in_img.weight"] = {(const float*)w8, (int64_t)kBlockOut[0] * 8 * 9};
+      ext.m["conv_in_img.bias"] = {bias, kBlockOut[0]};
+      b.wm = &ext;
+      const int r = b.conv("conv_in_img", kBlockOut[0], 8, 3, cp, &u->conv_in_img);
+      b.wm = &wm;
+      TRY(r);
+      b.nparams -= (int64_t)kBlockOut[0] * 4 * 9;      // (the four zero channels are not parameters)
+    }
+    int ioff = 0;
+    int ci = kBlockOut[0];
+    for (int i = 0; i < 4; ++i) {
+      const std::string p = "down_blocks_additional." + std::to_string(i);
+      for (int j = 0; j < 2; ++j) {
+        TRY(build_resnet(b, p + ".resnets." + std::to_string(j) + ".", ci, kBlockOut[i], &ioff, &u->img_res[i][j]));
+        ci = kBlockOut[i];
+        if (i < 3) TRY(build_transformer(b, p + ".attentions." + std::to_string(j) + ".", ci, &u->img_attn[i][j], false));
+      }
+      if (i < 3) TRY(b.conv(p + ".downsamplers.0.conv", ci, ci, 3, ci, &u->img_conv[i]));
+    }
+    u->adaptor = wm.m.count("adaptor_layers.0.weight") != 0;
+    if (u->adaptor)
+      for (int i = 0; i < 4; ++i)
+        TRY(b.conv("adaptor_layers." + std::to_string(i), kBlockOut[i], kBlockOut[i], 3, kBlockOut[i], &u->adapt[i], true, 0, EPI_STORE,
+                   kBlockOut[i] <= 640));
+    // its 8 time_emb_proj (7,040 rows) as a table of their own: they see emb(timestep_img)
+    u->temb_img_total = ioff;
+    void *pw, *pb;
+    TRY(u->arena.alloc(&pw, (size_t)ioff * kTimeDim * sizeof(float)));
+    TRY(u->arena.alloc(&pb, (size_t)ioff * sizeof(float)));
+    put_w = u->tproj_img_w = (float*)pw;
+    put_b = u->tproj_img_b = (float*)pb;
+    for (int i = 0; i < 4; ++i)
+      for (int j = 0; j < 2; ++j)
+        TRY(put("down_blocks_additional." + std::to_string(i) + ".resnets." + std::to_string(j) + ".", u->img_res[i][j]));
   }
   TRY(b.finish());
   u->nparams = b.nparams;
@@ -1022,6 +1093,116 @@ int run_transformer(Exec& ex, const TransformerW& t, const Act& x, Act* out, con
   return 0;
 }
 
+// The 12 residual tensors of the separate image encoder, in the order of the skip connections: elements of each and of all
+struct ImgResidLayout {
+  size_t elems[12], off[12], total = 0;      // off: in elements
+  ImgResidLayout(int B, int L) {
+    int k = 0;
+    auto add = [&](int C, int side) { elems[k] = (size_t)B * side * side * C; off[k] = total; total += rup(elems[k], 128); ++k; };
+    add(kBlockOut[0], L);
+    for (int i = 0; i < 4; ++i) {
+      add(kBlockOut[i], L >> i);
+      add(kBlockOut[i], L >> i);
+      if (i < 3) add(kBlockOut[i], L >> (i + 1));
+    }
+  }
+};
+// room for them at (B, L); growth synchronises the device (ldmseg_unet_reserve does it up front)
+int img_resid_reserve(ldmseg_unet* u, int B, int L) {
+  if (!u->sepenc) return 0;
+  const size_t need = ImgResidLayout(B, L).total * esize(u->dt);
+  if (need <= u->img_resid_bytes) return 0;
+  HIP_TRY(hipDeviceSynchronize());
+  if (u->img_resid) (void)hipFree(u->img_resid);
+  u->img_resid = nullptr; u->img_resid_bytes = 0;
+  if (hipMalloc(&u->img_resid, need) != hipSuccess) return fail(LDMSEG_E_OOM, "hipMalloc of the image-encoder residuals failed");
+  u->img_resid_bytes = need;
+  return 0;
+}
+
+// timestep_img of a call: device int64 (count 1 or B) or, dev null, the host value
+struct ImgTime { const int64_t* dev = nullptr; int count = 1; int64_t host = 0; };
+
+// The image branch of a separate-encoder handle as a workspace pass of its own (unet.py:309-351): emb(timestep_img), conv_in_img on
+// the RGB half of the packed input, down_blocks_additional, adaptor_layers - its 12 outputs land in u->img_resid.  (a | b: the
+// 8-channel input or its two halves, as unet_forward_impl takes them; the segmentation half meets zero weights.)
+int unet_img_branch_impl(ldmseg_unet* u, const float* a, int Ca, const float* b, int Cb, const ImgTime& ti, int B, int L, hipStream_t s,
+                         bool dry, size_t scratch_base) {
+  if (B < 1 || L < 8 || L % 8 != 0) return fail(LDMSEG_E_SHAPE, "L must be a positive multiple of 8, B >= 1");
+  if (Ca + Cb != 8) return fail(LDMSEG_E_SHAPE, "input channel count != in_channels");
+  if (ti.count != 1 && ti.count != B) return fail(LDMSEG_E_ARG, "timg_count must be 1 or B");
+  Workspace* ws = &u->ws;
+  Exec ex = make_exec(*u, B, s, dry, scratch_base);
+  ex.attn_fp8_min_tokens = u->attn_fp8_min_tokens;
+  ex.gn_poll_us = u->gn_backoff_calls > 0 ? 2 : -1;
+  const int dt = u->dt;
+  const ImgResidLayout lay(B, L);
+  if (!dry && lay.total * esize(dt) > u->img_resid_bytes) return fail(LDMSEG_E_OOM, "image-encoder residual buffer too small");
+  auto resid = [&](int k) { return (void*)((char*)u->img_resid + lay.off[k] * esize(dt)); };
+
+  const bool per_sample_t = ti.dev != nullptr && ti.count > 1;
+  const int TB = per_sample_t ? B : 1;
+  float* sinus = (float*)ws->persist((size_t)B * 320 * sizeof(float));
+  float* e1 = (float*)ws->persist((size_t)B * kTimeDim * sizeof(float));
+  float* emb = (float*)ws->persist((size_t)B * kTimeDim * sizeof(float));
+  float* temb = (float*)ws->persist((size_t)B * u->temb_img_total * sizeof(float));
+  {
+    ProfScope ps(4, s, 0, 0, dry);
+    if (!dry) {
+      TRY(ex.ws_ok());
+      TRY(launch_time_embed(ti.dev, ti.count, ti.host, TB, sinus, s));
+      TRY(launch_small_linear(sinus, u->te1_w, u->te1_b, e1, TB, 320, kTimeDim, 0, 1, s));
+      TRY(launch_small_linear(e1, u->te2_w, u->te2_b, emb, TB, kTimeDim, kTimeDim, 0, 0, s));
+      TRY(launch_small_linear(emb, u->tproj_img_w, u->tproj_img_b, temb, TB, kTimeDim, u->temb_img_total, 1, 0, s));
+    }
+  }
+  const int tstride = per_sample_t ? u->temb_img_total : 0;
+
+  Act xin = ex.new_act(bke(dt), L, L, true);
+  {
+    ProfScope ps(4, s, 0, 0, dry);
+    if (!dry) TRY(ex.ws_ok());
+    if (!dry) TRY(launch_pack_concat3(a, Ca, b, Cb, nullptr, 0, xin.p, B, L * L, bke(dt), dt, s));
+  }
+  int k = 0;
+  // residual k <- h (the first: conv_in_img's output as it is) or adaptor_layers[block](h)
+  auto emit = [&](const Act& h, int block) -> int {
+    if (block >= 0 && u->adaptor) {
+      const size_t m = ws->mark();
+      Act o;
+      TRY(ex.conv(u->adapt[block], h, nullptr, &o, 1, 0, false, nullptr, 0, nullptr, 0, -1, resid(k)));
+      ws->reset(m);
+    } else if (!dry) {
+      TRY(ex.ws_ok());
+      HIP_TRY(hipMemcpyAsync(resid(k), h.p, lay.elems[k] * esize(dt), hipMemcpyDeviceToDevice, s));
+    }
+    ++k;
+    return 0;
+  };
+  Act h;
+  TRY(ex.conv(u->conv_in_img, xin, nullptr, &h, 1, 0, true, nullptr, 0, nullptr));
+  TRY(emit(h, -1));
+  for (int i = 0; i < 4; ++i) {
+    for (int j = 0; j < 2; ++j) {
+      Act o;
+      TRY(run_resnet(ex, u->img_res[i][j], h, nullptr, temb, tstride, &o));
+      h = o;
+      if (i < 3) {
+        TRY(run_transformer(ex, u->img_attn[i][j], h, &o));
+        h = o;
+      }
+      TRY(emit(h, i));
+    }
+    if (i < 3) {
+      Act o;
+      TRY(ex.conv(u->img_conv[i], h, nullptr, &o, 2, 0, true, nullptr, 0, nullptr));
+      h = o;
+      TRY(emit(h, i));
+    }
+  }
+  return 0;
+}
+
 // dry = true only measures the workspace
 int unet_forward_impl(ldmseg_unet* u, const float* a, int Ca, const float* b, int Cb, const float* c, int Cc,
                       const int64_t* t_dev, int t_count, int64_t t_host, int B, int L, float* out, hipStream_t s,
@@ -1128,6 +1309,28 @@ int unet_forward_impl(ldmseg_unet* u, const float* a, int Ca, const float* b, in
       skips.push_back(h);
     }
   }
+  if (u->sepenc) {
+    // skip k += residual k of the image branch (unet.py:375-385), one launch.  The last skip is also the mid block's input, which
+    // stays un-summed: its sum goes to a tensor of its own; the other 11 are summed in place.
+    const ImgResidLayout lay(B, L);
+    Act last = ex.new_act(skips[11].C, skips[11].H, skips[11].W, true);
+    SkipAddSeg segs[12];
+    for (int k = 0; k < 12; ++k) {
+      if ((size_t)B * skips[k].H * skips[k].W * skips[k].C != lay.elems[k]) return fail(LDMSEG_E_SHAPE, "skip / residual shape mismatch");
+      segs[k].dst = k == 11 ? last.p : skips[k].p;
+      segs[k].a = skips[k].p;
+      segs[k].b = (const char*)u->img_resid + lay.off[k] * esize(dt);
+      segs[k].elems = (long long)lay.elems[k];
+    }
+    skips[11] = last;
+    ProfScope ps(4, s, 0, 3.0 * lay.total * esize(dt), dry, "skip_add");
+    if (!dry) {
+      TRY(ex.ws_ok());
+      if (lay.total * esize(dt) > u->img_resid_bytes) return fail(LDMSEG_E_OOM, "image-encoder residual buffer too small");
+      const int r = launch_skip_add(segs, 12, dt, s);
+      if (r) return fail(r == -2 ? LDMSEG_E_SHAPE : LDMSEG_E_HIP, "launch_skip_add failed");
+    }
+  }
   {
     Act o;
     TRY(run_resnet(ex, u->mid_res[0], h, nullptr, temb, tstride, &o)); h = o;
@@ -1231,15 +1434,42 @@ int plan_and_run(HandleBase& h, const PlanKey* key, Impl&& impl) {
   }
 }
 
+// One forward = the image branch (separate-encoder handles whose residuals are not standing, see ldmseg_sample_loop), then the UNet
+// itself.  Both are passes over the same workspace from its start - the branch leaves its results in u->img_resid - so the offsets
+// of the UNet's pass are those of a plain handle whether the branch ran or not; a dry run measures both and keeps the larger peaks.
+int unet_forward_passes(ldmseg_unet* u, const float* a, int Ca, const float* b, int Cb, const float* c, int Cc,
+                        const int64_t* t_dev, int t_count, int64_t t_host, const ImgTime& ti, int B, int L, float* out, hipStream_t s,
+                        bool dry, size_t scratch_base) {
+  size_t pp = 0, sp = 0;
+  if (u->sepenc && (dry || !u->img_ready)) {
+    if (Cc) return fail(LDMSEG_E_SHAPE, "input channel count != in_channels");
+    TRY(unet_img_branch_impl(u, a, Ca, b, Cb, ti, B, L, s, dry, scratch_base));
+    pp = u->ws.persist_peak; sp = u->ws.scratch_peak;
+    if (!dry) {
+      u->img_ready = u->img_keep;
+      u->xin_ready = false; u->xin_ptr = nullptr;      // (the pass went over the place where a step tail left the next input)
+    }
+  }
+  TRY(unet_forward_impl(u, a, Ca, b, Cb, c, Cc, t_dev, t_count, t_host, B, L, out, s, dry, scratch_base));
+  if (dry) {
+    u->ws.persist_peak = std::max(u->ws.persist_peak, pp);
+    u->ws.scratch_peak = std::max(u->ws.scratch_peak, sp);
+  }
+  return 0;
+}
+
 int unet_forward_checked(ldmseg_unet* u, const float* a, int Ca, const float* b, int Cb, const float* c, int Cc,
-                         const int64_t* t_dev, int t_count, int64_t t_host, int B, int L, float* out, hipStream_t s) {
+                         const int64_t* t_dev, int t_count, int64_t t_host, int B, int L, float* out, hipStream_t s,
+                         const ImgTime& ti = {}) {
+  if (B < 1 || L < 8 || L % 8 != 0) return fail(LDMSEG_E_SHAPE, "L must be a positive multiple of 8, B >= 1");
+  TRY(img_resid_reserve(u, B, L));      // no-op after ldmseg_unet_reserve or a previous call at this size
   const PlanKey key{B, L, u->ctx_S, u->ctx_dim};
   const void* before = u->ws_mem;
   const size_t cap_before = u->ws_cap;
   return plan_and_run(*u, &key, [&](bool dry, size_t scratch_base) {
     // (the workspace moved or grew: a new arena may reuse the old address, so the tail's hand-over is void either way)
     if (!dry && (u->ws_mem != before || u->ws_cap != cap_before)) { u->xin_ready = false; u->xin_ptr = nullptr; }
-    return unet_forward_impl(u, a, Ca, b, Cb, c, Cc, t_dev, t_count, t_host, B, L, out, s, dry, scratch_base);
+    return unet_forward_passes(u, a, Ca, b, Cb, c, Cc, t_dev, t_count, t_host, ti, B, L, out, s, dry, scratch_base);
   });
 }
 
@@ -1938,9 +2168,14 @@ const char* ldmseg_version(void) { return "ldmseg_hip 0.1 (gfx950)"; }
 
 int ldmseg_unet_create(const ldmseg_unet_cfg* cfg, int n_weights, const char* const* names,
                        const void* const* dev_ptrs, const int64_t* numels, ldmseg_unet** out) {
-  auto check = [](const ldmseg_unet_cfg& c) {
+  bool sepenc = false;
+  for (int i = 0; names && i < n_weights; ++i) sepenc = sepenc || (names[i] && std::strcmp(names[i], "conv_in_img.weight") == 0);
+  auto check = [sepenc](const ldmseg_unet_cfg& c) {
     if (c.cross_attention != 0 && c.cross_attention != 1) return fail(LDMSEG_E_ARG, "cross_attention must be 0 or 1");
     if (c.in_channels != 4 && c.in_channels != 8 && c.in_channels != 12) return fail(LDMSEG_E_ARG, "in_channels must be 4, 8 or 12");
+    // (before any device work: a state dict with conv_in_img.* is a separate-encoder UNet, unet.py:42-63)
+    if (sepenc && c.cross_attention) return fail(LDMSEG_E_ARG, "separate image encoder (conv_in_img.*) with cross_attention is not supported");
+    if (sepenc && c.in_channels != 8) return fail(LDMSEG_E_ARG, "separate image encoder (conv_in_img.*) needs in_channels 8");
     return 0;
   };
   return create_handle(cfg, n_weights, names, dev_ptrs, numels, check, unet_build, true, out);
@@ -1955,7 +2190,7 @@ size_t ldmseg_unet_workspace_bytes(const ldmseg_unet* h, int B, int L) {
   ldmseg_unet* u = const_cast<ldmseg_unet*>(h);
   DeviceGuard dg(u->cfg.device);
   const int ci = u->cfg.in_channels;
-  if (unet_forward_impl(u, nullptr, ci, nullptr, 0, nullptr, 0, nullptr, 1, 0, B, L, nullptr, nullptr, true, 0) != 0) return 0;
+  if (unet_forward_passes(u, nullptr, ci, nullptr, 0, nullptr, 0, nullptr, 1, 0, ImgTime{}, B, L, nullptr, nullptr, true, 0) != 0) return 0;
   return rup(u->ws.persist_peak, 4096) + rup(u->ws.scratch_peak, 4096);
 }
 
@@ -1977,6 +2212,17 @@ int ldmseg_unet_forward_parts(ldmseg_unet* h, const float* latents, const float*
   DeviceGuard dg(h->cfg.device);
   return unet_forward_checked(h, latents, 4, rgb_latents, 4, cond, cond ? 4 : 0, t_dev, t_count, t_host, B, L, out,
                               (hipStream_t)stream);
+}
+
+int ldmseg_unet_forward_img(ldmseg_unet* h, const float* x, const int64_t* t_dev, int t_count, int64_t t_host,
+                            const int64_t* timg_dev, int timg_count, int64_t timg_host, int B, int L, float* out, void* stream) {
+  g_err.clear();
+  if (!h || !x || !out) return fail(LDMSEG_E_ARG, "null argument");
+  if (h->cfg.cross_attention) return fail(LDMSEG_E_ARG, "cross-attention handle: the context goes through ldmseg_unet_forward_ctx");
+  if (timg_count != 1 && timg_count != B) return fail(LDMSEG_E_ARG, "timg_count must be 1 or B");
+  DeviceGuard dg(h->cfg.device);
+  return unet_forward_checked(h, x, h->cfg.in_channels, nullptr, 0, nullptr, 0, t_dev, t_count, t_host, B, L, out,
+                              (hipStream_t)stream, ImgTime{timg_dev, timg_count, timg_host});
 }
 
 namespace {
@@ -2361,8 +2607,9 @@ int ldmseg_unet_reserve(ldmseg_unet* h, int B, int L) {
   const int ci = h->cfg.in_channels;
   const PlanKey key{B, L, h->ctx_S, h->ctx_dim};
   TRY(plan_workspace(*h, &key, [&](bool dry, size_t scratch_base) {
-    return unet_forward_impl(h, nullptr, ci, nullptr, 0, nullptr, 0, nullptr, 1, 0, B, L, nullptr, nullptr, dry, scratch_base);
+    return unet_forward_passes(h, nullptr, ci, nullptr, 0, nullptr, 0, nullptr, 1, 0, ImgTime{}, B, L, nullptr, nullptr, dry, scratch_base);
   }));
+  TRY(img_resid_reserve(h, B, L));
   TRY(loop_reserve(h, (size_t)B * 4 * L * L));
   TRY(temb_reserve(h, 64));
   TRY(igemm_warm());
@@ -2407,7 +2654,12 @@ int ldmseg_sample_loop(ldmseg_unet* h, const ldmseg_sample_cfg* cfg, float* late
   const float* temb_rows = nullptr;
   TRY(loop_time_embeddings(h, cfg->timesteps, cfg->n_steps, s, &temb_rows));
   TRY(gn_backoff_update(h));
-  struct Clear { ldmseg_unet* u; ~Clear() { u->temb_override = nullptr; u->tail_req = nullptr; u->tail_done = false; u->xin_ready = false; u->xin_ptr = nullptr; } } clear{h};     // (also on the error returns below)
+  struct Clear { ldmseg_unet* u; ~Clear() { u->temb_override = nullptr; u->tail_req = nullptr; u->tail_done = false; u->xin_ready = false; u->xin_ptr = nullptr; u->img_keep = u->img_ready = false; } } clear{h};     // (also on the error returns below)
+  // Separate-encoder handles: the image branch reads rgb_latents and timestep_img = 0 only (sample() passes no timestep_img,
+  // trainers_ldm_cond.py:1141), so its residuals are the same in every step: step 0's forward computes them and they stand until
+  // this call returns (nothing is kept across calls: the caller may change rgb_latents).  Debug key 25: every step computes them.
+  h->img_ready = false;
+  h->img_keep = h->sepenc && !g_sepenc_every_step;
   for (int i = 0; i < cfg->n_steps; ++i) {
     h->temb_override = temb_rows + (size_t)i * h->temb_total;
     const float* c = cfg->coef + 4 * i;
@@ -2458,6 +2710,7 @@ int ldmseg_sample_loop_guided(ldmseg_unet* h, const ldmseg_sample_cfg* cfg, floa
   if (selfc && multiplier == 2) return fail(LDMSEG_E_ARG, "self_condition with classifier-free guidance (multiplier 2) is not defined");
   if ((h->cfg.in_channels == 12) != selfc) return fail(LDMSEG_E_ARG, "self_condition needs the 12-channel conv_in (and vice versa)");
   if (cfg->known_dev || cfg->z0_dev || cfg->noise_dev || cfg->paste_coef) return fail(LDMSEG_E_ARG, "inpainting is not combined with guidance");
+  if (h->sepenc) return fail(LDMSEG_E_ARG, "separate-encoder handle: no cross-attention, sample with ldmseg_sample_loop");
   TRY(set_ctx(h, ctx, S, ctx_dim));
   CtxClear cc{h};
   DeviceGuard dg(h->cfg.device);
@@ -2619,6 +2872,7 @@ int ldmseg_debug_set(int key, int value) {
   if (key == 24) { igemm_set_table_override(value); ++g_plan_epoch; return 0; }   // tuning: launch-table override, -1 = off (igemm_set_table_override)
   if (key == 19) { igemm_set_xt_mode(value); ++g_plan_epoch; return 0; }   // 1 (default): resnet conv2 + conv_shortcut as one launch (bf16)
   if (key == 20) { g_ffp_mode = value ? 1 : 0; ++g_plan_epoch; return 0; }
+  if (key == 25) { g_sepenc_every_step = value ? 1 : 0; return 0; }   // 1: ldmseg_sample_loop runs the separate image encoder in every step; default 0 = once per call
   if (key == 22) { g_gnfold_mode = value < 0 ? 0 : value; ++g_plan_epoch; return 0; }   // GroupNorm folded into the fused transformer entry: 0 off, 1 on, n > 1 on with n pixel chunks
   if (key == 21) { igemm_set_up4_mode(value); ++g_plan_epoch; return 0; }   // 1 (default): upsampler convs as four 2x2 phase convs (bf16)
   if (key == 6 || key == 7) { ops_bench_knob(key, value); return 0; }   // ldmseg_bench_igemm: 6 = weight copies rotated, 7 = folded-LN launch
@@ -2640,6 +2894,7 @@ int ldmseg_debug_get(int key) {
   if (key == 23) return igemm_get_cf_mode();
   if (key == 19) return igemm_get_xt_mode();
   if (key == 20) return g_ffp_mode;
+  if (key == 25) return g_sepenc_every_step;
   if (key == 22) return g_gnfold_mode;
   if (key == 21) return igemm_get_up4_mode();
   if (key == 10) { const long long n = gn_coop_fallbacks(nullptr); return n > 0x7fffffffll ? 0x7fffffff : (int)n; }   // ring regions (ldmseg_op_* launches)

@@ -364,6 +364,12 @@ int launch_pack_nchw(const float* x, void* y, int B, int C, int HW, int Cpad, fl
 int launch_pack_concat3(const float* a, int Ca, const float* b, int Cb, const float* c, int Cc,
                         void* y, int B, int HW, int Cpad, int dtype, hipStream_t s);
 
+// dst = a + b over up to kSkipAddMaxSegs dense tensors of `elems` elements each in one launch (skipadd.hip): the separate image
+// encoder's residuals onto the skip connections.  fp32 sum, one rounding to the storage type; dst may be a or b
+struct SkipAddSeg { void* dst = nullptr; const void* a = nullptr; const void* b = nullptr; long long elems = 0; };
+constexpr int kSkipAddMaxSegs = 12;
+int launch_skip_add(const SkipAddSeg* segs, int n_segs, int dtype, hipStream_t s);
+
 // timestep embedding + time MLP + all time_emb_proj: see misc.hip
 int launch_time_embed(const int64_t* t_dev, int t_count, int64_t t_host, int B, float* sinus /*[B,320]*/,
                       hipStream_t s);

@@ -167,6 +167,38 @@ int ldmseg_op_conv2d(const float* x, const float* x2, const float* w, const floa
   return launch_igemm(p, dtype, s);
 }
 
+// out = a + b over n_segs tensors (see ldmseg_hip_ops.h for the guard layout)
+int ldmseg_op_skip_add(const float* a, const float* b, const int64_t* seg_elems, int n_segs, int dtype, float* out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!a || !b || !seg_elems || !out || n_segs < 1 || n_segs > kSkipAddMaxSegs || (dtype != DT_F32 && dtype != DT_BF16)) return -2;
+  Temp t;
+  constexpr int kGuard = 8;
+  size_t total = 0;
+  for (int k = 0; k < n_segs; ++k) {
+    if (seg_elems[k] < 0) return -2;
+    total += (size_t)seg_elems[k] + kGuard;
+  }
+  char* ap = (char*)t.get(total * es(dtype));
+  char* bp = (char*)t.get(total * es(dtype));
+  char* op = (char*)t.get(total * es(dtype));
+  if (!ap || !bp || !op) return -6;
+  to_dev_dtype(a, ap, total, dtype, s);
+  to_dev_dtype(b, bp, total, dtype, s);
+  to_dev_dtype(out, op, total, dtype, s);
+  SkipAddSeg segs[kSkipAddMaxSegs];
+  size_t off = 0;
+  for (int k = 0; k < n_segs; ++k) {
+    segs[k].dst = op + off * es(dtype);
+    segs[k].a = ap + off * es(dtype);
+    segs[k].b = bp + off * es(dtype);
+    segs[k].elems = (long long)seg_elems[k];
+    off += (size_t)seg_elems[k] + kGuard;
+  }
+  const int r = launch_skip_add(segs, n_segs, dtype, s);
+  if (r) return r;
+  return from_dev_dtype(op, out, total, dtype, s);
+}
+
 // out = proj_out(h + ff.net.2(g)) + x  (diffusers BasicTransformerBlock.ff.net[2] + residual, Transformer2DModel.proj_out + residual;
 // /root/reference/ldmseg/models/unet.py:401-425) exactly as the bf16 / fp32 engines launch it at the 640- / 1280-channel levels:
 // chained matrix [Wp W2 | Wp] and bias bp + Wp b2 formed in fp32 by launch_chain_weights (the create-time kernel), packed to the

@@ -59,6 +59,7 @@ SIGNATURES = {
     "ldmseg_unet_destroy": (None, [_vp]),
     "ldmseg_unet_forward": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp]),
     "ldmseg_unet_forward_parts": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp]),
+    "ldmseg_unet_forward_img": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _i, _i64, _i, _i, _vp, _vp]),
     "ldmseg_unet_forward_ctx": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, _i, _i, _vp, _vp]),
     "ldmseg_unet_workspace_bytes": (_sz, [_vp, _i, _i]),
     "ldmseg_unet_num_params": (_i64, [_vp]),
@@ -115,6 +116,7 @@ SIGNATURES = {
     "ldmseg_op_conv2d": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ldmseg_op_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ldmseg_op_groupnorm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp]),
+    "ldmseg_op_skip_add": (_i, [_vp, _vp, C.POINTER(_i64), _i, _i, _vp, _vp]),
     "ldmseg_op_layernorm": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _i, _vp, _vp]),
     "ldmseg_op_attention": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ldmseg_op_attention_causal": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),

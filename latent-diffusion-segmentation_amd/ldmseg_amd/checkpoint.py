@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-from .weights import hid_proj_schema, unet_schema, vae_schema
+from .weights import hid_proj_schema, separate_conv_schema, separate_encoder_schema, unet_schema, vae_schema
 
 
 def _strip(sd):
@@ -28,11 +28,24 @@ def unet_state_from(data: dict, use_ema: bool = False, cross_attention: bool = F
     sd = _strip(sd)
     in_ch = int(sd["conv_in.weight"].shape[1])
     cross = any(".attn2." in k for k in sd)
+    sep_enc = "conv_in_img.weight" in sd          # modify_encoder(separate_encoder=True), unet.py:42-63
+    sep_conv = "conv_in_seg.weight" in sd         # modify_encoder(separate_conv=True), unet.py:140-173
+    if sep_enc and (cross or cross_attention):
+        raise NotImplementedError("a separate image encoder (conv_in_img.*) together with cross-attention (attn2) is not supported")
+    if sep_enc and sep_conv:
+        raise ValueError("checkpoint holds both conv_in_img.* and conv_in_seg.*: the reference builds one or the other")
+    if (sep_enc or sep_conv) and in_ch != 4:
+        raise ValueError(f"conv_in.weight: a separate_{'encoder' if sep_enc else 'conv'} checkpoint keeps the 4-channel conv_in, "
+                         f"this one has {in_ch} input channels")
     if cross and not cross_attention:
         raise NotImplementedError("checkpoint has cross-attention (attn2) weights: load it with cross_attention=True")
     schema = unet_schema(in_ch, bool(cross_attention))
     if cross_attention and any(k.startswith("encoder_hid_proj.") for k in sd):
         schema.update(hid_proj_schema())
+    if sep_enc:
+        schema.update(separate_encoder_schema(any(k.startswith("adaptor_layers.") for k in sd)))
+    if sep_conv:
+        schema.update(separate_conv_schema())
     out = OrderedDict()
     for k, shp in schema.items():
         if k not in sd:
@@ -40,6 +53,11 @@ def unet_state_from(data: dict, use_ema: bool = False, cross_attention: bool = F
         if tuple(sd[k].shape) != tuple(shp):
             raise ValueError(f"{k}: checkpoint shape {tuple(sd[k].shape)} != expected {tuple(shp)}")
         out[k] = sd[k]
+    if sep_conv:
+        # conv_in_seg(seg) + conv_in(img) (unet.py:352-355) is ONE conv over the 8-channel input: filters side by side, biases summed
+        w = torch.cat([out.pop("conv_in_seg.weight"), out["conv_in.weight"]], dim=1)
+        b = out.pop("conv_in_seg.bias") + out["conv_in.bias"]
+        out["conv_in.weight"], out["conv_in.bias"] = w, b
     return out
 
 
@@ -86,7 +104,8 @@ def build_models(ldm_path: str, ae_path: Optional[str] = None, device="cuda:0", 
     from .models import UNet, GeneralVAESeg
     ck = load_ldm_checkpoint(ldm_path)
     vsd = load_ae_checkpoint(ae_path) if ae_path else ck["vae_semseg"]
-    unet = UNet(ck["unet"], in_channels=int(ck["unet"]["conv_in.weight"].shape[1]), device=device,
-                compute_dtype=compute_dtype)
+    # (a separate-encoder state dict keeps its 4-channel conv_in and takes the 8-channel [segmentation | image] input)
+    in_ch = 8 if "conv_in_img.weight" in ck["unet"] else int(ck["unet"]["conv_in.weight"].shape[1])
+    unet = UNet(ck["unet"], in_channels=in_ch, device=device, compute_dtype=compute_dtype)
     vae = GeneralVAESeg(vsd, scaling_factor=scaling_factor, device=device, compute_dtype=compute_dtype)
     return unet, vae

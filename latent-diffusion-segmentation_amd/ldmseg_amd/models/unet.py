@@ -20,7 +20,7 @@ import torch
 
 from .. import _lib
 from ..utils import UNetOutput
-from ..weights import BLOCK_OUT, CROSS_DIM, unet_schema
+from ..weights import BLOCK_OUT, CROSS_DIM, separate_encoder_schema, unet_schema
 
 
 class UNet(object):
@@ -43,7 +43,19 @@ class UNet(object):
                                       cross_attention_dim=CROSS_DIM if self.cross_attention else None,
                                       sample_size=64, layers_per_block=2)
         self.has_encoder_hid_proj = self.cross_attention and "encoder_hid_proj.weight" in state_dict
-        missing = [k for k in unet_schema(self.in_channels, self.cross_attention) if k not in state_dict]
+        # separate_encoder (unet.py:42-63): conv_in_img + down_blocks_additional (+ adaptor_layers) on the RGB half of the 8-channel
+        # input; conv_in itself keeps 4 input channels.  The library detects it by the same key.
+        self.separate_encoder = "conv_in_img.weight" in state_dict
+        if self.separate_encoder:
+            if self.in_channels != 8:
+                raise ValueError("a separate-encoder state dict (conv_in_img.*) needs in_channels=8")
+            if self.cross_attention:
+                raise NotImplementedError("a separate image encoder together with cross_attention is not supported")
+            schema = unet_schema(4, False)
+            schema.update(separate_encoder_schema("adaptor_layers.0.weight" in state_dict))
+        else:
+            schema = unet_schema(self.in_channels, self.cross_attention)
+        missing = [k for k in schema if k not in state_dict]
         if missing:
             raise KeyError(f"state dict lacks {len(missing)} UNet tensors, e.g. {missing[:3]}")
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
@@ -147,6 +159,11 @@ class UNet(object):
                 _lib.check(_lib.lib().ldmseg_unet_forward_ctx(self._h, _lib.ptr(x), tptr, tcount, thost, B, H, _lib.ptr(ctx),
                                                               ctx.shape[1], ctx.shape[2], _lib.ptr(out),
                                                               _lib.stream_ptr(x.device)), "ldmseg_unet_forward_ctx")
+            elif self.separate_encoder and timestep_img is not None:
+                keep_i, iptr, icount, ihost = self._timestep_args(timestep_img, B)
+                _lib.check(_lib.lib().ldmseg_unet_forward_img(self._h, _lib.ptr(x), tptr, tcount, thost, iptr, icount, ihost, B, H,
+                                                              _lib.ptr(out), _lib.stream_ptr(x.device)), "ldmseg_unet_forward_img")
+                del keep_i
             else:    # (a cross-attention handle refuses this: the reference needs the context too)
                 _lib.check(_lib.lib().ldmseg_unet_forward(self._h, _lib.ptr(x), tptr, tcount, thost, B, H, _lib.ptr(out),
                                                           _lib.stream_ptr(x.device)), "ldmseg_unet_forward")

@@ -31,6 +31,31 @@ def hid_proj_schema():
     return OrderedDict([("encoder_hid_proj.weight", (CROSS_DIM, HID_PROJ_IN)), ("encoder_hid_proj.bias", (CROSS_DIM,))])
 
 
+def separate_encoder_schema(add_adaptor=False):
+    """The extra tensors of ``modify_encoder(separate_encoder=True)`` (unet.py:42-63): ``conv_in_img`` and
+    ``down_blocks_additional`` - deep copies of the 4-channel ``conv_in`` and of ``down_blocks`` after
+    ``remove_cross_attention`` (main_ldm.py:155-159 runs it first) - and, with ``add_adaptor``, one 3x3 conv C -> C per level.
+    Together with ``unet_schema(4)``: 1,049,661,444 parameters in 780 tensors, 1,083,764,164 in 788 with the adaptors."""
+    base = unet_schema(4, False)
+    sd = OrderedDict()
+    sd["conv_in_img.weight"] = base["conv_in.weight"]
+    sd["conv_in_img.bias"] = base["conv_in.bias"]
+    for k, shp in base.items():
+        if k.startswith("down_blocks."):
+            sd["down_blocks_additional." + k[len("down_blocks."):]] = shp
+    if add_adaptor:
+        for i, c in enumerate(BLOCK_OUT):
+            sd[f"adaptor_layers.{i}.weight"] = (c, c, 3, 3)
+            sd[f"adaptor_layers.{i}.bias"] = (c,)
+    return sd
+
+
+def separate_conv_schema():
+    """``conv_in_seg`` of ``modify_encoder(separate_conv=True)`` (unet.py:140-173): a second 4-channel conv_in for the
+    segmentation half; ``conv_in`` itself then reads the image half."""
+    return OrderedDict([("conv_in_seg.weight", (BLOCK_OUT[0], 4, 3, 3)), ("conv_in_seg.bias", (BLOCK_OUT[0],))])
+
+
 def _resnet(sd, p, cin, cout):
     sd[p + "norm1.weight"] = (cin,)
     sd[p + "norm1.bias"] = (cin,)

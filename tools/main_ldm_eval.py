@@ -68,8 +68,9 @@ def build_trainer(args, device):
             schema = weights.clip_vision_schema(projection_dim=768 if proj else 0)
             csd = weights.generate(schema, seed=13, norm_keys=weights.clip_vision_norm_keys(schema))
         desc = CLIPVisionDescriptor(csd, projection=proj, device=device, compute_dtype=args.dtype)
-    unet = UNet(usd, in_channels=int(usd["conv_in.weight"].shape[1]), device=device, compute_dtype=args.dtype,
-                cross_attention=cross)
+    # (a separate-encoder checkpoint keeps its 4-channel conv_in and takes the 8-channel [segmentation | image] input)
+    in_ch = 8 if "conv_in_img.weight" in usd else int(usd["conv_in.weight"].shape[1])
+    unet = UNet(usd, in_channels=in_ch, device=device, compute_dtype=args.dtype, cross_attention=cross)
     vae = GeneralVAESeg(vsd, scaling_factor=args.scaling_factor, device=device, compute_dtype=args.dtype)
     enc = GeneralVAEImage(isd, scaling_factor=0.18215, device=device, compute_dtype=args.dtype)
     return TrainerDiffusion(vae, unet, DDIMNoiseScheduler(**NOISE_SCHEDULER_KWARGS), vae_image=enc,
