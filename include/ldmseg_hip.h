@@ -397,6 +397,49 @@ int ldmseg_remove_noise(const float* noisy, const float* noise, const int64_t* t
                         const float* alphas_cumprod_dev, int n_train_timesteps, float scale, float* out, int B,
                         size_t per_sample, void* stream);
 
+/* ---- denoising loss: the forward half of the training step (trainers_ldm_cond.py:445-661) -------------------- */
+#define LDMSEG_LOSS_L1 0
+#define LDMSEG_LOSS_L2 1
+#define LDMSEG_LOSS_SMOOTH_L1 2          /* beta = 1 */
+/* Everything of compute_loss / predict_sample behind the UNet forward (:594-615, :483-492), on [B,C,HW] fp32 tensors:
+ *   element loss  l1 |x - y|, l2 (x - y) * (x - y), smooth_l1 (z < 1 ? 0.5 * z * z : z - 0.5), x = prediction, y = target
+ *                 (:515-520), times loss_mask[b][pixel] (:525) if given, times weights_dev[t_b] (:597) if given; every product
+ *                 and difference rounded separately, bit-identical to the reference's fp32 values.  Written to elem_loss if
+ *                 non-NULL.  target NULL: no loss at all (mean / sample_sums / elem_loss are not written).
+ *   pred_latents  (if non-NULL) prediction_type 0 'epsilon': remove_noise(noisy, prediction, t) with ldmseg_remove_noise's own
+ *                 arithmetic (scale 1); 1 'sample': prediction (:605-611); then paste_src where paste_mask != 0 (:614-615);
+ *                 then clamp(., minmax_dev[0], minmax_dev[1]) (:492) if minmax_dev is non-NULL (ldmseg_tensor_minmax's pair; a NaN bound
+ *                 makes every value NaN, like torch.clamp).
+ *   sample_sums   [B] fp32 (may be NULL): the sample's element losses added in fp64, rounded once.
+ *   mean          [1] fp32: ohem_ratio >= 1: sum of all element losses (fp64) / (B*C*HW).  ohem_ratio < 1 (needs elem_loss):
+ *                 torch.topk(loss.view(-1), k)[0].mean() with k = (int64)(ohem_ratio * (double)(B*C*HW)) (:600-602), exact: a
+ *                 radix select over the bit patterns finds the k-th largest value, the strictly larger elements are added in
+ *                 fp64 and the ties enter as count * value.  k == 0 is LDMSEG_E_ARG.  A NaN element makes the mean NaN.
+ * Workgroups store fp64 partial sums that one finishing launch adds in a fixed order: no float atomics, two calls on the same
+ * inputs agree bit for bit.  timesteps_dev [B] int64 is clamped into the table like ldmseg_add_noise.  paste_mask is uint8 / bool
+ * [B,C,HW].  scratch: ldmseg_diffusion_loss_scratch_bytes(B, C, HW) bytes of device memory, owned by the caller, reusable by a
+ * later call on the same stream.  2 launches (7 + one memset node with OHEM); no host synchronisation, no allocation. */
+size_t ldmseg_diffusion_loss_scratch_bytes(int B, int C, int HW);
+int ldmseg_diffusion_loss(const float* prediction, const float* target, const float* noisy, const int64_t* timesteps_dev,
+                          const float* alphas_cumprod_dev, int n_train_timesteps, const float* weights_dev,
+                          const float* loss_mask, const uint8_t* paste_mask, const float* paste_src, const float* minmax_dev,
+                          int loss_type, int prediction_type, double ohem_ratio, int B, int C, int HW, float* elem_loss,
+                          float* pred_latents, float* mean, float* sample_sums, void* scratch, void* stream);
+/* get_loss_weight_mask (:643-661): src [B,Hi,Wi] (src_dtype 0 int64, 1 uint8 / bool, 2 fp32) -> out [B,h,w] fp32 through the source
+ * pixel of F.interpolate(mode='nearest').  LDMSEG_MASK_IGNORE: value != ignore_label; LDMSEG_MASK_PADDING: the resized value;
+ * LDMSEG_MASK_COUNTS: 1 / (pixels of the same id in the resized map of the image), 0 on ignore_label.  COUNTS keeps one 256-entry
+ * table per image: an id outside [0, 256) (the bit codec's range) sets bit 0 of *flag (device int32, reset by the call) and gets
+ * the weight NaN, so that it can neither index out of bounds nor go unnoticed in the loss.  One launch, one workgroup per image. */
+#define LDMSEG_MASK_IGNORE 0
+#define LDMSEG_MASK_PADDING 1
+#define LDMSEG_MASK_COUNTS 2
+int ldmseg_loss_weight_mask(const void* src, int src_dtype, int B, int Hi, int Wi, int h, int w, int mode, int64_t ignore_label,
+                            float* out, int32_t* flag, void* stream);
+/* minmax[0] = x.min(), minmax[1] = x.max() of n fp32 values, on the device (NaN if x holds one, like torch).  scratch:
+ * LDMSEG_MINMAX_SCRATCH_BYTES of device memory.  Two launches: per-workgroup partials, then one fixed-order finish. */
+#define LDMSEG_MINMAX_SCRATCH_BYTES 3072
+int ldmseg_tensor_minmax(const float* x, size_t n, float* minmax, void* scratch, void* stream);
+
 /* ---- sampler: TrainerDiffusion.sample (trainers_ldm_cond.py:1045-1170) -------------------- */
 typedef struct {
   int32_t n_steps;               /* len(scheduler.timesteps) */

@@ -195,6 +195,10 @@ int ldmseg_igemm_log_read(char* buf, int n);
 /* q[i] = n[i] / d (0 <= n[i] < 2^31, d >= 1) computed the way the kernels divide: host-prepared multiply-shift pair */
 int ldmseg_op_fastdiv(const int* n, int count, int d, int* q, void* stream);
 
+/* src[i], i in [0, out_size): the source index ldmseg_loss_weight_mask reads for output index i when it resizes in_size to
+ * out_size (csrc/nearest_index.h, the rule of F.interpolate(mode='nearest')).  Host only: src is a host array, no GPU is touched. */
+int ldmseg_op_nearest_index(int in_size, int out_size, int* src);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2541,6 +2541,60 @@ int ldmseg_remove_noise(const float* noisy, const float* noise, const int64_t* t
   return 0;
 }
 
+size_t ldmseg_diffusion_loss_scratch_bytes(int B, int C, int HW) { return diffusion_loss_scratch_bytes(B, C, HW); }
+
+int ldmseg_diffusion_loss(const float* prediction, const float* target, const float* noisy, const int64_t* timesteps_dev,
+                          const float* alphas_cumprod_dev, int n_train_timesteps, const float* weights_dev,
+                          const float* loss_mask, const uint8_t* paste_mask, const float* paste_src, const float* minmax_dev,
+                          int loss_type, int prediction_type, double ohem_ratio, int B, int C, int HW, float* elem_loss,
+                          float* pred_latents, float* mean, float* sample_sums, void* scratch, void* stream) {
+  g_err.clear();
+  if (!prediction || !timesteps_dev || !alphas_cumprod_dev || !scratch) return fail(LDMSEG_E_ARG, "null argument");
+  if (!target && !pred_latents) return fail(LDMSEG_E_ARG, "nothing to compute: neither a target nor pred_latents");
+  if (target && !mean) return fail(LDMSEG_E_ARG, "a loss needs the mean output");
+  if (B < 1 || B > 65535 || C < 1 || HW < 1 || n_train_timesteps < 1 || (int64_t)C * HW > (int64_t)0x7fff0000)
+    return fail(LDMSEG_E_SHAPE, "B in 1..65535, C, HW and n_train_timesteps positive, C * HW < 2^31");
+  if (loss_type != LDMSEG_LOSS_L1 && loss_type != LDMSEG_LOSS_L2 && loss_type != LDMSEG_LOSS_SMOOTH_L1)
+    return fail(LDMSEG_E_ARG, "unknown loss_type");
+  if (prediction_type != 0 && prediction_type != 1) return fail(LDMSEG_E_ARG, "prediction_type: 0 epsilon, 1 sample");
+  if (pred_latents && prediction_type == 0 && !noisy) return fail(LDMSEG_E_ARG, "epsilon pred_latents need the noisy latents");
+  if ((paste_mask != nullptr) != (paste_src != nullptr)) return fail(LDMSEG_E_ARG, "paste_mask and paste_src come together");
+  double k = 0;
+  if (target && ohem_ratio < 1.0) {
+    if (!elem_loss) return fail(LDMSEG_E_ARG, "ohem_ratio < 1 needs the elem_loss buffer");
+    k = (double)(int64_t)(ohem_ratio * (double)((int64_t)B * C * HW));
+    if (!(k >= 1)) return fail(LDMSEG_E_ARG, "ohem_ratio selects no element (k == 0)");
+  }
+  LossTail t{};
+  t.pred = prediction; t.target = target; t.noisy = noisy; t.t = timesteps_dev; t.ac = alphas_cumprod_dev;
+  t.n_train = n_train_timesteps; t.weights = weights_dev; t.mask = loss_mask; t.paste = paste_mask; t.paste_src = paste_src;
+  t.minmax = minmax_dev; t.elem = elem_loss; t.pred_latents = pred_latents; t.C = C; t.HW = HW;
+  t.loss_type = loss_type; t.pred_type = prediction_type;
+  TRY(launch_diffusion_loss(t, B, k, sample_sums, mean, scratch, (hipStream_t)stream));
+  return 0;
+}
+
+int ldmseg_loss_weight_mask(const void* src, int src_dtype, int B, int Hi, int Wi, int h, int w, int mode, int64_t ignore_label,
+                            float* out, int32_t* flag, void* stream) {
+  g_err.clear();
+  if (!src || !out || !flag) return fail(LDMSEG_E_ARG, "null argument");
+  if (src_dtype < 0 || src_dtype > 2) return fail(LDMSEG_E_ARG, "src_dtype: 0 int64, 1 uint8, 2 fp32");
+  if (mode != LDMSEG_MASK_IGNORE && mode != LDMSEG_MASK_PADDING && mode != LDMSEG_MASK_COUNTS) return fail(LDMSEG_E_ARG, "unknown mode");
+  if (B < 1 || Hi < 1 || Wi < 1 || h < 1 || w < 1 || (int64_t)h * w > (int64_t)0x7fff0000) return fail(LDMSEG_E_SHAPE, "sizes must be positive");
+  TRY(launch_loss_weight_mask(src, src_dtype, B, Hi, Wi, h, w, mode, ignore_label, out, flag, (hipStream_t)stream));
+  return 0;
+}
+
+int ldmseg_tensor_minmax(const float* x, size_t n, float* minmax, void* scratch, void* stream) {
+  g_err.clear();
+  static_assert(LDMSEG_MINMAX_SCRATCH_BYTES == 256 * 3 * sizeof(float), "header and kernel disagree on the partials");
+  if (!x || !minmax || !scratch) return fail(LDMSEG_E_ARG, "null argument");
+  if (n < 1) return fail(LDMSEG_E_ARG, "min / max of an empty tensor");
+  if (tensor_minmax_scratch_bytes() > (size_t)LDMSEG_MINMAX_SCRATCH_BYTES) return fail(LDMSEG_E_ARG, "scratch size mismatch");
+  TRY(launch_tensor_minmax(x, n, minmax, scratch, (hipStream_t)stream));
+  return 0;
+}
+
 // (re)allocate the sampler's eps / self-condition buffers; growth synchronises the device
 // time-embedding rows of every step of a sampling loop: rows[i] = time_emb_proj_all(silu(MLP(sinusoid(timesteps[i]))))
 // room for the time-embedding rows of `n_steps` steps (at least 64: 6 MB, so that a short warm-up call followed by a longer

@@ -458,6 +458,33 @@ int launch_pq_match(const int32_t* pred, const void* gt, int gt_format, int B, c
                     const int64_t* gt_offsets_host, const uint8_t* keep, int P, const int32_t* gt_counts_host, int Gpad,
                     const int32_t* slot_ids, const uint8_t* slot_crowd, const int64_t* slot_area, const int32_t* slot_meta,
                     int32_t* inter, int32_t* stats, double* match_iou, hipStream_t s);
+// the forward half of the training step behind the UNet output (loss.hip); arguments as ldmseg_diffusion_loss (include/ldmseg_hip.h)
+struct LossTail {
+  const float* pred;          // [B][C][HW] the UNet's output
+  const float* target;        // noise or latents; null: no loss (pred_latents only)
+  const float* noisy;         // read for pred_type 0 when pred_latents is written
+  const int64_t* t;           // [B]
+  const float* ac;            // alphas_cumprod [n_train]
+  int n_train;
+  const float* weights;       // [n_train] or null
+  const float* mask;          // [B][HW] or null
+  const uint8_t* paste;       // [B][C][HW] or null
+  const float* paste_src;
+  const float* minmax;        // device {min, max} or null
+  float* elem;                // element loss or null
+  float* pred_latents;        // or null
+  int C, HW;
+  int loss_type, pred_type;
+  int per;                    // filled by the launcher
+  double* partial;
+};
+size_t diffusion_loss_scratch_bytes(int B, int C, int HW);
+// ohem_k: 0 = plain mean; k >= 1 = mean of the k largest element losses (needs elem)
+int launch_diffusion_loss(const LossTail& t, int B, double ohem_k, float* sample_sums, float* mean, void* scratch, hipStream_t s);
+size_t tensor_minmax_scratch_bytes();
+int launch_tensor_minmax(const float* x, size_t n, float* out, void* scratch, hipStream_t s);
+int launch_loss_weight_mask(const void* src, int src_dtype, int B, int Hi, int Wi, int h, int w, int mode, int64_t ignore_label,
+                            float* out, int32_t* flag, hipStream_t s);
 int launch_bit_encode(const int64_t* ids, float* out, uint8_t* ignore, int B, int n, int HW, int64_t ignore_label,
                       float fill, float mul, float add, hipStream_t s);
 int launch_bit_decode(const float* x, int64_t* out, int B, int n, int HW, hipStream_t s);

@@ -14,6 +14,7 @@
 #include "attn_plan.h"
 #include "gn_plan.h"
 #include "kernels.h"
+#include "nearest_index.h"
 
 using namespace ldmseg;
 
@@ -687,6 +688,13 @@ int ldmseg_op_fastdiv(const int* n, int count, int d, int* q, void* stream) {
   const FastDiv f = fastdiv_make(d);
   hipLaunchKernelGGL(fastdiv_probe_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, count, f, q);
   return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// the nearest-resize source index of the loss-weight mask (nearest_index.h), evaluated on the host: CPU-suite test hook
+int ldmseg_op_nearest_index(int in_size, int out_size, int* src) {
+  if (!src || in_size < 1 || out_size < 1) return -2;
+  for (int i = 0; i < out_size; ++i) src[i] = nearest_src_index(i, in_size, out_size);
+  return 0;
 }
 }  // extern "C"
 namespace ldmseg {

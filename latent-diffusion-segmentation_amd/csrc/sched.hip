@@ -48,12 +48,8 @@ __global__ void add_noise_kernel(const float* x0, const float* noise, const int6
 #pragma clang fp contract(off)
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const size_t b = i / per;
-    int64_t tb = t[b];
-    tb = tb < 0 ? 0 : (tb >= n_train ? n_train - 1 : tb);
-    const float a = ac[tb];
-    const float sa = __fsqrt_rn(a), sb = __fsqrt_rn(__fsub_rn(1.0f, a));
-    if (!remove) out[i] = __fadd_rn(__fmul_rn(__fmul_rn(sa, scale), x0[i]), __fmul_rn(sb, noise[i]));
-    else out[i] = __fdiv_rn(__fsub_rn(x0[i], __fmul_rn(sb, noise[i])), __fmul_rn(sa, scale));
+    const NoiseCoef c = noise_coef(ac[clamp_timestep(t[b], n_train)], scale);
+    out[i] = remove ? remove_noise_elem(x0[i], noise[i], c) : add_noise_elem(x0[i], noise[i], c);
   }
 }
 

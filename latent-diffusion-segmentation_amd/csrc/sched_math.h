@@ -26,4 +26,33 @@ __device__ __forceinline__ void ddim_update(float mo, float x, const DdimCoef& c
   x0_out = x0;
 }
 
+// add_noise / remove_noise of one element (ddim_scheduler.py:155-216), shared by add_noise_kernel (sched.hip) and the loss
+// tail (loss.hip).  `a` is alphas_cumprod[t]; the two coefficients are formed once per sample, the element op per element.
+struct NoiseCoef {
+  float sa_scaled;   // sqrt(a) * scale
+  float sb;          // sqrt(1 - a)
+};
+
+__device__ __forceinline__ int64_t clamp_timestep(int64_t t, int n_train) {
+  return t < 0 ? 0 : (t >= n_train ? (int64_t)n_train - 1 : t);
+}
+
+__device__ __forceinline__ NoiseCoef noise_coef(float a, float scale) {
+#pragma clang fp contract(off)
+  NoiseCoef c;
+  c.sa_scaled = __fmul_rn(__fsqrt_rn(a), scale);
+  c.sb = __fsqrt_rn(__fsub_rn(1.0f, a));
+  return c;
+}
+
+__device__ __forceinline__ float add_noise_elem(float x0, float noise, const NoiseCoef& c) {
+#pragma clang fp contract(off)
+  return __fadd_rn(__fmul_rn(c.sa_scaled, x0), __fmul_rn(c.sb, noise));
+}
+
+__device__ __forceinline__ float remove_noise_elem(float noisy, float noise, const NoiseCoef& c) {
+#pragma clang fp contract(off)
+  return __fdiv_rn(__fsub_rn(noisy, __fmul_rn(c.sb, noise)), c.sa_scaled);
+}
+
 }  // namespace ldmseg

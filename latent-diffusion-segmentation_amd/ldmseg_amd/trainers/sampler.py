@@ -14,7 +14,11 @@ plus two things the reference does elsewhere or not at all:
     detectron2 ``comm.gather`` of PNGs (evaluations/panoptic_evaluation_agnostic.py:129-131);
   * ``sample_inpaint`` - the build-defined mask-inpainting sampler.
 
-Training, logging, datasets and PQ evaluation are out of scope.
+The forward half of the training step is in scope (the loss of a checkpoint needs no backward pass):
+``process_inputs`` (:677-765), ``compute_loss`` (:528-617), ``loss_fn`` (:495-526), ``predict_sample`` (:445-493) and
+``get_loss_weight_mask`` (:620-661) with the reference's signatures, plus the build-defined driver ``validation_loss``.
+Everything behind the UNet output runs in csrc/loss.hip (ldmseg_diffusion_loss / ldmseg_loss_weight_mask /
+ldmseg_tensor_minmax) without a host synchronisation.  Backward, optimiser, EMA, logging and data loading stay out of scope.
 """
 import ctypes as C
 from typing import List, Optional
@@ -23,12 +27,40 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..utils import OutputDict
+
+LOSS_TYPES = {"l1": 0, "l2": 1, "smooth_l1": 2}                  # LDMSEG_LOSS_*
+MASK_MODES = {"ignore": 0, "padding": 1, "counts": 2}            # LDMSEG_MASK_*
+
+
+class ModelInputs(OutputDict):
+    """What `process_inputs` returns (trainers_ldm_cond.py:40-50): text, rgb_images, latents, rgb_latents,
+    encoder_hidden_states, original_latents, loss_mask, inpainting_masks, dropout."""
 
 
 class TrainerDiffusion(object):
     def __init__(self, vae_semseg, unet, noise_scheduler, self_condition: Optional[bool] = None,
                  device=None, latent_size: int = 64, vae_image=None, image_descriptor_model=None, textencoder=None,
-                 tokenizer=None):
+                 tokenizer=None, training_loss_type: str = 'l2', rgb_noise_level: int = 0, cond_noise_level: int = 0,
+                 ohem_ratio: float = 1.0, type_mask: str = 'ignore', prob_train_on_pred: float = 0.0,
+                 prob_inpainting: float = 0.0, min_noise_level: int = 0, sample_posterior: bool = False,
+                 ignore_label: int = 0):
+        # the loss side of the training step (base.yaml's defaults; trainers_ldm_cond.py:129-160)
+        self.training_loss_type = training_loss_type
+        self.rgb_noise_level = rgb_noise_level
+        self.cond_noise_level = cond_noise_level
+        self.ohem_ratio = ohem_ratio
+        self.type_mask = type_mask
+        self.prob_train_on_pred = prob_train_on_pred
+        self.prob_inpainting = prob_inpainting
+        self.min_noise_level = min_noise_level
+        self.sample_posterior = sample_posterior
+        self.sample_posterior_rgb = False
+        self.rgb_size = None
+        self.dropout = 0.
+        self.ignore_label = ignore_label
+        self.loss_mask_flag = None            # device int32 [1] of the last get_loss_weight_mask call (bit 0: an id outside [0, 256))
+        self._loss_tables = {}
         self.vae_image = vae_image            # RGB encoder (trainers_ldm_cond.py:58,111); optional here
         self.vae_semseg = vae_semseg
         self.unet_model = unet
@@ -522,3 +554,334 @@ class TrainerDiffusion(object):
             latents = F.interpolate(latents, size=size, mode='bilinear', align_corners=False)
             mean = F.interpolate(mean, size=size, mode='bilinear', align_corners=False)
         return latents * scaling_factor, mean * scaling_factor
+
+    # ------------------------------------------------------------------ denoising loss (forward half of the training step)
+    def _scheduler_tables(self, device):
+        """(alphas_cumprod, weights or None) of the scheduler as fp32 device tensors, cached per device and table."""
+        sch = self.noise_scheduler
+        w = getattr(sch, "weights", None)
+        key = (str(device), id(sch.alphas_cumprod), id(w))
+        if key not in self._loss_tables:
+            ac = sch.alphas_cumprod.to(device=device, dtype=torch.float32).contiguous()
+            wd = w.to(device=device, dtype=torch.float32).contiguous() if w is not None else None
+            self._loss_tables = {key: (ac, wd, sch.alphas_cumprod, w)}        # (the host tables are kept so that the ids stay theirs)
+        return self._loss_tables[key][:2]
+
+    def _loss_type(self):
+        if self.training_loss_type not in LOSS_TYPES:
+            raise ValueError('Unknown loss type: {}'.format(self.training_loss_type))
+        return LOSS_TYPES[self.training_loss_type]
+
+    def _loss_tail(self, prediction, timesteps, target=None, noisy=None, loss_mask=None, paste_mask=None, paste_src=None,
+                   minmax=None, prediction_type='sample', use_weights=False, ohem_ratio=1.0, want_pred=False, want_elem=False):
+        """ldmseg_diffusion_loss on [B,C,...] tensors; returns (mean [1] or None, elem or None, pred_latents or None,
+        sample_sums [B] or None).  Nothing is read back."""
+        pred = _lib.require_cuda_f32(prediction, "prediction")
+        dev = pred.device
+        B, Cn = pred.shape[0], pred.shape[1]
+        HW = pred.numel() // (B * Cn)
+
+        def same(t, name):
+            if t is None:
+                return None
+            t = _lib.require_cuda_f32(t.to(dev) if isinstance(t, torch.Tensor) else t, name)
+            if t.shape != pred.shape:
+                raise ValueError(f"{name} must have the prediction's shape {tuple(pred.shape)}, got {tuple(t.shape)}")
+            return t
+        target, noisy, paste_src = same(target, "target"), same(noisy, "noisy_latents"), same(paste_src, "original_latents")
+        if loss_mask is not None:
+            loss_mask = _lib.require_cuda_f32(loss_mask.to(dev), "loss_mask")
+            if loss_mask.numel() != B * HW or loss_mask.shape[0] != B:
+                raise ValueError(f"loss_mask must be [B,H,W] = [{B}, ...] with {HW} pixels per sample, got {tuple(loss_mask.shape)}")
+        if paste_mask is not None:
+            if paste_mask.dtype != torch.bool or paste_mask.shape != pred.shape:
+                raise ValueError("inpainting_masks must be a bool mask of the latents' shape "
+                                 f"{tuple(pred.shape)} (True = paste the original latents)")
+            if paste_src is None:
+                raise ValueError("inpainting_masks needs original_latents")
+            paste_mask = paste_mask.to(dev).contiguous()
+        k = None
+        if target is not None and ohem_ratio < 1.:
+            k = int(ohem_ratio * pred.numel())
+            if k == 0:
+                raise ValueError(f"ohem_ratio {ohem_ratio} selects none of the {pred.numel()} elements")
+            want_elem = True
+        ac, wd = self._scheduler_tables(dev)
+        if timesteps is None:                                 # no timestep-dependent term is asked for (loss_fn): any valid index
+            t = torch.zeros(B, dtype=torch.int64, device=dev)
+        else:
+            t = torch.as_tensor(timesteps).to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+        if t.numel() == 1 and B > 1:
+            t = t.expand(B).contiguous()
+        if t.numel() != B:
+            raise ValueError("timesteps must hold one entry per sample")
+        lib = _lib.lib()
+        mean = torch.empty(1, device=dev) if target is not None else None
+        sums = torch.empty(B, device=dev) if target is not None else None
+        elem = torch.empty_like(pred) if (want_elem and target is not None) else None
+        out = torch.empty_like(pred) if want_pred else None
+        scratch = torch.empty(int(lib.ldmseg_diffusion_loss_scratch_bytes(B, Cn, HW)), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.ldmseg_diffusion_loss(
+                _lib.ptr(pred), _lib.ptr(target), _lib.ptr(noisy), _lib.ptr(t), _lib.ptr(ac), int(ac.numel()),
+                _lib.ptr(wd if use_weights else None), _lib.ptr(loss_mask), _lib.ptr(paste_mask),
+                _lib.ptr(paste_src if paste_mask is not None else None), _lib.ptr(minmax), self._loss_type(),
+                _lib.PRED[prediction_type], float(ohem_ratio if k is not None else 1.0), B, Cn, HW, _lib.ptr(elem), _lib.ptr(out),
+                _lib.ptr(mean), _lib.ptr(sums), _lib.ptr(scratch), _lib.stream_ptr(dev)), "ldmseg_diffusion_loss")
+        return mean, elem, out, sums
+
+    def loss_fn(self, x: torch.Tensor, y: torch.Tensor, reduction: str = 'none', mask: Optional[torch.Tensor] = None):
+        """:495-526 - l1 / l2 / smooth_l1 element loss of x and y [B,C,...], times mask[:, None] if given, on the device.
+        reduction 'none' (what compute_loss uses) returns the element losses, 'mean' / 'sum' the reduced scalar (a mask
+        together with a reduction is refused: the reference would multiply the scalar by the mask)."""
+        self._loss_type()
+        if reduction not in ('none', 'mean', 'sum'):
+            raise ValueError(f"unknown reduction {reduction!r}")
+        if reduction != 'none' and mask is not None:
+            raise ValueError("a mask needs reduction='none'")
+        mean, elem, _, sums = self._loss_tail(x, None, target=y, loss_mask=mask, want_elem=reduction == 'none')
+        if reduction == 'mean':
+            return mean[0]
+        if reduction == 'sum':
+            return sums.double().sum().float()                # the kernel's per-sample sums (fp64 sums rounded once), added in fp64
+        return elem.view(x.shape)
+
+    def _predict(self, noisy_latents, rgb_latents, condition, timesteps, encoder_hidden_states, timesteps_img=None):
+        """The UNet on [noisy | rgb | condition]: through forward_parts (nothing concatenated in torch) when the handle takes the
+        parts; with a context or an image timestep the concatenated input goes to forward (forward_ctx / forward_img)."""
+        u = self.unet_model
+        if (encoder_hidden_states is None and timesteps_img is None and hasattr(u, "forward_parts")
+                and not getattr(u, "cross_attention", False) and rgb_latents is not None):
+            return u.forward_parts(noisy_latents, rgb_latents, condition, timesteps).sample
+        parts = [noisy_latents] + ([rgb_latents] if rgb_latents is not None else []) + ([condition] if condition is not None else [])
+        inputs = torch.cat(parts, dim=1) if len(parts) > 1 else noisy_latents
+        if timesteps_img is not None:
+            return u(inputs, timesteps, encoder_hidden_states, timestep_img=timesteps_img).sample
+        return u(inputs, timesteps, encoder_hidden_states).sample
+
+    @staticmethod
+    def _gen(generator, device):
+        """`generator` if it lives on `device`'s kind of device, else None (the default generator of that device)."""
+        if generator is not None and generator.device.type == torch.device(device).type:
+            return generator
+        return None
+
+    @torch.no_grad()
+    def compute_loss(self, noise: torch.Tensor, timesteps: torch.Tensor, noisy_latents: torch.Tensor,
+                     rgb_latents: Optional[torch.Tensor], encoder_hidden_states: Optional[torch.Tensor],
+                     loss_mask: Optional[torch.Tensor], latents: Optional[torch.Tensor] = None,
+                     original_latents: Optional[torch.Tensor] = None, inpainting_masks: Optional[torch.Tensor] = None,
+                     condition: Optional[torch.Tensor] = None, generator=None):
+        """:528-617 without the graph: (loss, noisy_latents, pred_latents, timesteps), all on the device, nothing read back.
+        One UNet forward, then ONE loss-tail launch (+ a finishing launch; + the radix select when ohem_ratio < 1) computes the
+        element loss, its mask and timestep weight, the mean and pred_latents.  `inpainting_masks`: bool [B,4,H,W], True = paste
+        original_latents (the only form the reference's `pred[m] = orig[m]` accepts).  `generator=` (extension) seeds the RGB /
+        condition noise draws.  ohem_ratio * numel < 1 raises ValueError (the reference would return the mean of an empty
+        tensor, NaN)."""
+        assert rgb_latents is not None
+        sch = self.noise_scheduler
+        noisy = _lib.require_cuda_f32(noisy_latents, "noisy_latents")
+        dev = noisy.device
+        rgb = _lib.require_cuda_f32(rgb_latents, "rgb_latents")
+        B = noisy.shape[0]
+        gen = self._gen(generator, dev)
+        if self.self_condition and condition is None:
+            condition = torch.zeros_like(noisy)
+        timesteps_img = None
+        if self.rgb_noise_level > 0:                                                          # :568-572
+            rgb_noise = torch.randn(rgb.shape, device=dev, dtype=rgb.dtype, generator=gen)
+            timesteps_img = torch.randint(0, self.rgb_noise_level, (B,), device=dev, dtype=torch.long, generator=gen)
+            rgb = sch.add_noise(rgb, rgb_noise, timesteps_img)
+        if condition is not None and self.cond_noise_level > 0:                               # :577-581
+            condition = _lib.require_cuda_f32(condition, "condition")
+            cond_noise = torch.randn(condition.shape, device=dev, dtype=condition.dtype, generator=gen)
+            timesteps_cond = torch.randint(0, self.cond_noise_level, (B,), device=dev, dtype=torch.long, generator=gen)
+            condition = sch.add_noise(condition, cond_noise, timesteps_cond)
+        if sch.prediction_type == "epsilon":
+            target = noise
+        elif sch.prediction_type == "sample":
+            target = original_latents if original_latents is not None else latents
+        else:
+            raise ValueError(f"Unknown prediction type: {sch.prediction_type}")
+        self._loss_type()
+        timesteps = torch.as_tensor(timesteps).to(device=dev, dtype=torch.long)
+        prediction = self._predict(noisy, rgb, condition, timesteps, encoder_hidden_states, timesteps_img)
+        mean, _, pred_latents, sums = self._loss_tail(
+            prediction, timesteps, target=target, noisy=noisy, loss_mask=loss_mask, paste_mask=inpainting_masks,
+            paste_src=original_latents, prediction_type=sch.prediction_type, use_weights=hasattr(sch, 'weights'),
+            ohem_ratio=self.ohem_ratio, want_pred=True)
+        self.last_sample_loss_sums = sums
+        return mean[0], noisy, pred_latents, timesteps
+
+    def tensor_minmax(self, x: torch.Tensor) -> torch.Tensor:
+        """Device pair [x.min(), x.max()] (ldmseg_tensor_minmax; what the loss tail's clamp reads through a pointer)."""
+        x = _lib.require_cuda_f32(x, "x")
+        out = torch.empty(2, device=x.device)
+        scratch = torch.empty(3072, dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().ldmseg_tensor_minmax(_lib.ptr(x), x.numel(), _lib.ptr(out), _lib.ptr(scratch),
+                                                       _lib.stream_ptr(x.device)), "ldmseg_tensor_minmax")
+        return out
+
+    @torch.no_grad()
+    def predict_sample(self, latents: torch.Tensor, rgb_latents: Optional[torch.Tensor] = None,
+                       encoder_hidden_states: Optional[torch.Tensor] = None, tmax: Optional[int] = None, generator=None,
+                       noise: Optional[torch.Tensor] = None, timesteps: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """:445-493 - one-step prediction of the clean latents from a random noise level below `tmax`, clamped to the range
+        of `latents`.  The clamp bounds never leave the device: ldmseg_tensor_minmax writes the pair the loss tail reads.
+        `generator=`, `noise=` and `timesteps=` (extensions) make the draws reproducible."""
+        sch = self.noise_scheduler
+        if sch.prediction_type not in ('epsilon', 'sample'):
+            raise ValueError('Unknown prediction type: {}'.format(sch.prediction_type))
+        if tmax is None:
+            tmax = sch.num_train_timesteps
+        lat = _lib.require_cuda_f32(latents, "latents")
+        dev = lat.device
+        gen = self._gen(generator, dev)
+        if noise is None:
+            noise = torch.randn(lat.shape, device=dev, dtype=lat.dtype, generator=gen)
+        if timesteps is None:
+            timesteps = torch.randint(0, tmax, (lat.shape[0],), device=dev, dtype=torch.long, generator=gen)
+        timesteps = torch.as_tensor(timesteps).to(device=dev, dtype=torch.long)
+        noisy = sch.add_noise(lat, noise.to(dev), timesteps)
+        prediction = self._predict(noisy, rgb_latents, None, timesteps, encoder_hidden_states)
+        _, _, pred_latents, _ = self._loss_tail(prediction, timesteps, noisy=noisy, minmax=self.tensor_minmax(lat),
+                                                prediction_type=sch.prediction_type, want_pred=True)
+        return pred_latents
+
+    @torch.no_grad()
+    def get_loss_weight_mask(self, targets: torch.Tensor, ignore_label: int = 0, mode: str = 'nearest', size=(64, 64),
+                             device=None, type_mask: str = 'ignore', padding_mask: Optional[torch.Tensor] = None):
+        """:620-661 - the loss weight mask [B,h,w] fp32 in one launch: the nearest resize picks F.interpolate's source pixel;
+        'ignore': target != ignore_label (the reference reads its dataset's ignore label there; this takes the argument),
+        'padding': the resized padding mask, 'counts': 1 / (pixels of the id in the resized map), 0 on ignore_label, from a
+        256-entry table per image in LDS instead of the torch.unique loop.  Any other type_mask: None, as in the reference.
+        'counts' serves ids in [0, 256) (the bit codec's range): another id gets the weight NaN and sets `self.loss_mask_flag`
+        (device int32 [1], bit 0), which stays on the device for the caller to read together with the loss."""
+        if type_mask not in MASK_MODES:
+            return None
+        if mode != 'nearest':
+            raise ValueError("only mode='nearest' is served")
+        device = torch.device(device) if device is not None else self.device
+        src = padding_mask if type_mask == 'padding' else targets
+        if src is None:
+            raise ValueError(f"type_mask={type_mask!r} needs its input map")
+        src = src.to(device)
+        if src.dim() != 3:
+            raise ValueError("expected a [B,H,W] map")
+        if src.dtype in (torch.bool, torch.uint8):
+            code, src = 1, src.contiguous().view(torch.uint8) if src.dtype == torch.bool else src.contiguous()
+        elif src.dtype.is_floating_point:
+            code, src = 2, src.float().contiguous()
+        else:
+            code, src = 0, src.long().contiguous()
+        B, Hi, Wi = src.shape
+        h, w = (int(size[0]), int(size[1])) if isinstance(size, (tuple, list)) else (int(size), int(size))
+        out = torch.empty((B, h, w), dtype=torch.float32, device=device)
+        flag = torch.empty(1, dtype=torch.int32, device=device)
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().ldmseg_loss_weight_mask(_lib.ptr(src), code, B, Hi, Wi, h, w, MASK_MODES[type_mask],
+                                                          int(ignore_label), _lib.ptr(out), _lib.ptr(flag),
+                                                          _lib.stream_ptr(device)), "ldmseg_loss_weight_mask")
+        self.loss_mask_flag = flag
+        return out
+
+    @torch.no_grad()
+    def process_inputs(self, data: dict, generator=None) -> ModelInputs:
+        """:677-765 - a batch of the training loader ({'image', 'image_semseg', 'text', 'semseg', 'mask'} + 'inpainting_mask'
+        / 'tokens' where used) -> ModelInputs.  `generator=` (extension) seeds the per-batch Bernoulli draws (made on the host
+        like the reference's) when it is a CPU generator, and the device draws below it otherwise.
+
+        With `prob_inpainting > 0` the returned `inpainting_masks` is, as in the reference, the resized fp32 map [B,h,w]
+        (zeroed for the samples the draw left out).  `compute_loss` takes a bool [B,4,H,W] paste mask only - the one form the
+        reference's `pred[m] = orig[m]` accepts - so the two cannot be chained on that path without the caller turning the map
+        into such a mask (e.g. `(m > 0)[:, None].expand(-1, 4, -1, -1)`); the reference has the same gap."""
+        dev = self.device
+        rgb_images = data['image'].to(dev, non_blocking=True)
+        bit_maps = data['image_semseg'].to(dev, non_blocking=True)
+        B = bit_maps.shape[0]
+        gen_dev, gen_cpu = self._gen(generator, dev), self._gen(generator, 'cpu')
+
+        # both VAEs: segmentation bit maps -> latents (+ their posterior mean, the 'original' latents), RGB -> rgb_latents
+        seg, img = self.vae_semseg, self.vae_image
+        latents, original = self.encode_inputs(bit_maps, encode_func=seg.encode, scaling_factor=seg.scaling_factor,
+                                               sample_posterior=self.sample_posterior, generator=gen_dev)
+        rgb_latents = self.encode_inputs(rgb_images, encode_func=img.encode if img is not None else None,
+                                         scaling_factor=img.scaling_factor if img is not None else None,
+                                         sample_posterior=self.sample_posterior_rgb, resize=self.rgb_size, generator=gen_dev)[0]
+        latents, original, rgb_latents = latents.float(), original.float(), rgb_latents.float()
+        fields = ModelInputs()
+        fields['text'] = data.get('text')
+        fields['rgb_images'] = rgb_images
+
+        # inpainting (:712-717): one Bernoulli draw per sample on the host; the nearest resize is the mask kernel's 'padding' mode
+        paste_map = None
+        if self.prob_inpainting > 0.:
+            drawn = torch.rand(B, generator=gen_cpu) < self.prob_inpainting
+            paste_map = self.get_loss_weight_mask(None, size=tuple(latents.shape[-2:]), device=dev, type_mask='padding',
+                                                  padding_mask=data['inpainting_mask'])
+            paste_map[~drawn] = 0.
+
+        # conditioning (:721-733): image descriptors [B,S,D], or the text encoder's embeddings of the batch's tokens
+        context = None
+        desc = self.image_descriptor_model
+        if desc is not None:
+            if hasattr(desc, "describe"):
+                context = desc.describe(rgb_images).to(torch.float32)
+            else:
+                feat = desc(self.norm_resize_images(rgb_images).to(self.weight_dtype))['last_feat']
+                context = feat.flatten(2).transpose(1, 2).to(torch.float32)
+        if self.textencoder is not None:
+            context = self.textencoder(data['tokens'].to(dev, non_blocking=True))[0].to(torch.float32)
+
+        # train on the model's own one-step prediction (:736-742): the drawn samples' latents are replaced, tmax = T // 2
+        if self.prob_train_on_pred > 0.:
+            drawn = torch.rand(B, generator=gen_cpu) < self.prob_train_on_pred
+            if bool(drawn.any()):
+                latents[drawn] = self.predict_sample(latents[drawn], rgb_latents[drawn], None if context is None else context[drawn],
+                                                     tmax=self.noise_scheduler.num_train_timesteps // 2, generator=gen_dev)
+
+        fields['latents'] = latents
+        fields['rgb_latents'] = rgb_latents
+        fields['encoder_hidden_states'] = context
+        fields['original_latents'] = original
+        fields['loss_mask'] = self.get_loss_weight_mask(data.get('semseg'), ignore_label=self.ignore_label, device=dev,
+                                                        size=(self.latent_size, self.latent_size), type_mask=self.type_mask,
+                                                        padding_mask=data.get('mask'))
+        fields['inpainting_masks'] = paste_map
+        fields['dropout'] = self.dropout if self.dropout > 0 else None
+        return fields
+
+    @torch.no_grad()
+    def validation_loss(self, dataloader, timesteps=tuple(range(50, 1000, 100)), seed: Optional[int] = None,
+                        max_iter: Optional[int] = None):
+        """The denoising loss of a checkpoint over a loader, per timestep.  NOT in the reference (its loss is only ever logged
+        from inside the training loop): for every batch `process_inputs`, then for every t of the grid all samples are noised to
+        t with the `draw_noise(seed)` draw (the same for every batch, like `sample`), a self-conditioned handle runs the no-grad
+        pre-pass of train_single_epoch (:822-831), and `compute_loss` gives the batch's loss.  The sums stay on the device; one
+        read at the end returns {'loss': mean over the grid, 'per_timestep': {t: image-weighted mean loss}, 'images': n}."""
+        sch = self.noise_scheduler
+        grid = [int(t) for t in timesteps]
+        sums = torch.zeros(len(grid), dtype=torch.float64, device=self.device)
+        images = 0
+        for batch_idx, data in enumerate(dataloader):
+            if max_iter is not None and batch_idx >= max_iter:
+                break
+            mi = self.process_inputs(data)
+            B, L = mi.latents.shape[0], mi.latents.shape[-1]
+            noise = self.draw_noise(B, L, seed).to(self.device)
+            for j, t in enumerate(grid):
+                tt = torch.full((B,), t, dtype=torch.long, device=self.device)
+                noisy = sch.add_noise(mi.latents, noise, tt)
+                condition = None
+                if self.self_condition:
+                    pred = self._predict(noisy, mi.rgb_latents, torch.zeros_like(noisy), tt, mi.encoder_hidden_states)
+                    condition = sch.remove_noise(noisy, pred, tt)
+                loss, _, _, _ = self.compute_loss(noise, tt, noisy, mi.rgb_latents, mi.encoder_hidden_states, mi.loss_mask,
+                                                  latents=mi.latents, original_latents=mi.original_latents, condition=condition)
+                sums[j] += loss.double() * B
+            images += B
+        if images == 0:
+            raise ValueError("validation_loss: the loader gave no batch")
+        per = (sums / images).cpu().tolist()
+        return {'loss': float(np.mean(per)), 'per_timestep': {t: v for t, v in zip(grid, per)}, 'images': images}

@@ -6,6 +6,7 @@ detectron2 and cannot run here).
     python tools/main_ldm_eval.py --images DIR [--panoptic DIR] [--ldm ldmseg.pt --ae ae.pt --vae-image vae.pt]
                                   [--size 512] [--steps 50] [--batch 8] [--dtype bf16]
                                   [--image-descriptors {remove,clip_image,clip_image_proj}] [--clip-vision clip.pt]
+                                  [--val-loss]
 
 It assembles what main_worker assembles (image VAE encoder, seg-VAE, UNet with the 12-channel conv_in and cross-attention
 removed, DDIM scheduler with base.yaml's noise_scheduler_kwargs), then runs `TrainerDiffusion.compute_pq`:
@@ -15,9 +16,15 @@ One process per GPU under torch.distributed.run shards the images over ranks (Di
 trainers_ldm_cond.py:245); the evaluator gathers the predictions on rank 0.
 Without checkpoints (none ship with this repo: the released ones are 3.3 GB downloads) deterministic random weights
 of the right architecture are used - the pipeline then runs end to end but the PQ is meaningless.
+
+`--val-loss` (needs `--panoptic`) scores the checkpoint by its denoising loss instead: the panoptic PNGs become 7-plane bit maps
+the way tools/main_ae_eval.py makes them (segment ids -> random distinct labels -> bit codec), resized like the RGB image, and
+`TrainerDiffusion.validation_loss` prints {'loss', 'per_timestep', 'images'} as one JSON line: one UNet forward per image and
+timestep.  One process only (the sums are not reduced across ranks).
 """
 import argparse
 import glob
+import json
 import os
 import sys
 
@@ -91,6 +98,25 @@ def batches(files, size, batch, panoptic_dir):
         yield {"image": torch.stack(imgs), "mask": torch.ones(len(imgs), size, size, dtype=torch.bool), "meta": meta}
 
 
+def val_batches(files, size, batch, panoptic_dir, device, seed=1):
+    """Batches of the training loader's shape for `process_inputs`: the RGB batch of `batches` plus 'image_semseg' [B,7,S,S] bit
+    maps, 'semseg' [B,S,S] int64 labels and the all-ones 'mask'.  The label map is resized like the image (nearest)."""
+    from PIL import Image
+    from main_ae_eval import IGNORE_LABEL, remap_labels            # (tools/ is the script directory)
+    from ldmseg_amd.data.bitcodec import encode_bitmap
+    from ldmseg_amd.evaluations import rgb2id
+    for i, data in enumerate(batches(files, size, batch, panoptic_dir)):
+        labs = []
+        for j, m in enumerate(data["meta"]):
+            ids = rgb2id(np.asarray(Image.open(os.path.join(panoptic_dir, m["image_id"] + ".png")).convert("RGB")))
+            lab = remap_labels(ids, np.random.RandomState(seed + i * batch + j))
+            small = Image.fromarray(lab.astype(np.uint8)).resize((size, size), resample=getattr(Image, "Resampling", Image).NEAREST)
+            labs.append(torch.from_numpy(np.asarray(small).astype(np.int64)))
+        semseg = torch.stack(labs)
+        bits, _ = encode_bitmap(semseg.to(device), n=7, fill_value=0.5, ignore_label=IGNORE_LABEL)
+        yield dict(data, image_semseg=bits, semseg=semseg, text=[""] * len(labs))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", required=True, help="folder of RGB images (e.g. data/examples/coco/rgb_images)")
@@ -108,7 +134,13 @@ def main():
                          "generated weights without it")
     ap.add_argument("--device-pq", action="store_true",
                     help="score PQ on the GPU (PanopticEvaluatorAgnostic.process_device): no map is copied to the host")
+    ap.add_argument("--val-loss", action="store_true",
+                    help="print the denoising loss per timestep (TrainerDiffusion.validation_loss) instead of PQ; needs --panoptic")
     args = ap.parse_args()
+    if args.val_loss and not args.panoptic:
+        ap.error("--val-loss needs --panoptic (the ground-truth maps are the loss's targets)")
+    if args.val_loss and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        ap.error("--val-loss runs on one process: the per-timestep sums are not reduced across ranks")
     import torch.distributed as dist
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -130,7 +162,10 @@ def main():
             iid = os.path.splitext(os.path.basename(f))[0]
             gt_maps[iid] = rgb2id(np.asarray(Image.open(f).convert("RGB")))
             gt_anns.append(gt_from_png(gt_maps[iid], iid, os.path.basename(f)))
-    if gt_anns is None:                                                     # no ground truth: predictions only
+    if args.val_loss:
+        out = trainer.validation_loss(val_batches(files, args.size, args.batch, args.panoptic, device), seed=args.seed)
+        print(json.dumps(out))                                              # one JSON line (per_timestep keyed by str(t))
+    elif gt_anns is None:                                                   # no ground truth: predictions only
         from ldmseg_amd.data.transforms import load_rgb
         res = []
         for data in batches(files, args.size, args.batch, None):
