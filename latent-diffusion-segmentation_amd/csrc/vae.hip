@@ -1,0 +1,517 @@
+// The two VAEs of libldmseg_hip.so with their C ABI (include/ldmseg_hip.h): the seg-VAE (encoder, decoder, the fused evaluation
+// tails and the reconstruct chain) and the encoder of SD-1.x's image VAE (AutoencoderKL).  The runtime underneath: runtime.h.
+#include <cmath>
+
+#include "runtime.h"
+
+#pragma clang diagnostic ignored "-Wc++20-designator"      // ConvOpt and its like are filled by field name
+
+using namespace ldmseg;
+using namespace ldmseg::rt;
+
+// =================================================================== seg-VAE
+struct ldmseg_vae : HandleBase {
+  ldmseg_vae_cfg cfg{};
+  // encoder
+  ConvW enc[10];          // encoder.{0,2,3,5,6,8,9,11,15} in order (9 used)
+  NormW enc_gn;
+  int enc_ch[5]{};        // storage channel counts
+  // decoder
+  ConvW dec_in, dec_out;
+  ConvW convt[4];
+  NormW ln[4], dec_gn;
+};
+
+// =================================================================== image VAE encoder (AutoencoderKL, SD-1.x)
+struct ldmseg_vae_image : HandleBase {
+  ldmseg_vae_image_cfg cfg{};
+  ConvW conv_in, downs[3], conv_out, quant;
+  ResnetW down[4][2], mid[2];
+  NormW attn_gn, norm_out;
+  ConvW q, k, proj;
+  void* wv = nullptr;       // value projection [512][512], used as the X operand of the V^T GEMM
+  float* bv = nullptr;
+};
+
+namespace {
+
+inline int cstore(int c, int dt) { return (int)rup(c, bke(dt)); }
+
+int vae_build(ldmseg_vae* v, const WeightMap& wm) {
+  Builder b(*v, wm);
+  hipStream_t s = b.s;
+  const ldmseg_vae_cfg& c = v->cfg;
+  const int dt = v->dt;
+  if (c.in_channels > bke(dt) || c.latent_channels > bke(dt)) return fail(LDMSEG_E_ARG, "too many boundary channels");
+  if (c.int_channels % 64 || c.upscale_channels % 64 || c.num_upscalers < 1 || c.num_upscalers > 4)
+    return fail(LDMSEG_E_ARG, "unsupported seg-VAE configuration");
+  // ---- encoder (vae.py:174-244) ----
+  const int* boc = c.block_out_channels;
+  int k = 0;
+  TRY(b.conv("encoder.0", boc[0], c.in_channels, 3, bke(dt), &v->enc[k++], true, cstore(boc[0], dt)));
+  int idx = 2;
+  for (int i = 0; i < 3; ++i) {
+    TRY(b.conv("encoder." + std::to_string(idx), boc[i], boc[i], 3, cstore(boc[i], dt), &v->enc[k++], true, cstore(boc[i], dt)));
+    TRY(b.conv("encoder." + std::to_string(idx + 1), boc[i + 1], boc[i], 3, cstore(boc[i], dt), &v->enc[k++], true,
+               cstore(boc[i + 1], dt)));
+    idx += 3;
+  }
+  TRY(b.conv("encoder." + std::to_string(idx), c.int_channels, boc[3], 3, cstore(boc[3], dt), &v->enc[k++]));
+  TRY(b.norm("encoder." + std::to_string(idx + 2), c.int_channels, &v->enc_gn));
+  TRY(b.conv("encoder." + std::to_string(idx + 4), c.latent_channels * c.num_latents, c.int_channels, 3, c.int_channels,
+             &v->enc[k++]));
+  // ---- decoder (vae.py:123-172) ----
+  TRY(b.conv("decoder.0", c.int_channels, c.latent_channels, 3, bke(dt), &v->dec_in));
+  idx = 2;
+  int cin = c.int_channels;
+  for (int i = 0; i < c.num_upscalers; ++i) {
+    ConvW& t = v->convt[i];
+    const int Co = c.upscale_channels;
+    const float *w, *bias;
+    TRY(wm.get("decoder." + std::to_string(idx) + ".weight", (int64_t)cin * Co * 4, &w));
+    TRY(wm.get("decoder." + std::to_string(idx) + ".bias", Co, &bias));
+    t.N = 4 * Co; t.n_valid = 4 * Co; t.cin_pad = cin; t.taps = 1; t.cout = Co;
+    TRY(v->arena.alloc(&t.w, (size_t)4 * Co * cin * esize(dt)));
+    TRY(launch_repack_convt2(w, t.w, cin, Co, dt, s));
+    b.weights(t.w, (size_t)4 * Co * cin);
+    void* pb;
+    TRY(v->arena.alloc(&pb, (size_t)4 * Co * sizeof(float)));
+    for (int q = 0; q < 4; ++q)
+      HIP_TRY(hipMemcpyAsync((float*)pb + q * Co, bias, Co * sizeof(float), hipMemcpyDeviceToDevice, s));
+    t.bias = (float*)pb;
+    b.nparams += (int64_t)cin * Co * 4 + Co;
+    TRY(b.norm("decoder." + std::to_string(idx + 1), Co, &v->ln[i]));
+    cin = Co;
+    idx += 3;
+  }
+  TRY(b.norm("decoder." + std::to_string(idx), cin, &v->dec_gn));
+  TRY(b.conv("decoder." + std::to_string(idx + 2), c.out_channels, cin, 3, cin, &v->dec_out));
+  return b.finish(*v);
+}
+
+struct ArgmaxOut { int64_t* ids = nullptr; float* prob = nullptr; float mask_th = -1.f; int64_t ignore_label = 0; };
+// fused evaluation tail (ldmseg_vae_decode_panoptic): host-side per-image geometry + device outputs
+struct PanopticOut {
+  int in_h = 0, in_w = 0;
+  const int32_t* boxes = nullptr; const int32_t* sizes = nullptr; const int64_t* offsets = nullptr;
+  int threshold_output = 0, threshold_mode = 0;
+  float mask_th = 0.5f; int count_th = 0; double overlap_th = 0.0; int64_t ignore_label = 0;
+  int32_t* labels = nullptr; int32_t* panoptic = nullptr; uint8_t* keep = nullptr; int32_t* counts = nullptr; int32_t* mask_counts = nullptr;
+  int mask_rule = 0;       // overlap mask: 0 sigmoid(logit) >= mask_th (trainers_ldm_cond.py:1288,1301), 1 logit >= mask_th (trainers_ae.py:656)
+};
+// fused mIoU tail (ldmseg_vae_decode_semseg / ldmseg_vae_reconstruct_semseg): trainers_ae.py:754-761 + SemsegMeter.update
+struct SemsegOut {
+  int out_h = 0, out_w = 0;
+  float mask_th = -1.f; int64_t ignore_label = 0;
+  const int64_t* targets = nullptr; int64_t ignore_index = 255; int K = 0;
+  int64_t* preds = nullptr; int64_t* counts = nullptr;
+};
+
+// What becomes of the decoder's logits: fp32 NCHW at 4L straight from the last conv | bilinear x2 -> fp32 NCHW | x2 + argmax + max-softmax |
+// resampling + panoptic post-processing | align_corners=True resampling + argmax / threshold + meter counters; and that tail's outputs
+struct DecodeTail {
+  enum Kind { LOGITS, LOGITS_X2, ARGMAX, PANOPTIC, SEMSEG } kind = LOGITS;
+  float* logits = nullptr;
+  const ArgmaxOut* am = nullptr;
+  const PanopticOut* po = nullptr;
+  const SemsegOut* so = nullptr;
+};
+
+// the decoder on an executor that is already set up (the reconstruct chain runs encoder and decoder on ONE workspace pass)
+int vae_decode_body(Exec& ex, ldmseg_vae* v, const float* z, float z_scale, int L, const DecodeTail& tail) {
+  const int B = ex.B;
+  hipStream_t s = ex.s;
+  const int dt = v->dt;
+  const ldmseg_vae_cfg& c = v->cfg;
+  Act zin = ex.new_act(bke(dt), L, L, true);
+  TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, no_label, [&] { return launch_pack_nchw(z, zin.p, B, c.latent_channels, L * L, bke(dt), z_scale, 0.f, dt, s); }));
+  Act h;
+  TRY(ex.conv(v->dec_in, zin, &h));
+  for (int i = 0; i < c.num_upscalers; ++i) {
+    const ConvW& t = v->convt[i];
+    Act o = ex.new_act(t.cout, 2 * h.H, 2 * h.W, true);
+    IgemmParams p;
+    p.src0 = h.p; p.C0 = h.C; p.B = B; p.Hi = p.Ho = h.H; p.Wi = p.Wo = h.W;
+    p.M = B * h.H * h.W; p.N = t.N; p.n_valid = t.N; p.W = t.w; p.bias = t.bias;
+    p.out = o.p; p.ldo = t.cout; p.epi = EPI_CONVT2; p.cout = t.cout;
+    TRY(ex.igemm(p));
+    Act n;
+    TRY(ex.layernorm(v->ln[i], o, 1e-6f, 1, &n, true));   // LayerNorm2d + SiLU, in place
+    h = n;
+  }
+  Act g;
+  TRY(ex.groupnorm(v->dec_gn, h, nullptr, 1e-5f, 1, &g));
+  const int H4 = h.H, W4 = h.W, Co = c.out_channels;
+  IgemmParams p;
+  p.src0 = g.p; p.C0 = g.C; p.B = B; p.Hi = p.Ho = H4; p.Wi = p.Wo = W4;
+  p.taps = 9; p.M = B * H4 * W4; p.N = v->dec_out.N; p.n_valid = Co;
+  p.W = v->dec_out.w; p.bias = v->dec_out.bias;
+  if (tail.kind == DecodeTail::LOGITS) {
+    p.out = tail.logits; p.epi = EPI_NCHW_F32;
+    TRY(ex.igemm(p));
+    return 0;
+  }
+  // every other tail reads NHWC logits at 4L
+  Act lo = ex.new_act(Co, H4, W4, false);
+  p.out = lo.p; p.ldo = Co; p.epi = EPI_STORE;
+  TRY(ex.igemm(p));
+  const double lo_bytes = (double)B * H4 * W4 * Co * esize(dt);
+  if (tail.kind == DecodeTail::PANOPTIC) {
+    const PanopticOut* po = tail.po;
+    return ex.launch("launch_panoptic_from_decoder failed", 4, 0, lo_bytes, no_label, [&] {
+      return launch_panoptic_from_decoder(lo.p, B, H4, W4, Co, dt, po->in_h, po->in_w, po->boxes, po->sizes, po->offsets, po->threshold_output,
+                                          po->threshold_mode, po->mask_th, po->count_th, po->overlap_th, po->ignore_label, po->labels,
+                                          po->panoptic, po->keep, po->counts, po->mask_counts, s, nullptr, po->mask_rule);
+    }, "decode_panoptic: bad crop box / output size / class count");
+  }
+  if (tail.kind == DecodeTail::SEMSEG) {
+    const SemsegOut* so = tail.so;
+    return ex.launch("launch_semseg_from_decoder failed", 4, 0, lo_bytes + (double)B * so->out_h * so->out_w * 16.0,
+                     [&] { return "semseg_tail " + std::to_string(so->out_h) + "x" + std::to_string(so->out_w); }, [&] {
+      return launch_semseg_from_decoder(lo.p, B, H4, W4, Co, dt, so->out_h, so->out_w, so->mask_th, so->ignore_label, so->targets,
+                                        so->ignore_index, so->K, so->preds, so->counts, s);
+    }, "decode_semseg: bad output size / class count");
+  }
+  if (const ArgmaxOut* am = tail.kind == DecodeTail::ARGMAX ? tail.am : nullptr)
+    return ex.launch("launch_bilinear2x_argmax failed", 4, 0, lo_bytes + (double)B * 4 * H4 * W4 * 12.0, no_label,
+                     [&] { return launch_bilinear2x_argmax(lo.p, am->ids, am->prob, B, H4, W4, Co, am->mask_th, am->ignore_label, dt, s); });
+  return ex.launch("launch_bilinear2x_nchw failed", 4, 0, (double)B * H4 * W4 * Co * (esize(dt) + 16.0), no_label,
+                   [&] { return launch_bilinear2x_nchw(lo.p, tail.logits, B, H4, W4, Co, dt, s); });
+}
+
+// a decode as a planned pass of its own
+int vae_decode(ldmseg_vae* v, const float* z, float z_scale, int B, int L, const DecodeTail& tail, void* stream) {
+  return plan_and_run(*v, nullptr, [&](bool dry, size_t scratch_base) {
+    Exec ex = make_exec(*v, B, (hipStream_t)stream, dry, scratch_base);
+    return vae_decode_body(ex, v, z, z_scale, L, tail);
+  });
+}
+
+int vae_encode_body(Exec& ex, ldmseg_vae* v, const float* x, float mul, float add, int H, float* moments) {
+  const int B = ex.B;
+  hipStream_t s = ex.s;
+  const int dt = v->dt;
+  const ldmseg_vae_cfg& c = v->cfg;
+  Act xin = ex.new_act(bke(dt), H, H, true);
+  TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, no_label, [&] { return launch_pack_nchw(x, xin.p, B, c.in_channels, H * H, bke(dt), mul, add, dt, s); }));
+  Act h, o;
+  int k = 0;
+  TRY(ex.conv(v->enc[k++], xin, &h, {.silu = 1}));  // conv + SiLU
+  for (int i = 0; i < 3; ++i) {
+    TRY(ex.conv(v->enc[k++], h, &o)); h = o;
+    TRY(ex.conv(v->enc[k++], h, &o, {.stride = 2, .silu = 1})); h = o;
+  }
+  TRY(ex.conv(v->enc[k++], h, &o)); h = o;
+  Act g;
+  TRY(ex.groupnorm(v->enc_gn, h, nullptr, 1e-6f, 1, &g));
+  const ConvW& last = v->enc[k];
+  IgemmParams p;
+  p.src0 = g.p; p.C0 = g.C; p.B = B; p.Hi = p.Ho = h.H; p.Wi = p.Wo = h.W;
+  p.taps = 9; p.M = B * h.H * h.W; p.N = last.N; p.n_valid = c.latent_channels * c.num_latents;
+  p.W = last.w; p.bias = last.bias; p.out = moments; p.epi = EPI_NCHW_F32;
+  TRY(ex.igemm(p));
+  return 0;
+}
+
+// vae_model(images, sample_posterior=False).sample (vae.py:273-307) behind one workspace plan: encode -> posterior mode -> decode
+// (interpolate=False, no scaling factor) -> the tail `po` / `so`.  Moments [B,8,l,l] and latents [B,4,l,l] (fp32 NCHW, what
+// ldmseg_vae_encode / ldmseg_vae_posterior hand over; the callers refuse latent_channels != 4, which launch_posterior_sample assumes)
+// are persistent regions of the handle's workspace.  The plan is the SUM of both halves' persistent activations and the MAXIMUM of
+// their scratch peaks: the scratch stack is reset between the halves, which is safe because every launch is on the one stream.
+int vae_reconstruct(ldmseg_vae* v, const float* x, float mul, float add, int B, int H, const DecodeTail& tail, void* stream) {
+  return plan_and_run(*v, nullptr, [&](bool dry, size_t scratch_base) -> int {
+    hipStream_t s = (hipStream_t)stream;
+    Exec ex = make_exec(*v, B, s, dry, scratch_base);
+    const int l = H / 8;
+    float* moments = (float*)v->ws.persist((size_t)B * 8 * l * l * sizeof(float));
+    float* z = (float*)v->ws.persist((size_t)B * 4 * l * l * sizeof(float));
+    TRY(vae_encode_body(ex, v, x, mul, add, H, moments));
+    TRY(ex.launch("launch_posterior_sample failed", 4, 0, 0, no_label, [&] { return launch_posterior_sample(moments, nullptr, z, B, l * l, s); }));
+    v->ws.reset(0);      // the decoder reuses the encoder's scratch (same stream: the encoder's launches are ordered before)
+    return vae_decode_body(ex, v, z, 1.0f, l, tail);
+  });
+}
+
+// what the two panoptic entries share: geometry, thresholds and outputs, by name (the caller adds threshold_mode / mask_rule)
+PanopticOut panoptic_out(int in_h, int in_w, const int32_t* crop_boxes, const int32_t* out_sizes, const int64_t* out_offsets, int threshold_output,
+                         float mask_th, int count_th, double overlap_th, int64_t ignore_label, int32_t* labels, int32_t* panoptic, uint8_t* keep,
+                         int32_t* counts, int32_t* mask_counts) {
+  return PanopticOut{.in_h = in_h, .in_w = in_w, .boxes = crop_boxes, .sizes = out_sizes, .offsets = out_offsets, .threshold_output = threshold_output,
+                     .mask_th = mask_th, .count_th = count_th, .overlap_th = overlap_th, .ignore_label = ignore_label, .labels = labels,
+                     .panoptic = panoptic, .keep = keep, .counts = counts, .mask_counts = mask_counts};
+}
+
+int semseg_out_check(const ldmseg_vae* h, int out_h, int out_w, const int64_t* targets, int num_classes, const int64_t* counts) {
+  if (out_h < 1 || out_w < 1) return fail(LDMSEG_E_SHAPE, "bad output size");
+  if (h->cfg.out_channels > 256 || h->cfg.out_channels % 8) return fail(LDMSEG_E_ARG, "the fused tail needs out_channels <= 256, a multiple of 8");
+  if (targets && counts && (num_classes < 1 || num_classes > 256)) return fail(LDMSEG_E_ARG, "num_classes must be 1..256");
+  return 0;
+}
+
+// ------------------------------------------------------------------ image VAE encoder
+constexpr int kKLCh[4] = {128, 256, 512, 512};
+constexpr int kKLMid = 512;
+
+int klenc_build(ldmseg_vae_image* v, const WeightMap& wm) {
+  Builder b(*v, wm);
+  hipStream_t s = b.s;
+  const int cp = bke(v->dt);
+  TRY(b.conv("encoder.conv_in", kKLCh[0], 3, 3, cp, &v->conv_in));
+  int cin = kKLCh[0], dummy = 0;
+  for (int i = 0; i < 4; ++i) {
+    for (int j = 0; j < 2; ++j) {
+      TRY(build_resnet(b, "encoder.down_blocks." + std::to_string(i) + ".resnets." + std::to_string(j) + ".", cin, kKLCh[i],
+                       &dummy, &v->down[i][j]));
+      cin = kKLCh[i];
+    }
+    if (i < 3) TRY(b.conv("encoder.down_blocks." + std::to_string(i) + ".downsamplers.0.conv", cin, cin, 3, cin, &v->downs[i]));
+  }
+  for (int j = 0; j < 2; ++j)
+    TRY(build_resnet(b, "encoder.mid_block.resnets." + std::to_string(j) + ".", kKLMid, kKLMid, &dummy, &v->mid[j]));
+  // single-head attention block; diffusers 0.16.1 names (query/key/value/proj_attn) or the later to_q/.../to_out.0
+  const std::string ap = "encoder.mid_block.attentions.0.";
+  const bool old_names = wm.m.count(ap + "query.weight") != 0;
+  const std::string qn = old_names ? "query" : "to_q", kn = old_names ? "key" : "to_k", vn = old_names ? "value" : "to_v",
+                    pn = old_names ? "proj_attn" : "to_out.0";
+  TRY(b.norm(ap + "group_norm", kKLMid, &v->attn_gn));
+  TRY(b.conv(ap + qn, kKLMid, kKLMid, 1, kKLMid, &v->q));
+  TRY(b.conv(ap + kn, kKLMid, kKLMid, 1, kKLMid, &v->k));
+  TRY(b.conv(ap + pn, kKLMid, kKLMid, 1, kKLMid, &v->proj));
+  {
+    const float* w;
+    TRY(wm.get(ap + vn + ".weight", (int64_t)kKLMid * kKLMid, &w));
+    TRY(b.arena->alloc(&v->wv, (size_t)kKLMid * kKLMid * esize(v->dt)));
+    TRY(launch_repack_conv(w, v->wv, kKLMid, kKLMid, 1, 1, kKLMid, kKLMid, v->dt, s));
+    b.nparams += (int64_t)kKLMid * kKLMid;
+    TRY(b.f32_copy(ap + vn + ".bias", kKLMid, &v->bv));
+  }
+  TRY(b.norm("encoder.conv_norm_out", kKLMid, &v->norm_out));
+  // conv_out writes its 8 channels into a full K tile (zero padded) so that quant_conv (1x1) can consume it
+  TRY(b.conv("encoder.conv_out", 8, kKLMid, 3, kKLMid, &v->conv_out, true, cp));
+  TRY(b.conv("quant_conv", 8, 8, 1, cp, &v->quant, true, 0, EPI_NCHW_F32));
+  return b.finish(*v);
+}
+
+// diffusers ResnetBlock2D with temb=None, eps 1e-6 (AutoencoderKL)
+int run_resnet_plain(Exec& ex, const ResnetW& r, const Act& x, Act* out) {
+  Workspace* ws = ex.ws;
+  const size_t m = ws->mark();
+  Act n1, h1, n2, sc;
+  TRY(ex.groupnorm(r.norm1, x, nullptr, 1e-6f, 1, &n1));
+  TRY(ex.conv(r.conv1, n1, &h1, {.persist = false}));
+  TRY(ex.groupnorm(r.norm2, h1, nullptr, 1e-6f, 1, &n2));
+  const Act* resid = &x;
+  if (r.has_shortcut) {
+    TRY(ex.conv(r.shortcut, x, &sc, {.persist = false}));
+    resid = &sc;
+  }
+  TRY(ex.conv(r.conv2, n2, out, {.resid = resid}));
+  ws->reset(m);
+  return 0;
+}
+
+// AttentionBlock of the mid block: one head of width C=512 over the N=H*W tokens of each image.  Built from the
+// implicit-GEMM kernel: S_b = Q_b K_b^T (fp32 rows) -> row softmax -> V_b^T = W_v X_b^T -> O_b = P_b V_b (+b_v, since
+// softmax rows sum to one) -> proj + residual.  Runs once per image, not per denoising step.
+int klenc_attention(Exec& ex, const ldmseg_vae_image* v, const Act& x, Act* out) {
+  Workspace* ws = ex.ws;
+  const size_t m = ws->mark();
+  const int C = kKLMid, N = x.H * x.W;
+  const size_t es = esize(ex.dt);
+  if (N % 64 != 0) return fail(LDMSEG_E_SHAPE, "image VAE attention: (H/8)*(W/8) must be a multiple of 64");
+  Act n, q, k, att;
+  TRY(ex.groupnorm(v->attn_gn, x, nullptr, 1e-6f, 0, &n));
+  TRY(ex.conv(v->q, n, &q, {.persist = false}));
+  TRY(ex.conv(v->k, n, &k, {.persist = false}));
+  att = ex.new_act(C, x.H, x.W, false);
+  float* S = (float*)ws->scratch((size_t)N * N * sizeof(float));
+  void* P = ws->scratch((size_t)N * N * es);
+  void* Vt = ws->scratch((size_t)C * N * es);
+  for (int b = 0; b < ex.B; ++b) {
+    const size_t off = (size_t)b * N * C * es;
+    {
+      IgemmParams p;                                   // S = Q_b K_b^T
+      p.src0 = (const char*)q.p + off; p.C0 = C; p.B = 1; p.Hi = p.Ho = N; p.Wi = p.Wo = 1;
+      p.M = N; p.N = N; p.n_valid = N; p.W = (const char*)k.p + off; p.out = S; p.ldo = N; p.epi = EPI_ROWS_F32;
+      p.w_dynamic = 1;
+      TRY(ex.igemm(p));
+    }
+    TRY(ex.launch("launch_softmax_rows failed", 4, 0, (double)N * N * (4 + es), no_label, [&] { return launch_softmax_rows(S, P, N, N, 1.0f / std::sqrt((float)C), ex.dt, ex.s); }));
+    {
+      IgemmParams p;                                   // V_b^T [C][N] = W_v X_b^T
+      p.src0 = v->wv; p.C0 = C; p.B = 1; p.Hi = p.Ho = C; p.Wi = p.Wo = 1;
+      p.M = C; p.N = N; p.n_valid = N; p.W = (const char*)n.p + off; p.out = Vt; p.ldo = N;
+      p.w_dynamic = 1;
+      TRY(ex.igemm(p));
+    }
+    {
+      IgemmParams p;                                   // O_b = P_b V_b + b_v
+      p.src0 = P; p.C0 = N; p.B = 1; p.Hi = p.Ho = N; p.Wi = p.Wo = 1;
+      p.M = N; p.N = C; p.n_valid = C; p.W = Vt; p.bias = v->bv; p.out = (char*)att.p + off; p.ldo = C;
+      p.w_dynamic = 1;
+      TRY(ex.igemm(p));
+    }
+  }
+  TRY(ex.conv(v->proj, att, out, {.resid = &x}));
+  ws->reset(m);
+  return 0;
+}
+
+int klenc_encode_impl(ldmseg_vae_image* v, const float* x, float mul, float add, int B, int H, int W, float* moments,
+                      hipStream_t s, bool dry, size_t scratch_base) {
+  Exec ex = make_exec(*v, B, s, dry, scratch_base);
+  const int dt = v->dt;
+  Act xin = ex.new_act(bke(dt), H, W, true);
+  TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, no_label, [&] { return launch_pack_nchw(x, xin.p, B, 3, H * W, bke(dt), mul, add, dt, s); }));
+  Act h, o;
+  TRY(ex.conv(v->conv_in, xin, &h));
+  for (int i = 0; i < 4; ++i) {
+    for (int j = 0; j < 2; ++j) { TRY(run_resnet_plain(ex, v->down[i][j], h, &o)); h = o; }
+    if (i < 3) { TRY(ex.conv(v->downs[i], h, &o, {.stride = 2, .pad = 0})); h = o; }
+  }
+  TRY(run_resnet_plain(ex, v->mid[0], h, &o)); h = o;
+  TRY(klenc_attention(ex, v, h, &o)); h = o;
+  TRY(run_resnet_plain(ex, v->mid[1], h, &o)); h = o;
+  Act g, c8;
+  TRY(ex.groupnorm(v->norm_out, h, nullptr, 1e-6f, 1, &g));
+  TRY(ex.conv(v->conv_out, g, &c8));
+  IgemmParams p;
+  p.src0 = c8.p; p.C0 = c8.C; p.B = B; p.Hi = p.Ho = h.H; p.Wi = p.Wo = h.W;
+  p.taps = 1; p.M = B * h.H * h.W; p.N = v->quant.N; p.n_valid = 8;
+  p.W = v->quant.w; p.bias = v->quant.bias; p.out = moments; p.epi = EPI_NCHW_F32;
+  TRY(ex.igemm(p));
+  return 0;
+}
+
+}  // namespace
+
+// =================================================================== C ABI
+extern "C" {
+
+int ldmseg_vae_create(const ldmseg_vae_cfg* cfg, int n_weights, const char* const* names, const void* const* dev_ptrs,
+                      const int64_t* numels, ldmseg_vae** out) {
+  auto check = [](const ldmseg_vae_cfg& c) {
+    if (c.num_latents != 2 || c.norm_num_groups != 32) return fail(LDMSEG_E_ARG, "only the gaussian parametrization with 32 groups is supported");
+    return 0;
+  };
+  return create_handle(cfg, n_weights, names, dev_ptrs, numels, check, vae_build, true, out);
+}
+LDMSEG_HANDLE_ABI(ldmseg_vae)
+
+int ldmseg_vae_decode(ldmseg_vae* h, const float* z, float z_scale, int B, int L, int interpolate, float* logits,
+                      void* stream) {
+  g_err.clear();
+  if (!h || !z || !logits) return fail(LDMSEG_E_ARG, "null argument");
+  DeviceGuard dg(h->cfg.device);
+  if (B < 1 || L < 1) return fail(LDMSEG_E_SHAPE, "bad B/L");
+  const DecodeTail tail{.kind = interpolate ? DecodeTail::LOGITS_X2 : DecodeTail::LOGITS, .logits = logits};
+  return vae_decode(h, z, z_scale, B, L, tail, stream);
+}
+
+int ldmseg_vae_decode_argmax(ldmseg_vae* h, const float* z, float z_scale, int B, int L, float mask_th, int64_t ignore_label,
+                             int64_t* ids, float* max_prob, void* stream) {
+  g_err.clear();
+  if (!h || !z || !ids) return fail(LDMSEG_E_ARG, "null argument");
+  DeviceGuard dg(h->cfg.device);
+  if (B < 1 || L < 1) return fail(LDMSEG_E_SHAPE, "bad B/L");
+  if (h->cfg.num_upscalers != 2) return fail(LDMSEG_E_ARG, "the fused tail assumes interpolation_factor 2 (num_upscalers 2)");
+  ArgmaxOut am{ids, max_prob, mask_th, ignore_label};
+  const DecodeTail tail{.kind = DecodeTail::ARGMAX, .am = &am};
+  return vae_decode(h, z, z_scale, B, L, tail, stream);
+}
+
+int ldmseg_vae_decode_panoptic(ldmseg_vae* h, const float* z, float z_scale, int B, int L, int in_h, int in_w,
+                               const int32_t* crop_boxes, const int32_t* out_sizes, const int64_t* out_offsets,
+                               int threshold_output, int threshold_mode, float mask_th, int count_th, double overlap_th,
+                               int64_t ignore_label, int32_t* labels, int32_t* panoptic, uint8_t* keep, int32_t* counts,
+                               int32_t* mask_counts, void* stream) {
+  g_err.clear();
+  if (!h || !z || !out_sizes || !out_offsets || !labels || !panoptic || !keep || !counts || !mask_counts)
+    return fail(LDMSEG_E_ARG, "null argument");
+  if (B < 1 || L < 1 || in_h < 1 || in_w < 1) return fail(LDMSEG_E_SHAPE, "bad B/L/input size");
+  if (threshold_mode != 0 && threshold_mode != 1) return fail(LDMSEG_E_ARG, "threshold_mode must be 0 (max) or 1 (topk_diff)");
+  if (h->cfg.num_upscalers != 2) return fail(LDMSEG_E_ARG, "the fused tail assumes interpolation_factor 2 (num_upscalers 2)");
+  DeviceGuard dg(h->cfg.device);
+  PanopticOut po = panoptic_out(in_h, in_w, crop_boxes, out_sizes, out_offsets, threshold_output, mask_th, count_th, overlap_th, ignore_label,
+                                labels, panoptic, keep, counts, mask_counts);
+  po.threshold_mode = threshold_mode;
+  const DecodeTail tail{.kind = DecodeTail::PANOPTIC, .po = &po};
+  return vae_decode(h, z, z_scale, B, L, tail, stream);
+}
+
+int ldmseg_vae_encode(ldmseg_vae* h, const float* x, float in_mul, float in_add, int B, int H, float* moments,
+                      void* stream) {
+  g_err.clear();
+  if (!h || !x || !moments) return fail(LDMSEG_E_ARG, "null argument");
+  DeviceGuard dg(h->cfg.device);
+  if (B < 1 || H < 8 || H % 8) return fail(LDMSEG_E_SHAPE, "H must be a multiple of 8");
+  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
+    Exec ex = make_exec(*h, B, (hipStream_t)stream, dry, scratch_base);
+    return vae_encode_body(ex, h, x, in_mul, in_add, H, moments);
+  });
+}
+
+int ldmseg_vae_decode_semseg(ldmseg_vae* h, const float* z, float z_scale, int B, int L, int out_h, int out_w, float mask_th,
+                             int64_t ignore_label, const int64_t* targets, int64_t ignore_index, int num_classes, int64_t* preds,
+                             int64_t* counts, void* stream) {
+  g_err.clear();
+  if (!h || !z) return fail(LDMSEG_E_ARG, "null argument");
+  if (B < 1 || L < 1) return fail(LDMSEG_E_SHAPE, "bad B/L");
+  TRY(semseg_out_check(h, out_h, out_w, targets, num_classes, counts));
+  DeviceGuard dg(h->cfg.device);
+  SemsegOut so{out_h, out_w, mask_th, ignore_label, targets, ignore_index, num_classes, preds, counts};
+  const DecodeTail tail{.kind = DecodeTail::SEMSEG, .so = &so};
+  return vae_decode(h, z, z_scale, B, L, tail, stream);
+}
+
+int ldmseg_vae_reconstruct_semseg(ldmseg_vae* h, const float* x, float in_mul, float in_add, int B, int H, int out_h, int out_w,
+                                  float mask_th, int64_t ignore_label, const int64_t* targets, int64_t ignore_index,
+                                  int num_classes, int64_t* preds, int64_t* counts, void* stream) {
+  g_err.clear();
+  if (!h || !x) return fail(LDMSEG_E_ARG, "null argument");
+  if (B < 1 || H < 8 || H % 8) return fail(LDMSEG_E_SHAPE, "H must be a multiple of 8");
+  if (h->cfg.latent_channels != 4) return fail(LDMSEG_E_ARG, "the reconstruct chain assumes 4 latent channels");
+  TRY(semseg_out_check(h, out_h, out_w, targets, num_classes, counts));
+  DeviceGuard dg(h->cfg.device);
+  SemsegOut so{out_h, out_w, mask_th, ignore_label, targets, ignore_index, num_classes, preds, counts};
+  const DecodeTail tail{.kind = DecodeTail::SEMSEG, .so = &so};
+  return vae_reconstruct(h, x, in_mul, in_add, B, H, tail, stream);
+}
+
+int ldmseg_vae_reconstruct_panoptic(ldmseg_vae* h, const float* x, float in_mul, float in_add, int B, int H, int in_h, int in_w,
+                                    const int32_t* crop_boxes, const int32_t* out_sizes, const int64_t* out_offsets,
+                                    int threshold_output, float mask_th, int count_th, double overlap_th, int64_t ignore_label,
+                                    int32_t* labels, int32_t* panoptic, uint8_t* keep, int32_t* counts, int32_t* mask_counts,
+                                    void* stream) {
+  g_err.clear();
+  if (!h || !x || !out_sizes || !out_offsets || !labels || !panoptic || !keep || !counts || !mask_counts)
+    return fail(LDMSEG_E_ARG, "null argument");
+  if (B < 1 || H < 8 || H % 8 || in_h < 1 || in_w < 1) return fail(LDMSEG_E_SHAPE, "bad B/H/input size");
+  if (h->cfg.latent_channels != 4) return fail(LDMSEG_E_ARG, "the reconstruct chain assumes 4 latent channels");
+  if (h->cfg.num_upscalers != 2) return fail(LDMSEG_E_ARG, "the fused tail assumes interpolation_factor 2 (num_upscalers 2)");
+  DeviceGuard dg(h->cfg.device);
+  PanopticOut po = panoptic_out(in_h, in_w, crop_boxes, out_sizes, out_offsets, threshold_output, mask_th, count_th, overlap_th, ignore_label,
+                                labels, panoptic, keep, counts, mask_counts);
+  po.mask_rule = 1;
+  const DecodeTail tail{.kind = DecodeTail::PANOPTIC, .po = &po};
+  return vae_reconstruct(h, x, in_mul, in_add, B, H, tail, stream);
+}
+
+int ldmseg_vae_image_create(const ldmseg_vae_image_cfg* cfg, int n_weights, const char* const* names,
+                            const void* const* dev_ptrs, const int64_t* numels, ldmseg_vae_image** out) {
+  return create_handle(cfg, n_weights, names, dev_ptrs, numels, [](const ldmseg_vae_image_cfg&) { return 0; }, klenc_build, true, out);
+}
+LDMSEG_HANDLE_ABI(ldmseg_vae_image)
+
+int ldmseg_vae_image_encode(ldmseg_vae_image* h, const float* x, float in_mul, float in_add, int B, int H, int W,
+                            float* moments, void* stream) {
+  g_err.clear();
+  if (!h || !x || !moments) return fail(LDMSEG_E_ARG, "null argument");
+  DeviceGuard dg(h->cfg.device);
+  if (B < 1 || H < 8 || W < 8 || H % 8 || W % 8) return fail(LDMSEG_E_SHAPE, "H and W must be multiples of 8");
+  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
+    return klenc_encode_impl(h, x, in_mul, in_add, B, H, W, moments, (hipStream_t)stream, dry, scratch_base);
+  });
+}
+
+}  // extern "C"

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.normpath(os.path.join(HERE, "..", "csrc"))
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "..", "include"))
 LIB_PATH = os.path.join(HERE, "libldmseg_hip.so")
-SOURCES = ["igemm.hip", "tfuse.hip", "tproj.hip", "tail.hip", "norm.hip", "attention.hip", "attention3.hip", "attention4.hip", "attention_fp8.hip", "attention_mx.hip", "attention_cross.hip", "clip_vision.hip", "clip_text.hip", "guided.hip", "misc.hip", "skipadd.hip", "postproc.hip", "pq_meter.hip", "sched.hip", "loss.hip", "engine.hip", "ops_api.hip"]
+SOURCES = ["igemm.hip", "tfuse.hip", "tproj.hip", "tail.hip", "norm.hip", "attention.hip", "attention3.hip", "attention4.hip", "attention_fp8.hip", "attention_mx.hip", "attention_cross.hip", "clip_vision.hip", "clip_text.hip", "guided.hip", "misc.hip", "skipadd.hip", "postproc.hip", "pq_meter.hip", "sched.hip", "loss.hip", "runtime.hip", "unet_build.hip", "unet.hip", "vae.hip", "clip.hip", "debug_knobs.hip", "ops_api.hip"]
 EXTRA_FLAGS = {
     "sched.hip": ["-ffp-contract=off"],                       # bit-exact scheduler arithmetic
     "tail.hip": ["-ffp-contract=off"],                        # the fused step tail carries the same arithmetic
@@ -59,7 +59,8 @@ def build_library(force=False, verbose=False):
     hipcc = _hipcc()
     objdir = os.path.join(CSRC, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "kernels.h", "igemm_types.h", "igemm_plan.h", "gn_plan.h", "attn_plan.h", "attn_dev.h", "igemm_tuned.inc", "sched_math.h", "nearest_index.h")]
+    # every header takes part in every object's digest: a new one cannot be forgotten
+    headers = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith((".h", ".inc"))]
     headers += [os.path.join(INCLUDE, h) for h in ("ldmseg_hip.h", "ldmseg_hip_ops.h")]
     jobs = []
     objs = []

@@ -513,7 +513,7 @@ def check_conv_groupnorm_fused_finish(L, seen, dt, cfg):
 
 # ---- self-attention: every (map side at L = 64, C) level of the UNet, 8 heads (head dim 40 / 80 / 160 / 160)
 ATTN_LEVELS = [(64, 320), (32, 640), (16, 1280), (8, 1280)]
-ATTN_DT = {"bf16": BF16, "fp32": F32, "bf16x3": 2}      # 2: fp32 tensors, split-bf16 products (engine.hip launches it so)
+ATTN_DT = {"bf16": BF16, "fp32": F32, "bf16x3": 2}      # 2: fp32 tensors, split-bf16 products (unet.hip launches it so)
 
 
 def attention_rows(qkv, B, N, Cc):
