@@ -440,6 +440,42 @@ int ldmseg_loss_weight_mask(const void* src, int src_dtype, int B, int Hi, int W
 #define LDMSEG_MINMAX_SCRATCH_BYTES 3072
 int ldmseg_tensor_minmax(const float* x, size_t n, float* minmax, void* scratch, void* stream);
 
+/* ---- seg-VAE stage-1 loss: point CE, mask and KL terms (trainers_ae.py:204-216, losses.py:117-185, :303-394) ---------- */
+#define LDMSEG_POINT_LOSS_MAX_C 128
+/* present[b][c] = 1 where id c != ignore_label occurs in image b of targets [B,Ht,Wt] int64 once the pixels with valid == 0
+ * (uint8 [B,Ht,Wt], may be NULL) count as ignore_label (losses.py:326; the caller's tensor is not written), else 0: what
+ * prepare_targets (:397-439) finds with torch.unique.  Bit 0 of *flag (device int32) is set if an id other than ignore_label lies
+ * outside [0, C).  Both outputs are reset by the call.  One launch; the caller reads the table once to size the draws. */
+int ldmseg_class_presence(const int64_t* targets, const uint8_t* valid, int B, int Ht, int Wt, int C, int64_t ignore_label,
+                          uint8_t* present, int32_t* flag, void* stream);
+/* SegmentationLosses.point_loss (:364-394) without the matcher, forward only, on fp32 NCHW logits x [B,C,H,W] and targets / valid
+ * as above.  Rows: B cross-entropy rows (one per image), then N mask rows; mask_rows_dev [N] int32 holds b * C + c of each object
+ * mask, by image, then ascending class id (the order of prepare_targets).  Draws (device fp32 in [0, 1), [...,0] = x, [...,1] = y):
+ * ce_over [B,S,2], ce_fresh [B,P-kU,2], mask_over [N,S,2], mask_fresh [N,P-kU,2]; S = int(P * oversample_ratio), kU =
+ * int(importance_sample_ratio * P).  S == kU == 0 is oversample_ratio 0: the P fresh points serve directly (:164-165, :338-339).
+ *   uncertainty  per oversampled point: CE rows second - first of the top two bilinear samples over the C channels (:296-301),
+ *                mask rows -|bilinear sample of x[b,c]| (:294); the taps are those of F.grid_sample(align_corners=False, zeros
+ *                padding) (csrc/point_sample.h).
+ *   selection    exact top-kU of the S uncertainties of each row (radix select on the bit patterns); ties at the threshold go to
+ *                the lower index (torch.topk defines no rule).  selected (may be NULL): int32 [B+N,kU], ascending per row.
+ *   out[0]       ce: mean over the kept points of the batch of logsumexp(x / temperature) - x[label] / temperature at the kU
+ *                selected + P-kU fresh points; label = nearest tap of the effective targets (0 outside the map), points with
+ *                label == ignore_label are dropped; NaN if none is kept, like F.cross_entropy.
+ *   out[1]       sum over mask rows of mean_P(binary_cross_entropy_with_logits(x, t)) / num_masks, t = bilinear sample of
+ *                (effective target == c);  out[2]: sum of 1 - (2 sum(sigmoid(x) t) + 1) / (sum(sigmoid(x)) + sum(t) + 1) / num_masks.
+ *                loss_masks (:117-185) returns out[1] + out[2].  N == 0: both 0.
+ * Partial sums are fp64, stored per workgroup and added by one finishing launch in a fixed order: no float atomics, two calls on
+ * the same inputs agree bit for bit.  scratch: ldmseg_point_loss_scratch_bytes(B + N, S, kU, P) bytes of device memory.  4 launches
+ * (2 with kU == 0); no host synchronisation, no allocation. */
+size_t ldmseg_point_loss_scratch_bytes(int rows, int S, int kU, int P);
+int ldmseg_point_loss(const float* x, int B, int C, int H, int W, const int64_t* targets, const uint8_t* valid, int Ht, int Wt,
+                      const int32_t* mask_rows_dev, int N, const float* ce_over, const float* ce_fresh, const float* mask_over,
+                      const float* mask_fresh, int S, int kU, int P, int64_t ignore_label, float temperature, double num_masks,
+                      float* out, int32_t* selected, void* scratch, void* stream);
+/* DiagonalGaussianDistribution.kl() (vae.py:416-417) on moments [B, 2 * latent_channels, HW] (mean | logvar, logvar clamped to
+ * [-30, 20]): per_image[b] = 0.5 * sum(mean^2 + exp(logvar) - 1 - logvar), added in fp64; mean (may be NULL) = their batch mean. */
+int ldmseg_gaussian_kl(const float* moments, int B, int latent_channels, int HW, float* per_image, float* mean, void* stream);
+
 /* ---- sampler: TrainerDiffusion.sample (trainers_ldm_cond.py:1045-1170) -------------------- */
 typedef struct {
   int32_t n_steps;               /* len(scheduler.timesteps) */

@@ -199,6 +199,12 @@ int ldmseg_op_fastdiv(const int* n, int count, int d, int* q, void* stream);
  * out_size (csrc/nearest_index.h, the rule of F.interpolate(mode='nearest')).  Host only: src is a host array, no GPU is touched. */
 int ldmseg_op_nearest_index(int in_size, int out_size, int* src);
 
+/* The taps ldmseg_point_loss reads for n points u [n,2] (u[...,0] = x, u[...,1] = y) of a [H,W] map: those of
+ * F.grid_sample(input, 2 * u - 1, align_corners=False, padding_mode='zeros') (csrc/point_sample.h).  mode 0 bilinear: index [n,4]
+ * (y * W + x of the north-west, north-east, south-west, south-east tap, -1 outside the map) and weight [n,4]; mode 1 nearest (half
+ * to even): index [n], -1 outside the map, weight unused.  Host only: the arrays are host arrays, no GPU is touched. */
+int ldmseg_op_point_taps(int n, const float* u, int H, int W, int mode, int32_t* index, float* weight);
+
 #ifdef __cplusplus
 }
 #endif

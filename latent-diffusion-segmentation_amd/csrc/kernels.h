@@ -485,6 +485,32 @@ size_t tensor_minmax_scratch_bytes();
 int launch_tensor_minmax(const float* x, size_t n, float* out, void* scratch, hipStream_t s);
 int launch_loss_weight_mask(const void* src, int src_dtype, int B, int Hi, int Wi, int h, int w, int mode, int64_t ignore_label,
                             float* out, int32_t* flag, hipStream_t s);
+// the seg-VAE's stage-1 loss (point_loss.hip); arguments as ldmseg_point_loss / ldmseg_class_presence / ldmseg_gaussian_kl
+// (include/ldmseg_hip.h)
+struct PointLoss {
+  const float* x;             // [B][C][H][W] logits
+  int B, C, H, W;
+  const int64_t* tgt;         // [B][Ht][Wt]
+  const uint8_t* valid;       // [B][Ht][Wt] or null
+  int Ht, Wt;
+  const int32_t* rows;        // [N] b * C + c of the mask rows, by image, then class id
+  int N;
+  const float* ce_over;       // [B][S][2] or null (S == 0)
+  const float* ce_fresh;      // [B][P - kU][2] or null (P == kU)
+  const float* m_over;        // [N][S][2]
+  const float* m_fresh;       // [N][P - kU][2]
+  int S, kU, P;
+  int64_t ignore;
+  float temperature;
+  float* unc;                 // filled by the launcher
+  int32_t* sel;
+  double* partial;
+};
+int launch_class_presence(const int64_t* targets, const uint8_t* valid, int B, int Ht, int Wt, int C, int64_t ignore_label,
+                          uint8_t* present, int32_t* flag, hipStream_t s);
+size_t point_loss_scratch_bytes(int rows, int S, int kU, int P);
+int launch_point_loss(const PointLoss& p, double num_masks, float* out, int32_t* selected, void* scratch, hipStream_t s);
+int launch_gaussian_kl(const float* moments, int B, int n, float* per_image, float* mean, hipStream_t s);
 int launch_bit_encode(const int64_t* ids, float* out, uint8_t* ignore, int B, int n, int HW, int64_t ignore_label,
                       float fill, float mul, float add, hipStream_t s);
 int launch_bit_decode(const float* x, int64_t* out, int B, int n, int HW, hipStream_t s);

@@ -225,6 +225,51 @@ int ldmseg_tensor_minmax(const float* x, size_t n, float* minmax, void* scratch,
   return 0;
 }
 
+size_t ldmseg_point_loss_scratch_bytes(int rows, int S, int kU, int P) { return point_loss_scratch_bytes(rows, S, kU, P); }
+
+int ldmseg_class_presence(const int64_t* targets, const uint8_t* valid, int B, int Ht, int Wt, int C, int64_t ignore_label,
+                          uint8_t* present, int32_t* flag, void* stream) {
+  g_err.clear();
+  if (!targets || !present || !flag) return fail(LDMSEG_E_ARG, "null argument");
+  if (B < 1 || B > 65535 || Ht < 1 || Wt < 1 || (int64_t)Ht * Wt > (int64_t)0x7fff0000) return fail(LDMSEG_E_SHAPE, "B in 1..65535, Ht * Wt in 1..2^31");
+  if (C < 1 || C > LDMSEG_POINT_LOSS_MAX_C) return fail(LDMSEG_E_SHAPE, "C must be 1..LDMSEG_POINT_LOSS_MAX_C");
+  TRY(launch_class_presence(targets, valid, B, Ht, Wt, C, ignore_label, present, flag, (hipStream_t)stream));
+  return 0;
+}
+
+int ldmseg_point_loss(const float* x, int B, int C, int H, int W, const int64_t* targets, const uint8_t* valid, int Ht, int Wt,
+                      const int32_t* mask_rows_dev, int N, const float* ce_over, const float* ce_fresh, const float* mask_over,
+                      const float* mask_fresh, int S, int kU, int P, int64_t ignore_label, float temperature, double num_masks,
+                      float* out, int32_t* selected, void* scratch, void* stream) {
+  g_err.clear();
+  if (!x || !targets || !out || !scratch) return fail(LDMSEG_E_ARG, "null argument");
+  if (C < 1 || C > LDMSEG_POINT_LOSS_MAX_C) return fail(LDMSEG_E_SHAPE, "C must be 1..LDMSEG_POINT_LOSS_MAX_C");
+  if (B < 1 || N < 0 || N > B * C || B + N > 65535) return fail(LDMSEG_E_SHAPE, "B >= 1, 0 <= N <= B * C, B + N <= 65535");
+  if (H < 1 || W < 1 || Ht < 1 || Wt < 1 || (int64_t)H * W > (int64_t)0x7fff0000 || (int64_t)Ht * Wt > (int64_t)0x7fff0000)
+    return fail(LDMSEG_E_SHAPE, "map sizes must be positive, H * W and Ht * Wt below 2^31");
+  if (P < 1 || kU < 0 || kU > P || S < kU || (kU > 0 && S < 1) || (int64_t)(B + N) * (S > P ? S : P) > (int64_t)0x3fff0000)
+    return fail(LDMSEG_E_ARG, "need 0 <= kU <= P, kU <= S, (B + N) * max(S, P) below 2^30");
+  if (!(temperature > 0.0f)) return fail(LDMSEG_E_ARG, "temperature must be positive");
+  if (N > 0 && (!mask_rows_dev || !(num_masks > 0.0))) return fail(LDMSEG_E_ARG, "mask rows need mask_rows_dev and num_masks > 0");
+  if (kU > 0 && (!ce_over || (N > 0 && !mask_over))) return fail(LDMSEG_E_ARG, "kU > 0 needs the oversampled draws");
+  if (P > kU && (!ce_fresh || (N > 0 && !mask_fresh))) return fail(LDMSEG_E_ARG, "P > kU needs the fresh draws");
+  PointLoss p{};
+  p.x = x; p.B = B; p.C = C; p.H = H; p.W = W; p.tgt = targets; p.valid = valid; p.Ht = Ht; p.Wt = Wt;
+  p.rows = mask_rows_dev; p.N = N; p.ce_over = ce_over; p.ce_fresh = ce_fresh; p.m_over = mask_over; p.m_fresh = mask_fresh;
+  p.S = S; p.kU = kU; p.P = P; p.ignore = ignore_label; p.temperature = temperature;
+  TRY(launch_point_loss(p, num_masks, out, selected, scratch, (hipStream_t)stream));
+  return 0;
+}
+
+int ldmseg_gaussian_kl(const float* moments, int B, int latent_channels, int HW, float* per_image, float* mean, void* stream) {
+  g_err.clear();
+  if (!moments || !per_image) return fail(LDMSEG_E_ARG, "null argument");
+  if (B < 1 || B > 65535 || latent_channels < 1 || HW < 1 || (int64_t)latent_channels * HW > (int64_t)0x3fff0000)
+    return fail(LDMSEG_E_SHAPE, "B in 1..65535, latent_channels * HW in 1..2^30");
+  TRY(launch_gaussian_kl(moments, B, latent_channels * HW, per_image, mean, (hipStream_t)stream));
+  return 0;
+}
+
 int ldmseg_bit_encode(const int64_t* ids, int B, int n_bits, int HW, int64_t ignore_label, float fill_value, float mul,
                       float add, float* bits, uint8_t* ignore_mask, void* stream) {
   g_err.clear();

@@ -77,6 +77,11 @@ SIGNATURES = {
     "ldmseg_diffusion_loss": (_i, [_vp] * 5 + [_i] + [_vp] * 5 + [_i, _i, _d, _i, _i, _i] + [_vp] * 6),
     "ldmseg_loss_weight_mask": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i64, _vp, _vp, _vp]),
     "ldmseg_tensor_minmax": (_i, [_vp, _sz, _vp, _vp, _vp]),
+    "ldmseg_class_presence": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp]),
+    "ldmseg_point_loss_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "ldmseg_point_loss": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _f, _d,
+                               _vp, _vp, _vp, _vp]),
+    "ldmseg_gaussian_kl": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "ldmseg_unet_reserve": (_i, [_vp, _i, _i]),
     "ldmseg_unet_set_attention_fp8": (_i, [_vp, _i]),
     "ldmseg_unet_gn_fallbacks": (_i, [_vp, _vp]),
@@ -156,6 +161,7 @@ SIGNATURES = {
     "ldmseg_op_attention_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i]),
     "ldmseg_op_fastdiv": (_i, [_vp, _i, _i, _vp, _vp]),
     "ldmseg_op_nearest_index": (_i, [_i, _i, C.POINTER(_i)]),
+    "ldmseg_op_point_taps": (_i, [_i, C.POINTER(_f), _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(_f)]),
     "ldmseg_igemm_log": (_i, [_i]),
     "ldmseg_igemm_log_read": (_i, [C.c_char_p, _i]),
 }

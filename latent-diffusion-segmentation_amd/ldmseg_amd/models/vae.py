@@ -52,6 +52,18 @@ class DiagonalGaussianDistribution(object):
         noise = torch.randn(shape, generator=generator, device=p.device, dtype=p.dtype)
         return self._posterior(noise)
 
+    def kl(self, return_mean: bool = False):
+        """:416-417: 0.5 * sum(mean^2 + var - 1 - logvar) per image, [B] on the device (ldmseg_gaussian_kl; fp64 sums).  With
+        return_mean the pair (per image [B], batch mean 0-d) of the same call."""
+        p = _lib.require_cuda_f32(self.parameters, "moments")
+        B, C2 = p.shape[0], p.shape[1]
+        per = torch.empty(B, device=p.device, dtype=torch.float32)
+        mean = torch.empty(1, device=p.device, dtype=torch.float32) if return_mean else None
+        with torch.cuda.device(p.device):
+            _lib.check(_lib.lib().ldmseg_gaussian_kl(_lib.ptr(p), B, C2 // 2, p[0, 0].numel(), _lib.ptr(per), _lib.ptr(mean),
+                                                     _lib.stream_ptr(p.device)), "ldmseg_gaussian_kl")
+        return (per, mean[0]) if return_mean else per
+
 
 class GeneralVAESeg(object):
     def __init__(self, state_dict, in_channels: int = 7, int_channels: int = 256, out_channels: int = 128,

@@ -2,7 +2,8 @@
 
 Stands behind the evaluation half of the reference's ldmseg/trainers/trainers_ae.py::TrainerAE
 (`compute_metrics` :546-569, `compute_pq` :580-680, `compute_miou` :728-803) - what `tools/main_ae.py` runs with
-`eval_only` (:189-190).  Training, image dumps and overlays (`save_images`) are not built.
+`eval_only` (:189-190) - and behind the forward half of its training step: `compute_point_loss` (:204-224), the number
+the stage-1 loop logs and selects checkpoints by.  Backward, optimiser, image dumps and overlays (`save_images`) are not built.
 
 Per batch ONE library call does encode -> posterior mode -> decode -> the metric's tail
 (`GeneralVAESeg.reconstruct_semseg` / `reconstruct_panoptic`); the [B,128,S,S] logits are never materialised and the
@@ -13,14 +14,19 @@ from typing import List, Optional, Union
 import torch
 
 from ..evaluations.semseg_evaluation import SemsegMeter
+from .losses import SegmentationLosses
 from .sampler import TrainerDiffusion
 
 METRICS = ("miou", "pq")
+LOSS_WEIGHTS = {"mask": 1.0, "ce": 1.0, "kl": 0.0}                                     # base.yaml:101-104
+LOSS_KWARGS = dict(num_points=12544, oversample_ratio=3, importance_sample_ratio=0.75, cost_mask=1.0, cost_class=1.0,
+                   temperature=1.0)                                                    # base.yaml:107-113
 
 
 class TrainerAE(object):
     def __init__(self, vae_model, num_classes: int = 128, ignore_label: int = 0, mask_th: float = 0.5, count_th: int = 512,
-                 overlap_th: float = 0.5, class_names: Optional[List[str]] = None, device=None):
+                 overlap_th: float = 0.5, class_names: Optional[List[str]] = None, device=None,
+                 loss_weights: Optional[dict] = None, loss_kwargs: Optional[dict] = None):
         self.vae_model = vae_model
         self.num_classes = num_classes
         self.ignore_label = ignore_label
@@ -29,6 +35,10 @@ class TrainerAE(object):
         self.overlap_th = overlap_th
         self.class_names = class_names if class_names is not None else [str(i) for i in range(num_classes)]
         self.device = torch.device(device) if device is not None else getattr(vae_model, "device", None)
+        self.loss_weights = dict(LOSS_WEIGHTS if loss_weights is None else loss_weights)
+        # :195; the trainer's ignore_label is the one that counts (an 'ignore_label' among loss_kwargs is overridden)
+        self.segmentation_losses = SegmentationLosses(**{**(LOSS_KWARGS if loss_kwargs is None else loss_kwargs),
+                                                         'ignore_label': ignore_label})
 
     def compute_metrics(self, names: Union[List[str], str] = ['miou'], dataloader=None, evaluator=None,
                         threshold_output: bool = False) -> dict:
@@ -54,6 +64,40 @@ class TrainerAE(object):
         return out
 
     crop_padding = staticmethod(TrainerDiffusion.crop_padding)          # :571-577
+
+    @torch.no_grad()
+    def compute_point_loss(self, outputs, targets, do_matching: bool = False, masks=None, generator=None):
+        """:204-216 on the VAEOutput of `vae_model(...)` (`.sample` logits [B,C,4L,4L], `.posterior`) and targets [B,h,w]:
+        (total, ce, kl, mask) as 0-d device tensors; total is the three terms weighted by `loss_weights`, added in the order
+        ce, mask, kl.  Forward only."""
+        parts = self.segmentation_losses.point_loss(outputs.sample, targets, do_matching, masks, generator=generator)
+        ce, mask = parts['ce'], parts['mask']
+        kl = outputs.posterior.kl(return_mean=True)[1]
+        w = self.loss_weights
+        total = w['ce'] * ce + w['mask'] * mask + w['kl'] * kl
+        return total, ce, kl, mask
+
+    @torch.no_grad()
+    def validation_loss(self, dataloader, sample_posterior: bool = False, seed: int = 0) -> dict:
+        """The stage-1 loss of a checkpoint over a loader.  NOT in the reference (its loss is only ever logged from inside the
+        training loop): per batch {'image_semseg': [B,7,S,S] bit maps in [0,1], 'semseg': [B,h,w]} the forward of :253-287
+        without corruption, then `compute_point_loss`; every draw comes from one CPU generator seeded `seed`.  The four values
+        are averaged over batches (image-weighted) on the device and read once at the end (each batch's `point_loss` reads its
+        class-presence table): {'loss', 'ce', 'kl', 'mask', 'images'}."""
+        g = torch.Generator().manual_seed(int(seed))
+        gd = torch.Generator(device=self.device).manual_seed(int(seed)) if sample_posterior else None
+        sums = torch.zeros(4, dtype=torch.float64, device=self.device)
+        images = 0
+        for data in dataloader:
+            x = data['image_semseg'].to(self.device, non_blocking=True)
+            targets = data['semseg'].to(self.device, non_blocking=True)
+            out = self.vae_model(2. * x - 1., sample_posterior=sample_posterior, generator=gd)
+            sums += torch.stack(self.compute_point_loss(out, targets, generator=g)).double() * x.shape[0]
+            images += x.shape[0]
+        if images == 0:
+            raise ValueError("validation_loss: the loader gave no batch")
+        total, ce, kl, mask = (sums / images).cpu().tolist()
+        return {'loss': total, 'ce': ce, 'kl': kl, 'mask': mask, 'images': images}
 
     @torch.no_grad()
     def compute_miou(self, dataloader, threshold_output: bool = False) -> dict:

@@ -1,0 +1,106 @@
+"""Cost of the seg-VAE's stage-1 loss: `TrainerAE.compute_point_loss` (csrc/point_loss.hip: class presence, uncertainty, radix
+select, loss and finish kernels + the KL launch) against the same loss written as a chain of torch ops (tests/point_loss_ref.py:
+grid_sample, topk over [B,128,3P] and [N,1,3P], gathers, BCE / Dice) around the SAME VAE handle.
+
+  python tools/ae_loss_cost.py [--B 8] [--size 512] [--segments 20] [--points 12544] [--dtype bf16] [--regions 15]
+                               [--out profiles/ae_loss_cost.json]
+
+Shape: B = 8 maps of 512 x 512 with about 20 segments each -> logits [8,128,256,256]; P = 12544, oversample 3, importance 0.75.
+Both paths read the host once per call (the number of object masks), so a call is timed with the host clock around a
+synchronised call; the calls of the two paths alternate in one process after a warm-up of each; reported: median and min-max of
+the milliseconds per call.  `loss` rows time the loss alone on fixed logits and moments, `forward+loss` rows include the VAE
+forward.  Both paths draw on the device from a generator with the same seed (same shapes, same order: the same points), so their
+values are compared as well.  A record, not a gate."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "latent-diffusion-segmentation_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+DEV = "cuda:0"
+
+
+def main():
+    import torch
+    import point_loss_ref as R
+    from ldmseg_amd import weights
+    from ldmseg_amd.data.bitcodec import encode_bitmap
+    from ldmseg_amd.models import GeneralVAESeg
+    from ldmseg_amd.trainers import TrainerAE
+    from ldmseg_amd.trainers.losses import draw_plan
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=8); ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--segments", type=int, default=20); ap.add_argument("--points", type=int, default=12544)
+    ap.add_argument("--dtype", default="bf16"); ap.add_argument("--regions", type=int, default=15)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ae_loss_cost.json"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("ae_loss_cost.py measures on the GPU; none found")
+    B, S, P = args.B, args.size, args.points
+    g = torch.Generator().manual_seed(0)
+    # blocky maps: 64 x 64 blocks whose ids come from `segments` labels per image (0 = ignore_label among them)
+    blocks = S // 64
+    ids = torch.stack([torch.randperm(127, generator=g)[:args.segments][torch.randint(0, args.segments, (blocks, blocks), generator=g)]
+                       for _ in range(B)])
+    targets = ids.repeat_interleave(64, 1).repeat_interleave(64, 2).to(DEV)
+    segments = [int(t.unique().numel()) for t in targets]
+    bits, _ = encode_bitmap(targets, n=7, fill_value=0.5, ignore_label=0)
+    vae = GeneralVAESeg(weights.generate(weights.vae_schema(), seed=7, norm_keys=weights.VAE_NORM_KEYS), device=DEV,
+                        compute_dtype=args.dtype)
+    tr = TrainerAE(vae, device=DEV, loss_weights={"mask": 1.0, "ce": 1.0, "kl": 1e-6},
+                   loss_kwargs=dict(num_points=P, oversample_ratio=3, importance_sample_ratio=0.75))
+    fixed = vae(2. * bits - 1., sample_posterior=False)
+
+    def torch_loss(out):
+        x = out.sample
+        rows = R.mask_rows(targets, x.shape[1], 0)                       # (one host read: nonzero)
+        gg = torch.Generator(device=DEV).manual_seed(1)
+        draws = {n: torch.rand(s, generator=gg, device=DEV) for n, s in draw_plan(B, int(rows.numel()), P, 3, 0.75)}
+        r = R.point_loss(x, targets, None, draws, P, 3, 0.75, 1.0, 0)
+        kl = R.gaussian_kl(out.posterior.parameters).mean()
+        return r["ce"] + r["mask"] + 1e-6 * kl, r["ce"], kl, r["mask"]
+
+    def new_loss(out):
+        return tr.compute_point_loss(out, targets, generator=torch.Generator(device=DEV).manual_seed(1))
+
+    fns = {"loss": {"new": lambda: new_loss(fixed), "torch": lambda: torch_loss(fixed)},
+           "forward+loss": {"new": lambda: new_loss(vae(2. * bits - 1., sample_posterior=False)),
+                            "torch": lambda: torch_loss(vae(2. * bits - 1., sample_posterior=False))}}
+    records = []
+
+    def emit(**r):
+        records.append(r)
+        print(json.dumps(r), flush=True)
+
+    a, b = new_loss(fixed), torch_loss(fixed)
+    torch.cuda.synchronize()
+    emit(what="value_check", **{n: dict(new=float(x), torch=float(y), rel_diff=abs(float(x) - float(y)) / max(abs(float(y)), 1e-30))
+                                for n, x, y in zip(("total", "ce", "kl", "mask"), a, b)})
+    base = dict(B=B, size=S, logits=list(fixed.sample.shape), points=P, segments_per_image=segments, dtype=args.dtype,
+                regions=args.regions, clock="host, synchronised call")
+    for what, pair in fns.items():
+        res = {k: [] for k in pair}
+        for it in range(3 + args.regions):                               # 3 warm-up rounds of each path
+            for name, fn in pair.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if it >= 3:
+                    res[name].append(1e3 * (time.perf_counter() - t0))
+        for name, ms in res.items():
+            emit(**dict(base, what=what, impl=name, ms=round(statistics.median(ms), 4), ms_min=round(min(ms), 4),
+                        ms_max=round(max(ms), 4)))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(records, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

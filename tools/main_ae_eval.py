@@ -6,17 +6,21 @@ sampler can reach, and the check to run after loading `ae.pt`.
 
     python tools/main_ae_eval.py --panoptic DIR [--ae ae.pt] [--size 512] [--batch 8] [--dtype bf16]
                                  [--mask-th 0.5] [--count-th 512] [--overlap-th 0.5] [--out DIR] [--device-pq]
+                                 [--val-loss [--seed 0]]
 
 Per image: COCO panoptic PNG -> segment ids -> remapped to random distinct labels in [1, 128) with the background (0) fixed
 (coco.py:320-348, seeded here) -> nearest-neighbour resize of the longer side to --size and zero padding to a square (the
 padding is `ignore_label`, the padding mask marks the image) -> 7 bit planes through the library's bit codec.  Then
 `TrainerAE.compute_miou` (reconstruction against the remapped map at the network size) and `TrainerAE.compute_pq`
 (reconstruction cropped and resized to the original size, class-agnostic PQ against the PNG itself).
+With --val-loss also the stage-1 loss the reference's training loop logs (`TrainerAE.validation_loss`: point CE + mask + KL), as
+one extra JSON line.
 Without --ae deterministic random weights of the right architecture are used: the pipeline runs end to end but the numbers
 are meaningless.
 """
 import argparse
 import glob
+import json
 import os
 import sys
 
@@ -86,13 +90,13 @@ def build_trainer(args, device):
                      overlap_th=args.overlap_th, device=device)
 
 
-def evaluate(args, device, files):
+def evaluate(args, device, files, trainer=None):
     """-> (mIoU result dict, PQ result dict, evaluator)."""
     import torch.distributed as dist
     from ldmseg_amd.evaluations import PanopticEvaluatorAgnostic, rgb2id
     from ldmseg_amd.evaluations.panoptic_evaluation_agnostic import gt_from_png
     from PIL import Image
-    trainer = build_trainer(args, device)
+    trainer = trainer if trainer is not None else build_trainer(args, device)
     gt_maps, gt_anns = {}, []
     for f in sorted(glob.glob(os.path.join(args.panoptic, "*.png"))):
         iid = os.path.splitext(os.path.basename(f))[0]
@@ -119,6 +123,9 @@ def main():
     ap.add_argument("--out", default=None, help="folder for the prediction PNGs and the evaluator's predictions.json")
     ap.add_argument("--device-pq", action="store_true",
                     help="score PQ on the GPU (PanopticEvaluatorAgnostic.process_device): no map is copied to the host")
+    ap.add_argument("--val-loss", action="store_true",
+                    help="also print the stage-1 loss (TrainerAE.validation_loss: total / ce / kl / mask) as one JSON line")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the point draws of --val-loss")
     args = ap.parse_args()
     if args.size % 8:
         ap.error("--size must be a multiple of 8")
@@ -131,12 +138,17 @@ def main():
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
     files = sorted(glob.glob(os.path.join(args.panoptic, "*.png")))[rank::world]      # images sharded over ranks
-    miou, pq, ev = evaluate(args, device, files)
+    trainer = build_trainer(args, device)
+    miou, pq, ev = evaluate(args, device, files, trainer)
+    # the stage-1 loss of this rank's images (the point draws are per process; ranks are not averaged)
+    val = trainer.validation_loss(batches(files, args.size, args.batch, device), seed=args.seed) if args.val_loss else None
     if rank == 0:
         print(f"mIoU {float(100 * miou['mIoU'])!r}")
         print(ev.table)
         r = pq["panoptic_seg"]
         print(f"PQ {float(r['PQ'])!r} SQ {float(r['SQ'])!r} RQ {float(r['RQ'])!r} num_predictions {r['num_predictions']}")
+        if val is not None:
+            print(json.dumps({"val_loss": val}))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
