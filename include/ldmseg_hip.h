@@ -475,6 +475,30 @@ int ldmseg_point_loss(const float* x, int B, int C, int H, int W, const int64_t*
 /* DiagonalGaussianDistribution.kl() (vae.py:416-417) on moments [B, 2 * latent_channels, HW] (mean | logvar, logvar clamped to
  * [-30, 20]): per_image[b] = 0.5 * sum(mean^2 + exp(logvar) - 1 - logvar), added in fp64; mean (may be NULL) = their batch mean. */
 int ldmseg_gaussian_kl(const float* moments, int B, int latent_channels, int HW, float* per_image, float* mean, void* stream);
+/* Backward of ldmseg_point_loss to the logits: grad_x [B,C,H,W] = grad_ce * d ce / d x + grad_mask * d (out[1] + out[2]) / d x for
+ * the call that had these arguments and returned `selected` (int32 [B+N,kU]; may be NULL only when kU == 0).  Coordinates, the
+ * selection, the labels and the targets carry no gradient (the reference computes them under no_grad); the one differentiable path
+ * is the bilinear sample of x at the chosen points.  grad_ce_dev / grad_mask_dev: device fp32 scalars; NULL = 0, and that term's
+ * rows are then not evaluated at all.
+ *   ce    point p of image b: (softmax_c(x_p / T) - [c == label_p]) / (T * K), K = kept points of the batch; dropped points give 0,
+ *         and K == 0 gives 0 everywhere (the forward's ce is NaN there).
+ *   mask  row (b, c), s = sigmoid(l), I = sum s t, D = sum s + sum t:
+ *         ((s - t) / P - (2 t (D + 1) - (2 I + 1)) / (D + 1)^2 * s (1 - s)) / num_masks.
+ * Each point gradient reaches grad_x[b, c] through its (up to four) taps inside the map.  No float atomics: every tap is stored
+ * once into a per-pixel list (integer atomics count and place them), each list is ordered by (row, point, tap), and one pass over
+ * the pixels adds every list in that order - two calls on the same inputs agree bit for bit.  grad_x is written completely (0.0
+ * where no tap lands); the caller clears nothing.  scratch: ldmseg_point_loss_backward_scratch_bytes(...) bytes of device memory
+ * (0 for sizes the call would refuse).  4 launches and one memset on `stream`; no host synchronisation, no allocation. */
+size_t ldmseg_point_loss_backward_scratch_bytes(int B, int C, int H, int W, int N, int kU, int P);
+int ldmseg_point_loss_backward(const float* x, int B, int C, int H, int W, const int64_t* targets, const uint8_t* valid, int Ht,
+                               int Wt, const int32_t* mask_rows_dev, int N, const float* ce_over, const float* ce_fresh,
+                               const float* mask_over, const float* mask_fresh, const int32_t* selected, int S, int kU, int P,
+                               int64_t ignore_label, float temperature, double num_masks, const float* grad_ce_dev,
+                               const float* grad_mask_dev, float* grad_x, void* scratch, void* stream);
+/* Backward of ldmseg_gaussian_kl: grad_moments [B, 2 * latent_channels, HW] = grad_per_image[b] * (mean | 0.5 * (exp(logvar) - 1)
+ * where -30 <= logvar <= 20, else 0) - the clamp passes gradient at its bounds, like torch.clamp.  One elementwise launch. */
+int ldmseg_gaussian_kl_backward(const float* moments, int B, int latent_channels, int HW, const float* grad_per_image_dev,
+                                float* grad_moments, void* stream);
 
 /* ---- sampler: TrainerDiffusion.sample (trainers_ldm_cond.py:1045-1170) -------------------- */
 typedef struct {

@@ -511,6 +511,26 @@ int launch_class_presence(const int64_t* targets, const uint8_t* valid, int B, i
 size_t point_loss_scratch_bytes(int rows, int S, int kU, int P);
 int launch_point_loss(const PointLoss& p, double num_masks, float* out, int32_t* selected, void* scratch, hipStream_t s);
 int launch_gaussian_kl(const float* moments, int B, int n, float* per_image, float* mean, hipStream_t s);
+// its backward to the logits and to the moments (point_loss_bwd.hip); arguments as ldmseg_point_loss_backward /
+// ldmseg_gaussian_kl_backward
+struct PointLossGrad {
+  PointLoss f;                // the forward's arguments; f.sel = the forward's `selected`
+  double num_masks;
+  const float* g_ce;          // device scalars d(result) / d(ce), d(result) / d(mask); null: that term's rows take no part
+  const float* g_mask;
+  float* grad_x;              // [B][C][H][W], every element written
+  double* stat;               // filled by the launcher
+  float* rec_a;
+  float* rec_b;
+  int32_t* rec_label;
+  int32_t* count;
+  int32_t* cursor;
+  int32_t* img_base;
+  unsigned long long* entries;
+};
+size_t point_loss_backward_scratch_bytes(int B, int C, int H, int W, int N, int kU, int P);
+int launch_point_loss_backward(const PointLossGrad& g, void* scratch, hipStream_t s);
+int launch_gaussian_kl_backward(const float* moments, int B, int n, const float* grad_per_image, float* grad_moments, hipStream_t s);
 int launch_bit_encode(const int64_t* ids, float* out, uint8_t* ignore, int B, int n, int HW, int64_t ignore_label,
                       float fill, float mul, float add, hipStream_t s);
 int launch_bit_decode(const float* x, int64_t* out, int B, int n, int HW, hipStream_t s);

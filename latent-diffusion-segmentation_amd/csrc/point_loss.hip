@@ -1,4 +1,5 @@
-// The seg-VAE's stage-1 loss (trainers_ae.py:204-216), forward only: SegmentationLosses.point_loss (losses.py:364-394) - the
+// The seg-VAE's stage-1 loss (trainers_ae.py:204-216), the forward value (its gradient to the logits and the moments is
+// point_loss_bwd.hip; what both evaluate per point is point_loss_dev.h): SegmentationLosses.point_loss (losses.py:364-394) - the
 // PointRend cross entropy on uncertain points (loss_ce, :303-362) and the per-object BCE + Dice on uncertain points (loss_masks,
 // :117-185 with prepare_targets :397-439) - and posterior.kl() (vae.py:416-417).  fp32 NCHW logits x [B,C,H,W], int64 targets
 // [B,Ht,Wt], an optional validity mask, and device buffers of uniform draws (nothing is drawn here).
@@ -30,19 +31,13 @@
 #include "../../include/ldmseg_hip_ops.h"
 #include "common.h"
 #include "kernels.h"
+#include "point_loss_dev.h"
 #include "point_sample.h"
 
 namespace ldmseg {
 namespace {
 
-constexpr int kThreads = 256;
-
-// effective target of pixel i of image b: the masked pixels count as ignore_label (losses.py:326, without touching the caller's tensor)
-__device__ __forceinline__ int64_t eff_target(const PointLoss& p, int b, int i) {
-  const size_t at = (size_t)b * p.Ht * p.Wt + i;
-  if (p.valid && !p.valid[at]) return p.ignore;
-  return p.tgt[at];
-}
+using namespace pointloss;      // point_loss_dev.h: what the backward (point_loss_bwd.hip) evaluates per point too
 
 // ---------------------------------------------------------------- class presence
 __global__ __launch_bounds__(kThreads) void class_presence_kernel(const int64_t* tgt, const uint8_t* valid, int n, int C, int64_t ignore,
@@ -64,28 +59,6 @@ __global__ __launch_bounds__(kThreads) void class_presence_kernel(const int64_t*
   for (int c = threadIdx.x; c < C; c += kThreads)
     if (s_seen[c]) present[(size_t)b * C + c] = 1;   // (the table is zeroed by the launcher; workgroups of an image store the same 1)
   if (bad) atomicOr(flag, 1);
-}
-
-// ---------------------------------------------------------------- rows
-struct Row {
-  int b, c;                  // c < 0: the cross-entropy row of image b
-  const float* over;         // [S][2] or null
-  const float* fresh;        // [P - kU][2]
-};
-__device__ __forceinline__ Row row_of(const PointLoss& p, int r) {
-  Row w;
-  if (r < p.B) {
-    w.b = r; w.c = -1;
-    w.over = p.ce_over ? p.ce_over + (size_t)r * p.S * 2 : nullptr;
-    w.fresh = p.ce_fresh ? p.ce_fresh + (size_t)r * (p.P - p.kU) * 2 : nullptr;
-  } else {
-    const int m = r - p.B;
-    const int bc = p.rows[m];
-    w.b = bc / p.C; w.c = bc - w.b * p.C;
-    w.over = p.m_over ? p.m_over + (size_t)m * p.S * 2 : nullptr;
-    w.fresh = p.m_fresh ? p.m_fresh + (size_t)m * (p.P - p.kU) * 2 : nullptr;
-  }
-  return w;
 }
 
 // ---------------------------------------------------------------- uncertainty
@@ -184,19 +157,6 @@ __global__ __launch_bounds__(kThreads) void point_select_kernel(const float* unc
 }
 
 // ---------------------------------------------------------------- loss
-// sum over the workgroup in a fixed order: lanes by xor-shuffle tree, then the four waves in order; valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double* s_red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) s_red[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kThreads / 64; ++w) t += s_red[w];
-  return t;
-}
-
 // partial[(r * nchunk + chunk) * 4 + k]: CE rows {sum of point losses, kept points, -, -}; mask rows {bce, sigmoid * t, sigmoid, t}
 __global__ __launch_bounds__(kThreads) void point_loss_kernel(const PointLoss p) {
 #pragma clang fp contract(off)
@@ -206,48 +166,20 @@ __global__ __launch_bounds__(kThreads) void point_loss_kernel(const PointLoss p)
   const Row w = row_of(p, r);
   double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
   if (j < p.P) {
-    float ux, uy;
-    if (j < p.kU) {
-      int i = p.sel[(size_t)r * p.kU + j];
-      i = i < 0 ? 0 : (i >= p.S ? p.S - 1 : i);
-      ux = w.over[2 * i]; uy = w.over[2 * i + 1];
-    } else {
-      ux = w.fresh[2 * (j - p.kU)]; uy = w.fresh[2 * (j - p.kU) + 1];
-    }
-    const BilinearTaps t = bilinear_taps(ux, uy, p.H, p.W);
-    const size_t plane = (size_t)p.H * p.W;
+    const PointUV u = point_uv(p, w, r, j);
+    const BilinearTaps t = bilinear_taps(u.x, u.y, p.H, p.W);
     if (w.c < 0) {
-      // grid_sample(mode='nearest') of the float target map with zeros padding: outside the map the label is 0
-      const int ti = nearest_tap(ux, uy, p.Ht, p.Wt);
-      const int64_t label = ti < 0 ? 0 : eff_target(p, w.b, ti);
-      if (label != p.ignore) {
-        const float* xb = p.x + (size_t)w.b * p.C * plane;
-        float mx = -INFINITY, at_label = 0.0f;
-        for (int c = 0; c < p.C; ++c) {
-          const float* xc = xb + (size_t)c * plane;
-          const float v = __fdiv_rn(bilinear_sample(t, p.H, p.W, [&](int i) { return xc[i]; }), p.temperature);
-          mx = fmaxf(mx, v);
-          if (c == label) at_label = v;
-        }
-        double sum = 0.0;
-        for (int c = 0; c < p.C; ++c) {
-          const float* xc = xb + (size_t)c * plane;
-          const float v = __fdiv_rn(bilinear_sample(t, p.H, p.W, [&](int i) { return xc[i]; }), p.temperature);
-          sum += (double)expf(v - mx);
-        }
-        a0 = ((double)mx + log(sum)) - (double)at_label;
+      const CePoint q = ce_point(p, w, u, t);
+      if (q.kept) {
+        a0 = ((double)q.mx + log(q.sum)) - (double)q.at_label;
         a1 = 1.0;
       }
     } else {
-      const float* xc = p.x + ((size_t)w.b * p.C + w.c) * plane;
-      const float x = bilinear_sample(t, p.H, p.W, [&](int i) { return xc[i]; });
-      const BilinearTaps tt = bilinear_taps(ux, uy, p.Ht, p.Wt);
-      const int64_t cls = w.c;
-      const float y = bilinear_sample(tt, p.Ht, p.Wt, [&](int i) { return eff_target(p, w.b, i) == cls ? 1.0f : 0.0f; });
+      const MaskPoint q = mask_point(p, w, u, t);
       // binary_cross_entropy_with_logits: (1 - y) * x + max(-x, 0) + log(1 + exp(-|x|))
-      const double xd = (double)x, yd = (double)y;
+      const double xd = (double)q.x, yd = (double)q.y;
       a0 = (1.0 - yd) * xd + (xd < 0.0 ? -xd : 0.0) + log1p(exp(-fabs(xd)));
-      const double sg = (double)(1.0f / (1.0f + expf(-x)));
+      const double sg = (double)q.sg;
       a1 = sg * yd; a2 = sg; a3 = yd;
     }
   }
@@ -311,7 +243,6 @@ inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 struct PointScratch {
   size_t partial, unc, sel, total;
 };
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline PointScratch point_scratch(int rows, int S, int kU, int P) {
   PointScratch l;
   const size_t nchunk = (size_t)(P + kThreads - 1) / kThreads;

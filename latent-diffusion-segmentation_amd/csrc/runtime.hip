@@ -270,6 +270,51 @@ int ldmseg_gaussian_kl(const float* moments, int B, int latent_channels, int HW,
   return 0;
 }
 
+size_t ldmseg_point_loss_backward_scratch_bytes(int B, int C, int H, int W, int N, int kU, int P) {
+  if (C > LDMSEG_POINT_LOSS_MAX_C) return 0;
+  return point_loss_backward_scratch_bytes(B, C, H, W, N, kU, P);
+}
+
+int ldmseg_point_loss_backward(const float* x, int B, int C, int H, int W, const int64_t* targets, const uint8_t* valid, int Ht,
+                               int Wt, const int32_t* mask_rows_dev, int N, const float* ce_over, const float* ce_fresh,
+                               const float* mask_over, const float* mask_fresh, const int32_t* selected, int S, int kU, int P,
+                               int64_t ignore_label, float temperature, double num_masks, const float* grad_ce_dev,
+                               const float* grad_mask_dev, float* grad_x, void* scratch, void* stream) {
+  g_err.clear();
+  if (!x || !targets || !grad_x || !scratch) return fail(LDMSEG_E_ARG, "null argument");
+  if (C < 1 || C > LDMSEG_POINT_LOSS_MAX_C) return fail(LDMSEG_E_SHAPE, "C must be 1..LDMSEG_POINT_LOSS_MAX_C");
+  if (B < 1 || N < 0 || N > B * C || B + N > 65535) return fail(LDMSEG_E_SHAPE, "B >= 1, 0 <= N <= B * C, B + N <= 65535");
+  if (H < 1 || W < 1 || Ht < 1 || Wt < 1 || (int64_t)H * W > (int64_t)0x7fff0000 || (int64_t)Ht * Wt > (int64_t)0x7fff0000)
+    return fail(LDMSEG_E_SHAPE, "map sizes must be positive, H * W and Ht * Wt below 2^31");
+  if (P < 1 || kU < 0 || kU > P || S < kU || (kU > 0 && S < 1) || (int64_t)(B + N) * (S > P ? S : P) > (int64_t)0x1fff0000)
+    return fail(LDMSEG_E_ARG, "need 0 <= kU <= P, kU <= S, (B + N) * max(S, P) below 2^29");
+  if (!(temperature > 0.0f)) return fail(LDMSEG_E_ARG, "temperature must be positive");
+  if (N > 0 && (!mask_rows_dev || !(num_masks > 0.0))) return fail(LDMSEG_E_ARG, "mask rows need mask_rows_dev and num_masks > 0");
+  if (kU > 0 && (!selected || !ce_over || (N > 0 && !mask_over)))
+    return fail(LDMSEG_E_ARG, "kU > 0 needs the oversampled draws and the forward's selected indices");
+  if (P > kU && (!ce_fresh || (N > 0 && !mask_fresh))) return fail(LDMSEG_E_ARG, "P > kU needs the fresh draws");
+  PointLossGrad g{};
+  PointLoss& p = g.f;
+  p.x = x; p.B = B; p.C = C; p.H = H; p.W = W; p.tgt = targets; p.valid = valid; p.Ht = Ht; p.Wt = Wt;
+  p.rows = mask_rows_dev; p.N = N; p.ce_over = ce_over; p.ce_fresh = ce_fresh; p.m_over = mask_over; p.m_fresh = mask_fresh;
+  p.S = S; p.kU = kU; p.P = P; p.ignore = ignore_label; p.temperature = temperature;
+  p.sel = const_cast<int32_t*>(selected);            // (read only)
+  g.num_masks = N > 0 ? num_masks : 1.0;
+  g.g_ce = grad_ce_dev; g.g_mask = N > 0 ? grad_mask_dev : nullptr; g.grad_x = grad_x;
+  TRY(launch_point_loss_backward(g, scratch, (hipStream_t)stream));
+  return 0;
+}
+
+int ldmseg_gaussian_kl_backward(const float* moments, int B, int latent_channels, int HW, const float* grad_per_image_dev,
+                                float* grad_moments, void* stream) {
+  g_err.clear();
+  if (!moments || !grad_per_image_dev || !grad_moments) return fail(LDMSEG_E_ARG, "null argument");
+  if (B < 1 || B > 65535 || latent_channels < 1 || HW < 1 || (int64_t)latent_channels * HW > (int64_t)0x3fff0000)
+    return fail(LDMSEG_E_SHAPE, "B in 1..65535, latent_channels * HW in 1..2^30");
+  TRY(launch_gaussian_kl_backward(moments, B, latent_channels * HW, grad_per_image_dev, grad_moments, (hipStream_t)stream));
+  return 0;
+}
+
 int ldmseg_bit_encode(const int64_t* ids, int B, int n_bits, int HW, int64_t ignore_label, float fill_value, float mul,
                       float add, float* bits, uint8_t* ignore_mask, void* stream) {
   g_err.clear();

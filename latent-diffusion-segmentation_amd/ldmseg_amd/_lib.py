@@ -82,6 +82,10 @@ SIGNATURES = {
     "ldmseg_point_loss": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _f, _d,
                                _vp, _vp, _vp, _vp]),
     "ldmseg_gaussian_kl": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "ldmseg_point_loss_backward_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "ldmseg_point_loss_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _f,
+                                        _d, _vp, _vp, _vp, _vp, _vp]),
+    "ldmseg_gaussian_kl_backward": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "ldmseg_unet_reserve": (_i, [_vp, _i, _i]),
     "ldmseg_unet_set_attention_fp8": (_i, [_vp, _i]),
     "ldmseg_unet_gn_fallbacks": (_i, [_vp, _vp]),

@@ -10,6 +10,7 @@ import ctypes as C
 from typing import Optional, Tuple, Union
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from .. import _lib
 from ..utils import EncoderOutput, VAEOutput
@@ -54,8 +55,16 @@ class DiagonalGaussianDistribution(object):
 
     def kl(self, return_mean: bool = False):
         """:416-417: 0.5 * sum(mean^2 + var - 1 - logvar) per image, [B] on the device (ldmseg_gaussian_kl; fp64 sums).  With
-        return_mean the pair (per image [B], batch mean 0-d) of the same call."""
-        p = _lib.require_cuda_f32(self.parameters, "moments")
+        return_mean the pair (per image [B], batch mean 0-d) of the same call.  With grad mode on and `parameters` requiring
+        grad the results are differentiable with respect to them (once: ldmseg_gaussian_kl_backward)."""
+        if torch.is_grad_enabled() and isinstance(self.parameters, torch.Tensor) and self.parameters.requires_grad:
+            per, mean = _GaussianKLFunction.apply(_lib.require_cuda_f32(self.parameters, "moments"))
+            return (per, mean) if return_mean else per
+        with torch.no_grad():
+            return self._kl_forward(_lib.require_cuda_f32(self.parameters, "moments"), return_mean)
+
+    @staticmethod
+    def _kl_forward(p: torch.Tensor, return_mean: bool):
         B, C2 = p.shape[0], p.shape[1]
         per = torch.empty(B, device=p.device, dtype=torch.float32)
         mean = torch.empty(1, device=p.device, dtype=torch.float32) if return_mean else None
@@ -63,6 +72,37 @@ class DiagonalGaussianDistribution(object):
             _lib.check(_lib.lib().ldmseg_gaussian_kl(_lib.ptr(p), B, C2 // 2, p[0, 0].numel(), _lib.ptr(per), _lib.ptr(mean),
                                                      _lib.stream_ptr(p.device)), "ldmseg_gaussian_kl")
         return (per, mean[0]) if return_mean else per
+
+
+class _GaussianKLFunction(torch.autograd.Function):
+    """(kl per image [B], batch mean) of fp32 contiguous moments with a backward to them: d kl_b / d mean = mean,
+    d kl_b / d logvar = 0.5 * (exp(logvar) - 1) where the clamp passes gradient; the batch mean adds grad / B per image."""
+
+    @staticmethod
+    def forward(ctx, p):
+        per, mean = DiagonalGaussianDistribution._kl_forward(p, True)
+        ctx.save_for_backward(p)
+        ctx.set_materialize_grads(False)
+        return per, mean.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_per, grad_mean):
+        p, = ctx.saved_tensors
+        if grad_per is None and grad_mean is None:
+            return None
+        B, C2 = p.shape[0], p.shape[1]
+        g = torch.zeros(B, device=p.device, dtype=torch.float32)
+        if grad_per is not None:
+            g = g + grad_per.to(device=p.device, dtype=torch.float32)
+        if grad_mean is not None:
+            g = g + grad_mean.to(device=p.device, dtype=torch.float32) / B
+        g = g.contiguous()
+        grad = torch.empty_like(p)
+        with torch.cuda.device(p.device):
+            _lib.check(_lib.lib().ldmseg_gaussian_kl_backward(_lib.ptr(p), B, C2 // 2, p[0, 0].numel(), _lib.ptr(g), _lib.ptr(grad),
+                                                              _lib.stream_ptr(p.device)), "ldmseg_gaussian_kl_backward")
+        return grad
 
 
 class GeneralVAESeg(object):

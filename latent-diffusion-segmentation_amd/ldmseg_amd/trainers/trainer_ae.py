@@ -2,8 +2,9 @@
 
 Stands behind the evaluation half of the reference's ldmseg/trainers/trainers_ae.py::TrainerAE
 (`compute_metrics` :546-569, `compute_pq` :580-680, `compute_miou` :728-803) - what `tools/main_ae.py` runs with
-`eval_only` (:189-190) - and behind the forward half of its training step: `compute_point_loss` (:204-224), the number
-the stage-1 loop logs and selects checkpoints by.  Backward, optimiser, image dumps and overlays (`save_images`) are not built.
+`eval_only` (:189-190) - and behind the loss of its training step: `compute_point_loss` (:204-224), the number the stage-1
+loop logs and selects checkpoints by, differentiable with respect to the logits and the moments it is given (the `loss.backward()`
+of :286-296 as far as the loss goes).  Network backward, optimiser, image dumps and overlays (`save_images`) are not built.
 
 Per batch ONE library call does encode -> posterior mode -> decode -> the metric's tail
 (`GeneralVAESeg.reconstruct_semseg` / `reconstruct_panoptic`); the [B,128,S,S] logits are never materialised and the
@@ -65,11 +66,11 @@ class TrainerAE(object):
 
     crop_padding = staticmethod(TrainerDiffusion.crop_padding)          # :571-577
 
-    @torch.no_grad()
     def compute_point_loss(self, outputs, targets, do_matching: bool = False, masks=None, generator=None):
         """:204-216 on the VAEOutput of `vae_model(...)` (`.sample` logits [B,C,4L,4L], `.posterior`) and targets [B,h,w]:
         (total, ce, kl, mask) as 0-d device tensors; total is the three terms weighted by `loss_weights`, added in the order
-        ce, mask, kl.  Forward only."""
+        ce, mask, kl.  With grad mode on, the values are differentiable with respect to the logits and the posterior's moments
+        where those require grad (`total.backward()`); the library's own seg-VAE produces neither with a graph."""
         parts = self.segmentation_losses.point_loss(outputs.sample, targets, do_matching, masks, generator=generator)
         ce, mask = parts['ce'], parts['mask']
         kl = outputs.posterior.kl(return_mean=True)[1]

@@ -10,7 +10,14 @@ Both paths read the host once per call (the number of object masks), so a call i
 synchronised call; the calls of the two paths alternate in one process after a warm-up of each; reported: median and min-max of
 the milliseconds per call.  `loss` rows time the loss alone on fixed logits and moments, `forward+loss` rows include the VAE
 forward.  Both paths draw on the device from a generator with the same seed (same shapes, same order: the same points), so their
-values are compared as well.  A record, not a gate."""
+values are compared as well.  A record, not a gate.
+
+  python tools/ae_loss_cost.py --backward [--out profiles/ae_loss_backward_cost.json]
+
+times forward + backward instead: `compute_point_loss` on leaf logits and moments that require grad, then `total.backward()`
+(csrc/point_loss_bwd.hip), against forward + backward of the torch-op chain under autograd, on the same fixed fp32 logits
+[B,128,S/2,S/2] and moments, alternating in one process; the two gradients are compared (max|diff| / max|grad|).  The chain's
+selection runs as tests/point_loss_ref.py writes it, with grad recording on; its backward does not pass through it."""
 import argparse
 import json
 import os
@@ -37,8 +44,11 @@ def main():
     ap.add_argument("--B", type=int, default=8); ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--segments", type=int, default=20); ap.add_argument("--points", type=int, default=12544)
     ap.add_argument("--dtype", default="bf16"); ap.add_argument("--regions", type=int, default=15)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ae_loss_cost.json"))
+    ap.add_argument("--backward", action="store_true", help="time forward + backward of the loss on fixed logits and moments")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "ae_loss_backward_cost.json" if args.backward else "ae_loss_cost.json")
     if not torch.cuda.is_available():
         raise SystemExit("ae_loss_cost.py measures on the GPU; none found")
     B, S, P = args.B, args.size, args.points
@@ -68,19 +78,37 @@ def main():
     def new_loss(out):
         return tr.compute_point_loss(out, targets, generator=torch.Generator(device=DEV).manual_seed(1))
 
-    fns = {"loss": {"new": lambda: new_loss(fixed), "torch": lambda: torch_loss(fixed)},
-           "forward+loss": {"new": lambda: new_loss(vae(2. * bits - 1., sample_posterior=False)),
-                            "torch": lambda: torch_loss(vae(2. * bits - 1., sample_posterior=False))}}
     records = []
 
     def emit(**r):
         records.append(r)
         print(json.dumps(r), flush=True)
 
-    a, b = new_loss(fixed), torch_loss(fixed)
-    torch.cuda.synchronize()
-    emit(what="value_check", **{n: dict(new=float(x), torch=float(y), rel_diff=abs(float(x) - float(y)) / max(abs(float(y)), 1e-30))
-                                for n, x, y in zip(("total", "ce", "kl", "mask"), a, b)})
+    if args.backward:
+        from ldmseg_amd.models.vae import DiagonalGaussianDistribution
+        from ldmseg_amd.utils import VAEOutput
+        xg = fixed.sample.detach().float().contiguous().requires_grad_(True)
+        mg = fixed.posterior.parameters.detach().float().contiguous().requires_grad_(True)
+
+        def step(loss):
+            xg.grad = mg.grad = None
+            total = loss(VAEOutput(sample=xg, posterior=DiagonalGaussianDistribution(mg)))[0]
+            total.backward()
+            return total.detach(), xg.grad, mg.grad
+        fns = {"loss+backward": {"new": lambda: step(new_loss), "torch": lambda: step(torch_loss)}}
+        a, b = step(new_loss), step(torch_loss)
+        torch.cuda.synchronize()
+        rel = lambda x, y: float((x - y).abs().max()) / max(float(y.abs().max()), 1e-30)
+        emit(what="gradient_check", total=dict(new=float(a[0]), torch=float(b[0])), grad_logits_rel_diff=rel(a[1], b[1]),
+             grad_moments_rel_diff=rel(a[2], b[2]), grad_logits_max=float(b[1].abs().max()))
+    else:
+        fns = {"loss": {"new": lambda: new_loss(fixed), "torch": lambda: torch_loss(fixed)},
+               "forward+loss": {"new": lambda: new_loss(vae(2. * bits - 1., sample_posterior=False)),
+                                "torch": lambda: torch_loss(vae(2. * bits - 1., sample_posterior=False))}}
+        a, b = new_loss(fixed), torch_loss(fixed)
+        torch.cuda.synchronize()
+        emit(what="value_check", **{n: dict(new=float(x), torch=float(y), rel_diff=abs(float(x) - float(y)) / max(abs(float(y)), 1e-30))
+                                    for n, x, y in zip(("total", "ce", "kl", "mask"), a, b)})
     base = dict(B=B, size=S, logits=list(fixed.sample.shape), points=P, segments_per_image=segments, dtype=args.dtype,
                 regions=args.regions, clock="host, synchronised call")
     for what, pair in fns.items():
