@@ -56,9 +56,33 @@ int ldmseg_op_attention_cross(const float* q, const float* kv, int B, int N, int
  * + kernel) into *us_per_launch; out may be NULL then. */
 int ldmseg_op_attention_fp8(const float* qkv, int B, int N, int C, int heads, float* out, int time_iters, float* us_per_launch,
                             void* stream);
-/* nn.ConvTranspose2d(Ci, Co, kernel_size=2, stride=2)  (vae.py:154) */
+/* nn.ConvTranspose2d(Ci, Co, kernel_size=2, stride=2)  (vae.py:154); dtype 0 / 1 / 2 / 3 as ldmseg_op_conv2d */
 int ldmseg_op_convt2(const float* x, const float* w, const float* bias, int B, int Ci, int H, int W, int Co, int dtype,
                      float* out, void* stream);
+/* The launch forms of the two VAEs (csrc/vae.hip), filled the way the models fill them; dtype as ldmseg_op_conv2d (0 / 1 / 2 / 3).
+ * _vae_conv: one conv as Exec::conv and the VAE heads launch it.  pad -1 = padding k/2; pad 0 (k 3, stride 2 only) =
+ * F.conv2d(F.pad(x, (0,1,0,1)), w, bias, stride=2), Ho = H / 2 (diffusers Downsample2D(padding=0) of AutoencoderKL).  epi 0: the
+ * store epilogue, + resid [B,Co,Ho,Wo], then SiLU; n_store > Co stores explicit zero channels up to n_store as the seg-VAE encoder
+ * does below a K tile (out still receives the Co real ones).  epi 2: fp32 NCHW straight from the launch (moments / logits heads;
+ * no resid, no SiLU). */
+int ldmseg_op_vae_conv(const float* x, const float* w, const float* bias, const float* resid, int B, int Ci, int H, int W, int Co, int k,
+                       int stride, int pad, int silu, int epi, int n_store, int dtype, float* out, void* stream);
+/* out [M,N] = a [M,K] @ b [N,K]^T (+ bias [N]) with an activation tensor as the weight operand (the three GEMMs of the image VAE's
+ * single-head attention: Q K^T, W_v X^T, P V + b_v).  rows_f32 != 0: fp32 rows whatever the compute dtype (the scores).  dtype 2 / 3:
+ * both operands are split in the K loop.  K a multiple of 64 (bf16) / 32, N of 32. */
+int ldmseg_op_gemm_dynamic(const float* a, const float* b, const float* bias, int M, int N, int K, int rows_f32, int dtype, float* out,
+                           void* stream);
+/* torch.softmax(scale * s, -1) of fp32 rows s [rows,n] stored in `dtype` (0 / 1), returned as fp32; scale > 0, n % 4 == 0 */
+int ldmseg_op_softmax_rows(const float* s, int rows, int n, float scale, int dtype, float* out, void* stream);
+/* The fused tail of ldmseg_vae_decode_argmax on given logits x [B,C,H,W]: y = F.interpolate(x, scale_factor=2, 'bilinear'),
+ * ids = y.argmax(1) (ignore_label where the max-softmax probability < mask_th, if mask_th >= 0), prob = softmax(y, 1).max(1) or NULL
+ * (trainers_ldm_cond.py:427-433).  dtype 0 / 1; C a multiple of 4 / 8. */
+int ldmseg_op_bilinear2x_argmax(const float* x, int B, int C, int H, int W, float mask_th, int64_t ignore_label, int dtype, int64_t* ids,
+                                float* prob, void* stream);
+/* ldmseg_op_layernorm with the buffers named: inplace != 0 normalises the tensor where it lies (what the seg-VAE decoder does behind
+ * each ConvTranspose2d), 0 writes a second buffer */
+int ldmseg_op_layernorm_io(const float* x, const float* gamma, const float* beta, int M, int C, float eps, int silu, int inplace, int dtype,
+                           float* out, void* stream);
 /* F.interpolate(scale_factor=2, mode='bilinear', align_corners=False)  (vae.py:270) */
 int ldmseg_op_bilinear2x(const float* x, int B, int C, int H, int W, int dtype, float* out, void* stream);
 

@@ -331,10 +331,10 @@ int launch_bilinear2x_nchw(const void* x, float* y, int B, int H, int W, int C, 
   dim3 grid((2 * W + 255) / 256, 2 * H, B), block(256);
   if (dtype == DT_BF16) {
     if (C % 8) return -2;
-    hipLaunchKernelGGL(bilinear2x_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)x, y, H, W, C);
+    LDMSEG_LAUNCH("bilinear2x<bf16>", bilinear2x_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)x, y, H, W, C);
   } else {
     if (C % 4) return -2;
-    hipLaunchKernelGGL(bilinear2x_kernel<float>, grid, block, 0, s, (const float*)x, y, H, W, C);
+    LDMSEG_LAUNCH("bilinear2x<f32>", bilinear2x_kernel<float>, grid, block, 0, s, (const float*)x, y, H, W, C);
   }
   return ok();
 }
@@ -344,18 +344,18 @@ int launch_bilinear2x_argmax(const void* x, int64_t* ids, float* prob, int B, in
   dim3 grid((2 * W + 255) / 256, 2 * H, B), block(256);
   if (dtype == DT_BF16) {
     if (C % 8) return -2;
-    hipLaunchKernelGGL(bilinear_argmax_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)x, ids, prob, H, W, C, mask_th, ignore_label);
+    LDMSEG_LAUNCH("bilinear_argmax<bf16>", bilinear_argmax_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)x, ids, prob, H, W, C, mask_th, ignore_label);
   } else {
     if (C % 4) return -2;
-    hipLaunchKernelGGL(bilinear_argmax_kernel<float>, grid, block, 0, s, (const float*)x, ids, prob, H, W, C, mask_th, ignore_label);
+    LDMSEG_LAUNCH("bilinear_argmax<f32>", bilinear_argmax_kernel<float>, grid, block, 0, s, (const float*)x, ids, prob, H, W, C, mask_th, ignore_label);
   }
   return ok();
 }
 
 int launch_softmax_rows(const float* sc, void* p, int rows, int n, float scale, int dtype, hipStream_t st) {
   if (n % 4) return -2;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(softmax_rows_kernel<bf16_t>, dim3((rows + 3) / 4), dim3(256), 0, st, sc, (bf16_t*)p, rows, n, scale);
-  else hipLaunchKernelGGL(softmax_rows_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, st, sc, (float*)p, rows, n, scale);
+  if (dtype == DT_BF16) LDMSEG_LAUNCH("softmax_rows<bf16>", softmax_rows_kernel<bf16_t>, dim3((rows + 3) / 4), dim3(256), 0, st, sc, (bf16_t*)p, rows, n, scale);
+  else LDMSEG_LAUNCH("softmax_rows<f32>", softmax_rows_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, st, sc, (float*)p, rows, n, scale);
   return ok();
 }
 
@@ -495,7 +495,7 @@ int launch_bit_decode(const float* x, int64_t* out, int B, int n, int HW, hipStr
 
 int launch_posterior_sample(const float* moments, const float* noise, float* out, int B, int HW, hipStream_t s) {
   const size_t total = (size_t)B * 4 * HW;
-  hipLaunchKernelGGL(posterior_sample_kernel, dim3(grid_for(total)), dim3(256), 0, s, moments, noise, out, HW, total);
+  LDMSEG_LAUNCH("posterior_sample<f32>", posterior_sample_kernel, dim3(grid_for(total)), dim3(256), 0, s, moments, noise, out, HW, total);
   return ok();
 }
 

@@ -496,6 +496,8 @@ int ldmseg_op_convt2(const float* x, const float* w, const float* bias, int B, i
                      float* out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   Temp t;
+  const int x3 = dtype == 2 ? 1 : (dtype == 3 ? 2 : 0);   // split-bf16 products on fp32 tensors (3: weights as hi | lo planes, as a bf16x3 handle)
+  if (x3) dtype = DT_F32;
   if (Ci % bke(dtype) || Co % 4) return -2;
   void* xp = t.get((size_t)B * H * W * Ci * es(dtype));
   if (launch_pack_nchw(x, xp, B, Ci, H * W, Ci, 1.f, 0.f, dtype, s)) return -3;
@@ -512,9 +514,139 @@ int ldmseg_op_convt2(const float* x, const float* w, const float* bias, int B, i
   IgemmParams p;
   p.src0 = xp; p.C0 = Ci; p.B = B; p.Hi = p.Ho = H; p.Wi = p.Wo = W; p.M = B * H * W; p.N = Np; p.n_valid = N;
   p.W = wp; p.bias = bp; p.out = op; p.ldo = Co; p.epi = EPI_CONVT2; p.cout = Co;
+  p.x3 = x3;
+  if (x3 == 2 && launch_split_planes(wp, (size_t)Np * Ci, s)) return -3;
   const int r = launch_igemm(p, dtype, s);
   if (r) return r;
   return unpack_nhwc(op, out, B, Co, 4 * H * W, Co, dtype, s);
+}
+
+// ---- the launch forms of the two VAEs (vae.hip), each with IgemmParams filled the way the model fills them
+// One conv the way Exec::conv / the VAE heads launch it: the `pad` argument of the stride-2 convs (-1: pad 1 both sides; 0: pad 0 +
+// one zero row / column at the bottom / right, Ho = H / 2), SiLU and residual in the store epilogue, `n_store` > Co = explicit zero
+// output channels up to the next layer's K tile (Builder::conv), epi = EPI_STORE or EPI_NCHW_F32 (the 8-channel heads and the
+// logits).  No channel-major packing and no extra tap: the VAE builders make neither.
+int ldmseg_op_vae_conv(const float* x, const float* w, const float* bias, const float* resid, int B, int Ci, int H, int W, int Co, int k,
+                       int stride, int pad, int silu, int epi, int n_store, int dtype, float* out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  Temp t;
+  const int x3 = dtype == 2 ? 1 : (dtype == 3 ? 2 : 0);
+  if (x3) dtype = DT_F32;
+  if (!x || !w || !out || B < 1 || Ci < 1 || Co < 1 || H < 1 || W < 1 || (k != 1 && k != 3) || (stride != 1 && stride != 2) ||
+      (pad != -1 && pad != 0) || (pad == 0 && (k != 3 || stride != 2)) || (epi != EPI_STORE && epi != EPI_NCHW_F32) ||
+      (epi == EPI_NCHW_F32 && (resid || silu)))
+    return -2;
+  const int a = bke(dtype);
+  const int c0 = rupi(Ci, a);
+  const int nreal = n_store > Co ? n_store : Co;
+  const int Np = rupi(nreal, igemm_pick_bn(nreal, epi));
+  const int Ho = (k == 3 && stride == 2) ? (pad == 0 ? H / 2 : (H - 1) / 2 + 1) : H;
+  const int Wo = (k == 3 && stride == 2) ? (pad == 0 ? W / 2 : (W - 1) / 2 + 1) : W;
+  if (Ho < 1 || Wo < 1) return -2;
+  void* xp = t.get((size_t)B * H * W * c0 * es(dtype));
+  void* wp = t.get((size_t)Np * k * k * c0 * es(dtype));
+  if (!xp || !wp) return -6;
+  if (launch_pack_nchw(x, xp, B, Ci, H * W, c0, 1.f, 0.f, dtype, s)) return -3;
+  if (launch_repack_conv(w, wp, Co, Ci, k, k, Np, c0, dtype, s)) return -3;
+  float* bp = padded_bias(t, bias, Co, Np, s);
+  void* rp = nullptr;
+  if (resid) {
+    rp = t.get((size_t)B * Ho * Wo * nreal * es(dtype));
+    if (!rp || launch_pack_nchw(resid, rp, B, Co, Ho * Wo, nreal, 1.f, 0.f, dtype, s)) return -3;
+  }
+  IgemmParams p;
+  p.src0 = xp; p.C0 = c0;
+  p.B = B; p.Hi = H; p.Wi = W; p.Ho = Ho; p.Wo = Wo;
+  p.taps = k * k; p.stride = stride; p.pad = pad;
+  p.M = B * Ho * Wo; p.N = Np; p.W = wp; p.bias = bp;
+  p.x3 = x3;
+  if (x3 == 2 && launch_split_planes(wp, (size_t)Np * k * k * c0, s)) return -3;
+  p.cf_ctr = op_cf_region();
+  void* op = nullptr;
+  if (epi == EPI_NCHW_F32) {
+    p.n_valid = Co; p.out = out; p.epi = EPI_NCHW_F32;
+  } else {
+    op = t.get((size_t)B * Ho * Wo * nreal * es(dtype));
+    if (!op) return -6;
+    p.n_valid = nreal; p.out = op; p.ldo = nreal; p.epi = EPI_STORE; p.silu = silu;
+    if (rp) { p.resid = rp; p.ldr = nreal; }
+  }
+  const int sp = igemm_plan_splits(p, dtype);
+  if (sp > 1) { p.splits = sp; p.partial = (float*)t.get((size_t)sp * p.M * Np * sizeof(float)); if (!p.partial) return -6; }
+  const int r = launch_igemm(p, dtype, s);
+  if (r || epi == EPI_NCHW_F32) return r;
+  return unpack_nhwc(op, out, B, Co, Ho * Wo, nreal, dtype, s);
+}
+
+// out [M][N] = a [M][K] b[N][K]^T (+ bias[N]): both operands are activations (klenc_attention: S = Q K^T, V^T = W_v X^T, O = P V + b_v),
+// so W is taken as it is (w_dynamic) and a split-bf16 mode splits it in the K loop (dtype 2 and 3 both run x3 = 1, as Exec::igemm
+// sets it).  rows_f32: EPI_ROWS_F32 (fp32 rows whatever the compute dtype), else the store epilogue.
+int ldmseg_op_gemm_dynamic(const float* a, const float* b, const float* bias, int M, int N, int K, int rows_f32, int dtype, float* out,
+                           void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  Temp t;
+  const int x3 = dtype >= 2 ? 1 : 0;
+  if (x3) dtype = DT_F32;
+  if (!a || !b || !out || M < 1 || N < 1 || K < 1 || K % bke(dtype) || N % 32) return -2;
+  void* ap = t.get((size_t)M * K * es(dtype));
+  void* bp = t.get((size_t)N * K * es(dtype));
+  if (!ap || !bp) return -6;
+  to_dev_dtype(a, ap, (size_t)M * K, dtype, s);
+  to_dev_dtype(b, bp, (size_t)N * K, dtype, s);
+  void* op = rows_f32 ? nullptr : t.get((size_t)M * N * es(dtype));
+  IgemmParams p;
+  p.src0 = ap; p.C0 = K; p.B = 1; p.Hi = p.Ho = M; p.Wi = p.Wo = 1;
+  p.M = M; p.N = N; p.n_valid = N; p.W = bp; p.bias = bias; p.ldo = N;
+  p.out = rows_f32 ? (void*)out : op; p.epi = rows_f32 ? EPI_ROWS_F32 : EPI_STORE;
+  p.w_dynamic = 1;
+  p.x3 = x3;
+  p.cf_ctr = op_cf_region();
+  const int sp = igemm_plan_splits(p, dtype);
+  if (sp > 1) { p.splits = sp; p.partial = (float*)t.get((size_t)sp * M * N * sizeof(float)); if (!p.partial) return -6; }
+  const int r = launch_igemm(p, dtype, s);
+  if (r || rows_f32) return r;
+  return from_dev_dtype(op, out, (size_t)M * N, dtype, s);
+}
+
+// softmax(scale * s, dim=-1) of fp32 rows s [rows][n] into the compute dtype (the P operand of O = P V); scale > 0, n % 4 == 0
+int ldmseg_op_softmax_rows(const float* sc, int rows, int n, float scale, int dtype, float* out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  Temp t;
+  if (!sc || !out || rows < 1 || n < 1 || !(scale > 0.f) || (dtype != DT_F32 && dtype != DT_BF16)) return -2;
+  void* pp = t.get((size_t)rows * n * es(dtype));
+  if (!pp) return -6;
+  const int r = launch_softmax_rows(sc, pp, rows, n, scale, dtype, s);
+  if (r) return r;
+  return from_dev_dtype(pp, out, (size_t)rows * n, dtype, s);
+}
+
+// argmax over C and the max-softmax probability of F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=False): x NCHW f32
+// [B,C,H,W] -> ids [B,2H,2W] int64 (ignore_label where prob < mask_th, if mask_th >= 0), prob [B,2H,2W] f32 or NULL
+int ldmseg_op_bilinear2x_argmax(const float* x, int B, int C, int H, int W, float mask_th, int64_t ignore_label, int dtype, int64_t* ids,
+                                float* prob, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  Temp t;
+  if (!x || !ids || B < 1 || C < 1 || H < 1 || W < 1 || (dtype != DT_F32 && dtype != DT_BF16)) return -2;
+  void* xp = t.get((size_t)B * H * W * C * es(dtype));
+  if (!xp) return -6;
+  if (launch_pack_nchw(x, xp, B, C, H * W, C, 1.f, 0.f, dtype, s)) return -3;
+  return launch_bilinear2x_argmax(xp, ids, prob, B, H, W, C, mask_th, ignore_label, dtype, s);
+}
+
+// ldmseg_op_layernorm with the choice the seg-VAE decoder makes: inplace != 0 normalises the staged tensor where it lies
+// (Exec::layernorm(..., inplace = true) behind each transposed conv), 0 writes a second buffer
+int ldmseg_op_layernorm_io(const float* x, const float* gamma, const float* beta, int M, int C, float eps, int silu, int inplace, int dtype,
+                           float* out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  Temp t;
+  if (!x || !out || M < 1 || C < 1 || (dtype != DT_F32 && dtype != DT_BF16)) return -2;
+  void* xp = t.get((size_t)M * C * es(dtype));
+  void* op = inplace ? xp : t.get((size_t)M * C * es(dtype));
+  if (!xp || !op) return -6;
+  to_dev_dtype(x, xp, (size_t)M * C, dtype, s);
+  const int r = launch_layernorm(xp, op, gamma, beta, M, C, eps, silu, dtype, s);
+  if (r) return r;
+  return from_dev_dtype(op, out, (size_t)M * C, dtype, s);
 }
 
 // F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=False): NCHW f32 in/out

@@ -138,6 +138,11 @@ SIGNATURES = {
     "ldmseg_op_attention_cross": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ldmseg_op_attention_fp8": (_i, [_vp, _i, _i, _i, _i, _vp, _i, C.POINTER(C.c_float), _vp]),
     "ldmseg_op_convt2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ldmseg_op_vae_conv": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ldmseg_op_gemm_dynamic": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ldmseg_op_softmax_rows": (_i, [_vp, _i, _i, _f, _i, _vp, _vp]),
+    "ldmseg_op_bilinear2x_argmax": (_i, [_vp, _i, _i, _i, _i, _f, _i64, _i, _vp, _vp, _vp]),
+    "ldmseg_op_layernorm_io": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _i, _i, _vp, _vp]),
     "ldmseg_op_bilinear2x": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ldmseg_op_chained_ff_out": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ldmseg_op_igemm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),

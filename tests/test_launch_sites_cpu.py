@@ -24,9 +24,6 @@ ALLOWED = {
     ("misc.hip", "pack_concat3_kernel"): "layout: fp32 NCHW inputs -> NHWC compute dtype at the API boundary",
     ("misc.hip", "time_sinus_kernel"): "time embedding: sinusoidal features of the timestep (fp32, no compute-mode variants)",
     ("misc.hip", "small_linear_kernel"): "time embedding MLP (fp32, B rows, no compute-mode variants)",
-    ("misc.hip", "bilinear2x_kernel"): "seg-VAE decode tail, not in the UNet forward",
-    ("misc.hip", "bilinear_argmax_kernel"): "seg-VAE decode tail, not in the UNet forward",
-    ("misc.hip", "softmax_rows_kernel"): "image-VAE single-head attention, not in the UNet forward",
     ("misc.hip", "repack_conv_kernel"): "create time: conv weight repack",
     ("misc.hip", "repack_convt2_kernel"): "create time: ConvTranspose2d weight repack",
     ("misc.hip", "repack_rows_kernel"): "create time: Linear weight repack",
@@ -34,7 +31,6 @@ ALLOWED = {
     ("misc.hip", "rowsum_kernel"): "create time: row sums of the folded LayerNorm weights (epilogue constants)",
     ("misc.hip", "bit_encode_kernel"): "data preparation: COCO bitmap encode, not in the UNet forward",
     ("misc.hip", "bit_decode_kernel"): "data preparation: COCO bitmap decode, not in the UNet forward",
-    ("misc.hip", "posterior_sample_kernel"): "image-VAE posterior sample, not in the UNet forward",
 }
 
 
