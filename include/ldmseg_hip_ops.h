@@ -202,6 +202,10 @@ int ldmseg_op_igemm_plan(const int* desc, int dtype, int cus, char* buf, int n);
  * GroupNorm launch of ldmseg_op_conv_groupnorm over Co channels; -4 where that returns -4. */
 int ldmseg_op_groupnorm_plan(int B, int C, int C2, int HW, int groups, int dtype, int cus, int region_ok, char* buf, int n);
 int ldmseg_op_conv_groupnorm_plan(int B, int Co, int HW, int dtype, char* buf, int n);
+/* What ldmseg_op_layernorm (stats = 0) or the row-statistics pass of ldmseg_op_ln_linear (stats = 1) would launch for M rows of C
+ * channels under the current debug key 8 (csrc/ln_plan.h; needs no device).  buf receives "name grid=GX block=T" with the
+ * dispatch-log name.  Returns 0, or -2 where the launch returns -2. */
+int ldmseg_op_layernorm_plan(int M, int C, int dtype, int stats, char* buf, int n);
 /* What an attention operator would launch under the current debug keys 2 and 15 (csrc/attn_plan.h; needs no device): kind 0 =
  * ldmseg_op_attention, 1 = ldmseg_op_attention_causal, 2 = ldmseg_op_attention_fp8 (dtype ignored), 3 = ldmseg_op_attention_cross
  * over S context rows (S is ignored otherwise).  buf receives, per launch, "name grid=GXxGY block=T" (the fp8 pre-passes and the

@@ -432,7 +432,7 @@ int run(const AttnPlan& p, const void* qkv, void* out, hipStream_t s) {
                                   : (X3 ? launch_name("attn_x3<%d,%d>", D, QF) : launch_name("attn<%s,%d,%d>", dtype_tag<T>(), D, QF));
   LDMSEG_LAUNCH(name, kern,
                 dim3(p.grid_x), dim3(p.block), lds, s, (const IO*)qkv, (IO*)out, p.q.N, p.q.C, p.q.heads, scale_log2e);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 int g_attn_qf1 = 0;

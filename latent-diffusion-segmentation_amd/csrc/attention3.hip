@@ -4,7 +4,7 @@
 // v_exp_f32 as such (a transcendental costs ~1.7 plain VALU slots), but VALU *issue* - one wave issues a VALU
 // instruction every ~5 cycles, so at 2 waves per SIMD a softmax of ~4.2 VALU slots per score runs at half the MFMA
 // rate.  Hence:
-//   * K and V tiles arrive by LDS-DMA (global_load_lds_dwordx4) as "chunk planes": plane c holds the 16-byte chunk c
+//   * K and V tiles arrive by LDS-DMA (lds_dma.h) as "chunk planes": plane c holds the 16-byte chunk c
 //     (8 head-dim columns) of all 64 keys of the tile, 1 KiB = one wave instruction, lane = key.  No staging
 //     registers, no ds_write pass, no transpose: V^T fragments are read with ds_read_b64_tr_b16 (hardware transpose),
 //     K fragments with ds_read_b128; both are bank-conflict free by construction (K planes 1024 B apart, V planes
@@ -361,7 +361,7 @@ int run3(const AttnPlan& p, const void* qkv, void* out, hipStream_t s) {
   raise_lds_limit_once((const void*)kern, lds, lds_raised);
   const float scale_log2e = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
   LDMSEG_LAUNCH(launch_name("attn3<%d,%d,%d,%d,%d,%d,%d>", D, QF, WPS, NST, PIPE ? 1 : 0, LAZY, NWV), kern, dim3(p.grid_x), dim3(p.block), lds, s, (const bf16_t*)qkv, (bf16_t*)out, p.q.N, p.q.C, p.q.heads, scale_log2e);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 }  // namespace

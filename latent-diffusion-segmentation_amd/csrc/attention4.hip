@@ -300,7 +300,7 @@ int run4(const AttnPlan& p, const void* qkv, void* out, hipStream_t s) {
   raise_lds_limit_once((const void*)kern, lds, lds_raised);
   const float scale_log2e = (1.0f / sqrtf((float)D4)) * 1.4426950408889634f;
   LDMSEG_LAUNCH(launch_name("attn4<d40,%d,%d,%d>", NST, LAZY, NWV), kern, dim3(p.grid_x), dim3(p.block), lds, s, (const bf16_t*)qkv, (bf16_t*)out, p.q.N, p.q.C, p.q.heads, scale_log2e);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 }  // namespace

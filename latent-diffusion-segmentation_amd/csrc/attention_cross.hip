@@ -125,7 +125,7 @@ int launch_d(const AttnPlan& p, const void* q, const void* kv, void* out, hipStr
   const float qscale = 1.4426950408889634f / sqrtf((float)D);
   LDMSEG_LAUNCH(launch_name("attention_cross_kernel<%s,%d>", dtype_tag<T>(), D), (attention_cross_kernel<T, D>),
                 dim3(p.grid_x, p.grid_y, p.grid_z), dim3(p.block), 0, s, (const T*)q, (const T*)kv, (T*)out, p.q.N, p.q.S, p.q.C, qscale);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 template <typename T>
@@ -161,7 +161,7 @@ int launch_rows_to_dtype(const float* x, void* y, size_t n, int dtype, hipStream
   else
     LDMSEG_LAUNCH(launch_name("rows_to_dtype_kernel<%s>", "f32"), rows_to_dtype_kernel<float>, grid, dim3(256), 0, s, x,
                   (float*)y, n);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 }  // namespace ldmseg

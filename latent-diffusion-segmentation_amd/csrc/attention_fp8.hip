@@ -29,16 +29,6 @@ namespace {
 constexpr int BKV8 = 64;
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ float clamp448(float x) { return fminf(fmaxf(x, -448.f), 448.f); }
-// four floats -> one dword of e4m3 (RNE; inputs must be within +-448)
-__device__ __forceinline__ uint32_t pack_fp8x4(float a, float b, float c, float d) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  return (uint32_t)w;
-}
-__device__ __forceinline__ float fp8_to_f32(uint32_t byte) { return __builtin_amdgcn_cvt_f32_fp8((int)byte, 0); }
-
-
 // ---- pre-pass: K and V of qkv [B, N, 3C] bf16 -> k8 / v8 [B, H, N, DP] e4m3 with the constant columns ----
 template <int D, int DP>
 __global__ __launch_bounds__(256) void kv_to_fp8_kernel(const bf16_t* __restrict__ qkv, unsigned char* __restrict__ k8,
@@ -343,7 +333,7 @@ int run8(const AttnPlan& p, const void* qkv, void* kv8, void* out, hipStream_t s
   const float scale_log2e = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
   LDMSEG_LAUNCH(launch_name("attn_fp8<%d,%d,%d,%d>", D, QF, WPS, NST), kern, dim3(p.grid_x), dim3(p.block), lds, s, (const bf16_t*)qkv, k8, v8, (bf16_t*)out, N, C, heads,
                      scale_log2e);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 }  // namespace

@@ -19,6 +19,7 @@
 // e4m3 range, row sum through a ones row of V^T: as in attention_fp8.hip.
 #include <type_traits>
 
+#include "attn_dev.h"
 #include "attn_plan.h"
 #include "common.h"
 #include "kernels.h"
@@ -33,23 +34,6 @@ constexpr int kVB = 48 * kTile;            // 6144: V^T image of a tile
 constexpr int kStage = kKB + kVB;          // 14336
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float clamp448m(float x) { return fminf(fmaxf(x, -448.f), 448.f); }
-__device__ __forceinline__ uint32_t pack_fp8x4m(float a, float b, float c, float d) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  return (uint32_t)w;
-}
-__device__ __forceinline__ float fp8_to_f32m(uint32_t byte) { return __builtin_amdgcn_cvt_f32_fp8((int)byte, 0); }
-__device__ __forceinline__ void glds16m(const void* gsrc, unsigned lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, off"
-      :
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
 
 // contraction slot s = 32 g + j of a 128-key tile -> key (what lane (q, h) of the QK^T result holds after the permlane swap)
 __host__ __device__ constexpr int slot_key(int s) {
@@ -73,10 +57,10 @@ __global__ __launch_bounds__(256) void kv_to_mx_kernel(const bf16_t* __restrict_
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int d = c * 16 + e;
-      f[e] = d < kD ? clamp448m(bf16_to_f32(src[e])) : ((d == kD || d == kD + 1) ? 1.0f : 0.f);
+      f[e] = d < kD ? clamp448(bf16_to_f32(src[e])) : ((d == kD || d == kD + 1) ? 1.0f : 0.f);
     }
-    const uint4 o = make_uint4(pack_fp8x4m(f[0], f[1], f[2], f[3]), pack_fp8x4m(f[4], f[5], f[6], f[7]),
-                               pack_fp8x4m(f[8], f[9], f[10], f[11]), pack_fp8x4m(f[12], f[13], f[14], f[15]));
+    const uint4 o = make_uint4(pack_fp8x4(f[0], f[1], f[2], f[3]), pack_fp8x4(f[4], f[5], f[6], f[7]),
+                               pack_fp8x4(f[8], f[9], f[10], f[11]), pack_fp8x4(f[12], f[13], f[14], f[15]));
     *(uint4*)(k8 + (bh * ntiles + T) * kKB + key * 64 + ((c ^ ((key >> 2) & 3)) << 4)) = o;
   }
   // V: stage the tile as fp8 [key][d] ...
@@ -87,10 +71,10 @@ __global__ __launch_bounds__(256) void kv_to_mx_kernel(const bf16_t* __restrict_
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int d = c * 16 + e;
-      f[e] = d < kD ? clamp448m(bf16_to_f32(src[e])) : (d == kD ? 1.0f : 0.f);          // row 40 of V^T = ones: the row sum
+      f[e] = d < kD ? clamp448(bf16_to_f32(src[e])) : (d == kD ? 1.0f : 0.f);          // row 40 of V^T = ones: the row sum
     }
-    *(uint4*)(&vs[key][c * 16]) = make_uint4(pack_fp8x4m(f[0], f[1], f[2], f[3]), pack_fp8x4m(f[4], f[5], f[6], f[7]),
-                                             pack_fp8x4m(f[8], f[9], f[10], f[11]), pack_fp8x4m(f[12], f[13], f[14], f[15]));
+    *(uint4*)(&vs[key][c * 16]) = make_uint4(pack_fp8x4(f[0], f[1], f[2], f[3]), pack_fp8x4(f[4], f[5], f[6], f[7]),
+                                             pack_fp8x4(f[8], f[9], f[10], f[11]), pack_fp8x4(f[12], f[13], f[14], f[15]));
   }
   __syncthreads();
   // ... and write V^T: thread -> (row d, physical granule cp): 16 contraction slots of one row
@@ -113,12 +97,12 @@ template <int NST, int NW, bool FEXP>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_mx_kernel(const bf16_t* __restrict__ qkv, const unsigned char* __restrict__ k8,
                                                          const unsigned char* __restrict__ v8, bf16_t* __restrict__ out, int N, int C,
                                                          int heads, float scale_log2e, float pshift) {
-  // Exact form: p = 2^(s - m + 7) through v_exp_f32 + v_cvt_pk_fp8_f32 (p uses the top of the e4m3 range, see attention_fp8.hip).
+  // Exact form: p = 2^(s - m + 7) through v_exp_f32 + pack_fp8x4 (p uses the top of the e4m3 range, see attention_fp8.hip).
   // FEXP: the e4m3 BYTE of p is built directly.  An e4m3 number is 2^(e-7) (1 + f/8) with byte 8e + f, i.e. byte ~ 8 log2 p + 56
   // with the mantissa interpolated linearly (2^x ~ 1 + x on [0, 1): within +6 % / centred by a constant: +-3 %, the size of the
   // e4m3 rounding step itself).  The QK^T product leaves the MFMA times 8 for free (E8M0 scale 2^3 on the Q operand), the
   // folded reference is m - pshift (pshift ~ 13.96: score = maximum <-> byte 112 - 0.3), and ONE v_cvt_pk_u8_f32 per score
-  // (saturating at 0) replaces v_exp_f32 + half a v_cvt_pk_fp8_f32: 64 instead of ~140 VALU slots per 128-key tile and wave.
+  // (saturating at 0) replaces v_exp_f32 + half a pack_fp8x4: 64 instead of ~140 VALU slots per 128-key tile and wave.
   // Row sums come out of the same bytes through the ones row of V^T, so numerator and denominator see the same weights.
   const float PSHIFT = FEXP ? pshift : 7.0f, THR = PSHIFT + 1.25f;
   constexpr float SMUL = FEXP ? 8.0f : 1.0f;                // scores are SMUL x (log2 units)
@@ -153,8 +137,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_mx_kernel(const
 #pragma unroll
     for (int j = 0; j < PPW; ++j) {
       const int p = wave + NW * j;
-      if (p < 8) glds16m(kt + p * 1024, dst + p * 1024);
-      else if (p < 14) glds16m(vt + (p - 8) * 1024, dst + p * 1024);
+      if (p < 8) glds16(kt + p * 1024, dst + p * 1024);
+      else if (p < 14) glds16(vt + (p - 8) * 1024, dst + p * 1024);
     }
   };
   auto wait_tiles_ahead = [&](int ahead) __attribute__((always_inline)) {
@@ -184,15 +168,15 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_mx_kernel(const
         float t[8];
         Chunk<bf16_t>::unpack(*(const uint4*)(qp + d0), t);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = clamp448m(t[e] * scale_log2e);
+        for (int e = 0; e < 8; ++e) f[e] = clamp448(t[e] * scale_log2e);
         if (d0 + 8 < kD) {
           Chunk<bf16_t>::unpack(*(const uint4*)(qp + d0 + 8), t);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) f[8 + e] = clamp448m(t[e] * scale_log2e);
+          for (int e = 0; e < 8; ++e) f[8 + e] = clamp448(t[e] * scale_log2e);
         }
       }
 #pragma unroll
-      for (int w = 0; w < 4; ++w) qf[c * 4 + w] = (int)pack_fp8x4m(f[4 * w], f[4 * w + 1], f[4 * w + 2], f[4 * w + 3]);
+      for (int w = 0; w < 4; ++w) qf[c * 4 + w] = (int)pack_fp8x4(f[4 * w], f[4 * w + 1], f[4 * w + 2], f[4 * w + 3]);
     }
   }
 
@@ -245,11 +229,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_mx_kernel(const
     if (!__any(need)) return;
     float one;
     asm volatile("v_mov_b32 %0, 1.0" : "=v"(one));
-    const float target = clamp448m(mrow + tm * (1.0f / SMUL) - PSHIFT);
-    const uint32_t b_hi = pack_fp8x4m(target, 0.f, 0.f, 0.f) & 0xffu;
-    const float m_hi = fp8_to_f32m(b_hi);
-    const uint32_t b_lo = pack_fp8x4m(target - m_hi, 0.f, 0.f, 0.f) & 0xffu;
-    const float mnew = need ? (m_hi + fp8_to_f32m(b_lo)) : mrow;
+    const float target = clamp448(mrow + tm * (1.0f / SMUL) - PSHIFT);
+    const uint32_t b_hi = pack_fp8x4(target, 0.f, 0.f, 0.f) & 0xffu;
+    const float m_hi = fp8_to_f32(b_hi);
+    const uint32_t b_lo = pack_fp8x4(target - m_hi, 0.f, 0.f, 0.f) & 0xffu;
+    const float mnew = need ? (m_hi + fp8_to_f32(b_lo)) : mrow;
     const float delta = (mnew - mrow) * one;
     mrow += delta;
 #pragma unroll
@@ -286,7 +270,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_mx_kernel(const
           pk = __builtin_amdgcn_cvt_pk_u8_f32(s[kb][4 * w + 2], 2, pk);
           pk = __builtin_amdgcn_cvt_pk_u8_f32(s[kb][4 * w + 3], 3, pk);
         } else {
-          pk = pack_fp8x4m(__builtin_amdgcn_exp2f(s[kb][4 * w]), __builtin_amdgcn_exp2f(s[kb][4 * w + 1]),
+          pk = pack_fp8x4(__builtin_amdgcn_exp2f(s[kb][4 * w]), __builtin_amdgcn_exp2f(s[kb][4 * w + 1]),
                            __builtin_amdgcn_exp2f(s[kb][4 * w + 2]), __builtin_amdgcn_exp2f(s[kb][4 * w + 3]));
         }
         if (kb < 2) U[(kb & 1) * 4 + w] = (int)pk;
@@ -375,7 +359,7 @@ int run_mx(const AttnPlan& p, const void* qkv, void* kv8, void* out, hipStream_t
   raise_lds_limit_once((const void*)kern, lds, lds_raised);
   LDMSEG_LAUNCH(launch_name("attn_mx<%d,%d,%d>", NST, NW, FEXP ? 1 : 0), kern, dim3(p.grid_x), dim3(p.block), lds, s, (const bf16_t*)qkv, k8, v8, (bf16_t*)out, N, C,
                      heads, scale_log2e, g_mx_pshift);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 }  // namespace

@@ -40,7 +40,6 @@ __global__ __launch_bounds__(256) void clip_text_final_ln_kernel(const T* __rest
   for (int i = 0; i < kClipMaxPer; ++i) { const int c = threadIdx.x + i * 256; if (c < C) out[row * C + c] = v[i]; }
 }
 
-inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 
 }  // namespace
 
@@ -54,7 +53,7 @@ int launch_clip_text_tokens(const int64_t* ids, const float* tok, const float* p
   else
     LDMSEG_LAUNCH(launch_name("clip_text_tokens<%s>", "f32"), clip_text_tokens_kernel<float>, grid, dim3(256), 0, s, ids, tok, pos,
                   (float*)h, T, C, vocab);
-  return ok();
+  return launch_status();
 }
 
 int launch_clip_text_final_ln(const void* h, const float* gamma, const float* beta, float* out, int M, int C, float eps, int dtype,
@@ -66,7 +65,7 @@ int launch_clip_text_final_ln(const void* h, const float* gamma, const float* be
   else
     LDMSEG_LAUNCH(launch_name("clip_text_final_ln<%s>", "f32"), clip_text_final_ln_kernel<float>, dim3(M), dim3(256), 0, s,
                   (const float*)h, gamma, beta, out, C, eps);
-  return ok();
+  return launch_status();
 }
 
 }  // namespace ldmseg

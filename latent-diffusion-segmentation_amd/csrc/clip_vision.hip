@@ -99,7 +99,6 @@ __global__ __launch_bounds__(256) void clip_rows_to_f32_kernel(const T* __restri
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) y[i] = to_f32<T>(x[i]);
 }
 
-inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 
 }  // namespace
 
@@ -121,7 +120,7 @@ int launch_clip_patch_rows(const float* img, void* rows, int B, int H, int W, in
   const std::string name = launch_name("clip_patch_rows<%s,%d>", dtype == DT_BF16 ? "bf16" : "f32", resample ? 1 : 0);
   if (dtype == DT_BF16) LDMSEG_LAUNCH(name, resample ? k_b1 : k_b0, grid, dim3(256), 0, s, f, (bf16_t*)rows);
   else LDMSEG_LAUNCH(name, resample ? k_f1 : k_f0, grid, dim3(256), 0, s, f, (float*)rows);
-  return ok();
+  return launch_status();
 }
 
 int launch_clip_tokens(const void* patch, const float* cls, const float* pos, const float* gamma, const float* beta, void* h,
@@ -134,7 +133,7 @@ int launch_clip_tokens(const void* patch, const float* cls, const float* pos, co
   else
     LDMSEG_LAUNCH(launch_name("clip_tokens<%s>", "f32"), clip_tokens_kernel<float>, grid, dim3(256), 0, s, (const float*)patch, cls, pos,
                   gamma, beta, (float*)h, T, C, eps);
-  return ok();
+  return launch_status();
 }
 
 int launch_clip_pooled_ln(const void* h, const float* gamma, const float* beta, float* out, int B, int T, int C, float eps,
@@ -146,7 +145,7 @@ int launch_clip_pooled_ln(const void* h, const float* gamma, const float* beta, 
   else
     LDMSEG_LAUNCH(launch_name("clip_pooled_ln<%s>", "f32"), clip_pooled_ln_kernel<float>, dim3(B), dim3(256), 0, s, (const float*)h, gamma,
                   beta, out, T, C, eps);
-  return ok();
+  return launch_status();
 }
 
 int launch_clip_rows_to_f32(const void* x, float* y, size_t n, int dtype, hipStream_t s) {
@@ -157,7 +156,7 @@ int launch_clip_rows_to_f32(const void* x, float* y, size_t n, int dtype, hipStr
     LDMSEG_LAUNCH(launch_name("clip_rows_to_f32<%s>", "bf16"), clip_rows_to_f32_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, y, n);
   else
     LDMSEG_LAUNCH(launch_name("clip_rows_to_f32<%s>", "f32"), clip_rows_to_f32_kernel<float>, grid, dim3(256), 0, s, (const float*)x, y, n);
-  return ok();
+  return launch_status();
 }
 
 }  // namespace ldmseg

@@ -16,7 +16,7 @@ constexpr int kGnNoCoop = 1;         // no cooperative kernel (64x64 maps on the
 constexpr int kGnCoopFrom256 = 2;    // cooperative kernel from 16x16 maps up
 constexpr int kGnTwoPass = 4;        // two-pass gn_fused where gn_one would run
 constexpr int kGnSplitFinish = 8;    // keep the split-K finish and the norm apart (finish_groupnorm_ok answers no)
-constexpr int kGnRowstats1 = 16;     // one-row-per-wave rowstats (run_rowstats)
+constexpr int kGnRowstats1 = 16;     // one-row-per-wave rowstats (ln_choose, ln_plan.h)
 constexpr int kGnNoGroup = 32;       // no gn_group
 // variant: key 8; coop_mode (key 10): 1 = every cooperative workgroup computes its partners' records itself (tests of the cold
 // path); poll_us (key 11): bound of the partner poll

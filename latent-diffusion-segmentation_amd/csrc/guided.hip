@@ -39,7 +39,7 @@ int launch_guided_step(const float* eps, float* latents, float* cond, float* lat
   if (mult != 1 && mult != 2) return -2;
   LDMSEG_LAUNCH(launch_name("guided_step_kernel"), guided_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, eps,
                 latents, cond, lat2, n, mult, g, c, last);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 }  // namespace ldmseg

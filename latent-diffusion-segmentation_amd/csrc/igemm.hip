@@ -18,7 +18,7 @@
 //    8-/16-byte stores along the NHWC channel axis and in-lane GEGLU.
 //  * LDS tiles are [rows][128 B] with the 16-B chunk index XOR (row & 7):
 //    conflict-free for ds_read_b128 over the 16-lane groups of gfx950.
-//  * a ring of NST LDS stages (2..4 full K tiles) filled by LDS-DMA (global_load_lds_dwordx4: no VGPR
+//  * a ring of NST LDS stages (2..4 full K tiles) filled by LDS-DMA (lds_dma.h: no VGPR
 //    round trip, no ds_write pass); the DMA stream runs NST-1 tiles ahead of the MFMA stream, also
 //    across work-item boundaries (persistent grid); counted vmcnt + one barrier per K tile.
 //    Out-of-image taps read a 16-B page of zeros.
@@ -33,6 +33,7 @@
 #include "common.h"
 #include "igemm_plan.h"
 #include "kernels.h"
+#include "lds_dma.h"
 
 namespace ldmseg {
 
@@ -43,33 +44,6 @@ constexpr int kRowBytes = 128;
 
 typedef __attribute__((address_space(1))) const void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
-
-// LDS-DMA: 64 lanes x 16 B from per-lane global addresses into LDS at (wave-uniform) lds_dst +
-// lane*16.  Issued through inline asm so that hipcc does not track it: with the builtin the
-// compiler waits vmcnt(0) before the next ds_read (it cannot prove the DMA target and the tile
-// being read are different stages), which serialises DMA and MFMA.  The caller owns the wait:
-// s_waitcnt vmcnt(0) + barrier before any wave reads the stage.
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, off"
-      :
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
-// same, address = wave-uniform 64-bit base (SGPR pair) + per-lane 32-bit offset: no VALU per tile
-__device__ __forceinline__ void glds16_sbase(unsigned voff, const void* sbase, unsigned lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 3\n\t"   // M0 write -> LDS-DMA needs 1 wait state; an SGPR base written by SALU / v_readfirstlane needs 5
-                       // before a VMEM instruction reads it, and the hazard recognizer does not look inside inline asm
-                       // (a register-load variant of this helper went to wild addresses without them)
-      "global_load_lds_dwordx4 %0, %1"
-      :
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory");
-}
 
 struct RowInfo {
   int pix_base;  // b * Hi * Wi
@@ -105,19 +79,6 @@ struct RowInfo {
 #define STAMP_WALL(p, slot)
 #define STAMP_XCC(p)
 #endif
-
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (N > 0) {
-    static_for<N - 1>(f);
-    f(std::integral_constant<int, N - 1>{});
-  }
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
 
 // Bytes of the row-major epilogue staging area (one 16-row x WTN fp32 block per wave).  It normally
 // borrows the ring stage that is free at the end of an item; a tile whose stage is smaller than
@@ -207,7 +168,7 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + LDR) * 64, (WAVES_M * WAVES_N 
     }
   };
 
-  // ---- direct-to-LDS staging (global_load_lds_dwordx4): one wave instruction fills one 8-row
+  // ---- direct-to-LDS staging (glds16, lds_dma.h): one wave instruction fills one 8-row
   // group (1 KiB, lane l -> row l>>3, physical chunk l&7).  The XOR swizzle therefore lives on the
   // SOURCE side: the lane fetches logical chunk (l&7)^(row&7).  Rows 0..BM-1 of a stage are X,
   // rows BM.. are W; group g = i*NW + wave belongs to wave (g % NW).
@@ -405,12 +366,12 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + LDR) * 64, (WAVES_M * WAVES_N 
   auto wait_dma = [&](auto ahead_tag) __attribute__((always_inline)) {
     constexpr int AHEAD = decltype(ahead_tag)::value;
     if constexpr (AHEAD == 0) {
-      wait_vmcnt<0>();
+      wait_vm<0>();
     } else if constexpr (WREM == 0) {
-      wait_vmcnt<AHEAD*(XG + WG)>();
+      wait_vm<AHEAD*(XG + WG)>();
     } else {
-      if (w_last) wait_vmcnt<AHEAD*(XG + WG)>();
-      else wait_vmcnt<AHEAD*(XG + WG - 1)>();
+      if (w_last) wait_vm<AHEAD*(XG + WG)>();
+      else wait_vm<AHEAD*(XG + WG - 1)>();
     }
   };
 
@@ -572,7 +533,7 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + LDR) * 64, (WAVES_M * WAVES_N 
           for (int j = 0; j + 1 < MF; ++j) acc[a][j] = acc[a][j + 1];
       }
     } else {
-      static_for<MF>([&](auto bi) __attribute__((always_inline)) { row_block(decltype(bi)::value, bi); });
+      static_for_n<MF>([&](auto bi) __attribute__((always_inline)) { row_block(decltype(bi)::value, bi); });
     }
   };
 
@@ -654,7 +615,7 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + LDR) * 64, (WAVES_M * WAVES_N 
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         st = st_next;
       };
-      static_for<MF>([&](auto bi) __attribute__((always_inline)) { row_block(decltype(bi)::value, bi); });
+      static_for_n<MF>([&](auto bi) __attribute__((always_inline)) { row_block(decltype(bi)::value, bi); });
     }
   };
 
@@ -783,7 +744,7 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + LDR) * 64, (WAVES_M * WAVES_N 
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[a][BI]), rs, off + a * 64, 0, 16);
         }
       };
-      static_for<MF>([&](auto bi) __attribute__((always_inline)) { row_block(decltype(bi)::value, bi); });
+      static_for_n<MF>([&](auto bi) __attribute__((always_inline)) { row_block(decltype(bi)::value, bi); });
       return;
     }
     auto row_block = [&](int b, auto bidx) __attribute__((always_inline)) {
@@ -795,7 +756,7 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + LDR) * 64, (WAVES_M * WAVES_N 
         for (int a = 0; a < NF; ++a) *(f32x4*)(dst + a * 16) = acc[a][BI];
       }
     };
-    static_for<MF>([&](auto bi) __attribute__((always_inline)) { row_block(decltype(bi)::value, bi); });
+    static_for_n<MF>([&](auto bi) __attribute__((always_inline)) { row_block(decltype(bi)::value, bi); });
   };
 
   if constexpr (LDR > 0) {
@@ -877,7 +838,7 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + LDR) * 64, (WAVES_M * WAVES_N 
       constexpr int NMMA = NF * MF * (sizeof(T) == 2 ? 1 : 4);   // MFMA instructions per half tile (fp32: four 16x16x4 per k-group)
       constexpr int MPR = NMMA / (NF + MF);
 #define IGEMM_INTERLEAVE                                                                                \
-  static_for<NF + MF>([&](auto) __attribute__((always_inline)) {                                        \
+  static_for_n<NF + MF>([&](auto) __attribute__((always_inline)) {                                        \
     __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                  \
     __builtin_amdgcn_sched_group_barrier(0x008, MPR, 0);                                                \
   });                                                                                                   \
@@ -1253,7 +1214,7 @@ int launch_finish(const IgemmParams& p, hipStream_t s) {
   int gy = (p.M + 3) / 4;
   if (gy > 2048 / gx) gy = 2048 / gx > 0 ? 2048 / gx : 1;
   LDMSEG_LAUNCH(launch_name("splitk_finish<%s>", dtype_tag<T>()), splitk_finish_kernel<T>, dim3(gx, gy), dim3(256), 0, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 // One instantiation, launched as the chooser planned it (d): what is left here needs the device.  CF: it has the twin with the
@@ -1276,14 +1237,11 @@ int run(const IgemmDispatch& d, const IgemmParams& pin, hipStream_t s) {
   const size_t lds = (size_t)NST * (BM + BN) * kRowBytes +
                      (epi_stage_dedicated<BM, BN, WM, WN>() ? epi_stage_bytes<BM, BN, WM, WN>() : 0);
   auto kern = igemm_kernel<T, BM, BN, WM, WN, NST, PIPE, LDR, LNF, CM, XT, UP4>;
-  static bool attr_set[kMaxDev] = {};
-  const int dev = cur_dev();
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if constexpr (CF)
-      (void)hipFuncSetAttribute((const void*)igemm_kernel<T, BM, BN, WM, WN, NST, PIPE, LDR, LNF, CM, XT, UP4, true>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set[dev] = true;
+  static bool lds_raised[64] = {};
+  raise_lds_limit_once((const void*)kern, lds, lds_raised);
+  if constexpr (CF) {
+    static bool lds_raised_cf[64] = {};
+    raise_lds_limit_once((const void*)igemm_kernel<T, BM, BN, WM, WN, NST, PIPE, LDR, LNF, CM, XT, UP4, true>, lds, lds_raised_cf);
   }
   p.cf = d.cf;
   if (p.cf) {
@@ -1296,12 +1254,12 @@ int run(const IgemmDispatch& d, const IgemmParams& pin, hipStream_t s) {
   if constexpr (CF) {
     if (p.cf) {
       LDMSEG_LAUNCH_GEMM(igemm_dispatch_name(d), (igemm_kernel<T, BM, BN, WM, WN, NST, PIPE, LDR, LNF, CM, XT, UP4, true>), grid, block, lds, s, p);
-      return hipGetLastError() == hipSuccess ? 0 : -3;
+      return launch_status();
     }
   }
   LDMSEG_LAUNCH_GEMM(igemm_dispatch_name(d), kern, grid, block, lds, s, p);
   if (p.splits > 1 && !p.no_finish) return launch_finish<T>(p, s);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 // One line of LDMSEG_IGEMM_FORMS (igemm_plan.h) in one dtype on one N tile: the instantiations the line says exist, nothing else.
@@ -1466,7 +1424,7 @@ int launch_split_planes(void* w, size_t nfloats, hipStream_t s) {
   const size_t ntiles = nfloats / 32;
   if (!ntiles) return 0;
   hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, s, (float*)w, ntiles);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 int launch_pack_up4(const float* w, void* out, int Co, int Ci, int Npad, int Cipad, int dtype, hipStream_t s) {
   const size_t total = (size_t)16 * Npad * Cipad;
@@ -1474,7 +1432,7 @@ int launch_pack_up4(const float* w, void* out, int Co, int Ci, int Npad, int Cip
   const unsigned g = (unsigned)(blocks < 16384 ? blocks : 16384);
   if (dtype == DT_BF16) hipLaunchKernelGGL(pack_up4_kernel<bf16_t>, dim3(g), dim3(256), 0, s, w, (bf16_t*)out, Co, Ci, Npad, Cipad);
   else hipLaunchKernelGGL(pack_up4_kernel<float>, dim3(g), dim3(256), 0, s, w, (float*)out, Co, Ci, Npad, Cipad);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 void igemm_set_xt_mode(int on) { g_knobs.xt_mode = on ? 1 : 0; }   // 0 = engines keep conv_shortcut as a launch of its own
 int igemm_get_xt_mode() { return g_knobs.xt_mode; }
@@ -1520,11 +1478,11 @@ __global__ void chain_weights_kernel(const float* __restrict__ wp, const float* 
 }  // namespace
 int launch_chain_weights(const float* wp, const float* w2, const float* b2, const float* bp, float* wcat, float* bcat, int C, hipStream_t s) {
   hipLaunchKernelGGL(chain_weights_kernel, dim3((5 * C + 255) / 256, C), dim3(256), 0, s, wp, w2, b2, bp, wcat, bcat, C);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 int launch_vec_add(const float* a, const float* b, float* out, int n, hipStream_t s) {
   hipLaunchKernelGGL(vec_add_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, b, out, n);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 int launch_concat_rows(const void* a, int K1, const void* b, int K2, void* out, int N, int dtype, hipStream_t s) {
   const size_t total = (size_t)N * (K1 + K2);
@@ -1532,7 +1490,7 @@ int launch_concat_rows(const void* a, int K1, const void* b, int K2, void* out, 
   const unsigned g = (unsigned)(blocks < 16384 ? blocks : 16384);
   if (dtype == DT_BF16) hipLaunchKernelGGL(concat_rows_kernel<bf16_t>, dim3(g), dim3(256), 0, s, (const bf16_t*)a, K1, (const bf16_t*)b, K2, (bf16_t*)out, total);
   else hipLaunchKernelGGL(concat_rows_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)a, K1, (const float*)b, K2, (float*)out, total);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 void igemm_set_cm_mode(int mode) { g_knobs.cm_mode = mode < -1 || mode > 1 ? -1 : mode; }

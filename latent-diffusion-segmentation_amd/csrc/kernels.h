@@ -174,6 +174,8 @@ constexpr const char* dtype_tag() { return sizeof(T) == 2 ? "bf16" : "f32"; }
   } while (0)
 #define LDMSEG_LAUNCH_GEMM(NAME, ...) LDMSEG_LAUNCH_AT(1, NAME, __VA_ARGS__)
 #define LDMSEG_LAUNCH(NAME, ...) LDMSEG_LAUNCH_AT(2, NAME, __VA_ARGS__)
+// what every launcher returns after its launches: 0, or -3 when HIP refused one
+inline int launch_status() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 // tile the launcher would pick (for weight padding): N tile size for a given N.
 int igemm_pick_bn(int n_real, int epi);
 
@@ -230,6 +232,10 @@ int finish_groupnorm_plan(int B, int HW, int C, int dtype, GnPlan* pl);
 // LayerNorm over the last dim of [M][C] (+ optional SiLU) - also LayerNorm2d in NHWC
 int launch_layernorm(const void* x, void* y, const float* gamma, const float* beta, int M, int C,
                      float eps, int silu, int dtype, hipStream_t s);
+// what launch_layernorm (q.stats = 0) / launch_rowstats (1) would run under the current knobs (ln_plan.h; no device): 0 and *pl, or -2
+struct LnDesc;
+struct LnPlan;
+int layernorm_plan(const LnDesc& q, LnPlan* pl);
 
 // self-attention on fused qkv [B, N, 3C] (q | k | v, channel = head*d + i) -> out [B, N, C]
 // dtype 2 = fp32 tensors with the products as three bf16 MFMAs on hi/lo splits (compute_dtype "bf16x3")

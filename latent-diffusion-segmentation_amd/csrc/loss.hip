@@ -19,6 +19,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "nearest_index.h"
+#include "reduce_dev.h"
 #include "sched_math.h"
 
 namespace ldmseg {
@@ -29,18 +30,7 @@ constexpr int kPerThread = 4;
 constexpr int kChunk = kThreads * kPerThread;     // elements of one sample per workgroup of the loss tail
 constexpr int kMaxBlocks = 256;                   // grid cap of the grid-stride passes (OHEM, min / max)
 
-// sum over the workgroup in a fixed order: lanes by xor-shuffle tree, then the four waves in order; valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double* s_red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();                                 // s_red may still be read from a previous call
-  if (lane == 0) s_red[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kThreads / 64; ++w) t += s_red[w];
-  return t;
-}
+static_assert(kThreads == kBlockSumThreads, "block_sum (reduce_dev.h) sums kBlockSumThreads / 64 waves");
 
 // ---------------------------------------------------------------- loss tail
 __device__ __forceinline__ float elem_loss(float x, float y, int loss_type) {
@@ -139,17 +129,7 @@ __global__ __launch_bounds__(kThreads) void loss_tail_kernel(const LossTail p) {
   if (threadIdx.x == 0) p.partial[(size_t)b * gridDim.x + blockIdx.x] = t;
 }
 
-// ---------------------------------------------------------------- OHEM: radix select
-// order-preserving key of an fp32 bit pattern (larger value <-> larger key; the losses are non-negative, the map also orders
-// negative values should a caller hand some in)
-__device__ __forceinline__ uint32_t f32_key(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_f32(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
+// ---------------------------------------------------------------- OHEM: radix select (keys: f32_key / key_f32, reduce_dev.h)
 struct SelectState {     // after `pass` digits: the key prefix of the k-th largest and how many of that prefix are still wanted
   uint32_t prefix;
   uint32_t pad;
@@ -359,7 +339,6 @@ __global__ __launch_bounds__(kThreads) void loss_mask_kernel(const MaskParams p)
   if (bad) atomicOr(p.flag, 1);
 }
 
-inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 inline int stride_blocks(size_t n) {
   const size_t g = (n + kChunk - 1) / kChunk;
@@ -403,7 +382,7 @@ int launch_diffusion_loss(const LossTail& in, int B, double ohem_k, float* sampl
                          dim3(nchunk, B), dim3(kThreads), 0, s, p);
   else LDMSEG_LAUNCH(launch_name("loss_tail<scalar,loss=%d,pred=%d>", p.loss_type, p.pred_type), loss_tail_kernel<false>,
                      dim3(nchunk, B), dim3(kThreads), 0, s, p);
-  if (!p.target) return ok();                      // pred_latents only: no loss, so nothing to finish (mean / sample_sums may be null)
+  if (!p.target) return launch_status();                      // pred_latents only: no loss, so nothing to finish (mean / sample_sums may be null)
   const size_t n = (size_t)B * p.per;
   int oblocks = 0;
   if (ohem) {
@@ -419,7 +398,7 @@ int launch_diffusion_loss(const LossTail& in, int B, double ohem_k, float* sampl
   LDMSEG_LAUNCH("loss_finish", loss_finish_kernel, dim3(1), dim3(kThreads), 0, s, p.partial, B, nchunk, (double)n, sample_sums, mean,
                 ohem ? (const double*)(sc + l.ohem_partial) : (const double*)nullptr, oblocks,
                 (const SelectState*)(sc + l.state), ohem_k);
-  return ok();
+  return launch_status();
 }
 
 size_t tensor_minmax_scratch_bytes() { return (size_t)kMaxBlocks * 3 * sizeof(float); }
@@ -428,7 +407,7 @@ int launch_tensor_minmax(const float* x, size_t n, float* out, void* scratch, hi
   const int blocks = stride_blocks(n);
   LDMSEG_LAUNCH("tensor_minmax", minmax_kernel, dim3(blocks), dim3(kThreads), 0, s, x, n, (float*)scratch);
   LDMSEG_LAUNCH("tensor_minmax_finish", minmax_finish_kernel, dim3(1), dim3(64), 0, s, (const float*)scratch, blocks, out);
-  return ok();
+  return launch_status();
 }
 
 int launch_loss_weight_mask(const void* src, int src_dtype, int B, int Hi, int Wi, int h, int w, int mode, int64_t ignore_label,
@@ -443,7 +422,7 @@ int launch_loss_weight_mask(const void* src, int src_dtype, int B, int Hi, int W
   p.out = out; p.flag = flag;
   if (hipMemsetAsync(flag, 0, sizeof(int32_t), s) != hipSuccess) return -3;
   LDMSEG_LAUNCH(launch_name("loss_mask<mode=%d,src=%d>", mode, src_dtype), loss_mask_kernel, dim3(B), dim3(kThreads), 0, s, p);
-  return ok();
+  return launch_status();
 }
 
 }  // namespace ldmseg

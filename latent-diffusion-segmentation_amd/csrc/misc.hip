@@ -290,7 +290,6 @@ inline int grid_for(size_t n, int block = 256, int cap = 4096) {
   if (g < 1) g = 1;
   return (int)g;
 }
-inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 
 }  // namespace
 
@@ -302,7 +301,7 @@ int launch_pack_concat3(const float* a, int Ca, const float* b, int Cb, const fl
     hipLaunchKernelGGL(pack_concat3_kernel<bf16_t>, grid, block, 0, s, a, Ca, b, Cb, c, Cc, (bf16_t*)y, HW, Cpad, 1.f, 0.f);
   else
     hipLaunchKernelGGL(pack_concat3_kernel<float>, grid, block, 0, s, a, Ca, b, Cb, c, Cc, (float*)y, HW, Cpad, 1.f, 0.f);
-  return ok();
+  return launch_status();
 }
 
 int launch_pack_nchw(const float* x, void* y, int B, int C, int HW, int Cpad, float mul, float add, int dtype,
@@ -313,18 +312,18 @@ int launch_pack_nchw(const float* x, void* y, int B, int C, int HW, int Cpad, fl
     hipLaunchKernelGGL(pack_concat3_kernel<bf16_t>, grid, block, 0, s, x, C, nullptr, 0, nullptr, 0, (bf16_t*)y, HW, Cpad, mul, add);
   else
     hipLaunchKernelGGL(pack_concat3_kernel<float>, grid, block, 0, s, x, C, nullptr, 0, nullptr, 0, (float*)y, HW, Cpad, mul, add);
-  return ok();
+  return launch_status();
 }
 
 int launch_time_embed(const int64_t* t_dev, int t_count, int64_t t_host, int B, float* sinus, hipStream_t s) {
   hipLaunchKernelGGL(time_sinus_kernel, dim3(B), dim3(192), 0, s, t_dev, t_count, t_host, B, sinus);
-  return ok();
+  return launch_status();
 }
 
 int launch_small_linear(const float* x, const float* W, const float* bias, float* y, int B, int K, int N, int silu_in,
                         int silu_out, hipStream_t s) {
   hipLaunchKernelGGL(small_linear_kernel<8>, dim3((N + 3) / 4), dim3(256), 0, s, x, W, bias, y, B, K, N, silu_in, silu_out);
-  return ok();
+  return launch_status();
 }
 
 int launch_bilinear2x_nchw(const void* x, float* y, int B, int H, int W, int C, int dtype, hipStream_t s) {
@@ -336,7 +335,7 @@ int launch_bilinear2x_nchw(const void* x, float* y, int B, int H, int W, int C, 
     if (C % 4) return -2;
     LDMSEG_LAUNCH("bilinear2x<f32>", bilinear2x_kernel<float>, grid, block, 0, s, (const float*)x, y, H, W, C);
   }
-  return ok();
+  return launch_status();
 }
 
 int launch_bilinear2x_argmax(const void* x, int64_t* ids, float* prob, int B, int H, int W, int C, float mask_th,
@@ -349,14 +348,14 @@ int launch_bilinear2x_argmax(const void* x, int64_t* ids, float* prob, int B, in
     if (C % 4) return -2;
     LDMSEG_LAUNCH("bilinear_argmax<f32>", bilinear_argmax_kernel<float>, grid, block, 0, s, (const float*)x, ids, prob, H, W, C, mask_th, ignore_label);
   }
-  return ok();
+  return launch_status();
 }
 
 int launch_softmax_rows(const float* sc, void* p, int rows, int n, float scale, int dtype, hipStream_t st) {
   if (n % 4) return -2;
   if (dtype == DT_BF16) LDMSEG_LAUNCH("softmax_rows<bf16>", softmax_rows_kernel<bf16_t>, dim3((rows + 3) / 4), dim3(256), 0, st, sc, (bf16_t*)p, rows, n, scale);
   else LDMSEG_LAUNCH("softmax_rows<f32>", softmax_rows_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, st, sc, (float*)p, rows, n, scale);
-  return ok();
+  return launch_status();
 }
 
 int launch_repack_conv(const float* w, void* out, int Co, int Ci, int KH, int KW, int Npad, int Cipad, int dtype,
@@ -367,7 +366,7 @@ int launch_repack_conv(const float* w, void* out, int Co, int Ci, int KH, int KW
     hipLaunchKernelGGL(repack_conv_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, w, (bf16_t*)out, Co, Ci, KH, KW, Npad, Cipad, cm_tile);
   else
     hipLaunchKernelGGL(repack_conv_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, w, (float*)out, Co, Ci, KH, KW, Npad, Cipad, cm_tile);
-  return ok();
+  return launch_status();
 }
 
 int launch_repack_rows(const float* w, void* out, const int* src_row_dev, int Npad, int K, int dtype, hipStream_t s) {
@@ -376,7 +375,7 @@ int launch_repack_rows(const float* w, void* out, const int* src_row_dev, int Np
     hipLaunchKernelGGL(repack_rows_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, w, (bf16_t*)out, src_row_dev, Npad, K);
   else
     hipLaunchKernelGGL(repack_rows_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, w, (float*)out, src_row_dev, Npad, K);
-  return ok();
+  return launch_status();
 }
 
 int launch_repack_rows_scaled(const float* w, void* out, const int* src_row_dev, int Npad, int K, const float* colscale,
@@ -386,7 +385,7 @@ int launch_repack_rows_scaled(const float* w, void* out, const int* src_row_dev,
     hipLaunchKernelGGL(repack_rows_scaled_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, w, (bf16_t*)out, src_row_dev, Npad, K, colscale);
   else
     hipLaunchKernelGGL(repack_rows_scaled_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, w, (float*)out, src_row_dev, Npad, K, colscale);
-  return ok();
+  return launch_status();
 }
 
 int launch_rowsum(const void* W, const float* add, float* out, int N, int K, int dtype, hipStream_t s) {
@@ -394,7 +393,7 @@ int launch_rowsum(const void* W, const float* add, float* out, int N, int K, int
     hipLaunchKernelGGL(rowsum_kernel<bf16_t>, dim3((N + 3) / 4), dim3(256), 0, s, (const bf16_t*)W, add, out, N, K);
   else
     hipLaunchKernelGGL(rowsum_kernel<float>, dim3((N + 3) / 4), dim3(256), 0, s, (const float*)W, add, out, N, K);
-  return ok();
+  return launch_status();
 }
 
 std::vector<int> geglu_row_map(int nout) {
@@ -474,7 +473,7 @@ int launch_repack_convt2(const float* w, void* out, int Ci, int Co, int dtype, h
     hipLaunchKernelGGL(repack_convt2_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, w, (bf16_t*)out, Ci, Co);
   else
     hipLaunchKernelGGL(repack_convt2_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, w, (float*)out, Ci, Co);
-  return ok();
+  return launch_status();
 }
 
 
@@ -485,18 +484,18 @@ int launch_bit_encode(const int64_t* ids, float* out, uint8_t* ignore, int B, in
                       float fill, float mul, float add, hipStream_t s) {
   const size_t total = (size_t)B * HW;
   hipLaunchKernelGGL(bit_encode_kernel, dim3(grid_for(total)), dim3(256), 0, s, ids, out, ignore, n, HW, total, ignore_label, fill, mul, add);
-  return ok();
+  return launch_status();
 }
 int launch_bit_decode(const float* x, int64_t* out, int B, int n, int HW, hipStream_t s) {
   const size_t total = (size_t)B * HW;
   hipLaunchKernelGGL(bit_decode_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, out, n, HW, total);
-  return ok();
+  return launch_status();
 }
 
 int launch_posterior_sample(const float* moments, const float* noise, float* out, int B, int HW, hipStream_t s) {
   const size_t total = (size_t)B * 4 * HW;
   LDMSEG_LAUNCH("posterior_sample<f32>", posterior_sample_kernel, dim3(grid_for(total)), dim3(256), 0, s, moments, noise, out, HW, total);
-  return ok();
+  return launch_status();
 }
 
 }  // namespace ldmseg

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "gn_plan.h"
 #include "kernels.h"
+#include "ln_plan.h"
 
 namespace ldmseg {
 namespace {
@@ -343,8 +344,6 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GNParams p) {
   GNSTAMP(6)
 }
 
-__device__ __forceinline__ float wave_sum(float v) { return wave64_sum(v); }
-
 // Each wave keeps gamma/beta of its channel vectors in registers and walks rows in batches of RPW
 // (all RPW row loads are issued before the first reduction, so several KB per wave are in flight);
 // C*sizeof(T)/16 <= 64*VPL chunks per row.
@@ -389,7 +388,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* x, T* y, const 
 #pragma unroll
         for (int e = 0; e < PC; ++e) s += f[k][e];      // padding vectors are zero
       }
-      const float mean = wave_sum(s) * invC;
+      const float mean = wave64_sum(s) * invC;
       float q = 0.f;
 #pragma unroll
       for (int k = 0; k < VPL; ++k) {
@@ -398,7 +397,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* x, T* y, const 
           for (int e = 0; e < PC; ++e) { const float d = f[k][e] - mean; q += d * d; }
         }
       }
-      const float rstd = 1.0f / sqrtf(wave_sum(q) * invC + eps);
+      const float rstd = 1.0f / sqrtf(wave64_sum(q) * invC + eps);
       if constexpr (STATS) {
         if (lane == 0) *(float2*)(stats + (size_t)(row0 + r) * 2) = make_float2(mean, rstd);
         continue;
@@ -1392,7 +1391,7 @@ int launch_gn_plan(const GnPlan& pl, GNParams p, hipStream_t s, const IgemmParam
   }
 #undef LDMSEG_FGN
 #undef LDMSEG_GN
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 GnDesc gn_describe(const GNParams& p, int dtype) { return {p.B, p.HW, p.C0, p.C1, p.groups, p.nchunk, dtype}; }
@@ -1420,63 +1419,46 @@ int run_gn(const GNParams& pin, hipStream_t s) {
   return launch_gn_plan<T>(pl, p, s);
 }
 
-template <typename T>
-int run_ln(const void* x, void* y, const float* g, const float* b, int M, int C, float eps, int silu, hipStream_t s) {
-  constexpr int PC = Chunk<T>::N;
-  if (C % PC != 0) return -2;
-  const int nvec = C / PC;
-  const int vpl = (nvec + 63) / 64;
-  dim3 block(256);
-  auto grid_for_rpw = [&](int rpw) {
-    int blocks = (M + 4 * rpw - 1) / (4 * rpw);
-    if (blocks > 2048) blocks = 2048;      // grid-stride over row batches beyond that
-    return dim3(blocks < 1 ? 1 : blocks);
-  };
-  switch (vpl) {
-    case 1: LDMSEG_LAUNCH(launch_name("layernorm<%s,1,4>", dtype_tag<T>()), (layernorm_kernel<T, 1, 4>), grid_for_rpw(4), block, 0, s, (const T*)x, (T*)y, g, b, M, C, eps, silu); break;
-    case 2: LDMSEG_LAUNCH(launch_name("layernorm<%s,2,4>", dtype_tag<T>()), (layernorm_kernel<T, 2, 4>), grid_for_rpw(4), block, 0, s, (const T*)x, (T*)y, g, b, M, C, eps, silu); break;
-    case 3: LDMSEG_LAUNCH(launch_name("layernorm<%s,3,2>", dtype_tag<T>()), (layernorm_kernel<T, 3, 2>), grid_for_rpw(2), block, 0, s, (const T*)x, (T*)y, g, b, M, C, eps, silu); break;
-    case 4: case 5: LDMSEG_LAUNCH(launch_name("layernorm<%s,5,1>", dtype_tag<T>()), (layernorm_kernel<T, 5, 1>), grid_for_rpw(1), block, 0, s, (const T*)x, (T*)y, g, b, M, C, eps, silu); break;
+// A plan as a launch: the only place that names the template arguments of layernorm_kernel and rowstats_kernel (one case per
+// instantiation the library contains; a plan outside the table is refused).  STATS: pl.stats at compile time - the statistics
+// launcher instantiates the statistics kernels and the normalising one the rest, so the library holds each kernel where it did.
+// y, g, b, silu: the normalising forms; stats: the others.
+constexpr int ln_key(int form, int stats, int v, int rpw) { return ((form * 2 + stats) * 100 + v) * 10 + rpw; }
+template <typename T, bool STATS>
+int launch_ln_plan(const LnPlan& pl, const T* x, T* y, const float* g, const float* b, float* stats, int M, int C, float eps, int silu,
+                   hipStream_t s) {
+  constexpr int DT = Elem<T>::kDType;
+  if ((pl.stats != 0) != STATS) return -2;
+  const dim3 grid(pl.grid_x), block(pl.block);
+#define LDMSEG_LN(KERNEL, ...) LDMSEG_LAUNCH(ln_plan_name(pl, DT), KERNEL, grid, block, 0, s, __VA_ARGS__)
+#define LDMSEG_LN_Y(V, R) case ln_key(LN_ROWS, 0, V, R): if constexpr (!STATS) LDMSEG_LN((layernorm_kernel<T, V, R>), x, y, g, b, M, C, eps, silu); break;
+#define LDMSEG_LN_S(V, R) case ln_key(LN_ROWS, 1, V, R): if constexpr (STATS) LDMSEG_LN((layernorm_kernel<T, V, R, true>), x, (T*)nullptr, nullptr, nullptr, M, C, eps, 0, stats); break;
+#define LDMSEG_LN_RS(L, R) case ln_key(LN_SHARED, 1, L, R): if constexpr (STATS) LDMSEG_LN((rowstats_kernel<T, L, R>), x, stats, M, C, eps); break;
+  switch (ln_key(pl.form, STATS, pl.form == LN_SHARED ? pl.LPR : pl.VPL, pl.RPW)) {
+    LDMSEG_LN_Y(1, 4) LDMSEG_LN_Y(2, 4) LDMSEG_LN_Y(3, 2) LDMSEG_LN_Y(5, 1)
+    LDMSEG_LN_RS(8, 2) LDMSEG_LN_RS(16, 2) LDMSEG_LN_RS(32, 2) LDMSEG_LN_RS(64, 2)
+    LDMSEG_LN_S(1, 4) LDMSEG_LN_S(2, 4) LDMSEG_LN_S(3, 2) LDMSEG_LN_S(5, 2)
     default: return -2;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+#undef LDMSEG_LN_RS
+#undef LDMSEG_LN_S
+#undef LDMSEG_LN_Y
+#undef LDMSEG_LN
+  return launch_status();
+}
+
+template <typename T>
+int run_ln(const void* x, void* y, const float* g, const float* b, int M, int C, float eps, int silu, hipStream_t s) {
+  LnPlan pl;
+  if (const int r = ln_choose(LnDesc{M, C, Elem<T>::kDType, 0}, g_gn_knobs, &pl)) return r;
+  return launch_ln_plan<T, false>(pl, (const T*)x, (T*)y, g, b, nullptr, M, C, eps, silu, s);
 }
 
 template <typename T>
 int run_rowstats(const void* x, float* stats, int M, int C, float eps, hipStream_t s) {
-  constexpr int PC = Chunk<T>::N;
-  if (C % PC != 0) return -2;
-  const int vpl = (C / PC + 63) / 64;
-  dim3 block(256);
-  auto grid_for_rpw = [&](int rpw) {
-    int blocks = (M + 4 * rpw - 1) / (4 * rpw);
-    if (blocks > 2048) blocks = 2048;
-    return dim3(blocks < 1 ? 1 : blocks);
-  };
-  const T* xp = (const T*)x;
-  {
-    const int nvec = C / PC;
-    constexpr int RPW = 2;
-    auto grid_rows = [&](int rows_per_wave) {
-      int blocks = (M + 4 * rows_per_wave - 1) / (4 * rows_per_wave);
-      if (blocks > 4096) blocks = 4096;
-      return dim3(blocks < 1 ? 1 : blocks);
-    };
-    if (!(g_gn_knobs.variant & kGnRowstats1)) {       // (the one-row-per-wave kernel below)
-      if (nvec <= 40) { LDMSEG_LAUNCH(launch_name("rowstats<%s,8,%d>", dtype_tag<T>(), RPW), (rowstats_kernel<T, 8, RPW>), grid_rows(8 * RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
-      if (nvec <= 80) { LDMSEG_LAUNCH(launch_name("rowstats<%s,16,%d>", dtype_tag<T>(), RPW), (rowstats_kernel<T, 16, RPW>), grid_rows(4 * RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
-      if (nvec <= 160) { LDMSEG_LAUNCH(launch_name("rowstats<%s,32,%d>", dtype_tag<T>(), RPW), (rowstats_kernel<T, 32, RPW>), grid_rows(2 * RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
-      if (nvec <= 320) { LDMSEG_LAUNCH(launch_name("rowstats<%s,64,%d>", dtype_tag<T>(), RPW), (rowstats_kernel<T, 64, RPW>), grid_rows(RPW), block, 0, s, xp, stats, M, C, eps); return hipGetLastError() == hipSuccess ? 0 : -3; }
-    }
-  }
-  switch (vpl) {
-    case 1: LDMSEG_LAUNCH(launch_name("layernorm<%s,1,4,stats>", dtype_tag<T>()), (layernorm_kernel<T, 1, 4, true>), grid_for_rpw(4), block, 0, s, xp, (T*)nullptr, nullptr, nullptr, M, C, eps, 0, stats); break;
-    case 2: LDMSEG_LAUNCH(launch_name("layernorm<%s,2,4,stats>", dtype_tag<T>()), (layernorm_kernel<T, 2, 4, true>), grid_for_rpw(4), block, 0, s, xp, (T*)nullptr, nullptr, nullptr, M, C, eps, 0, stats); break;
-    case 3: LDMSEG_LAUNCH(launch_name("layernorm<%s,3,2,stats>", dtype_tag<T>()), (layernorm_kernel<T, 3, 2, true>), grid_for_rpw(2), block, 0, s, xp, (T*)nullptr, nullptr, nullptr, M, C, eps, 0, stats); break;
-    case 4: case 5: LDMSEG_LAUNCH(launch_name("layernorm<%s,5,2,stats>", dtype_tag<T>()), (layernorm_kernel<T, 5, 2, true>), grid_for_rpw(2), block, 0, s, xp, (T*)nullptr, nullptr, nullptr, M, C, eps, 0, stats); break;
-    default: return -2;
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  LnPlan pl;
+  if (const int r = ln_choose(LnDesc{M, C, Elem<T>::kDType, 1}, g_gn_knobs, &pl)) return r;
+  return launch_ln_plan<T, true>(pl, (const T*)x, nullptr, nullptr, nullptr, stats, M, C, eps, 0, s);
 }
 
 }  // namespace
@@ -1495,6 +1477,7 @@ void groupnorm_set_coop(int mode, int poll_us) {
 int groupnorm_knob(int key) { return key == 8 ? g_gn_knobs.variant : key == 10 ? g_gn_knobs.coop_mode : g_gn_knobs.poll_us; }
 int groupnorm_plan(const GnDesc& q, int cus, bool region_ok, GnPlan* pl) { return gn_choose(q, g_gn_knobs, cus, region_ok, pl); }
 int finish_groupnorm_plan(int B, int HW, int C, int dtype, GnPlan* pl) { return gn_finish_choose(B, HW, C, dtype, g_gn_knobs, pl); }
+int layernorm_plan(const LnDesc& q, LnPlan* pl) { return ln_choose(q, g_gn_knobs, pl); }
 size_t gn_sync_bytes() { return kGnRegionWords * sizeof(unsigned long long); }
 int gn_sync_init(void* region, hipStream_t s) {
   return hipMemsetAsync(region, 0, gn_sync_bytes(), s) == hipSuccess ? 0 : -3;

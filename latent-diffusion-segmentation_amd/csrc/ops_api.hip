@@ -15,6 +15,7 @@
 #include "attn_plan.h"
 #include "gn_plan.h"
 #include "kernels.h"
+#include "ln_plan.h"
 #include "nearest_index.h"
 #include "runtime.h"
 
@@ -138,7 +139,7 @@ struct Stage {
     if (status) return status;
     if (dt == DT_BF16) hipLaunchKernelGGL(convert_back_kernel<bf16_t>, dim3(rows_grid(n)), dim3(256), 0, s, (const bf16_t*)p, out, n);
     else hipLaunchKernelGGL(convert_back_kernel<float>, dim3(rows_grid(n)), dim3(256), 0, s, (const float*)p, out, n);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
   }
   // NHWC compute dtype [B, HW, ld] -> NCHW fp32 [B, C, HW]
   int nchw_out(const void* p, float* out, int B, int C, int HW, int ld) {
@@ -146,7 +147,7 @@ struct Stage {
     dim3 grid((HW + 255) / 256, B), block(256);
     if (dt == DT_BF16) hipLaunchKernelGGL(unpack_nhwc_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)p, out, C, HW, ld);
     else hipLaunchKernelGGL(unpack_nhwc_kernel<float>, grid, block, 0, s, (const float*)p, out, C, HW, ld);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
   }
   // the split-K step of a launch that is filled in otherwise: `forced` K slices, or the engine's plan, and their partial sums
   void splitk(IgemmParams& p, int forced = 0) {
@@ -600,6 +601,17 @@ int ldmseg_op_conv_groupnorm_plan(int B, int Co, int HW, int dtype, char* buf, i
   return gn_plan_out(finish_groupnorm_plan(B, HW, Co, dtype, &pl), pl, dtype, buf, n);
 }
 
+// The dispatch string of a described LayerNorm (stats = 0: ldmseg_op_layernorm) or row-statistics launch (stats = 1: the pass in
+// front of a folded-LayerNorm GEMM) under the current debug key 8 (ln_plan.h; no device): the dispatch-log name, then
+// " grid=GX block=T"; -2 where the launch returns -2.
+int ldmseg_op_layernorm_plan(int M, int C, int dtype, int stats, char* buf, int n) {
+  if (!buf || n < 1) return -2;
+  LnPlan pl;
+  const int r = layernorm_plan(LnDesc{M, C, dtype, stats}, &pl);
+  if (r == 0) std::snprintf(buf, (size_t)n, "%s", ln_plan_line(pl, dtype).c_str());
+  return r;
+}
+
 // timing of one GroupNorm launch shape the way the engine launches it (tools/kbench.py gn): average microseconds over
 // `iters` back-to-back launches between two HIP events; the input is whatever the allocation holds (statistics of garbage
 // cost the same), gamma / beta are [C + C2] device vectors
@@ -946,7 +958,7 @@ int ldmseg_op_fastdiv(const int* n, int count, int d, int* q, void* stream) {
   if (!n || !q || count < 0 || d < 1) return -2;
   const FastDiv f = fastdiv_make(d);
   hipLaunchKernelGGL(fastdiv_probe_kernel, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, count, f, q);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 // the nearest-resize source index of the loss-weight mask (nearest_index.h), evaluated on the host: CPU-suite test hook

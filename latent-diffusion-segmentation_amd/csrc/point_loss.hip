@@ -88,12 +88,7 @@ __global__ __launch_bounds__(kThreads) void point_uncertainty_kernel(const Point
   p.unc[(size_t)r * p.S + j] = u + 0.0f;             // -0.0 -> +0.0: equal values get equal keys
 }
 
-// ---------------------------------------------------------------- select
-__device__ __forceinline__ uint32_t f32_key(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
+// ---------------------------------------------------------------- select (keys: f32_key, reduce_dev.h)
 __global__ __launch_bounds__(kThreads) void point_select_kernel(const float* unc, int S, int kU, int32_t* sel) {
   __shared__ uint32_t s_hist[256];
   __shared__ uint32_t s_prefix, s_want;
@@ -237,7 +232,6 @@ __global__ __launch_bounds__(64) void gaussian_kl_finish_kernel(const float* per
   }
 }
 
-inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 
 // scratch layout of launch_point_loss (bytes): partials | uncertainties | selected indices
 struct PointScratch {
@@ -264,7 +258,7 @@ int launch_class_presence(const int64_t* targets, const uint8_t* valid, int B, i
   gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
   LDMSEG_LAUNCH("class_presence", class_presence_kernel, dim3(gx, B), dim3(kThreads), 0, s, targets, valid, n, C, ignore_label, present,
                 flag);
-  return ok();
+  return launch_status();
 }
 
 size_t point_loss_scratch_bytes(int rows, int S, int kU, int P) {
@@ -288,13 +282,13 @@ int launch_point_loss(const PointLoss& in, double num_masks, float* out, int32_t
   LDMSEG_LAUNCH("point_loss", point_loss_kernel, dim3(nchunk, rows), dim3(kThreads), 0, s, p);
   LDMSEG_LAUNCH("point_loss_finish", point_loss_finish_kernel, dim3(1), dim3(kThreads), 0, s, (const double*)p.partial, p.B, p.N, nchunk,
                 p.P, num_masks, out);
-  return ok();
+  return launch_status();
 }
 
 int launch_gaussian_kl(const float* moments, int B, int n, float* per_image, float* mean, hipStream_t s) {
   LDMSEG_LAUNCH("gaussian_kl", gaussian_kl_kernel, dim3(B), dim3(kThreads), 0, s, moments, n, per_image);
   if (mean) LDMSEG_LAUNCH("gaussian_kl_finish", gaussian_kl_finish_kernel, dim3(1), dim3(64), 0, s, (const float*)per_image, B, mean);
-  return ok();
+  return launch_status();
 }
 
 }  // namespace ldmseg

@@ -256,7 +256,6 @@ __global__ __launch_bounds__(kThreads) void gaussian_kl_backward_kernel(const fl
   grad_moments[at] = out;
 }
 
-inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 
 // scratch layout of launch_point_loss_backward (bytes): partials | stat | rec_a | rec_b | rec_label | count | cursor | img_base | entries
 struct GradScratch {
@@ -308,13 +307,13 @@ int launch_point_loss_backward(const PointLossGrad& in, void* scratch, hipStream
   LDMSEG_LAUNCH("point_grad_scan", point_grad_scan_kernel, dim3(p.B + 1), dim3(kThreads), 0, s, g, nchunk);
   LDMSEG_LAUNCH("point_grad_fill", point_grad_fill_kernel, dim3(nchunk, rows), dim3(kThreads), 0, s, g);
   LDMSEG_LAUNCH("point_grad_gather", point_grad_gather_kernel, dim3((HW + kThreads - 1) / kThreads, p.B), dim3(kThreads), 0, s, g);
-  return ok();
+  return launch_status();
 }
 
 int launch_gaussian_kl_backward(const float* moments, int B, int n, const float* grad_per_image, float* grad_moments, hipStream_t s) {
   LDMSEG_LAUNCH("gaussian_kl_backward", gaussian_kl_backward_kernel, dim3((2 * n + kThreads - 1) / kThreads, B), dim3(kThreads), 0, s,
                 moments, n, grad_per_image, grad_moments);
-  return ok();
+  return launch_status();
 }
 
 }  // namespace ldmseg

@@ -11,11 +11,13 @@
 
 #include "kernels.h"
 #include "point_sample.h"
+#include "reduce_dev.h"
 
 namespace ldmseg {
 namespace pointloss {
 
 constexpr int kThreads = 256;
+static_assert(kThreads == kBlockSumThreads, "block_sum (reduce_dev.h) sums kBlockSumThreads / 64 waves");
 
 // effective target of pixel i of image b: the masked pixels count as ignore_label (losses.py:326, without touching the caller's tensor)
 __device__ __forceinline__ int64_t eff_target(const PointLoss& p, int b, int i) {
@@ -112,20 +114,6 @@ __device__ __forceinline__ MaskPoint mask_point(const PointLoss& p, const Row& w
   q.y = bilinear_sample(tt, p.Ht, p.Wt, [&](int i) { return eff_target(p, w.b, i) == cls ? 1.0f : 0.0f; });
   q.sg = 1.0f / (1.0f + expf(-q.x));
   return q;
-}
-
-// ---------------------------------------------------------------- fixed-order sums
-// sum over the workgroup in a fixed order: lanes by xor-shuffle tree, then the four waves in order; valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double* s_red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) s_red[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kThreads / 64; ++w) t += s_red[w];
-  return t;
 }
 
 inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }

@@ -403,7 +403,7 @@ int launch_panoptic_from_decoder(const void* x4, int B, int H4, int W4, int C, i
     hipLaunchKernelGGL(panoptic_remap_kernel, dim3((unsigned)blocks), dim3(256), 0, s, labels + offsets[b], keep + (size_t)b * C, C,
                        (int)total, total, panoptic + offsets[b]);
   }
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 int launch_panoptic_postprocess(const float* logits, int B, int C, int HW, int threshold_output, int threshold_mode,
@@ -420,7 +420,7 @@ int launch_panoptic_postprocess(const float* logits, int B, int C, int HW, int t
   size_t blocks = (total + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(panoptic_remap_kernel, dim3((unsigned)blocks), dim3(256), 0, s, labels, keep, C, HW, total, panoptic);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 // SemsegMeter.update on n (pred, gt) int64 pairs: counts int64 [3][K] += (tp | fp | fn); see semseg_meter_kernel
@@ -432,7 +432,7 @@ int launch_semseg_meter(const int64_t* pred, const int64_t* gt, size_t n, int K,
   if (n / blocks >= (size_t)1 << 31) return -2;        // (an int LDS counter per workgroup)
   hipLaunchKernelGGL(semseg_meter_kernel, dim3((unsigned)blocks), dim3(256), 0, s, pred, gt, n, K, ignore_index,
                      (unsigned long long*)counts);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 // Fused mIoU tail on the decoder's 4L NHWC output (see semseg_scan_kernel): one launch, grid (ceil(oh * ow / 256), B)
@@ -451,7 +451,7 @@ int launch_semseg_from_decoder(const void* x4, int B, int H4, int W4, int C, int
   const dim3 grid((oh * ow + 255) / 256, B);
   if (dtype == DT_BF16) hipLaunchKernelGGL(semseg_scan_kernel<bf16_t>, grid, dim3(256), 0, s, p);
   else hipLaunchKernelGGL(semseg_scan_kernel<float>, grid, dim3(256), 0, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 }  // namespace ldmseg

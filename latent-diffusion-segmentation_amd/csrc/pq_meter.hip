@@ -215,7 +215,7 @@ int launch_pq_match(const int32_t* pred, const void* gt, int gt_format, int B, c
   }
   hipLaunchKernelGGL(pq_match_kernel, dim3(B), dim3(kPqThreads), 0, s, inter, keep, slot_crowd, slot_area, slot_meta, P, Gpad, stats,
                      match_iou);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 }  // namespace ldmseg

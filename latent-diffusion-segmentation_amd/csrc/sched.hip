@@ -16,7 +16,6 @@ inline int grid_for(size_t n, int block = 256, int cap = 4096) {
   if (g < 1) g = 1;
   return (int)g;
 }
-inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 
 // ---------------------------------------------------------------- scheduler
 // ddim_scheduler.py:238-267; every product / sum rounded separately like the
@@ -63,26 +62,26 @@ __global__ void axpby_kernel(const float* x, float a, float b, float* y, size_t 
 
 int launch_ddim_step(const float* eps, const float* x, float* prev, float* x0, size_t n, DdimCoef c, hipStream_t s) {
   hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_for(n)), dim3(256), 0, s, eps, x, prev, x0, n, c);
-  return ok();
+  return launch_status();
 }
 
 int launch_inpaint_paste(float* cur, const float* z0, const float* noise, const uint8_t* known, float sa, float sb,
                          int B, int C, int HW, hipStream_t s) {
   const size_t total = (size_t)B * C * HW;
   hipLaunchKernelGGL(inpaint_paste_kernel, dim3(grid_for(total)), dim3(256), 0, s, cur, z0, noise, known, sa, sb, C, HW, total);
-  return ok();
+  return launch_status();
 }
 
 int launch_add_noise(const float* x0, const float* noise, const int64_t* t_dev, const float* ac_dev, int n_train, float scale,
                      float* out, int B, size_t per, int remove, hipStream_t s) {
   const size_t total = (size_t)B * per;
   hipLaunchKernelGGL(add_noise_kernel, dim3(grid_for(total)), dim3(256), 0, s, x0, noise, t_dev, ac_dev, n_train, scale, out, per, total, remove);
-  return ok();
+  return launch_status();
 }
 
 int launch_axpby(const float* x, float a, float b, float* y, size_t n, hipStream_t s) {
   hipLaunchKernelGGL(axpby_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, a, b, y, n);
-  return ok();
+  return launch_status();
 }
 
 }  // namespace ldmseg

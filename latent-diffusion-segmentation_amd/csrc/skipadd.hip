@@ -74,7 +74,7 @@ int launch_skip_add(const SkipAddSeg* segs, int n_segs, int dtype, hipStream_t s
     LDMSEG_LAUNCH(launch_name("skip_add<%s>", dtype_tag<bf16_t>()), skip_add_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, A);
   else
     LDMSEG_LAUNCH(launch_name("skip_add<%s>", dtype_tag<float>()), skip_add_kernel<float>, dim3(grid), dim3(256), 0, s, A);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 }  // namespace ldmseg

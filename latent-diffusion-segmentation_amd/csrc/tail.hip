@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lds_dma.h"
 #include "sched_math.h"
 
 namespace ldmseg {
@@ -33,16 +34,6 @@ constexpr int kXBytes = kKT * kSlice;                  // 117760
 constexpr int kWRow = 9 * kC * 2;                      // 5760 B: one output channel's weights, K = (tap, channel)
 constexpr int kWBytes = 4 * kWRow;                     // 23040
 constexpr int kLds = kXBytes + kWBytes + 16;           // + 16 zero bytes (A-operand rows 4..15)
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, off"
-      :
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
 
 struct TailParams {
   const bf16_t* x;        // [B, H*W, 320] SiLU(GroupNorm(h))
@@ -177,15 +168,10 @@ int launch_conv_out_tail(const StepTail& t, hipStream_t s) {
   p.B = t.B; p.H = t.H; p.W = t.W; p.eps_out = t.eps_out;
   p.ddim = t.ddim; p.last = t.last; p.c = t.c; p.latents = t.latents; p.cond = t.cond; p.rgb = t.rgb;
   p.xin_next = (bf16_t*)t.xin_next; p.known = t.known; p.z0 = t.z0; p.noise = t.noise; p.sa = t.sa; p.sb = t.sb;
-  static bool attr_set[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)conv_out_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    attr_set[dev] = true;
-  }
+  static bool lds_raised[64] = {};
+  raise_lds_limit_once((const void*)conv_out_tail_kernel, kLds, lds_raised);
   LDMSEG_LAUNCH_GEMM("conv_out_tail<bf16>", conv_out_tail_kernel, dim3(t.W / kTW, t.H / kTH, t.B), dim3(512), kLds, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 }  // namespace ldmseg

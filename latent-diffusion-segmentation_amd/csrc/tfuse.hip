@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lds_dma.h"
 
 namespace ldmseg {
 namespace {
@@ -44,46 +45,6 @@ constexpr int kChunkBytes = kKT * kW1Tile + kW2Unit;   // 122880
 constexpr int kW2A = 192 * 128, kW2B = 128 * 128;     // the W2 chunk as two units: output fragments 0..2 / 3..4 of every wave
 constexpr int kPUnit = 192 * 128;        // 24576: proj_out unit = [160 rows of one N half + 32 rows of padding][128 B] (two consecutive
                                          // 40 KB units would not fit the ring; 24 KB keeps every unit a multiple of the loaders' 8 KB round)
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, off"
-      :
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
-__device__ __forceinline__ void glds16_sbase(unsigned voff, const void* sbase, unsigned lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 3\n\t"   // (M0 write -> LDS-DMA: 1 wait state; SGPR base written by SALU -> VMEM: 5; see igemm.hip)
-      "global_load_lds_dwordx4 %0, %1"
-      :
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory");
-}
-// two consecutive pieces (2 KiB) from one base: the instruction's immediate offset moves the LDS address along with the global one
-__device__ __forceinline__ void glds16x2_sbase(unsigned voff, const void* sbase, unsigned lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 3\n\t"
-      "global_load_lds_dwordx4 %0, %1\n\t"
-      "global_load_lds_dwordx4 %0, %1 offset:1024"
-      :
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory");
-}
-// at most n of this wave's LDS-DMA pieces still in flight (n <= 16: the wave's share of the ring)
-__device__ __forceinline__ void wait_pieces(int n) {
-  switch (n) {
-#define TF_W(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-    TF_W(0) TF_W(1) TF_W(2) TF_W(3) TF_W(4) TF_W(5) TF_W(6) TF_W(7) TF_W(8) TF_W(9) TF_W(10) TF_W(11) TF_W(12) TF_W(13)
-    TF_W(14) TF_W(15)
-#undef TF_W
-    default: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-  }
-}
 
 struct MlpFusedParams {
   const bf16_t* x;         // [M][320] h (un-normalised): LayerNorm input and the residual of ff.net.2
@@ -580,7 +541,7 @@ int launch_pack_mlp_stream(const void* w1, const void* w2, const void* wp, void*
   const long long nvec = (long long)mlp_fused_stream_bytes(C) / 16;
   hipLaunchKernelGGL(tf_pack_stream_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s, (const bf16_t*)w1,
                      (const bf16_t*)w2, (const bf16_t*)wp, (uint4*)out, 4 * kC / kHC, nvec);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 // h [M][320] bf16 in place (proj = 0: out = h + ff(LN(h)))  or  out = proj_out(h + ff(LN(h))) + x2 (proj = 1)
@@ -596,17 +557,12 @@ int launch_mlp_fused(const void* h, void* out, const void* x2, const void* strea
   // start-chunk rotation by the tile's index inside its image (whole tiles per image only; otherwise by nothing)
   p.rot_tiles = (!(g_tfuse_dbg & 256) && rows_per_image > 0 && rows_per_image % kBM == 0) ? rows_per_image / kBM : 0;
   const dim3 grid((M + kBM - 1) / kBM), block(768);
-  static bool attr_set[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)mlp_fused_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    (void)hipFuncSetAttribute((const void*)mlp_fused_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    attr_set[dev] = true;
-  }
+  static bool lds_raised[2][64] = {};                 // one row of flags per instantiation
+  raise_lds_limit_once((const void*)mlp_fused_kernel<false>, kLds, lds_raised[0]);
+  raise_lds_limit_once((const void*)mlp_fused_kernel<true>, kLds, lds_raised[1]);
   if (proj) LDMSEG_LAUNCH_GEMM("mlp_fused<bf16,proj=1>", mlp_fused_kernel<true>, grid, block, kLds, s, p);
   else LDMSEG_LAUNCH_GEMM("mlp_fused<bf16,proj=0>", mlp_fused_kernel<false>, grid, block, kLds, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 }  // namespace ldmseg

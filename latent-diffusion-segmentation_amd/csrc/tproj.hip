@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lds_dma.h"
 
 namespace ldmseg {
 namespace {
@@ -34,45 +35,11 @@ constexpr int kNPass = 4;                 // proj_in, to_q, to_k, to_v
 constexpr int kUnitsPerPass = kKT;        // 5
 constexpr int kStreamBytes = kNPass * kUnitsPerPass * kUnit;   // 819200
 
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, off"
-      :
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
-// two consecutive pieces (2 KiB) from one base: the instruction's immediate offset moves the LDS address along with the global one
-__device__ __forceinline__ void glds16x2_sbase(unsigned voff, const void* sbase, unsigned lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 3\n\t"
-      "global_load_lds_dwordx4 %0, %1\n\t"
-      "global_load_lds_dwordx4 %0, %1 offset:1024"
-      :
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory");
-}
-__device__ __forceinline__ void wait_pieces(int n) {
-  switch (n) {
-#define TP_W(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-    TP_W(0) TP_W(1) TP_W(2) TP_W(3) TP_W(4) TP_W(5) TP_W(6) TP_W(7) TP_W(8) TP_W(9) TP_W(10) TP_W(11) TP_W(12) TP_W(13)
-    TP_W(14) TP_W(15)
-#undef TP_W
-    default: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-  }
-}
-
 #ifdef LDMSEG_TPROJ_ABLATE
 #define TPDBG(bit) ((LDMSEG_TPROJ_ABLATE) & (bit))     // compile-time phase ablation (results wrong): 1 no weight DMA, 2 no global stores, 4 no MFMA, 8 no fragment reads
 #else
 #define TPDBG(bit) 0
 #endif
-
-// workgroup barrier that waits for this wave's LDS traffic only (what __syncthreads() compiles to on gfx950 outside tgsplit mode;
-// spelled out because the compute waves must never wait for vmcnt here: their epilogue stores are still in flight)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 struct ProjQkvParams {
   const bf16_t* x;         // [M][320]: GroupNorm(transformer input)
@@ -425,7 +392,7 @@ int launch_pack_proj_qkv_stream(const void* wp, const void* wqkv, void* out, int
   if (C != kC || !wp || !wqkv || !out) return -2;
   const long long nvec = kStreamBytes / 16;
   hipLaunchKernelGGL(tp_pack_stream_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s, (const bf16_t*)wp, (const bf16_t*)wqkv, (uint4*)out, nvec);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 // x [M][320] bf16 -> h [M][320], qkv [M][960].  bias4: [4][320] fp32 (proj_in bias | W_q beta | W_k beta | W_v beta)
@@ -441,15 +408,10 @@ int launch_proj_qkv_fused(const void* x, void* h, void* qkv, const void* stream,
     p.gn_partial = gn->partial; p.gn_gamma = gn->gamma; p.gn_beta = gn->beta;
     p.gn_nchunk = gn->nchunk; p.gn_per = (gn->HW + gn->nchunk - 1) / gn->nchunk; p.gn_hw = gn->HW; p.gn_eps = gn->eps;
   }
-  static bool attr_set[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)proj_ln_qkv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    attr_set[dev] = true;
-  }
+  static bool lds_raised[64] = {};
+  raise_lds_limit_once((const void*)proj_ln_qkv_kernel, kLds, lds_raised);
   LDMSEG_LAUNCH_GEMM(gn ? "proj_ln_qkv<bf16,gn>" : "proj_ln_qkv<bf16>", proj_ln_qkv_kernel, dim3(M / kBM), dim3(768), kLds, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch_status();
 }
 
 }  // namespace ldmseg

@@ -167,6 +167,7 @@ SIGNATURES = {
     "ldmseg_op_igemm_plan": (_i, [C.POINTER(_i), _i, _i, C.c_char_p, _i]),
     "ldmseg_op_groupnorm_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i]),
     "ldmseg_op_conv_groupnorm_plan": (_i, [_i, _i, _i, _i, C.c_char_p, _i]),
+    "ldmseg_op_layernorm_plan": (_i, [_i, _i, _i, _i, C.c_char_p, _i]),
     "ldmseg_op_attention_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i]),
     "ldmseg_op_fastdiv": (_i, [_vp, _i, _i, _vp, _vp]),
     "ldmseg_op_nearest_index": (_i, [_i, _i, C.POINTER(_i)]),

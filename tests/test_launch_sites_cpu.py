@@ -101,7 +101,7 @@ def test_every_forward_family_logs():
 def test_scan_catches_a_bare_launch():
     """the scan itself: a logged launch turned back into a bare one, in one form per family, is reported"""
     src = read_sources()
-    for f, old in (("norm.hip", "LDMSEG_LAUNCH(launch_name(\"layernorm<%s,3,2>\", dtype_tag<T>()), "),
+    for f, old in (("norm.hip", "LDMSEG_LAUNCH(ln_plan_name(pl, DT), "),       # the one launch site of launch_ln_plan
                    ("attention4.hip", "LDMSEG_LAUNCH(launch_name(\"attn4<d40,%d,%d,%d>\", NST, LAZY, NWV), "),
                    ("tfuse.hip", "LDMSEG_LAUNCH_GEMM(\"mlp_fused<bf16,proj=1>\", ")):
         assert src[f].count(old) == 1, (f, old)

@@ -470,6 +470,37 @@ def test_groupnorm_plan_cases_straddle_the_rule(L):
         assert lines[a].split(" grid=")[0] != lines[b].split(" grid=")[0], (a, lines[a], b, lines[b])
 
 
+def test_layernorm_plan_equals_launch(L):
+    """ldmseg_op_layernorm_plan names what the launch then logs, for every case of tests/golden/ln_dispatch.json (recorded on an
+    MI355X before the chooser was factored out of the launchers: every form in both dtypes, both values of key 8, the refusals, and
+    row counts past the grid cap), that name is the recorded one, and the launch computes F.layer_norm - for the statistics cases
+    F.linear of it, which reads (mean, rstd) of every row - under the bounds of test_layernorm / test_layernorm_folded_into_linear."""
+    import json
+    import os
+    from conftest import GOLDEN
+    import ln_cases as G
+    lib = L.lib()
+    fx = json.load(open(os.path.join(GOLDEN, "ln_dispatch.json")))
+    torch.set_num_threads(32)
+    for *case, want in fx["cases"]:
+        case = tuple(case)
+        M, Cc, dt, stats, key8 = case
+        r, names, out = G.run_case(L, case)
+        lib.ldmseg_debug_set(8, key8)
+        try:
+            pr, line = G.plan(lib, M, Cc, dt, stats)
+        finally:
+            lib.ldmseg_debug_set(8, 0)
+        if not isinstance(want, str):
+            assert (r, pr, names) == (want, -2, []), (case, r, pr, names)
+            continue
+        assert (r, pr) == (0, 0) and names == [G.plan_name(line)] == [want], (case, names, line, want)
+        err = rel_err(out, G.reference(case))
+        if M > 9:
+            print(case, line, f"{err:.2e}")
+        assert err < ((1.5e-2 if dt == BF16 else 1e-4) if stats else (8e-3 if dt == BF16 else 2e-5)), (case, line, err)
+
+
 @pytest.mark.parametrize("dt", [F32, BF16])
 @pytest.mark.parametrize("M,Cc,eps,silu", [(77, 320, 1e-5, 0), (64, 640, 1e-5, 0), (33, 1280, 1e-5, 0), (50, 256, 1e-6, 1)])
 def test_layernorm(L, dt, M, Cc, eps, silu):
