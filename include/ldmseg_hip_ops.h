@@ -220,6 +220,26 @@ int ldmseg_op_attention_plan(int kind, int B, int N, int S, int C, int heads, in
 int ldmseg_igemm_log(int enable);
 int ldmseg_igemm_log_read(char* buf, int n);
 
+/* The time-embedding path, which runs in fp32 in every compute mode and stays out of the dispatch log.  Nothing is staged: every
+ * tensor is fp32 (timesteps int64) on the device already.
+ * _time_sinusoid: out [B,320] = diffusers Timesteps(320, flip_sin_to_cos=True, freq_shift=0) = [cos(t f_i) | sin(t f_i)],
+ *   f_i = exp(-ln(1e4) i / 160), of the timesteps given as a forward takes them: t_dev with t_count = B entries, or with t_count = 1
+ *   entry for all B rows, or (t_dev NULL) t_host for all rows.  -2: B < 1, out NULL, t_dev with t_count not in {1, B}.
+ * _small_linear: y [B,N] = act_out(F.linear(act_in(x [B,K]), W [N,K], bias [N] or NULL)), act = SiLU where its flag is set - the
+ *   Linear of TimestepEmbedding, of every time_emb_proj and of the CLIP visual projection.  Any B >= 1.  -2: x, W or y NULL,
+ *   B, K or N below 1.
+ * _unet_time_rows: the handle's own time-embedding pass (the one function behind every forward and both sampling loops) for n
+ *   timesteps (HOST array), the way the loops run it: linear_1 -> SiLU -> linear_2 -> time_emb_proj(SiLU(.)) of every resnet of
+ *   table 0 (the UNet's resnets in model order) or 1 (down_blocks_additional of a separate-encoder handle), in chunks of 64 rows,
+ *   into rows_dev [n, *total_out].  rows_dev NULL: only *total_out is set.  Any n >= 1; scratch memory of its own; waits for the
+ *   stream.  -2: a NULL handle / timesteps / total_out, n < 1, a negative timestep, table 1 on another handle, any other table. */
+struct ldmseg_unet;
+int ldmseg_op_time_sinusoid(const int64_t* t_dev, int t_count, int64_t t_host, int B, float* out, void* stream);
+int ldmseg_op_small_linear(const float* x, const float* W, const float* bias, int B, int K, int N, int silu_in, int silu_out, float* y,
+                           void* stream);
+int ldmseg_unet_time_rows(struct ldmseg_unet* h, const int64_t* timesteps_host, int n, int table, float* rows_dev, int* total_out,
+                          void* stream);
+
 /* q[i] = n[i] / d (0 <= n[i] < 2^31, d >= 1) computed the way the kernels divide: host-prepared multiply-shift pair */
 int ldmseg_op_fastdiv(const int* n, int count, int d, int* q, void* stream);
 

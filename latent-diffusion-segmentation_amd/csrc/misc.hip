@@ -35,7 +35,7 @@ __global__ void time_sinus_kernel(const int64_t* t_dev, int t_count, int64_t t_h
   out[b * 320 + 160 + i] = sinf(arg);
 }
 
-// y[b][n] = act_out( sum_k act_in(x[b][k]) W[n][k] + bias[n] ), f32, B <= 64; one wave per n
+// y[b][n] = act_out( sum_k act_in(x[b][k]) W[n][k] + bias[n] ), f32, any B >= 1 (BC rows per pass over w); one wave per n
 template <int BC>
 __global__ __launch_bounds__(256) void small_linear_kernel(const float* x, const float* W, const float* bias, float* y,
                                                            int B, int K, int N, int silu_in, int silu_out) {

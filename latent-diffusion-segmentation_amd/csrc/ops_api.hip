@@ -1128,4 +1128,17 @@ int ldmseg_op_attention_fp8(const float* qkv, int B, int N, int C, int heads, fl
   return 0;
 }
 
+// The two fp32 kernels of the time embedding (misc.hip) on the caller's device tensors: nothing is staged or converted.
+// _time_sinusoid: out [B][320] = [cos(t f_i) | sin(t f_i)] of t_dev (int64, t_count = 1 broadcasts, t_count = B per row) or, NULL, t_host.
+int ldmseg_op_time_sinusoid(const int64_t* t_dev, int t_count, int64_t t_host, int B, float* out, void* stream) {
+  if (B < 1 || !out || (t_dev && t_count != 1 && t_count != B)) return -2;
+  return launch_time_embed(t_dev, t_count, t_host, B, out, (hipStream_t)stream);
+}
+// _small_linear: y [B][N] = act_out(act_in(x [B][K]) W[N][K]^T + bias [N] or NULL), act = SiLU where its flag is set; any B >= 1.
+int ldmseg_op_small_linear(const float* x, const float* W, const float* bias, int B, int K, int N, int silu_in, int silu_out, float* y,
+                           void* stream) {
+  if (!x || !W || !y || B < 1 || K < 1 || N < 1) return -2;
+  return launch_small_linear(x, W, bias, y, B, K, N, silu_in, silu_out, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -179,7 +179,7 @@ int unet_check(const ldmseg_unet* u, const UnetCall& q) {
 }
 
 // The time-embedding MLP, written once: n timesteps -> sinusoid -> linear_1 -> SiLU -> linear_2 -> all time_emb_proj(SiLU(.)) of one
-// table (pw, pb: `total` columns) -> rows [n][total], in chunks of the 64 rows launch_small_linear takes.
+// table (pw, pb: `total` columns) -> rows [n][total], in chunks of 64 rows.
 struct TimeBufs { float *sinus, *e1, *emb, *rows; };     // [n][320], [n][kTimeDim] twice, [n][total]
 int time_mlp(const ldmseg_unet* u, const int64_t* t_dev, int t_count, int64_t t_host, int n, const TimeBufs& tb, const float* pw,
              const float* pb, int total, hipStream_t s) {
@@ -652,6 +652,40 @@ int ldmseg_unet_reserve(ldmseg_unet* h, int B, int L) {
   TRY(temb_reserve(h, 64));
   TRY(igemm_warm());
   return 0;
+}
+
+// Test support (include/ldmseg_hip_ops.h): the handle's own time_mlp for n host timesteps on one of its time_emb_proj tables, the way
+// the sampling loops call it (timesteps on the device, one per row), on scratch memory of this call.  Waits for the stream.
+int ldmseg_unet_time_rows(ldmseg_unet* h, const int64_t* timesteps_host, int n, int table, float* rows_dev, int* total_out,
+                          void* stream) {
+  g_err.clear();
+  if (!h || !timesteps_host || !total_out) return fail(LDMSEG_E_SHAPE, "null argument");
+  if (n < 1) return fail(LDMSEG_E_SHAPE, "n must be >= 1");
+  for (int i = 0; i < n; ++i)
+    if (timesteps_host[i] < 0) return fail(LDMSEG_E_SHAPE, "negative timestep");
+  if (table != 0 && !(table == 1 && h->sepenc)) return fail(LDMSEG_E_SHAPE, "table must be 0, or 1 on a separate-encoder handle");
+  const float* pw = table ? h->tproj_img_w : h->tproj_w;
+  const float* pb = table ? h->tproj_img_b : h->tproj_b;
+  const int total = table ? h->temb_img_total : h->temb_total;
+  *total_out = total;
+  if (!rows_dev) return 0;
+  DeviceGuard dg(h->cfg.device);
+  hipStream_t s = (hipStream_t)stream;
+  struct Scratch {
+    void* p = nullptr;
+    ~Scratch() { if (p) (void)hipFree(p); }
+  } mem;
+  HIP_TRY(hipMalloc(&mem.p, (size_t)n * (sizeof(int64_t) + (320 + 2 * (size_t)kTimeDim) * sizeof(float))));
+  int64_t* ts = (int64_t*)mem.p;
+  TimeBufs tb;
+  tb.sinus = (float*)(ts + n);
+  tb.e1 = tb.sinus + (size_t)n * 320;
+  tb.emb = tb.e1 + (size_t)n * kTimeDim;
+  tb.rows = rows_dev;
+  HIP_TRY(hipMemcpyAsync(ts, timesteps_host, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  const int rc = time_mlp(h, ts, n, 0, n, tb, pw, pb, total, s);
+  HIP_TRY(hipStreamSynchronize(s));      // (before the scratch goes, also after a failed launch)
+  return rc ? launch_code(rc, "time embedding failed") : 0;
 }
 
 int ldmseg_sample_loop(ldmseg_unet* h, const ldmseg_sample_cfg* cfg, float* latents, const float* rgb_latents, int B, int L,

@@ -169,6 +169,9 @@ SIGNATURES = {
     "ldmseg_op_conv_groupnorm_plan": (_i, [_i, _i, _i, _i, C.c_char_p, _i]),
     "ldmseg_op_layernorm_plan": (_i, [_i, _i, _i, _i, C.c_char_p, _i]),
     "ldmseg_op_attention_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i]),
+    "ldmseg_op_time_sinusoid": (_i, [_vp, _i, _i64, _i, _vp, _vp]),
+    "ldmseg_op_small_linear": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ldmseg_unet_time_rows": (_i, [_vp, C.POINTER(_i64), _i, _i, _vp, C.POINTER(_i), _vp]),
     "ldmseg_op_fastdiv": (_i, [_vp, _i, _i, _vp, _vp]),
     "ldmseg_op_nearest_index": (_i, [_i, _i, C.POINTER(_i)]),
     "ldmseg_op_point_taps": (_i, [_i, C.POINTER(_f), _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(_f)]),

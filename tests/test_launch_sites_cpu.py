@@ -12,25 +12,42 @@ CSRC = os.path.join(ROOT, "latent-diffusion-segmentation_amd", "csrc")
 SOURCES = ["igemm.hip", "norm.hip", "attention.hip", "attention3.hip", "attention4.hip", "attention_fp8.hip", "attention_mx.hip",
            "tfuse.hip", "tproj.hip", "tail.hip", "misc.hip"]
 
-# (file, kernel) -> why the launch stays out of the dispatch log
+# (file, kernel) -> (why the launch stays out of the dispatch log, the tests that pin the kernel instead: "file::test" under tests/)
 ALLOWED = {
-    ("igemm.hip", "split_planes_kernel"): "create time: fp32 weights -> hi | lo planes of a bf16x3 handle (launch_split_planes)",
-    ("igemm.hip", "pack_up4_kernel"): "create time: upsampler conv weights -> the four 2x2 phase kernels (launch_pack_up4)",
-    ("igemm.hip", "chain_weights_kernel"): "create time: chained ff.net.2 / proj_out matrix (launch_chain_weights)",
-    ("igemm.hip", "vec_add_kernel"): "create time: conv2 + conv_shortcut bias of the extra-tap launch (launch_vec_add)",
-    ("igemm.hip", "concat_rows_kernel"): "create time: conv2 | conv_shortcut weight rows of the extra-tap launch (launch_concat_rows)",
-    ("tfuse.hip", "tf_pack_stream_kernel"): "create time: weight stream of the fused feed-forward kernel",
-    ("tproj.hip", "tp_pack_stream_kernel"): "create time: weight stream of the fused transformer entry kernel",
-    ("misc.hip", "pack_concat3_kernel"): "layout: fp32 NCHW inputs -> NHWC compute dtype at the API boundary",
-    ("misc.hip", "time_sinus_kernel"): "time embedding: sinusoidal features of the timestep (fp32, no compute-mode variants)",
-    ("misc.hip", "small_linear_kernel"): "time embedding MLP (fp32, B rows, no compute-mode variants)",
-    ("misc.hip", "repack_conv_kernel"): "create time: conv weight repack",
-    ("misc.hip", "repack_convt2_kernel"): "create time: ConvTranspose2d weight repack",
-    ("misc.hip", "repack_rows_kernel"): "create time: Linear weight repack",
-    ("misc.hip", "repack_rows_scaled_kernel"): "create time: Linear weight repack with a folded column scale (LayerNorm gamma)",
-    ("misc.hip", "rowsum_kernel"): "create time: row sums of the folded LayerNorm weights (epilogue constants)",
-    ("misc.hip", "bit_encode_kernel"): "data preparation: COCO bitmap encode, not in the UNet forward",
-    ("misc.hip", "bit_decode_kernel"): "data preparation: COCO bitmap decode, not in the UNet forward",
+    ("igemm.hip", "split_planes_kernel"): ("create time: fp32 weights -> hi | lo planes of a bf16x3 handle (launch_split_planes)",
+        ["test_ops_gpu.py::test_split_bf16_gemm_vs_fp32_reference"]),
+    ("igemm.hip", "pack_up4_kernel"): ("create time: upsampler conv weights -> the four 2x2 phase kernels (launch_pack_up4)",
+        ["test_ops_gpu.py::test_upsampler_conv_as_phase_convs"]),
+    ("igemm.hip", "chain_weights_kernel"): ("create time: chained ff.net.2 / proj_out matrix (launch_chain_weights)",
+        ["test_ops_gpu.py::test_chained_ff_out_vs_oracle"]),
+    ("igemm.hip", "vec_add_kernel"): ("create time: conv2 + conv_shortcut bias of the extra-tap launch (launch_vec_add)",
+        ["test_ops_gpu.py::test_resnet_tail_extra_tap"]),
+    ("igemm.hip", "concat_rows_kernel"): ("create time: conv2 | conv_shortcut weight rows of the extra-tap launch (launch_concat_rows)",
+        ["test_ops_gpu.py::test_resnet_tail_extra_tap"]),
+    ("tfuse.hip", "tf_pack_stream_kernel"): ("create time: weight stream of the fused feed-forward kernel",
+        ["test_ops_gpu.py::test_transformer_ff_fused_vs_torch_and_unfused"]),
+    ("tproj.hip", "tp_pack_stream_kernel"): ("create time: weight stream of the fused transformer entry kernel",
+        ["test_ops_gpu.py::test_transformer_in_fused_vs_torch_and_unfused"]),
+    ("misc.hip", "pack_concat3_kernel"): ("layout: fp32 NCHW inputs -> NHWC compute dtype at the API boundary",
+        ["test_ops_gpu.py::test_conv2d"]),
+    ("misc.hip", "time_sinus_kernel"): ("time embedding: sinusoidal features of the timestep (fp32, no compute-mode variants)",
+        ["test_time_embed_gpu.py::test_sinusoid_vs_float64", "test_time_embed_gpu.py::test_rows_equal_the_composed_operators"]),
+    ("misc.hip", "small_linear_kernel"): ("time embedding MLP (fp32, B rows, no compute-mode variants)",
+        ["test_time_embed_gpu.py::test_small_linear_vs_float64", "test_time_embed_gpu.py::test_rows_equal_the_composed_operators"]),
+    ("misc.hip", "repack_conv_kernel"): ("create time: conv weight repack",
+        ["test_ops_gpu.py::test_conv2d"]),
+    ("misc.hip", "repack_convt2_kernel"): ("create time: ConvTranspose2d weight repack",
+        ["test_ops_gpu.py::test_convt2_and_bilinear"]),
+    ("misc.hip", "repack_rows_kernel"): ("create time: Linear weight repack",
+        ["test_ops_gpu.py::test_linear"]),
+    ("misc.hip", "repack_rows_scaled_kernel"): ("create time: Linear weight repack with a folded column scale (LayerNorm gamma)",
+        ["test_ops_gpu.py::test_layernorm_folded_into_linear"]),
+    ("misc.hip", "rowsum_kernel"): ("create time: row sums of the folded LayerNorm weights (epilogue constants)",
+        ["test_ops_gpu.py::test_layernorm_folded_into_linear"]),
+    ("misc.hip", "bit_encode_kernel"): ("data preparation: COCO bitmap encode, not in the UNet forward",
+        ["test_path_gpu.py::test_bitcodec_bit_exact_vs_reference_golden"]),
+    ("misc.hip", "bit_decode_kernel"): ("data preparation: COCO bitmap decode, not in the UNet forward",
+        ["test_path_gpu.py::test_bitcodec_bit_exact_vs_reference_golden"]),
 }
 
 
@@ -113,3 +130,16 @@ def test_scan_catches_a_bare_launch():
     patched = dict(src)
     patched["tail.hip"] = src["tail.hip"] + "\n// hipLaunchKernelGGL(foo_kernel, ...)\n/* hipLaunchKernelGGL(bar) */\n"
     assert scan(patched)[0] == []
+
+
+def test_every_allowed_launch_names_the_tests_that_pin_it():
+    """the other half of the allow-list: a kernel the dispatch log does not see is compared with a reference by the tests named
+    next to its reason, and each of them exists under that name in that file"""
+    here = os.path.dirname(os.path.abspath(__file__))
+    for key, (why, pins) in ALLOWED.items():
+        assert why and pins, key
+        for pin in pins:
+            fname, test = pin.split("::")
+            assert re.fullmatch(r"test_\w+_gpu\.py", fname), (key, pin)      # a kernel is pinned where it runs
+            txt = open(os.path.join(here, fname)).read()
+            assert re.search(r"^def " + re.escape(test) + r"\(", txt, flags=re.M), f"{key}: no test {test} in tests/{fname}"
