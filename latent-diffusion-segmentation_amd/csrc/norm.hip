@@ -1,14 +1,15 @@
 // GroupNorm(32) [+SiLU] and LayerNorm [+SiLU] over NHWC activations (HBM-bound).
 //
-// GroupNorm runs as two launches over [B, HW, C]:
-//   1. gn_partial: each workgroup owns a pixel chunk of one image, streams whole
-//      rows with 16-B loads (every lane a fixed channel vector, so the group of
-//      each element is a per-thread constant), and writes per-(chunk, group)
-//      {sum, sumsq} partials in a fixed order (deterministic, no atomics).
-//   2. gn_apply: reduces the partials of its image (tiny), then normalises,
-//      applies gamma/beta (+SiLU) and writes the tensor the next conv gathers.
-//      Two sources are read as one channel-concatenated tensor, which is how
-//      torch.cat([hidden, skip], 1) disappears from the up path.
+// GroupNorm over [B, HW, C] has eight forms; gn_plan.h holds the rule that picks one and launch_gn_plan() below expands it.
+// Two sources are read as one channel-concatenated tensor (torch.cat([hidden, skip], 1) disappears from the up path).
+//   gn_group              one workgroup per (image, group), the slice in registers in 8-byte pieces (bf16)
+//   gn_coop               S workgroups per (image, group block), one pass, statistics handed over through memory
+//   gn_one, gn_fused      one workgroup per (image, group block), the block in registers: shifted one-pass / two-pass sums
+//   finish_gn             gn_one whose load is the sum of a split-K conv's slabs (launch_finish_groupnorm)
+//   gn_small              one workgroup per (image, group) in 4-byte units (8x8 maps)
+//   gn_partial + gn_apply statistics per pixel chunk, then normalise: the last fallback; gn_partial alone = GN_STATS
+// The register kernels share their thread slot, register load, accumulation steps, affine and store (GnSlot .. gn_emit), and
+// gn_one / finish_gn everything behind their loads (gn_shifted_tail).
 // LayerNorm: one wavefront per row, values kept in registers, two-pass mean /
 // centred variance with wave shuffles (DPP) - same arithmetic as torch.
 #include <mutex>
@@ -27,7 +28,6 @@ __device__ unsigned long long g_gn_ts[8192 * 8];
 #else
 #define GNSTAMP(slot)
 #endif
-constexpr int kMaxIter = kGnMaxIter;   // ceil(nvec / 256) supported (C*sizeof(T)/16 <= 1024)
 
 template <typename T>
 __device__ __forceinline__ uint4 load_cat(const GNParams& p, int b, int pix, int v) {
@@ -35,6 +35,76 @@ __device__ __forceinline__ uint4 load_cat(const GNParams& p, int b, int pix, int
   const int c = v * PC;
   if (c < p.C0) return *(const uint4*)((const T*)p.src0 + ((size_t)b * p.HW + pix) * p.C0 + c);
   return *(const uint4*)((const T*)p.src1 + ((size_t)b * p.HW + pix) * p.C1 + (c - p.C0));
+}
+
+// ---- what the register-resident kernels (gn_fused, gn_one, finish_gn, gn_coop) share.  Thread t of a workgroup that holds a block
+// of GB groups (vpp = GB * cpg / PC vectors per pixel, first channel cfirst) of image b owns vector j = t % vpp of the pixels
+// t / vpp + ppi * k: its channels, groups and gamma / beta are fixed.  glo: block-local group of its first element (MAXG groups
+// per block at most); elements [0, split) belong to glo, the rest to glo + 1; src / cs: the torch.cat source that holds c0 at
+// pixel 0 of the image, and its pixel stride (finish_gn reads K-slice slabs instead and leaves them alone).
+template <typename T>
+struct GnSlot {
+  int pr, j, c0, glo, split, cs;
+  bool active;
+  const T* src;
+};
+template <typename T, int MAXG = 2>
+__device__ __forceinline__ GnSlot<T> gn_slot(const GNParams& p, int GB, int tid, int cfirst, int b) {
+  constexpr int PC = Chunk<T>::N;
+  const int cpg = p.cpg;
+  const int vpp = GB * cpg / PC;                    // vectors per pixel of this group block (PC is a power of two)
+  GnSlot<T> s;
+  s.pr = fd_div(tid, p.fd_aux);
+  s.j = tid - s.pr * vpp;
+  s.active = s.pr < p.ty;                           // p.ty: pixels per trip = threads / vpp (host)
+  s.c0 = cfirst + s.j * PC;
+  s.glo = 0;
+#pragma unroll
+  for (int g = 1; g < MAXG; ++g) s.glo += (s.j * PC >= g * cpg) ? 1 : 0;
+  s.split = min(PC, (s.glo + 1) * cpg - s.j * PC);
+  if (s.c0 < p.C0) { s.src = (const T*)p.src0 + (size_t)b * p.HW * p.C0 + s.c0; s.cs = p.C0; }
+  else { s.src = (const T*)p.src1 + (size_t)b * p.HW * p.C1 + (s.c0 - p.C0); s.cs = p.C1; }
+  return s;
+}
+// the slot's MAXV vectors of the pixels [q0, q1), zeros where absent; all loads are issued before the first use.  (ppi and q1 by
+// reference: by value, hipcc 7.2 schedules gn_coop_kernel's loads into 177 registers instead of 164 and the grid is no longer
+// resident at one workgroup per CU.  gn_one_kernel keeps a loop of its own: through this one its <float, 6> takes 66 registers
+// instead of 64, one wave per SIMD less.)
+template <typename T, int MAXV>
+__device__ __forceinline__ void gn_load_slot(const GnSlot<T>& s, const int& ppi, int q0, const int& q1, u32x4 (&raw)[MAXV]) {
+#pragma unroll
+  for (int k = 0; k < MAXV; ++k) {
+    const int pix = q0 + s.pr + ppi * k;
+    raw[k] = (s.active && pix < q1) ? *(const u32x4*)(s.src + (size_t)pix * s.cs) : u32x4{0u, 0u, 0u, 0u};
+  }
+}
+// one element into the sums of its group part: deviation from a shift sample, summed and squared; deviation from the mean, squared.
+// (Which part - e < split - stays an if / else at the call site: taken in here, hipcc selects the sample first and contracts
+// q += d * d into an FMA where the two-branch form adds a rounded square: other bytes out of gn_one and finish_gn.)
+__device__ __forceinline__ void gn_shifted_step(float f, float k, float& s, float& q) { const float d = f - k; s += d; q += d * d; }
+__device__ __forceinline__ void gn_centred_step(float f, float m, float& q) { const float d = f - m; q += d * d; }
+// every thread owns fixed channel vectors, so the per-channel affine (x*a + b with a = rstd*gamma, b = beta - mean*a) is computed
+// once per vector and a pixel costs one FMA per element
+template <int PC>
+__device__ __forceinline__ void gn_affine(float mlo, float rlo, float mhi, float rhi, const float* gamma, const float* beta, int split,
+                                          float (&a)[PC], float (&bb)[PC]) {
+#pragma unroll
+  for (int e = 0; e < PC; ++e) {
+    a[e] = (e < split ? rlo : rhi) * gamma[e];
+    bb[e] = beta[e] - (e < split ? mlo : mhi) * a[e];
+  }
+}
+// one vector out: y = f * a + bb, SiLU, 16-byte store
+template <typename T>
+__device__ __forceinline__ void gn_emit(float (&f)[Chunk<T>::N], const float (&a)[Chunk<T>::N], const float (&bb)[Chunk<T>::N], int silu,
+                                        T* dst) {
+#pragma unroll
+  for (int e = 0; e < Chunk<T>::N; ++e) {
+    float y = f[e] * a[e] + bb[e];
+    if (silu) y = silu_f(y);
+    f[e] = y;
+  }
+  *(uint4*)dst = Chunk<T>::pack(f);
 }
 
 // Parallel-variance combination (Chan et al.): (n, mean, M2) <- (n, mean, M2) + (nb, mb, M2b).  Used at every level of
@@ -116,7 +186,7 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const GNParams p) {
   const int p0 = chunk * per;
   const int p1 = min(p.HW, p0 + per);
 
-  __shared__ float red[kMaxIter][256][4];   // per thread: {mean, M2} of its low / high group part
+  __shared__ float red[kGnMaxIter][256][4];   // per thread: {mean, M2} of its low / high group part
   GNSTAMP(0)
 
   const int niter = (nvec + VX - 1) / VX;
@@ -147,8 +217,8 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const GNParams p) {
         }
 #pragma unroll
         for (int e = 0; e < PC; ++e) {
-          if (e < split) { const float d = f[e] - k0; s0 += d; q0 += d * d; }
-          else { const float d = f[e] - k1; s1 += d; q1 += d * d; }
+          if (e < split) gn_shifted_step(f[e], k0, s0, q0);
+          else gn_shifted_step(f[e], k1, s1, q1);
         }
       };
       for (; pix + 7 * TY < p1; pix += 8 * TY) {
@@ -252,8 +322,6 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GNParams p) {
   const int b = blockIdx.y;
   __shared__ float s_stat[64][2];
   GNSTAMP(4)
-  // every thread owns fixed channel vectors, so the per-channel affine (x*a + b with
-  // a = rstd*gamma, b = beta - mean*a) is computed once and the pixel loop is one FMA per element
   const int VX = p.vx;
   const int TY = p.ty;
   const int tid = threadIdx.x;
@@ -309,21 +377,11 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GNParams p) {
     const float m_lo = s_stat[g0][0], r_lo = s_stat[g0][1];
     const float m_hi = s_stat[split < PC ? g0 + 1 : g0][0], r_hi = s_stat[split < PC ? g0 + 1 : g0][1];
     float a[PC], bb[PC];
-#pragma unroll
-    for (int e = 0; e < PC; ++e) {
-      a[e] = (e < split ? r_lo : r_hi) * gam[e];
-      bb[e] = bet[e] - (e < split ? m_lo : m_hi) * a[e];
-    }
+    gn_affine<PC>(m_lo, r_lo, m_hi, r_hi, gam, bet, split, a, bb);
     auto emit = [&](const uint4& raw, int pix) __attribute__((always_inline)) {
       float f[PC];
       Chunk<T>::unpack(raw, f);
-#pragma unroll
-      for (int e = 0; e < PC; ++e) {
-        float y = f[e] * a[e] + bb[e];
-        if (p.silu) y = silu_f(y);
-        f[e] = y;
-      }
-      *(uint4*)(dst + (size_t)pix * C) = Chunk<T>::pack(f);
+      gn_emit<T>(f, a, bb, p.silu, dst + (size_t)pix * C);
     };
     int pix = p0 + ty;
     if (v == tx) {                                     // the trip that was requested up front
@@ -557,27 +615,14 @@ template <typename T, int MAXV>
 __global__ __launch_bounds__(256) void gn_fused_kernel(const GNParams p, int GB) {
   constexpr int PC = Chunk<T>::N;
   const int C = p.C0 + p.C1;
-  const int cpg = p.cpg;
-  const int vpp = GB * cpg / PC;                    // vectors per pixel of this group block (PC is a power of two)
-  const int ppi = p.ty;                             // pixels per trip = 256 / vpp (host)
+  const int ppi = p.ty;
   const int b = blockIdx.y;
-  const int cfirst = blockIdx.x * GB * cpg;
   const int tid = threadIdx.x;
-  const int pr = fd_div(tid, p.fd_aux), j = tid - pr * vpp;
-  const bool active = pr < ppi;
-  const int c0 = cfirst + j * PC;                   // first channel of this thread's vector
-  const int glo = (j * PC) >= cpg ? 1 : 0;          // block-local group of its first element (a block holds 1 or 2 groups)
-  const int split = min(PC, (glo + 1) * cpg - j * PC);   // elements [0,split) -> glo, the rest -> glo+1
-  const T* src;
-  int cs;
-  if (c0 < p.C0) { src = (const T*)p.src0 + (size_t)b * p.HW * p.C0 + c0; cs = p.C0; }
-  else { src = (const T*)p.src1 + (size_t)b * p.HW * p.C1 + (c0 - p.C0); cs = p.C1; }
+  const GnSlot<T> sl = gn_slot<T>(p, GB, tid, blockIdx.x * GB * p.cpg, b);
+  const int pr = sl.pr, glo = sl.glo, split = sl.split;
+  const bool active = sl.active;
   u32x4 raw[MAXV];
-#pragma unroll
-  for (int k = 0; k < MAXV; ++k) {
-    const int pix = pr + ppi * k;
-    raw[k] = (active && pix < p.HW) ? *(const u32x4*)(src + (size_t)pix * cs) : u32x4{0u, 0u, 0u, 0u};
-  }
+  gn_load_slot<T, MAXV>(sl, ppi, 0, p.HW, raw);
   // pass 1: group sums -> means; pass 2: centred second moments of the register-resident values
   float slo = 0.f, shi = 0.f;
 #pragma unroll
@@ -609,8 +654,8 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const GNParams p, int GB)
 #pragma unroll
         for (int e = 0; e < PC; ++e) {
           const float f = to_f32<T>(chunk_elem<T>(raw[k], e));
-          if (e < split) { const float d = f - mlo; qlo += d * d; }
-          else { const float d = f - mhi; qhi += d * d; }
+          if (e < split) gn_centred_step(f, mlo, qlo);
+          else gn_centred_step(f, mhi, qhi);
         }
       }
     }
@@ -625,81 +670,29 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const GNParams p, int GB)
   }
   if (!active) return;
   float a[PC], bb[PC];
-#pragma unroll
-  for (int e = 0; e < PC; ++e) {
-    const int g = (e < split) ? glo : glo + 1;
-    a[e] = (g == 0 ? rstd[0] : rstd[1]) * p.gamma[c0 + e];
-    bb[e] = p.beta[c0 + e] - (g == 0 ? mean[0] : mean[1]) * a[e];
-  }
-  T* dst = (T*)p.out + (size_t)b * p.HW * C + c0;
+  gn_affine<PC>(glo == 0 ? mean[0] : mean[1], glo == 0 ? rstd[0] : rstd[1], mean[1], rstd[1], p.gamma + sl.c0, p.beta + sl.c0, split, a, bb);
+  T* dst = (T*)p.out + (size_t)b * p.HW * C + sl.c0;
 #pragma unroll
   for (int k = 0; k < MAXV; ++k) {
     const int pix = pr + ppi * k;
     if (pix < p.HW) {
       float f[PC];
 #pragma unroll
-      for (int e = 0; e < PC; ++e) {
-        float y = to_f32<T>(chunk_elem<T>(raw[k], e)) * a[e] + bb[e];
-        if (p.silu) y = silu_f(y);
-        f[e] = y;
-      }
-      *(uint4*)(dst + (size_t)pix * C) = Chunk<T>::pack(f);
+      for (int e = 0; e < PC; ++e) f[e] = to_f32<T>(chunk_elem<T>(raw[k], e));
+      gn_emit<T>(f, a, bb, p.silu, dst + (size_t)pix * C);
     }
   }
 }
 
-// gn_fused_kernel with the dependent chain cut down - at these sizes (1 .. 10 MB) the kernel is a latency chain, not a
-// stream: [loads] -> reduce -> barrier -> reduce -> barrier -> [gamma / beta loads] -> store became
-// [loads of data, gamma, beta and the groups' shift samples, all issued together] -> ONE reduction -> barrier -> store.
-// The statistics are shifted sums around a sample of the group itself (its first element): sum(x - K) and sum((x - K)^2)
-// in one pass over the registers; with K a member of the group |mean - K| is a few standard deviations at most, so
-// var = E[(x-K)^2] - E[x-K]^2 loses nothing to cancellation (a mean of 1000 with deviation 1 is a test case).  MAXV is a
-// template parameter chosen by the launcher (2 / 6 / 12 / 22): the register loops carry no dead iterations.
-template <typename T, int MAXV>
-__global__ __launch_bounds__(256) void gn_one_kernel(const GNParams p, int GB) {
+// What gn_one_kernel and finish_gn_kernel do with their register-resident block once it is loaded: the one-pass shifted sums of
+// elem(k, e) (element e of the slot's vector k) around the groups' samples K, one reduction, one barrier, the affine and the
+// store.  ga / be: gamma and beta of the slot's channels, requested by the caller before the reduction.
+template <typename T, int MAXV, typename F>
+__device__ __forceinline__ void gn_shifted_tail(const GNParams& p, const GnSlot<T>& sl, const float (&K)[2], const float* ga, const float* be,
+                                                T* dst, int C, F elem) {
   constexpr int PC = Chunk<T>::N;
-  const int C = p.C0 + p.C1;
-  const int cpg = p.cpg;
-  const int vpp = GB * cpg / PC;
-  const int ppi = p.ty;
-  // consecutive workgroup ids go to consecutive XCDs: image = id % B keeps the group blocks of one image - whose 80 .. 320-byte
-  // runs share 128-byte lines with their neighbours' - on one XCD (one L2) when B is a multiple of 8
-  const int b = (int)(blockIdx.x % (unsigned)p.B);
-  const int cfirst = (int)(blockIdx.x / (unsigned)p.B) * GB * cpg;
-  const int tid = threadIdx.x;
-  const int pr = fd_div(tid, p.fd_aux), j = tid - pr * vpp;
-  const bool active = pr < ppi;
-  const int c0 = cfirst + j * PC;
-  const int glo = (j * PC) >= cpg ? 1 : 0;
-  const int split = min(PC, (glo + 1) * cpg - j * PC);
-  const T* src;
-  int cs;
-  if (c0 < p.C0) { src = (const T*)p.src0 + (size_t)b * p.HW * p.C0 + c0; cs = p.C0; }
-  else { src = (const T*)p.src1 + (size_t)b * p.HW * p.C1 + (c0 - p.C0); cs = p.C1; }
-  u32x4 raw[MAXV];
-#pragma unroll
-  for (int k = 0; k < MAXV; ++k) {
-    const int pix = pr + ppi * k;
-    raw[k] = (active && pix < p.HW) ? *(const u32x4*)(src + (size_t)pix * cs) : u32x4{0u, 0u, 0u, 0u};
-  }
-  // shift samples: pixel 0 of the first channel of the block's group(s) - the same two addresses for every thread
-  float K[2];
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    const int c = cfirst + (g < GB ? g : 0) * cpg;
-    const T* sp = c < p.C0 ? (const T*)p.src0 + (size_t)b * p.HW * p.C0 + c : (const T*)p.src1 + (size_t)b * p.HW * p.C1 + (c - p.C0);
-    K[g] = to_f32<T>(*sp);
-  }
-  // affine parameters of this thread's channels: requested now, used after the barrier
-  float ga[PC], be[PC];
-  if (active) {
-#pragma unroll
-    for (int e = 0; e < PC; e += 4) {
-      const f32x4 g4 = *(const f32x4*)(p.gamma + c0 + e), b4 = *(const f32x4*)(p.beta + c0 + e);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { ga[e + r] = g4[r]; be[e + r] = b4[r]; }
-    }
-  }
+  const int tid = threadIdx.x, pr = sl.pr, ppi = p.ty, glo = sl.glo, split = sl.split;
+  const bool active = sl.active;
   const float klo = glo == 0 ? K[0] : K[1], khi = K[1];
   float slo = 0.f, shi = 0.f, qlo = 0.f, qhi = 0.f;
 #pragma unroll
@@ -707,12 +700,12 @@ __global__ __launch_bounds__(256) void gn_one_kernel(const GNParams p, int GB) {
     if (active && pr + ppi * k < p.HW) {
 #pragma unroll
       for (int e = 0; e < PC; ++e) {
-        const float f = to_f32<T>(chunk_elem<T>(raw[k], e));
-        if (e < split) { const float d = f - klo; slo += d; qlo += d * d; }
-        else { const float d = f - khi; shi += d; qhi += d * d; }
+        if (e < split) gn_shifted_step(elem(k, e), klo, slo, qlo);
+        else gn_shifted_step(elem(k, e), khi, shi, qhi);
       }
     }
   }
+  // block-local group records: group 0 gets the low part of glo == 0 vectors, group 1 the rest
   __shared__ float red[4][4];     // [sum g0, sum g1, sq g0, sq g1][wave]
   {
     const float s0 = wave64_sum(glo == 0 ? slo : 0.f), s1 = wave64_sum(glo == 0 ? shi : slo);
@@ -739,9 +732,8 @@ __global__ __launch_bounds__(256) void gn_one_kernel(const GNParams p, int GB) {
       if (active && pr + ppi * k < p.HW) {
 #pragma unroll
         for (int e = 0; e < PC; ++e) {
-          const float f = to_f32<T>(chunk_elem<T>(raw[k], e));
-          if (e < split) { const float d = f - mlo; qlo += d * d; }
-          else { const float d = f - mhi; qhi += d * d; }
+          if (e < split) gn_centred_step(elem(k, e), mlo, qlo);
+          else gn_centred_step(elem(k, e), mhi, qhi);
         }
       }
     }
@@ -756,27 +748,63 @@ __global__ __launch_bounds__(256) void gn_one_kernel(const GNParams p, int GB) {
 #pragma unroll
   for (int g = 0; g < 2; ++g) rstd[g] = 1.0f / sqrtf(var[g] + p.eps);
   float a[PC], bb[PC];
-#pragma unroll
-  for (int e = 0; e < PC; ++e) {
-    const int g = (e < split) ? glo : glo + 1;
-    a[e] = (g == 0 ? rstd[0] : rstd[1]) * ga[e];
-    bb[e] = be[e] - (g == 0 ? mean[0] : mean[1]) * a[e];
-  }
-  T* dst = (T*)p.out + (size_t)b * p.HW * C + c0;
+  gn_affine<PC>(glo == 0 ? mean[0] : mean[1], glo == 0 ? rstd[0] : rstd[1], mean[1], rstd[1], ga, be, split, a, bb);
 #pragma unroll
   for (int k = 0; k < MAXV; ++k) {
     const int pix = pr + ppi * k;
     if (pix < p.HW) {
       float f[PC];
 #pragma unroll
-      for (int e = 0; e < PC; ++e) {
-        float y = to_f32<T>(chunk_elem<T>(raw[k], e)) * a[e] + bb[e];
-        if (p.silu) y = silu_f(y);
-        f[e] = y;
-      }
-      *(uint4*)(dst + (size_t)pix * C) = Chunk<T>::pack(f);
+      for (int e = 0; e < PC; ++e) f[e] = elem(k, e);
+      gn_emit<T>(f, a, bb, p.silu, dst + (size_t)pix * C);
     }
   }
+}
+
+// gn_fused_kernel with the dependent chain cut down - at these sizes (1 .. 10 MB) the kernel is a latency chain, not a
+// stream: [loads] -> reduce -> barrier -> reduce -> barrier -> [gamma / beta loads] -> store became
+// [loads of data, gamma, beta and the groups' shift samples, all issued together] -> ONE reduction -> barrier -> store.
+// The statistics are shifted sums around a sample of the group itself (its first element): sum(x - K) and sum((x - K)^2)
+// in one pass over the registers; with K a member of the group |mean - K| is a few standard deviations at most, so
+// var = E[(x-K)^2] - E[x-K]^2 loses nothing to cancellation (a mean of 1000 with deviation 1 is a test case).  MAXV is a
+// template parameter chosen by the launcher (2 / 6 / 12 / 22): the register loops carry no dead iterations.
+template <typename T, int MAXV>
+__global__ __launch_bounds__(256) void gn_one_kernel(const GNParams p, int GB) {
+  constexpr int PC = Chunk<T>::N;
+  const int C = p.C0 + p.C1;
+  const int cpg = p.cpg;
+  // consecutive workgroup ids go to consecutive XCDs: image = id % B keeps the group blocks of one image - whose 80 .. 320-byte
+  // runs share 128-byte lines with their neighbours' - on one XCD (one L2) when B is a multiple of 8
+  const int b = (int)(blockIdx.x % (unsigned)p.B);
+  const int cfirst = (int)(blockIdx.x / (unsigned)p.B) * GB * cpg;
+  const GnSlot<T> sl = gn_slot<T>(p, GB, threadIdx.x, cfirst, b);
+  const int c0 = sl.c0;
+  u32x4 raw[MAXV];
+#pragma unroll
+  for (int k = 0; k < MAXV; ++k) {                  // (not gn_load_slot: see there)
+    const int pix = sl.pr + p.ty * k;
+    raw[k] = (sl.active && pix < p.HW) ? *(const u32x4*)(sl.src + (size_t)pix * sl.cs) : u32x4{0u, 0u, 0u, 0u};
+  }
+  // shift samples: pixel 0 of the first channel of the block's group(s) - the same two addresses for every thread
+  float K[2];
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    const int c = cfirst + (g < GB ? g : 0) * cpg;
+    const T* sp = c < p.C0 ? (const T*)p.src0 + (size_t)b * p.HW * p.C0 + c : (const T*)p.src1 + (size_t)b * p.HW * p.C1 + (c - p.C0);
+    K[g] = to_f32<T>(*sp);
+  }
+  // affine parameters of this thread's channels: requested now, used after the barrier
+  float ga[PC], be[PC];
+  if (sl.active) {
+#pragma unroll
+    for (int e = 0; e < PC; e += 4) {
+      const f32x4 g4 = *(const f32x4*)(p.gamma + c0 + e), b4 = *(const f32x4*)(p.beta + c0 + e);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { ga[e + r] = g4[r]; be[e + r] = b4[r]; }
+    }
+  }
+  gn_shifted_tail<T, MAXV>(p, sl, K, ga, be, (T*)p.out + (size_t)b * p.HW * C + c0, C,
+                           [&](int k, int e) { return to_f32<T>(chunk_elem<T>(raw[k], e)); });
 }
 
 // Split-K finish + GroupNorm (+SiLU) in one launch (launch_finish_groupnorm): gn_one_kernel whose "load" is the sum of the
@@ -792,18 +820,13 @@ __global__ __launch_bounds__(256) void finish_gn_kernel(const GNParams p, int GB
   constexpr int PC = Chunk<T>::N;
   const int C = p.C0;
   const int cpg = p.cpg;
-  const int vpp = GB * cpg / PC;
   const int ppi = p.ty;
-  // consecutive workgroup ids go to consecutive XCDs: image = id % B keeps the group blocks of one image - whose 80 .. 320-byte
-  // runs share 128-byte lines with their neighbours' - on one XCD (one L2) when B is a multiple of 8
+  // the block-to-(image, group block) mapping of gn_one_kernel
   const int b = (int)(blockIdx.x % (unsigned)p.B);
   const int cfirst = (int)(blockIdx.x / (unsigned)p.B) * GB * cpg;
-  const int tid = threadIdx.x;
-  const int pr = fd_div(tid, p.fd_aux), j = tid - pr * vpp;
-  const bool active = pr < ppi;
-  const int c0 = cfirst + j * PC;
-  const int glo = (j * PC) >= cpg ? 1 : 0;
-  const int split = min(PC, (glo + 1) * cpg - j * PC);
+  const GnSlot<T> sl = gn_slot<T>(p, GB, threadIdx.x, cfirst, b);
+  const int pr = sl.pr, c0 = sl.c0;
+  const bool active = sl.active;
   float v[MAXV][PC];
   const float* src = partial + (size_t)b * p.HW * N + c0;
   // the slices of ZU K slices are requested together: one round trip per ZU slices instead of one per slice (a plain
@@ -854,83 +877,11 @@ __global__ __launch_bounds__(256) void finish_gn_kernel(const GNParams p, int GB
       for (int r = 0; r < 4; ++r) { ga[e + r] = g4[r]; be[e + r] = b4[r]; add[e + r] = a4[r]; }
     }
   }
-  const float klo = glo == 0 ? K[0] : K[1], khi = K[1];
-  float slo = 0.f, shi = 0.f, qlo = 0.f, qhi = 0.f;
 #pragma unroll
-  for (int k = 0; k < MAXV; ++k) {
-    const bool ok = active && pr + ppi * k < p.HW;
+  for (int k = 0; k < MAXV; ++k)
 #pragma unroll
-    for (int e = 0; e < PC; ++e) {
-      v[k][e] += add[e];
-      if (ok) {
-        if (e < split) { const float d = v[k][e] - klo; slo += d; qlo += d * d; }
-        else { const float d = v[k][e] - khi; shi += d; qhi += d * d; }
-      }
-    }
-  }
-  __shared__ float red[4][4];
-  {
-    const float s0 = wave64_sum(glo == 0 ? slo : 0.f), s1 = wave64_sum(glo == 0 ? shi : slo);
-    const float q0 = wave64_sum(glo == 0 ? qlo : 0.f), q1 = wave64_sum(glo == 0 ? qhi : qlo);
-    if ((tid & 63) == 0) { red[0][tid >> 6] = s0; red[1][tid >> 6] = s1; red[2][tid >> 6] = q0; red[3][tid >> 6] = q1; }
-  }
-  __syncthreads();
-  float mean[2], var[2], rstd[2];
-  const float inv_n = (float)p.inv_n;
-  bool far = false;
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    const float ms = (((red[g][0] + red[g][1]) + red[g][2]) + red[g][3]) * inv_n;
-    const float m2 = (((red[2 + g][0] + red[2 + g][1]) + red[2 + g][2]) + red[2 + g][3]) * inv_n;
-    mean[g] = K[g] + ms;
-    var[g] = fmaxf(m2 - ms * ms, 0.f);
-    far |= ms * ms > 64.f * var[g];
-  }
-  if (far) {
-    const float mlo = glo == 0 ? mean[0] : mean[1], mhi = mean[1];
-    qlo = 0.f; qhi = 0.f;
-#pragma unroll
-    for (int k = 0; k < MAXV; ++k) {
-      if (active && pr + ppi * k < p.HW) {
-#pragma unroll
-        for (int e = 0; e < PC; ++e) {
-          if (e < split) { const float d = v[k][e] - mlo; qlo += d * d; }
-          else { const float d = v[k][e] - mhi; qhi += d * d; }
-        }
-      }
-    }
-    const float q0 = wave64_sum(glo == 0 ? qlo : 0.f), q1 = wave64_sum(glo == 0 ? qhi : qlo);
-    __syncthreads();
-    if ((tid & 63) == 0) { red[2][tid >> 6] = q0; red[3][tid >> 6] = q1; }
-    __syncthreads();
-#pragma unroll
-    for (int g = 0; g < 2; ++g) var[g] = (((red[2 + g][0] + red[2 + g][1]) + red[2 + g][2]) + red[2 + g][3]) * inv_n;
-  }
-  if (!active) return;
-#pragma unroll
-  for (int g = 0; g < 2; ++g) rstd[g] = 1.0f / sqrtf(var[g] + p.eps);
-  float a[PC], bb[PC];
-#pragma unroll
-  for (int e = 0; e < PC; ++e) {
-    const int g = (e < split) ? glo : glo + 1;
-    a[e] = (g == 0 ? rstd[0] : rstd[1]) * ga[e];
-    bb[e] = be[e] - (g == 0 ? mean[0] : mean[1]) * a[e];
-  }
-  T* dst = (T*)p.out + (size_t)b * p.HW * C + c0;
-#pragma unroll
-  for (int k = 0; k < MAXV; ++k) {
-    const int pix = pr + ppi * k;
-    if (pix < p.HW) {
-      float f[PC];
-#pragma unroll
-      for (int e = 0; e < PC; ++e) {
-        float y = v[k][e] * a[e] + bb[e];
-        if (p.silu) y = silu_f(y);
-        f[e] = y;
-      }
-      *(uint4*)(dst + (size_t)pix * C) = Chunk<T>::pack(f);
-    }
-  }
+    for (int e = 0; e < PC; ++e) v[k][e] += add[e];
+  gn_shifted_tail<T, MAXV>(p, sl, K, ga, be, (T*)p.out + (size_t)b * p.HW * C + c0, C, [&](int k, int e) { return v[k][e]; });
 }
 
 // The 64x64 maps in ONE pass with every CU streaming: S workgroups share one (image, block of GB groups whose channels make
@@ -964,7 +915,6 @@ __global__ __launch_bounds__(NT) void gn_coop_kernel(const GNParams p, int GB) {
   const int C = p.C0 + p.C1;
   const int cpg = p.cpg;
   const int S = p.splits;
-  const int vpp = GB * cpg / PC;                    // vectors per pixel of this group block
   const int ppi = p.ty;                             // pixels per trip = NT / vpp (host)
   int logical;
   {
@@ -980,28 +930,13 @@ __global__ __launch_bounds__(NT) void gn_coop_kernel(const GNParams p, int GB) {
   const int per = p.per;                            // pixels per split
   const int pix0 = split * per, pix1 = min(p.HW, pix0 + per);
   const int tid = threadIdx.x;
-  const int pr = fd_div(tid, p.fd_aux), j = tid - pr * vpp;
-  const bool active = pr < ppi;
-  const int c0 = cfirst + j * PC;
-  int glo = 0;
-#pragma unroll
-  for (int g = 1; g < MAXG; ++g) glo += (j * PC >= g * cpg) ? 1 : 0;
-  const int split_e = min(PC, (glo + 1) * cpg - j * PC);   // elements [0,split_e) -> group glo, the rest -> glo+1
-  const T* src;
-  int cs;
-  if (c0 < p.C0) { src = (const T*)p.src0 + (size_t)b * p.HW * p.C0 + c0; cs = p.C0; }
-  else { src = (const T*)p.src1 + (size_t)b * p.HW * p.C1 + (c0 - p.C0); cs = p.C1; }
+  const GnSlot<T> sl = gn_slot<T, MAXG>(p, GB, tid, cfirst, b);
+  const int pr = sl.pr, c0 = sl.c0, glo = sl.glo;
+  const int split_e = sl.split;                     // (`split` is this workgroup's share of the pixels here)
+  const bool active = sl.active;
   u32x4 raw[MAXV];
-  // pixels of split `sp` as that split's own threads hold them (thread -> (pixel row, vector) does not depend on the split)
-  auto load_raw = [&](int sp) __attribute__((always_inline)) {
-    const int q0 = sp * per, q1 = min(p.HW, q0 + per);
-#pragma unroll
-    for (int k = 0; k < MAXV; ++k) {
-      const int pix = q0 + pr + ppi * k;
-      raw[k] = (active && pix < q1) ? *(const u32x4*)(src + (size_t)pix * cs) : u32x4{0u, 0u, 0u, 0u};
-    }
-  };
-  load_raw(split);
+  // pixels of a split as that split's own threads hold them: thread -> (pixel row, vector) does not depend on the split
+  gn_load_slot<T, MAXV>(sl, ppi, pix0, pix1, raw);
   // ---- this launch's generation: one returning agent-scope add per workgroup, requested behind the pixel loads and needed
   // only when the record is published
   unsigned long long ticket = 0;
@@ -1147,12 +1082,12 @@ __global__ __launch_bounds__(NT) void gn_coop_kernel(const GNParams p, int GB) {
     // ---- cold path: partners that are not running (yet).  Their records are a pure function of their pixels: compute them.
     for (int sx = 0; sx < S; ++sx) {
       if (!((missing >> sx) & 1u)) continue;
-      load_raw(sx);
+      gn_load_slot<T, MAXV>(sl, ppi, sx * per, min(p.HW, sx * per + per), raw);
       float v;
       split_stats(sx, v);
       if (tid < 2 * GB) s_rec[sx][tid] = v;
     }
-    load_raw(split);
+    gn_load_slot<T, MAXV>(sl, ppi, pix0, pix1, raw);
     if (tid == 0 && p.sync_diag) __hip_atomic_fetch_add(p.sync_diag, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
   }
@@ -1170,13 +1105,8 @@ __global__ __launch_bounds__(NT) void gn_coop_kernel(const GNParams p, int GB) {
   if (!active) return;
   float a[PC], bb[PC];
   {
-    const float m0 = s_stat[glo][0], r0 = s_stat[glo][1];
-    const float m1 = s_stat[glo + 1 < MAXG ? glo + 1 : glo][0], r1 = s_stat[glo + 1 < MAXG ? glo + 1 : glo][1];
-#pragma unroll
-    for (int e = 0; e < PC; ++e) {
-      a[e] = (e < split_e ? r0 : r1) * p.gamma[c0 + e];
-      bb[e] = p.beta[c0 + e] - (e < split_e ? m0 : m1) * a[e];
-    }
+    const int ghi = glo + 1 < MAXG ? glo + 1 : glo;
+    gn_affine<PC>(s_stat[glo][0], s_stat[glo][1], s_stat[ghi][0], s_stat[ghi][1], p.gamma + c0, p.beta + c0, split_e, a, bb);
   }
   T* dst = (T*)p.out + (size_t)b * p.HW * C + c0;
 #pragma unroll
@@ -1195,13 +1125,7 @@ __global__ __launch_bounds__(NT) void gn_coop_kernel(const GNParams p, int GB) {
 #pragma unroll
         for (int e = 0; e < PC; ++e) f[e] = to_f32<T>(chunk_elem<T>(raw[k], e));
       }
-#pragma unroll
-      for (int e = 0; e < PC; ++e) {
-        float y = f[e] * a[e] + bb[e];
-        if (p.silu) y = silu_f(y);
-        f[e] = y;
-      }
-      *(uint4*)(dst + (size_t)pix * C) = Chunk<T>::pack(f);
+      gn_emit<T>(f, a, bb, p.silu, dst + (size_t)pix * C);
     }
   }
 }

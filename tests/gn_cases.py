@@ -67,6 +67,7 @@ DIGEST_CASES = [
     (1, 320, 0, 4096, BF16, 0), (1, 320, 320, 4096, F32, 0), (2, 320, 0, 3969, BF16, 0),      # 8 splits
     (3, 256, 0, 100, BF16, 0), (3, 256, 0, 100, F32, 0), (8, 1280, 0, 64, BF16, 0), (8, 1280, 0, 64, F32, 0),      # gn_one
     (8, 1280, 0, 256, F32, 0), (4, 128, 0, 16, F32, 0),
+    (8, 1280, 0, 144, BF16, 0), (8, 1280, 0, 400, BF16, 32),                   # bf16 with 6 / 12 vectors per thread
     (8, 1280, 0, 256, F32, 4), (8, 640, 0, 400, BF16, 37), (4, 2560, 0, 64, BF16, 4), (4, 1280, 0, 400, F32, 0),     # gn_fused
     (4, 128, 0, 16, BF16, 0), (4, 640, 0, 100, BF16, 0), (8, 320, 0, 64, BF16, 0), (4, 320, 0, 16, F32, 0),          # gn_small
     (1, 256, 0, 100, BF16, 0), (1, 256, 0, 100, F32, 0), (2, 320, 0, 256, BF16, 0), (1, 640, 320, 64, F32, 0),       # gn_partial + gn_apply
@@ -91,7 +92,7 @@ PAIRS = [
 
 # finish + GroupNorm behind a small conv (B, Ci, H, Co, K slices, dtype): 2 / 6 / 12 vectors per thread, one and two groups per workgroup
 CONV_DIGEST_CASES = [(8, 64, 8, 1280, 2, BF16), (8, 64, 8, 1280, 2, F32), (8, 64, 16, 640, 3, BF16), (3, 64, 10, 256, 2, F32),
-                     (8, 64, 16, 1280, 2, F32), (6, 128, 12, 640, 2, BF16)]
+                     (8, 64, 16, 1280, 2, F32), (6, 128, 12, 640, 2, BF16), (8, 64, 20, 1280, 2, BF16)]
 
 
 def digest_cases():

@@ -18,6 +18,11 @@ _MEM = C.create_string_buffer(64)
 P = C.c_void_p(C.addressof(_MEM))                 # a non-null pointer that nothing reads
 
 
+def _args_id(args):
+    """test id of an argument tuple: the pointer by name, since its address differs from process to process"""
+    return "(" + ", ".join("P" if a is P else str(a) for a in args) + ")"
+
+
 def test_sinusoid_reference_vs_oracle():
     """every t of the training range: the oracle's fp32 sinusoid lies within half the bound the kernel is held to"""
     t = torch.arange(1000)
@@ -118,7 +123,7 @@ def lib():
 @pytest.mark.parametrize("args", [
     (None, 1, 5, 0, P), (None, 1, 5, -1, P), (None, 1, 5, 2, None),            # B < 1, no output
     (P, 0, 0, 2, P), (P, 3, 0, 2, P), (P, 2, 0, 3, P), (P, -1, 0, 3, P),       # t_dev with t_count not in {1, B}
-], ids=str)
+], ids=_args_id)
 def test_time_sinusoid_refusals(lib, args):
     assert lib.ldmseg_op_time_sinusoid(*args, None) == -2
 
@@ -126,7 +131,7 @@ def test_time_sinusoid_refusals(lib, args):
 @pytest.mark.parametrize("args", [
     (None, P, P, 1, 1, 1, 0, 0, P), (P, None, P, 1, 1, 1, 0, 0, P), (P, P, P, 1, 1, 1, 0, 0, None),
     (P, P, None, 0, 1, 1, 0, 0, P), (P, P, None, 1, 0, 1, 0, 0, P), (P, P, None, 1, 1, 0, 0, 0, P), (P, P, P, -3, 64, 8, 1, 1, P),
-], ids=str)
+], ids=_args_id)
 def test_small_linear_refusals(lib, args):
     assert lib.ldmseg_op_small_linear(*args, None) == -2
 
