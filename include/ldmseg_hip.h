@@ -181,6 +181,22 @@ void ldmseg_vae_destroy(ldmseg_vae* h);
  * `z_scale` multiplies z first (decode_latents' 1/scaling_factor, trainers_ldm_cond.py:421). */
 int ldmseg_vae_decode(ldmseg_vae* h, const float* z, float z_scale, int B, int L, int interpolate, float* logits,
                       void* stream);
+/* Backward of decode(z, interpolate=False): from grad_logits [B,Co,4L,4L] (fp32 NCHW, d loss / d logits) to the gradient
+ * of every decoder parameter asked for and of the latents.  Stateless: the decoder forward runs again inside the call's own workspace
+ * plan (one extra decoder forward), so nothing is carried from an earlier decode and other calls on the handle in between are
+ * harmless.  Everything on `stream`, no allocation after the plan, no host synchronisation, bitwise repeatable (no float atomics).
+ * grad_z [B,4,L,L] or NULL; it includes the z_scale factor.  names[i] is a reference key (decoder.0.weight ...), grad_ptrs[i] an
+ * fp32 device buffer of numels[i] elements in the state-dict layout ([Co,Ci,3,3], [Ci,Co,2,2], [C]), every element written.  A key
+ * that is absent, or a NULL pointer, skips that gradient; an unknown key or a wrong numel is LDMSEG_E_ARG, as is a bf16 handle (the
+ * backward needs an fp32-storage handle: compute_dtype fp32 or bf16x3).  Nothing is launched on an error. */
+int ldmseg_vae_decode_backward(ldmseg_vae* h, const float* z, float z_scale, int B, int L, const float* grad_logits, float* grad_z,
+                               int n, const char* const* names, float* const* grad_ptrs, const int64_t* numels, void* stream);
+/* Repacks the given decoder tensors (reference keys, fp32 device pointers) into the buffers the handle already owns: forward
+ * packing, data-gradient packing, the hi | lo planes of a bf16x3 handle, norm and bias vectors.  Afterwards every entry of the
+ * handle computes with the new values, bitwise as a handle created from them.  Nothing is allocated; the launches are on
+ * `stream`.  An unknown key or a wrong numel is LDMSEG_E_ARG. */
+int ldmseg_vae_load_decoder(ldmseg_vae* h, int n, const char* const* names, const void* const* dev_ptrs, const int64_t* numels,
+                            void* stream);
 /* Fused tail of TrainerDiffusion.decode_latents(return_logits=False, threshold_output) (trainers_ldm_cond.py:
  * 421-433): decode -> bilinear x2 -> argmax over the 128 classes and max-softmax probability, without writing the
  * logits.  ids [B,8L,8L] int64 (= ignore_label where max prob < mask_th; mask_th < 0 disables the threshold),

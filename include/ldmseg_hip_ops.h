@@ -240,6 +240,30 @@ int ldmseg_op_small_linear(const float* x, const float* W, const float* bias, in
 int ldmseg_unet_time_rows(struct ldmseg_unet* h, const int64_t* timesteps_host, int n, int table, float* rows_dev, int* total_out,
                           void* stream);
 
+/* The kernels of the seg-VAE decoder's backward (csrc/vae_bwd.hip), each by itself.  Every tensor is fp32 on the device;
+ * dtype picks the products: 0 = fp32, 2 / 3 = split-bf16 (3: data-gradient weights as hi | lo planes, as a bf16x3 handle holds
+ * them).  Gradients come back in the state-dict layout.  -2: a shape or dtype the kernels do not serve.
+ * _conv_wgrad:   x [B,Ci,H,W], dy [B,Co,H,W] -> dw [Co,Ci,3,3], db [Co] or NULL of F.conv2d(x, w, b, padding=1).
+ * _convt2_wgrad: x [B,Ci,H,W], dy [B,Co,2H,2W] -> dw [Ci,Co,2,2], db [Co] or NULL of F.conv_transpose2d(x, w, b, stride=2).
+ * _conv_dgrad:   dy [B,Co,H,W], w [Co,Ci,3,3] -> dx [B,Ci,H,W] (igemm on the transposed, tap-rotated packing); nchw_epi = 1 stores
+ *                through the fp32 NCHW epilogue, as the latents' gradient is stored.
+ * _convt2_dgrad: dy [B,Co,2H,2W], w [Ci,Co,2,2] -> dx [B,Ci,H,W].
+ * _groupnorm_silu_bwd: backward of silu(group_norm(x, 32, gamma, beta, eps)); x, dy, dx [B,C,HW]; dgamma / dbeta [C] or NULL.
+ * _layernorm_silu_bwd: backward of silu(layer_norm(x, (C,), gamma, beta, eps)) over rows; x, dy, dx [M,C]; pm = 1: the rows are the
+ *                pixels of maps H2 x W2 and dx is stored phase-major, [image][H2/2][W2/2][2x2][C], as the transposed-conv gradients
+ *                read it.
+ * _wgrad_plan:   what a weight-gradient launch of P pixels, N dY columns, C storage channels of X, taps 9 | 1 would run on a device
+ *                of `cus` CUs (csrc/wgrad_plan.h; needs no device): "name tiles=T slices=S steps=K/TOTAL grid=G block=256 one_per_cu=0|1". */
+int ldmseg_op_conv_wgrad(const float* x, const float* dy, int B, int Ci, int H, int W, int Co, int dtype, float* dw, float* db, void* stream);
+int ldmseg_op_convt2_wgrad(const float* x, const float* dy, int B, int Ci, int H, int W, int Co, int dtype, float* dw, float* db, void* stream);
+int ldmseg_op_conv_dgrad(const float* dy, const float* w, int B, int Ci, int H, int W, int Co, int nchw_epi, int dtype, float* dx, void* stream);
+int ldmseg_op_convt2_dgrad(const float* dy, const float* w, int B, int Ci, int H, int W, int Co, int dtype, float* dx, void* stream);
+int ldmseg_op_groupnorm_silu_bwd(const float* x, const float* dy, const float* gamma, const float* beta, int B, int C, int HW, float eps,
+                                 float* dx, float* dgamma, float* dbeta, void* stream);
+int ldmseg_op_layernorm_silu_bwd(const float* x, const float* dy, const float* gamma, const float* beta, int M, int C, float eps, int pm,
+                                 int H2, int W2, float* dx, float* dgamma, float* dbeta, void* stream);
+int ldmseg_op_wgrad_plan(int P, int N, int C, int taps, int x3, int cus, char* buf, int n);
+
 /* q[i] = n[i] / d (0 <= n[i] < 2^31, d >= 1) computed the way the kernels divide: host-prepared multiply-shift pair */
 int ldmseg_op_fastdiv(const int* n, int count, int d, int* q, void* stream);
 

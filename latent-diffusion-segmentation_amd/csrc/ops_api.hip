@@ -18,6 +18,7 @@
 #include "ln_plan.h"
 #include "nearest_index.h"
 #include "runtime.h"
+#include "vae_bwd.h"
 
 using namespace ldmseg;
 using rt::bke;
@@ -1126,6 +1127,147 @@ int ldmseg_op_attention_fp8(const float* qkv, int B, int N, int C, int heads, fl
   }
   if (out) return st.rows_out(op, out, (size_t)B * N * C);
   return 0;
+}
+
+// ------------------------------------------------------------------ the seg-VAE decoder's backward kernels (vae_bwd.hip), fp32 tensors
+// dtype: 0 = fp32 products, 2 / 3 = split-bf16 products (3: data-gradient weights as hi | lo planes, as a bf16x3 handle holds them)
+// rows (image, Y, X) of a [B, 2H * 2W, C] map -> phase-major [B, H, W, 2x2, C] (what launch_ln_silu_bwd stores with pm = 1)
+static __global__ void phase_major_rows_kernel(const float* x, float* y, int H2, int W2, int C, size_t total) {
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(e % C);
+    const size_t r = e / C;
+    const int hw = H2 * W2;
+    const int img = (int)(r / hw), rem = (int)(r - (size_t)img * hw);
+    const int Y = rem / W2, X = rem - Y * W2;
+    const size_t ro = (((size_t)img * (H2 >> 1) + (Y >> 1)) * (W2 >> 1) + (X >> 1)) * 4 + 2 * (Y & 1) + (X & 1);
+    y[ro * C + c] = x[e];
+  }
+}
+static float* stage_phase_major(Stage& st, const float* dy, int B, int Co, int H, int W) {
+  const size_t total = (size_t)B * 4 * H * W * Co;
+  float* rows = (float*)st.nchw(dy, B, Co, 4 * H * W, Co);
+  float* pm = (float*)st.buf(total * sizeof(float));
+  st.step([&] {
+    hipLaunchKernelGGL(phase_major_rows_kernel, dim3(rows_grid(total)), dim3(256), 0, st.s, rows, pm, 2 * H, 2 * W, Co, total);
+    return hipGetLastError() != hipSuccess;
+  });
+  return st.status ? nullptr : pm;
+}
+static int op_wgrad_run(Stage& st, WgradParams& wp, int form, int n_real, int c_real, int co, float* dw) {
+  WgradPlan pl;
+  if (wgrad_plan(wp, num_cus(), &pl)) return -2;
+  wp.partial = (float*)st.buf(wgrad_partial_bytes(wp, pl));
+  if (st.status) return st.status;
+  const int r = launch_wgrad(wp, pl, st.s);
+  return r ? r : launch_wgrad_finish(wp, pl, form, n_real, c_real, co, dw, st.s);
+}
+
+// grads of F.conv2d(x, w, b, padding=1) with respect to w and b: x [B,Ci,H,W], dy [B,Co,H,W] -> dw [Co,Ci,3,3], db [Co] or NULL
+int ldmseg_op_conv_wgrad(const float* x, const float* dy, int B, int Ci, int H, int W, int Co, int dtype, float* dw, float* db, void* stream) {
+  if (!x || !dy || !dw || B < 1 || Ci < 1 || Co < 1 || H < 1 || W < 1 || (dtype != 0 && dtype != 2 && dtype != 3)) return -2;
+  Stage st(stream, dtype, true);
+  const int Cip = (int)rup(Ci, 32), Cop = (int)rup(Co, 32), P = B * H * W;
+  WgradParams wp;
+  wp.x = (const float*)st.nchw(x, B, Ci, H * W, Cip); wp.C = Cip;
+  wp.dy = (const float*)st.nchw(dy, B, Co, H * W, Cop); wp.ldy = Cop; wp.N = Cop;
+  wp.B = B; wp.H = H; wp.W = W; wp.taps = 9; wp.x3 = st.x3 ? 1 : 0;
+  const int r = op_wgrad_run(st, wp, 0, Co, Ci, 0, dw);
+  if (r || !db) return r;
+  float* scratch = (float*)st.buf(colsum_scratch_bytes(P, Cop));
+  if (st.status) return st.status;
+  return launch_colsum(wp.dy, Cop, P, Cop, 1, 0, Co, scratch, db, st.s);
+}
+// grads of F.conv_transpose2d(x, w, b, stride=2) (kernel 2): x [B,Ci,H,W], dy [B,Co,2H,2W] -> dw [Ci,Co,2,2], db [Co] or NULL
+int ldmseg_op_convt2_wgrad(const float* x, const float* dy, int B, int Ci, int H, int W, int Co, int dtype, float* dw, float* db, void* stream) {
+  if (!x || !dy || !dw || B < 1 || Ci < 1 || Co < 4 || Co % 4 || H < 1 || W < 1 || (dtype != 0 && dtype != 2 && dtype != 3)) return -2;
+  Stage st(stream, dtype, true);
+  const int Cip = (int)rup(Ci, 32), P = B * H * W;
+  WgradParams wp;
+  wp.x = (const float*)st.nchw(x, B, Ci, H * W, Cip); wp.C = Cip;
+  wp.dy = stage_phase_major(st, dy, B, Co, H, W); wp.ldy = 4 * Co; wp.N = 4 * Co;
+  wp.B = B; wp.H = H; wp.W = W; wp.taps = 1; wp.x3 = st.x3 ? 1 : 0;
+  const int r = op_wgrad_run(st, wp, 1, 4 * Co, Ci, Co, dw);
+  if (r || !db) return r;
+  float* scratch = (float*)st.buf(colsum_scratch_bytes(P, 4 * Co));
+  if (st.status) return st.status;
+  return launch_colsum(wp.dy, 4 * Co, P, 4 * Co, 4, Co, Co, scratch, db, st.s);
+}
+// grad of F.conv2d(x, w, padding=1) with respect to x, the way ldmseg_vae_decode_backward runs it: igemm on the transposed, rotated
+// packing.  dy [B,Co,H,W], w [Co,Ci,3,3] -> dx [B,Ci,H,W]; nchw_epi: the fp32 NCHW store epilogue (the latents' gradient)
+int ldmseg_op_conv_dgrad(const float* dy, const float* w, int B, int Ci, int H, int W, int Co, int nchw_epi, int dtype, float* dx, void* stream) {
+  if (!dy || !w || !dx || B < 1 || Ci < 1 || Co < 1 || H < 1 || W < 1 || (dtype != 0 && dtype != 2 && dtype != 3)) return -2;
+  if (!nchw_epi && Ci % 4) return -2;
+  Stage st(stream, dtype, true);
+  hipStream_t s = st.s;
+  const int epi = nchw_epi ? EPI_NCHW_F32 : EPI_STORE;
+  const int Cop = (int)rup(Co, 32), Np = (int)rup(Ci, igemm_pick_bn(Ci, epi)), P = B * H * W;
+  float* wp = (float*)st.buf((size_t)Np * 9 * Cop * sizeof(float));
+  st.step([&] { return launch_pack_dgrad_conv(w, wp, Co, Ci, Np, Cop, s) || (st.x3 == 2 && launch_split_planes(wp, (size_t)Np * 9 * Cop, s)); });
+  IgemmParams p;
+  p.src0 = st.nchw(dy, B, Co, H * W, Cop); p.C0 = Cop; p.B = B; p.Hi = p.Ho = H; p.Wi = p.Wo = W;
+  p.taps = 9; p.M = P; p.N = Np; p.n_valid = Ci; p.W = wp; p.epi = epi; p.x3 = st.x3;
+  void* op = nchw_epi ? (void*)dx : st.buf((size_t)P * Ci * sizeof(float));
+  p.out = op; p.ldo = Ci;
+  p.cf_ctr = op_cf_region();
+  st.splitk(p);
+  if (st.status) return st.status;
+  const int r = launch_igemm(p, DT_F32, s);
+  if (r || nchw_epi) return r;
+  return st.nchw_out(op, dx, B, Ci, H * W, Ci);
+}
+// grad of F.conv_transpose2d(x, w, stride=2) (kernel 2) with respect to x: dy [B,Co,2H,2W], w [Ci,Co,2,2] -> dx [B,Ci,H,W]
+int ldmseg_op_convt2_dgrad(const float* dy, const float* w, int B, int Ci, int H, int W, int Co, int dtype, float* dx, void* stream) {
+  if (!dy || !w || !dx || B < 1 || Ci < 4 || Ci % 4 || Co < 8 || Co % 8 || H < 1 || W < 1 || (dtype != 0 && dtype != 2 && dtype != 3)) return -2;
+  Stage st(stream, dtype, true);
+  hipStream_t s = st.s;
+  const int Np = (int)rup(Ci, igemm_pick_bn(Ci, EPI_STORE)), P = B * H * W;
+  float* wp = (float*)st.buf((size_t)Np * 4 * Co * sizeof(float));
+  st.step([&] { return launch_pack_dgrad_convt(w, wp, Ci, Co, Np, s) || (st.x3 == 2 && launch_split_planes(wp, (size_t)Np * 4 * Co, s)); });
+  IgemmParams p;
+  p.src0 = stage_phase_major(st, dy, B, Co, H, W); p.C0 = 4 * Co; p.B = B; p.Hi = p.Ho = H; p.Wi = p.Wo = W;
+  p.taps = 1; p.M = P; p.N = Np; p.n_valid = Ci; p.W = wp; p.epi = EPI_STORE; p.x3 = st.x3;
+  void* op = st.buf((size_t)P * Ci * sizeof(float));
+  p.out = op; p.ldo = Ci;
+  p.cf_ctr = op_cf_region();
+  st.splitk(p);
+  if (st.status) return st.status;
+  const int r = launch_igemm(p, DT_F32, s);
+  if (r) return r;
+  return st.nchw_out(op, dx, B, Ci, H * W, Ci);
+}
+// backward of F.silu(F.group_norm(x, 32, gamma, beta, eps)): x, dy [B,C,HW] -> dx [B,C,HW], dgamma / dbeta [C] or NULL
+int ldmseg_op_groupnorm_silu_bwd(const float* x, const float* dy, const float* gamma, const float* beta, int B, int C, int HW, float eps,
+                                 float* dx, float* dgamma, float* dbeta, void* stream) {
+  if (!x || !dy || !gamma || !beta || !dx || B < 1 || C < 32 || C % 32 || HW < 1) return -2;
+  Stage st(stream, DT_F32);
+  const float* xp = (const float*)st.nchw(x, B, C, HW, C);
+  const float* dp = (const float*)st.nchw(dy, B, C, HW, C);
+  float* op = (float*)st.buf((size_t)B * HW * C * sizeof(float));
+  float* scratch = (float*)st.buf(gn_bwd_scratch_bytes(B, C));
+  if (st.status) return st.status;
+  const int r = launch_gn_silu_bwd(xp, dp, gamma, beta, op, dgamma, dbeta, B, HW, C, eps, scratch, st.s);
+  if (r) return r;
+  return st.nchw_out(op, dx, B, C, HW, C);
+}
+// backward of F.silu(F.layer_norm(x, (C,), gamma, beta, eps)) over rows: x, dy [M,C] -> dx [M,C], dgamma / dbeta [C] or NULL.
+// pm = 1: the rows are the pixels of maps H2 x W2 and dx is stored phase-major, [image][H2/2][W2/2][2x2][C].
+int ldmseg_op_layernorm_silu_bwd(const float* x, const float* dy, const float* gamma, const float* beta, int M, int C, float eps, int pm,
+                                 int H2, int W2, float* dx, float* dgamma, float* dbeta, void* stream) {
+  if (!x || !dy || !gamma || !beta || !dx || M < 1 || C < 64 || C % 64 || C > 1024) return -2;
+  if (pm && (H2 < 2 || W2 < 2 || (H2 & 1) || (W2 & 1) || M % (H2 * W2))) return -2;
+  Stage st(stream, DT_F32);
+  float* scratch = (float*)st.buf(ln_bwd_scratch_bytes(M, C));
+  if (st.status) return st.status;
+  return launch_ln_silu_bwd(x, dy, gamma, beta, dx, dgamma, dbeta, M, C, eps, pm, H2, W2, scratch, st.s);
+}
+// The plan of a weight-gradient launch (wgrad_plan.h; no device): P pixels, N columns of dY, C storage channels of X, taps 9 | 1,
+// x3 0 | 1, on a device of `cus` CUs.  buf receives wgrad_plan_line; -2 where there is no such launch.
+int ldmseg_op_wgrad_plan(int P, int N, int C, int taps, int x3, int cus, char* buf, int n) {
+  if (!buf || n < 1) return -2;
+  WgradPlan pl;
+  const int r = wgrad_choose(WgradDesc{P, N, C, taps, x3}, cus, &pl);
+  if (r == 0) std::snprintf(buf, (size_t)n, "%s", wgrad_plan_line(pl).c_str());
+  return r;
 }
 
 // The two fp32 kernels of the time embedding (misc.hip) on the caller's device tensors: nothing is staged or converted.

@@ -3,6 +3,7 @@
 #include <cmath>
 
 #include "runtime.h"
+#include "vae_bwd.h"
 
 #pragma clang diagnostic ignored "-Wc++20-designator"      // ConvOpt and its like are filled by field name
 
@@ -20,6 +21,8 @@ struct ldmseg_vae : HandleBase {
   ConvW dec_in, dec_out;
   ConvW convt[4];
   NormW ln[4], dec_gn;
+  // fp32-storage handles: the decoder's convs packed a second time for their data gradients (ldmseg_vae_decode_backward)
+  ConvW dec_in_d, dec_out_d, convt_d[4];
 };
 
 // =================================================================== image VAE encoder (AutoencoderKL, SD-1.x)
@@ -36,6 +39,104 @@ struct ldmseg_vae_image : HandleBase {
 namespace {
 
 inline int cstore(int c, int dt) { return (int)rup(c, bke(dt)); }
+
+// ---- the decoder's data-gradient packings: the same igemm reads them as ordinary [N][K] weights
+// dX = conv3x3(dY, W transposed and rotated by 180 degrees): N = Ci, K = 9 * Co (Co padded to a K tile)
+void dgrad_conv_shape(ConvW* d, int Co, int Ci, int epi) {
+  d->N = (int)rup(Ci, igemm_pick_bn(Ci, epi)); d->n_valid = Ci; d->cin_pad = (int)rup(Co, bke(DT_F32)); d->taps = 9; d->cout = Ci;
+}
+// dX[p] = dY[p, 2x2, :] W[ci][co][q]: N = Ci, K = 4 * Co on the phase-major dY
+void dgrad_convt_shape(ConvW* d, int Ci, int Co) {
+  d->N = (int)rup(Ci, igemm_pick_bn(Ci, EPI_STORE)); d->n_valid = Ci; d->cin_pad = 4 * Co; d->taps = 1; d->cout = Ci;
+}
+size_t convw_floats(const ConvW& d) { return (size_t)d.N * d.taps * d.cin_pad; }
+
+// reference keys of the decoder in model order with their element counts: (conv_in w, b), per upscaler (convT w, b, LayerNorm w, b),
+// (GroupNorm w, b), (conv_out w, b)
+struct DecKey { std::string name; int64_t numel; };
+std::vector<DecKey> decoder_keys(const ldmseg_vae_cfg& c) {
+  std::vector<DecKey> k;
+  auto add = [&](int idx, int64_t wn, int64_t bn) {
+    k.push_back({"decoder." + std::to_string(idx) + ".weight", wn});
+    k.push_back({"decoder." + std::to_string(idx) + ".bias", bn});
+  };
+  add(0, (int64_t)c.int_channels * c.latent_channels * 9, c.int_channels);
+  int idx = 2, cin = c.int_channels;
+  for (int i = 0; i < c.num_upscalers; ++i) {
+    add(idx, (int64_t)cin * c.upscale_channels * 4, c.upscale_channels);
+    add(idx + 1, c.upscale_channels, c.upscale_channels);
+    cin = c.upscale_channels;
+    idx += 3;
+  }
+  add(idx, cin, cin);
+  add(idx + 2, (int64_t)c.out_channels * cin * 9, c.out_channels);
+  return k;
+}
+
+// (Re)packs the decoder tensors `wm` holds into the buffers the handle owns - forward packing, data-gradient packing, the hi | lo
+// planes of a bf16x3 handle, norm and bias vectors - with the launches the build uses.  Keys that are absent are left alone.
+int vae_pack_decoder(ldmseg_vae* v, const WeightMap& wm, hipStream_t s, bool forward_too) {
+  const ldmseg_vae_cfg& c = v->cfg;
+  const int dt = v->dt;
+  const bool f32 = dt == DT_F32;
+  const std::vector<DecKey> keys = decoder_keys(c);
+  auto has = [&](size_t slot, const float** p) {
+    auto it = wm.m.find(keys[slot].name);
+    if (it == wm.m.end()) return false;
+    *p = it->second.first;
+    return true;
+  };
+  auto planes = [&](void* w, size_t nfloats) { return (v->x3 && f32) ? launch_split_planes(w, nfloats, s) : 0; };
+  auto conv3 = [&](size_t slot, ConvW& fw, ConvW& dg, int Co, int Ci) -> int {
+    const float* p;
+    if (has(slot, &p)) {
+      if (forward_too) {
+        TRY(launch_repack_conv(p, fw.w, Co, Ci, 3, 3, fw.N, fw.cin_pad, dt, s));
+        TRY(planes(fw.w, convw_floats(fw)));
+      }
+      if (f32) {
+        TRY(launch_pack_dgrad_conv(p, (float*)dg.w, Co, Ci, dg.N, dg.cin_pad, s));
+        TRY(planes(dg.w, convw_floats(dg)));
+      }
+    }
+    if (forward_too && has(slot + 1, &p)) TRY(launch_padded_bias(p, Co, fw.bias, fw.N, s));
+    return 0;
+  };
+  auto vec = [&](size_t slot, float* dst, int n) -> int {
+    const float* p;
+    if (forward_too && has(slot, &p)) HIP_TRY(hipMemcpyAsync(dst, p, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+  };
+  size_t slot = 0;
+  TRY(conv3(slot, v->dec_in, v->dec_in_d, c.int_channels, c.latent_channels));
+  slot += 2;
+  int cin = c.int_channels;
+  for (int i = 0; i < c.num_upscalers; ++i) {
+    const int Co = c.upscale_channels;
+    ConvW& t = v->convt[i];
+    const float* p;
+    if (has(slot, &p)) {
+      if (forward_too) {
+        TRY(launch_repack_convt2(p, t.w, cin, Co, dt, s));
+        TRY(planes(t.w, (size_t)4 * Co * cin));
+      }
+      if (f32) {
+        TRY(launch_pack_dgrad_convt(p, (float*)v->convt_d[i].w, cin, Co, v->convt_d[i].N, s));
+        TRY(planes(v->convt_d[i].w, convw_floats(v->convt_d[i])));
+      }
+    }
+    if (forward_too && has(slot + 1, &p))
+      for (int q = 0; q < 4; ++q) HIP_TRY(hipMemcpyAsync(t.bias + q * Co, p, Co * sizeof(float), hipMemcpyDeviceToDevice, s));
+    TRY(vec(slot + 2, v->ln[i].g, Co));
+    TRY(vec(slot + 3, v->ln[i].b, Co));
+    cin = Co;
+    slot += 4;
+  }
+  TRY(vec(slot, v->dec_gn.g, cin));
+  TRY(vec(slot + 1, v->dec_gn.b, cin));
+  TRY(conv3(slot + 2, v->dec_out, v->dec_out_d, c.out_channels, cin));
+  return 0;
+}
 
 int vae_build(ldmseg_vae* v, const WeightMap& wm) {
   Builder b(*v, wm);
@@ -86,6 +187,20 @@ int vae_build(ldmseg_vae* v, const WeightMap& wm) {
   }
   TRY(b.norm("decoder." + std::to_string(idx), cin, &v->dec_gn));
   TRY(b.conv("decoder." + std::to_string(idx + 2), c.out_channels, cin, 3, cin, &v->dec_out));
+  if (dt == DT_F32) {
+    // the data-gradient packings (the planes of a bf16x3 handle are made by vae_pack_decoder itself: not registered with b.weights)
+    dgrad_conv_shape(&v->dec_in_d, c.int_channels, c.latent_channels, EPI_NCHW_F32);
+    dgrad_conv_shape(&v->dec_out_d, c.out_channels, cin, EPI_STORE);
+    TRY(v->arena.alloc(&v->dec_in_d.w, convw_floats(v->dec_in_d) * sizeof(float)));
+    TRY(v->arena.alloc(&v->dec_out_d.w, convw_floats(v->dec_out_d) * sizeof(float)));
+    int ci = c.int_channels;
+    for (int i = 0; i < c.num_upscalers; ++i) {
+      dgrad_convt_shape(&v->convt_d[i], ci, c.upscale_channels);
+      TRY(v->arena.alloc(&v->convt_d[i].w, convw_floats(v->convt_d[i]) * sizeof(float)));
+      ci = c.upscale_channels;
+    }
+    TRY(vae_pack_decoder(v, wm, s, false));
+  }
   return b.finish(*v);
 }
 
@@ -185,6 +300,140 @@ int vae_decode(ldmseg_vae* v, const float* z, float z_scale, int B, int L, const
     Exec ex = make_exec(*v, B, (hipStream_t)stream, dry, scratch_base);
     return vae_decode_body(ex, v, z, z_scale, L, tail);
   });
+}
+
+// ---- the decoder's backward.  One planned pass: the decoder forward again up to the GroupNorm output (the logits
+// themselves are not needed), keeping what the backward reads, then the chain from d loss / d logits down to every parameter
+// gradient asked for (g[slot], slots as decoder_keys; null = skipped) and to grad_z.
+struct WgradJob {
+  const float* dy; int ldy, N;        // dY [P][ldy], N columns taken
+  const float* x; int C;              // X [P][C]
+  int H, W, taps, form, n_real, c_real, co;
+};
+int run_wgrad(Exec& ex, const WgradJob& j, float* out) {
+  if (!out) return 0;
+  Workspace* ws = ex.ws;
+  const size_t m = ws->mark();
+  WgradParams wp;
+  wp.dy = j.dy; wp.ldy = j.ldy; wp.x = j.x; wp.B = ex.B; wp.H = j.H; wp.W = j.W; wp.N = j.N; wp.C = j.C; wp.taps = j.taps;
+  wp.x3 = ex.x3 ? 1 : 0;
+  WgradPlan pl;
+  if (wgrad_plan(wp, num_cus(), &pl)) return fail(LDMSEG_E_SHAPE, "weight gradient: unsupported shape");
+  wp.partial = (float*)ws->scratch(wgrad_partial_bytes(wp, pl));
+  const double P = (double)ex.B * j.H * j.W;
+  const int r = ex.launch("launch_wgrad failed", 0, 2.0 * P * j.n_real * j.c_real * j.taps, P * (j.N + j.C) * 4.0 * pl.tiles / pl.n_tiles,
+                          [&] {      // (no commas: the profile dump is a CSV)
+                            return std::string(pl.x3 ? "wgrad x3" : "wgrad f32") + " P=" + std::to_string((long long)P) + " N=" + std::to_string(j.N) +
+                                   " C=" + std::to_string(j.C) + " taps=" + std::to_string(j.taps) + " slices=" + std::to_string(pl.slices) +
+                                   " grid=" + std::to_string(pl.grid_x);
+                          }, [&] {
+    const int e = launch_wgrad(wp, pl, ex.s);
+    return e ? e : launch_wgrad_finish(wp, pl, j.form, j.n_real, j.c_real, j.co, out, ex.s);
+  });
+  ws->reset(m);
+  return r;
+}
+int run_colsum(Exec& ex, const float* a, int lda, int P, int Q, int qstride, int n, float* out) {
+  if (!out) return 0;
+  Workspace* ws = ex.ws;
+  const size_t m = ws->mark();
+  float* scratch = (float*)ws->scratch(colsum_scratch_bytes(P, lda));
+  const int r = ex.launch("launch_colsum failed", 4, 0, (double)P * lda * 4.0, [&] { return "colsum P=" + std::to_string(P) + " N=" + std::to_string(lda); },
+                          [&] { return launch_colsum(a, lda, P, lda, Q, qstride, n, scratch, out, ex.s); });
+  ws->reset(m);
+  return r;
+}
+
+int vae_decode_backward_body(Exec& ex, ldmseg_vae* v, const float* z, float z_scale, int L, const float* grad_logits, float* grad_z,
+                             float* const* g) {
+  const int B = ex.B;
+  hipStream_t s = ex.s;
+  const int dt = v->dt;
+  const ldmseg_vae_cfg& c = v->cfg;
+  const int U = c.num_upscalers, Cu = c.upscale_channels, Co = c.out_channels;
+  // ---- forward again, everything the backward reads is kept
+  Act zin = ex.new_act(bke(dt), L, L, true);
+  TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, no_label, [&] { return launch_pack_nchw(z, zin.p, B, c.latent_channels, L * L, bke(dt), z_scale, 0.f, dt, s); }));
+  Act h;
+  TRY(ex.conv(v->dec_in, zin, &h));
+  Act hin[4], pre[4];
+  for (int i = 0; i < U; ++i) {
+    const ConvW& t = v->convt[i];
+    hin[i] = h;
+    pre[i] = ex.new_act(t.cout, 2 * h.H, 2 * h.W, true);
+    IgemmParams p;
+    p.src0 = h.p; p.C0 = h.C; p.B = B; p.Hi = p.Ho = h.H; p.Wi = p.Wo = h.W;
+    p.M = B * h.H * h.W; p.N = t.N; p.n_valid = t.N; p.W = t.w; p.bias = t.bias;
+    p.out = pre[i].p; p.ldo = t.cout; p.epi = EPI_CONVT2; p.cout = t.cout;
+    TRY(ex.igemm(p));
+    Act n;
+    TRY(ex.layernorm(v->ln[i], pre[i], 1e-6f, 1, &n, false));   // out of place: the transposed conv's own output is the backward's input
+    h = n;
+  }
+  Act gact;
+  TRY(ex.groupnorm(v->dec_gn, h, nullptr, 1e-5f, 1, &gact));
+  // ---- backward
+  Workspace* ws = ex.ws;
+  const int H4 = h.H, W4 = h.W, P4 = B * H4 * W4;
+  const int Cop = (int)rup(Co, bke(dt));
+  const size_t last = (size_t)2 + 4 * U;          // slot of the GroupNorm weight
+  float* dyp = (float*)ws->scratch((size_t)P4 * Cop * sizeof(float));
+  TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, [] { return std::string("pack grad_logits"); }, [&] { return launch_pack_nchw(grad_logits, dyp, B, Co, H4 * W4, Cop, 1.f, 0.f, dt, s); }));
+  TRY(run_wgrad(ex, {dyp, Cop, Cop, (const float*)gact.p, Cu, H4, W4, 9, 0, Co, Cu, 0}, g[last + 2]));
+  TRY(run_colsum(ex, dyp, Cop, P4, 1, 0, Co, g[last + 3]));
+  Act dg = ex.new_act(Cu, H4, W4, false);
+  {
+    IgemmParams p;
+    p.src0 = dyp; p.C0 = Cop; p.B = B; p.Hi = p.Ho = H4; p.Wi = p.Wo = W4;
+    p.taps = 9; p.M = P4; p.N = v->dec_out_d.N; p.n_valid = Cu; p.W = v->dec_out_d.w;
+    p.out = dg.p; p.ldo = Cu; p.epi = EPI_STORE;
+    TRY(ex.igemm(p));
+  }
+  Act dh = ex.new_act(Cu, H4, W4, false);
+  {
+    float* scratch = (float*)ws->scratch(gn_bwd_scratch_bytes(B, Cu));
+    TRY(ex.launch("launch_gn_silu_bwd failed", 2, 0, 4.0 * P4 * Cu * 4.0, [&] { return "gn_silu_bwd HW=" + std::to_string(H4 * W4) + " C=" + std::to_string(Cu); }, [&] {
+      return launch_gn_silu_bwd((const float*)h.p, (const float*)dg.p, v->dec_gn.g, v->dec_gn.b, (float*)dh.p, g[last], g[last + 1], B, H4 * W4, Cu,
+                                1e-5f, scratch, s);
+    }));
+  }
+  for (int i = U - 1; i >= 0; --i) {
+    const size_t slot = (size_t)2 + 4 * i;
+    const Act& x = hin[i];                         // the transposed conv's input, on the low-resolution map
+    const int Pl = B * x.H * x.W, M = 4 * Pl;
+    // LayerNorm2d + SiLU backward; its result is stored phase-major [B, H, W, 2x2, Cu]: both transposed-conv gradients read it as
+    // a [Pl][4 Cu] matrix without a repack
+    Act dpre = ex.new_act(Cu, pre[i].H, pre[i].W, false);
+    {
+      float* scratch = (float*)ws->scratch(ln_bwd_scratch_bytes(M, Cu));
+      TRY(ex.launch("launch_ln_silu_bwd failed", 3, 0, 3.0 * M * Cu * 4.0, [&] { return "ln_silu_bwd M=" + std::to_string(M) + " C=" + std::to_string(Cu); }, [&] {
+        return launch_ln_silu_bwd((const float*)pre[i].p, (const float*)dh.p, v->ln[i].g, v->ln[i].b, (float*)dpre.p, g[slot + 2], g[slot + 3], M, Cu,
+                                  1e-6f, 1, pre[i].H, pre[i].W, scratch, s);
+      }));
+    }
+    TRY(run_wgrad(ex, {(const float*)dpre.p, 4 * Cu, 4 * Cu, (const float*)x.p, x.C, x.H, x.W, 1, 1, 4 * Cu, x.C, Cu}, g[slot]));
+    TRY(run_colsum(ex, (const float*)dpre.p, 4 * Cu, Pl, 4, Cu, Cu, g[slot + 1]));
+    Act dx = ex.new_act(x.C, x.H, x.W, false);
+    IgemmParams p;
+    p.src0 = dpre.p; p.C0 = 4 * Cu; p.B = B; p.Hi = p.Ho = x.H; p.Wi = p.Wo = x.W;
+    p.taps = 1; p.M = Pl; p.N = v->convt_d[i].N; p.n_valid = x.C; p.W = v->convt_d[i].w;
+    p.out = dx.p; p.ldo = x.C; p.epi = EPI_STORE;
+    TRY(ex.igemm(p));
+    dh = dx;
+  }
+  const int P0 = B * L * L, Ci = c.int_channels;
+  TRY(run_wgrad(ex, {(const float*)dh.p, Ci, Ci, (const float*)zin.p, zin.C, L, L, 9, 0, Ci, c.latent_channels, 0}, g[0]));
+  TRY(run_colsum(ex, (const float*)dh.p, Ci, P0, 1, 0, Ci, g[1]));
+  if (grad_z) {
+    IgemmParams p;
+    p.src0 = dh.p; p.C0 = Ci; p.B = B; p.Hi = p.Ho = L; p.Wi = p.Wo = L;
+    p.taps = 9; p.M = P0; p.N = v->dec_in_d.N; p.n_valid = c.latent_channels; p.W = v->dec_in_d.w;
+    p.out = grad_z; p.epi = EPI_NCHW_F32;
+    TRY(ex.igemm(p));
+    if (z_scale != 1.0f)     // decode(z, z_scale) feeds z * z_scale
+      TRY(ex.launch("launch_axpby failed", 4, 0, 0, no_label, [&] { return launch_axpby(grad_z, z_scale, 0.f, grad_z, (size_t)P0 * c.latent_channels, s); }));
+  }
+  return 0;
 }
 
 int vae_encode_body(Exec& ex, ldmseg_vae* v, const float* x, float mul, float add, int H, float* moments) {
@@ -406,6 +655,49 @@ int ldmseg_vae_decode(ldmseg_vae* h, const float* z, float z_scale, int B, int L
   if (B < 1 || L < 1) return fail(LDMSEG_E_SHAPE, "bad B/L");
   const DecodeTail tail{.kind = interpolate ? DecodeTail::LOGITS_X2 : DecodeTail::LOGITS, .logits = logits};
   return vae_decode(h, z, z_scale, B, L, tail, stream);
+}
+
+int ldmseg_vae_decode_backward(ldmseg_vae* h, const float* z, float z_scale, int B, int L, const float* grad_logits, float* grad_z, int n,
+                               const char* const* names, float* const* grad_ptrs, const int64_t* numels, void* stream) {
+  g_err.clear();
+  if (!h || !z || !grad_logits) return fail(LDMSEG_E_ARG, "null argument");
+  if (n < 0 || (n > 0 && (!names || !grad_ptrs || !numels))) return fail(LDMSEG_E_ARG, "null argument");
+  if (h->dt != DT_F32) return fail(LDMSEG_E_ARG, "the decoder backward needs an fp32-storage handle (compute_dtype fp32 or bf16x3), not bf16");
+  if (B < 1 || L < 1) return fail(LDMSEG_E_SHAPE, "bad B/L");
+  const std::vector<DecKey> keys = decoder_keys(h->cfg);
+  std::vector<float*> g(keys.size(), nullptr);
+  for (int i = 0; i < n; ++i) {
+    if (!names[i]) return fail(LDMSEG_E_ARG, "null gradient name");
+    size_t k = 0;
+    while (k < keys.size() && keys[k].name != names[i]) ++k;
+    if (k == keys.size()) return fail(LDMSEG_E_ARG, std::string("not a decoder parameter: ") + names[i]);
+    if (numels[i] != keys[k].numel)
+      return fail(LDMSEG_E_ARG, keys[k].name + " has " + std::to_string(keys[k].numel) + " elements, the gradient buffer " + std::to_string(numels[i]));
+    g[k] = grad_ptrs[i];
+  }
+  DeviceGuard dg(h->cfg.device);
+  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
+    Exec ex = make_exec(*h, B, (hipStream_t)stream, dry, scratch_base);
+    return vae_decode_backward_body(ex, h, z, z_scale, L, grad_logits, grad_z, g.data());
+  });
+}
+
+int ldmseg_vae_load_decoder(ldmseg_vae* h, int n, const char* const* names, const void* const* dev_ptrs, const int64_t* numels, void* stream) {
+  g_err.clear();
+  if (!h || n < 0 || (n > 0 && (!names || !dev_ptrs || !numels))) return fail(LDMSEG_E_ARG, "null argument");
+  const std::vector<DecKey> keys = decoder_keys(h->cfg);
+  WeightMap wm;
+  for (int i = 0; i < n; ++i) {
+    if (!names[i] || !dev_ptrs[i]) return fail(LDMSEG_E_ARG, "null decoder tensor");
+    size_t k = 0;
+    while (k < keys.size() && keys[k].name != names[i]) ++k;
+    if (k == keys.size()) return fail(LDMSEG_E_ARG, std::string("not a decoder parameter: ") + names[i]);
+    if (numels[i] != keys[k].numel)
+      return fail(LDMSEG_E_ARG, keys[k].name + " has " + std::to_string(keys[k].numel) + " elements, got " + std::to_string(numels[i]));
+    wm.m[keys[k].name] = {(const float*)dev_ptrs[i], numels[i]};
+  }
+  DeviceGuard dg(h->cfg.device);
+  return vae_pack_decoder(h, wm, (hipStream_t)stream, true);
 }
 
 int ldmseg_vae_decode_argmax(ldmseg_vae* h, const float* z, float z_scale, int B, int L, float mask_th, int64_t ignore_label,

@@ -1,0 +1,55 @@
+// Host-side launch API of the seg-VAE decoder's backward kernels (vae_bwd.hip).  Every tensor is fp32: the backward runs on
+// fp32-storage handles only ("fp32" and "bf16x3"); x3 selects the split-bf16 products of the weight gradient.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "wgrad_plan.h"
+
+namespace ldmseg {
+
+// Weight gradient of a 3x3 conv (pad 1, stride 1; taps = 9) or of any GEMM over pixel rows (taps = 1):
+//   slab[s][n][tap * C + c] = sum over the pixels p of slice s of dy[p][n] * x[p + tap][c]   (zero outside the image)
+// dy [P][ldy] (the first N columns are taken, N <= ldy), x [P][C] on B maps of H x W pixels (P = B H W).  The slabs
+// (wgrad_partial_bytes) are added in slice order by launch_wgrad_finish.
+struct WgradParams {
+  const float* dy = nullptr; int ldy = 0;
+  const float* x = nullptr;
+  int B = 0, H = 0, W = 0;
+  int N = 0, C = 0, taps = 9;
+  int x3 = 0;
+  float* partial = nullptr;
+};
+int wgrad_plan(const WgradParams& p, int cus, WgradPlan* pl);
+size_t wgrad_partial_bytes(const WgradParams& p, const WgradPlan& pl);
+int launch_wgrad(const WgradParams& p, const WgradPlan& pl, hipStream_t s);
+// out = the slabs added in slice order, in the state-dict layout: form 0 = Conv2d [n_real][c_real][3][3] (taps 9) or Linear
+// [n_real][c_real] (taps 1); form 1 = ConvTranspose2d k2 s2 [c_real][co][2][2] from rows n = q * co + o (taps 1, n_real = 4 co)
+int launch_wgrad_finish(const WgradParams& p, const WgradPlan& pl, int form, int n_real, int c_real, int co, float* out, hipStream_t s);
+
+// out[j] = sum_p a[p][q * qstride + j] over rows p and q < Q, for j < n: the bias gradient of a conv (Q = 1) or a transposed conv
+// (Q = 4, qstride = Co).  Rows are cut into colsum_slices(P) runs whose sums (scratch: colsum_scratch_bytes) are added in order.
+int colsum_slices(int P);
+size_t colsum_scratch_bytes(int P, int N);
+int launch_colsum(const float* a, int lda, int P, int N, int Q, int qstride, int n, float* scratch, float* out, hipStream_t s);
+
+// LayerNorm over the last dim of [M][C] followed by SiLU, backward: x = the forward's INPUT, dy = d / d SiLU(LN(x)).  dx, dgamma,
+// dbeta as DESIGN 8.6.  pm: dx row r = (image, Y, X) of a map H2 x W2 is stored phase-major, at row
+// ((image * H2/2 + Y/2) * W2/2 + X/2) * 4 + 2 (Y & 1) + (X & 1) - the [B, H, W, 2x2, C] order both transposed-conv gradients read.
+// dgamma / dbeta null: not computed.  scratch: ln_bwd_scratch_bytes(M, C).  C a multiple of 64, at most 1024.
+size_t ln_bwd_scratch_bytes(int M, int C);
+int launch_ln_silu_bwd(const float* x, const float* dy, const float* gamma, const float* beta, float* dx, float* dgamma, float* dbeta,
+                       int M, int C, float eps, int pm, int H2, int W2, float* scratch, hipStream_t s);
+
+// GroupNorm (32 groups) + SiLU backward on [B][HW][C]; statistics are recomputed from x.  scratch: gn_bwd_scratch_bytes(B, C)
+size_t gn_bwd_scratch_bytes(int B, int C);
+int launch_gn_silu_bwd(const float* x, const float* dy, const float* gamma, const float* beta, float* dx, float* dgamma, float* dbeta,
+                       int B, int HW, int C, float eps, float* scratch, hipStream_t s);
+
+// Weights of the data gradients, read by launch_igemm as ordinary [Npad][K] fp32 matrices:
+// Conv2d OIHW [Co][Ci][3][3] -> [Npad][9][Cop], row ci, column (tap', co) = w[co][ci][8 - tap'] (transposed, taps rotated by 180 degrees)
+int launch_pack_dgrad_conv(const float* w, float* out, int Co, int Ci, int Npad, int Cop, hipStream_t s);
+// ConvTranspose2d [Ci][Co][2][2] -> [Npad][4 Co], row ci, column q * Co + co = w[ci][co][q]
+int launch_pack_dgrad_convt(const float* w, float* out, int Ci, int Co, int Npad, hipStream_t s);
+
+}  // namespace ldmseg

@@ -66,6 +66,8 @@ SIGNATURES = {
     "ldmseg_vae_create": (_i, [C.POINTER(VAECfg), _i, C.POINTER(C.c_char_p), C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_vp)]),
     "ldmseg_vae_destroy": (None, [_vp]),
     "ldmseg_vae_decode": (_i, [_vp, _vp, _f, _i, _i, _i, _vp, _vp]),
+    "ldmseg_vae_decode_backward": (_i, [_vp, _vp, _f, _i, _i, _vp, _vp, _i, C.POINTER(C.c_char_p), C.POINTER(_vp), C.POINTER(_i64), _vp]),
+    "ldmseg_vae_load_decoder": (_i, [_vp, _i, C.POINTER(C.c_char_p), C.POINTER(_vp), C.POINTER(_i64), _vp]),
     "ldmseg_vae_decode_argmax": (_i, [_vp, _vp, _f, _i, _i, _f, _i64, _vp, _vp, _vp]),
     "ldmseg_vae_encode": (_i, [_vp, _vp, _f, _f, _i, _i, _vp, _vp]),
     "ldmseg_vae_posterior": (_i, [_vp, _vp, _f, _i, _i, _vp, _vp]),
@@ -175,6 +177,13 @@ SIGNATURES = {
     "ldmseg_op_fastdiv": (_i, [_vp, _i, _i, _vp, _vp]),
     "ldmseg_op_nearest_index": (_i, [_i, _i, C.POINTER(_i)]),
     "ldmseg_op_point_taps": (_i, [_i, C.POINTER(_f), _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(_f)]),
+    "ldmseg_op_conv_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ldmseg_op_convt2_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ldmseg_op_conv_dgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ldmseg_op_convt2_dgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ldmseg_op_groupnorm_silu_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "ldmseg_op_layernorm_silu_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ldmseg_op_wgrad_plan": (_i, [_i, _i, _i, _i, _i, _i, C.c_char_p, _i]),
     "ldmseg_igemm_log": (_i, [_i]),
     "ldmseg_igemm_log_read": (_i, [C.c_char_p, _i]),
 }

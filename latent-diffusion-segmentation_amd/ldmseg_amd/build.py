@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.normpath(os.path.join(HERE, "..", "csrc"))
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "..", "include"))
 LIB_PATH = os.path.join(HERE, "libldmseg_hip.so")
-SOURCES = ["igemm.hip", "tfuse.hip", "tproj.hip", "tail.hip", "norm.hip", "attention.hip", "attention3.hip", "attention4.hip", "attention_fp8.hip", "attention_mx.hip", "attention_cross.hip", "clip_vision.hip", "clip_text.hip", "guided.hip", "misc.hip", "skipadd.hip", "postproc.hip", "pq_meter.hip", "sched.hip", "loss.hip", "point_loss.hip", "point_loss_bwd.hip", "runtime.hip", "unet_build.hip", "unet.hip", "vae.hip", "clip.hip", "debug_knobs.hip", "ops_api.hip"]
+SOURCES = ["igemm.hip", "tfuse.hip", "tproj.hip", "tail.hip", "norm.hip", "attention.hip", "attention3.hip", "attention4.hip", "attention_fp8.hip", "attention_mx.hip", "attention_cross.hip", "clip_vision.hip", "clip_text.hip", "guided.hip", "misc.hip", "skipadd.hip", "postproc.hip", "pq_meter.hip", "sched.hip", "loss.hip", "point_loss.hip", "point_loss_bwd.hip", "vae_bwd.hip", "runtime.hip", "unet_build.hip", "unet.hip", "vae.hip", "clip.hip", "debug_knobs.hip", "ops_api.hip"]
 EXTRA_FLAGS = {
     "sched.hip": ["-ffp-contract=off"],                       # bit-exact scheduler arithmetic
     "tail.hip": ["-ffp-contract=off"],                        # the fused step tail carries the same arithmetic

@@ -7,6 +7,7 @@ default (gaussian, num_mid_blocks=0) configuration of base.yaml:14-33:
     z = vae_semseg.encode(x).latent_dist.mode() / .sample() # trainers_ldm_cond.py:371-375
 """
 import ctypes as C
+from collections import OrderedDict
 from typing import Optional, Tuple, Union
 
 import torch
@@ -105,6 +106,44 @@ class _GaussianKLFunction(torch.autograd.Function):
         return grad
 
 
+class _DecodeFunction(torch.autograd.Function):
+    """decode(z, interpolate=False, z_scale) with a backward to the latents and the decoder parameters: forward is the no-grad
+    path's own ldmseg_vae_decode call, backward one ldmseg_vae_decode_backward call (stateless: the library runs the decoder
+    forward again inside it) that returns grad_z and the parameter gradients autograd asks for."""
+
+    @staticmethod
+    def forward(ctx, vae, z_scale, z, *params):
+        out = vae._decode_call(z, 0, z_scale)
+        ctx.vae, ctx.z_scale = vae, z_scale
+        ctx.save_for_backward(z)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        vae = ctx.vae
+        z, = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        keys = list(vae._dec_params) if len(need) > 3 else []
+        if grad is None:
+            return (None,) * len(need)
+        vae._check_decoder_fresh()
+        g = grad.to(device=z.device, dtype=torch.float32).contiguous()
+        B, _, L, _ = z.shape
+        grad_z = torch.empty_like(z) if need[2] else None
+        grads = {k: torch.empty_like(vae._dec_params[k]) for i, k in enumerate(keys) if need[3 + i]}
+        n = len(grads)
+        names = (C.c_char_p * max(n, 1))(*[k.encode() for k in grads])
+        ptrs = (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in grads.values()])
+        numels = (C.c_int64 * max(n, 1))(*[t.numel() for t in grads.values()])
+        with torch.cuda.device(z.device):
+            _lib.check(_lib.lib().ldmseg_vae_decode_backward(vae._h, _lib.ptr(z), float(ctx.z_scale), B, L, _lib.ptr(g), _lib.ptr(grad_z),
+                                                             n, names, ptrs, numels, _lib.stream_ptr(z.device)),
+                       "ldmseg_vae_decode_backward")
+        return (None, None, grad_z) + tuple(grads.get(k) for k in keys)
+
+
 class GeneralVAESeg(object):
     def __init__(self, state_dict, in_channels: int = 7, int_channels: int = 256, out_channels: int = 128,
                  block_out_channels: Tuple[int] = (32, 64, 128, 256), latent_channels: int = 4,
@@ -149,6 +188,12 @@ class GeneralVAESeg(object):
         self._h = handle
         self._in_channels = in_channels
         self._upscale = 2 ** num_upscalers
+        self._bf16 = cd == _lib.BF16
+        # the decoder tensors the object was built from, kept on the device (decoder_parameters() makes leaves of them)
+        self._dec_sd = OrderedDict((k, state_dict[k].detach().to(device=self.device, dtype=torch.float32).clone().contiguous())
+                                   for k in schema if k.startswith("decoder."))
+        self._dec_params = None
+        self._dec_versions = None
 
     @property
     def num_parameters(self) -> int:
@@ -184,8 +229,64 @@ class GeneralVAESeg(object):
     def encode(self, semseg: torch.Tensor) -> EncoderOutput:
         return EncoderOutput(latent_dist=DiagonalGaussianDistribution(self.encode_moments(semseg)))
 
+    def decoder_parameters(self):
+        """Ordered dict: reference key (decoder.0.weight ...) -> fp32 leaf tensor on the device with requires_grad=True, holding
+        the decoder tensors of the state dict the object was built from.  Once this has been called, `decode` / `forward` under
+        grad mode carry the decoder's graph to these tensors; after changing them in place (an optimiser step) call
+        `refresh_decoder()` so that the handle computes with the new values."""
+        if self._dec_params is None:
+            self._dec_params = OrderedDict((k, v.requires_grad_(True)) for k, v in self._dec_sd.items())
+            self._dec_versions = {k: v._version for k, v in self._dec_params.items()}
+        return self._dec_params
+
+    def refresh_decoder(self):
+        """Repacks the current values of `decoder_parameters()` into the handle (ldmseg_vae_load_decoder: nothing is allocated):
+        afterwards every entry of the object computes with them, bitwise as an object built from the updated state dict."""
+        params = self.decoder_parameters()
+        n = len(params)
+        ts = [p.detach() for p in params.values()]
+        names = (C.c_char_p * n)(*[k.encode() for k in params])
+        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+        numels = (C.c_int64 * n)(*[t.numel() for t in ts])
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ldmseg_vae_load_decoder(self._h, n, names, ptrs, numels, _lib.stream_ptr(self.device)),
+                       "ldmseg_vae_load_decoder")
+        self._dec_versions = {k: v._version for k, v in params.items()}
+
+    def _check_decoder_fresh(self):
+        if self._dec_params is None:
+            return
+        stale = [k for k, v in self._dec_params.items() if v._version != self._dec_versions[k]]
+        if stale:
+            raise RuntimeError(f"decoder parameter {stale[0]} was modified in place since the last refresh_decoder(): the handle "
+                               "would compute with stale weights; call refresh_decoder() after the optimiser step")
+
+    def _decode_call(self, z, interp, z_scale):
+        B, _, L, _ = z.shape
+        up = self._upscale * L * (2 if interp else 1)
+        out = torch.empty((B, self.out_channels, up, up), device=z.device, dtype=torch.float32)
+        with torch.cuda.device(z.device):
+            _lib.check(_lib.lib().ldmseg_vae_decode(self._h, _lib.ptr(z), float(z_scale), B, L, interp, _lib.ptr(out),
+                                                    _lib.stream_ptr(z.device)), "ldmseg_vae_decode")
+        return out
+
     def decode(self, z: torch.Tensor, interpolate: bool = True, z_scale: float = 1.0) -> torch.Tensor:
+        """vae.py:267-271.  With grad mode on and `z` or a tensor of `decoder_parameters()` requiring grad, the result carries a
+        graph (once differentiable): the values are bitwise those of the no-grad path, the backward is one
+        ldmseg_vae_decode_backward call.  The graph covers decode(interpolate=False); with interpolate=True torch's own
+        F.interpolate (bilinear, align_corners=False) is applied on top, so torch differentiates the resize.  bf16 objects raise
+        NotImplementedError when a graph is requested (the backward needs fp32 storage: "fp32" or "bf16x3")."""
         z = _lib.require_cuda_f32(z, "z")
+        if torch.is_grad_enabled():
+            params = [] if self._dec_params is None else list(self._dec_params.values())
+            if z.requires_grad or any(p.requires_grad for p in params):
+                if self._bf16:
+                    raise NotImplementedError("the decoder backward needs an fp32-storage object (compute_dtype 'fp32' or 'bf16x3')")
+                self._check_decoder_fresh()
+                out = _DecodeFunction.apply(self, float(z_scale), z, *params)
+                if interpolate and self.interpolation_factor == 2:
+                    out = torch.nn.functional.interpolate(out, scale_factor=2, mode="bilinear", align_corners=False)
+                return out
         B, _, L, _ = z.shape
         up = self._upscale * L * (self.interpolation_factor if interpolate else 1)
         interp = 1 if (interpolate and self.interpolation_factor == 2) else 0
@@ -342,6 +443,8 @@ class GeneralVAESeg(object):
 
     def forward(self, sample, sample_posterior: bool = True, return_dict: bool = True,
                 generator: Optional[torch.Generator] = None, rgb_sample=None, valid_mask=None):
+        """vae.py:273-307.  Under grad mode `.sample` carries the decoder's graph (see `decode`); the encoder half and the moments
+        stay without one."""
         if rgb_sample is not None:
             raise NotImplementedError("fuse_rgb is off in base.yaml:30")
         posterior = self.encode(sample).latent_dist

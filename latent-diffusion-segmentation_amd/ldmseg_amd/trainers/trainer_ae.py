@@ -70,7 +70,10 @@ class TrainerAE(object):
         """:204-216 on the VAEOutput of `vae_model(...)` (`.sample` logits [B,C,4L,4L], `.posterior`) and targets [B,h,w]:
         (total, ce, kl, mask) as 0-d device tensors; total is the three terms weighted by `loss_weights`, added in the order
         ce, mask, kl.  With grad mode on, the values are differentiable with respect to the logits and the posterior's moments
-        where those require grad (`total.backward()`); the library's own seg-VAE produces neither with a graph."""
+        where those require grad (`total.backward()`).  The library's own seg-VAE gives `.sample` the decoder's graph once
+        `vae_model.decoder_parameters()` has been called (fp32 / bf16x3 objects): `total.backward()` then fills the `.grad` of every
+        decoder parameter through ldmseg_point_loss_backward and ldmseg_vae_decode_backward.  The encoder half and the moments
+        still come without a graph."""
         parts = self.segmentation_losses.point_loss(outputs.sample, targets, do_matching, masks, generator=generator)
         ce, mask = parts['ce'], parts['mask']
         kl = outputs.posterior.kl(return_mean=True)[1]
