@@ -239,6 +239,25 @@ int ldmseg_vae_encode(ldmseg_vae* h, const float* x, float in_mul, float in_add,
  * out[B,4,l,l] = (mean + exp(0.5*clamp(logvar,-30,20))*noise) * out_scale; noise NULL -> mode(). */
 int ldmseg_vae_posterior(const float* moments, const float* noise, float out_scale, int B, int l, float* out,
                          void* stream);
+/* Backward of ldmseg_vae_posterior to the moments: grad_moments [B,8,l,l] = (d mean | d logvar) from grad_z [B,4,l,l] (the gradient
+ * of `out`, so `scale` = the out_scale of the forward): d mean = scale * grad_z, d logvar = scale * grad_z * noise * 0.5 * std where
+ * -30 <= logvar <= 20 (bounds included, as torch.clamp passes gradient) and 0 elsewhere; noise NULL (mode()): the logvar half is
+ * exact zeros.  Every element of grad_moments is written. */
+int ldmseg_vae_posterior_backward(const float* moments, const float* noise, float scale, int B, int l, const float* grad_z,
+                                  float* grad_moments, void* stream);
+/* Backward of ldmseg_vae_encode: from grad_moments [B,8,H/8,H/8] (fp32 NCHW) to the gradient of every encoder
+ * parameter asked for.  Stateless, like ldmseg_vae_decode_backward: the encoder forward runs again inside the call's own workspace
+ * plan, keeping what the backward reads (the four conv + SiLU layers keep their pre-activation).  Everything on `stream`, no
+ * allocation after the plan, no host synchronisation, bitwise repeatable (no float atomics).  names / grad_ptrs / numels as in
+ * ldmseg_vae_decode_backward with the encoder's reference keys (encoder.0.weight [32,7,3,3] ... encoder.15.bias): real channels
+ * only, every element written; an absent key or a NULL pointer skips that gradient and leaves the others bitwise unchanged; an
+ * unknown key, a wrong numel or a bf16 handle is LDMSEG_E_ARG and nothing is launched.  The input is data: it gets no gradient. */
+int ldmseg_vae_encode_backward(ldmseg_vae* h, const float* x, float in_mul, float in_add, int B, int H, const float* grad_moments,
+                               int n, const char* const* names, float* const* grad_ptrs, const int64_t* numels, void* stream);
+/* ldmseg_vae_load_decoder for the encoder's tensors (encoder.0.weight ...): forward packing, the data-gradient packings of an
+ * fp32-storage handle, the hi | lo planes of a bf16x3 handle, norm and bias vectors.  Nothing is allocated. */
+int ldmseg_vae_load_encoder(ldmseg_vae* h, int n, const char* const* names, const void* const* dev_ptrs, const int64_t* numels,
+                            void* stream);
 /* ---- stage-1 (seg-VAE reconstruction) evaluation: TrainerAE.compute_metrics(['miou', 'pq']), trainers_ae.py:546-803 ---- */
 /* SemsegMeter.update(pred, gt) (ldmseg/evaluations/semseg_evaluation.py:24-33) on n int64 (pred, gt) pairs on the device.
  * counts int64 [3][num_classes] = (tp | fp | fn) is ADDED to, never reset: per pixel with gt != ignore_index,

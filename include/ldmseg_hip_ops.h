@@ -264,6 +264,23 @@ int ldmseg_op_layernorm_silu_bwd(const float* x, const float* dy, const float* g
                                  int H2, int W2, float* dx, float* dgamma, float* dbeta, void* stream);
 int ldmseg_op_wgrad_plan(int P, int N, int C, int taps, int x3, int cus, char* buf, int n);
 
+/* What the seg-VAE encoder's backward adds; tensors and dtype as above.
+ * _conv_wgrad_ex: _conv_wgrad of F.conv2d(x, w, b, stride=stride, padding=1), stride 1 | 2, on the tile the storage widths choose
+ *                (32 | 64 | 128 rows of dY by 32 | 64 | 128 channels of X): x [B,Ci,H,W], dy [B,Co,Ho,Wo] with Ho = (H - 1) / stride + 1.
+ * _conv_s2_wgrad: _conv_wgrad_ex with stride 2.
+ * _conv_s2_dgrad: dy [B,Co,Ho,Wo], w [Co,Ci,3,3] -> dx [B,Ci,H,W] of F.conv2d(x, w, stride=2, padding=1): one igemm launch over dY
+ *                whose 4 Ci columns are the four output phases of dX, scattered by the transposed conv's epilogue.  Ci a multiple of 4.
+ * _silu_bwd:     du[i] = da[i] * silu'(u[i]) on n floats.  _silu_fwd: a[i] = silu(u[i]), the launch behind a SiLU-less conv there.
+ * _wgrad_plan_ex: _wgrad_plan of the by-width rule, P = the pixels of the OUTPUT map, stride 1 | 2; macs_per_pixel (or NULL)
+ *                receives tiles x tile area, the MACs the launch executes per pixel. */
+int ldmseg_op_conv_wgrad_ex(const float* x, const float* dy, int B, int Ci, int H, int W, int Co, int stride, int dtype, float* dw, float* db,
+                            void* stream);
+int ldmseg_op_conv_s2_wgrad(const float* x, const float* dy, int B, int Ci, int H, int W, int Co, int dtype, float* dw, float* db, void* stream);
+int ldmseg_op_conv_s2_dgrad(const float* dy, const float* w, int B, int Ci, int H, int W, int Co, int dtype, float* dx, void* stream);
+int ldmseg_op_silu_bwd(const float* u, const float* da, int64_t n, float* du, void* stream);
+int ldmseg_op_silu_fwd(const float* u, int64_t n, float* a, void* stream);
+int ldmseg_op_wgrad_plan_ex(int P, int N, int C, int taps, int x3, int stride, int cus, char* buf, int n, int64_t* macs_per_pixel);
+
 /* q[i] = n[i] / d (0 <= n[i] < 2^31, d >= 1) computed the way the kernels divide: host-prepared multiply-shift pair */
 int ldmseg_op_fastdiv(const int* n, int count, int d, int* q, void* stream);
 

@@ -1270,6 +1270,81 @@ int ldmseg_op_wgrad_plan(int P, int N, int C, int taps, int x3, int cus, char* b
   return r;
 }
 
+// ------------------------------------------------------------------ what the encoder's backward adds
+// grads of F.conv2d(x, w, b, stride=stride, padding=1) with respect to w and b on the by-width tile: x [B,Ci,H,W], dy [B,Co,Ho,Wo]
+int ldmseg_op_conv_wgrad_ex(const float* x, const float* dy, int B, int Ci, int H, int W, int Co, int stride, int dtype, float* dw, float* db,
+                            void* stream) {
+  if (!x || !dy || !dw || B < 1 || Ci < 1 || Co < 1 || H < 1 || W < 1 || (stride != 1 && stride != 2) || (dtype != 0 && dtype != 2 && dtype != 3))
+    return -2;
+  Stage st(stream, dtype, true);
+  const int Ho = stride == 2 ? (H - 1) / 2 + 1 : H, Wo = stride == 2 ? (W - 1) / 2 + 1 : W;
+  const int Cip = (int)rup(Ci, 32), Cop = (int)rup(Co, 32), P = B * Ho * Wo;
+  WgradParams wp;
+  wp.x = (const float*)st.nchw(x, B, Ci, H * W, Cip); wp.C = Cip;
+  wp.dy = (const float*)st.nchw(dy, B, Co, Ho * Wo, Cop); wp.ldy = Cop; wp.N = Cop;
+  wp.B = B; wp.H = H; wp.W = W; wp.taps = 9; wp.x3 = st.x3 ? 1 : 0; wp.stride = stride; wp.by_width = 1;
+  const int r = op_wgrad_run(st, wp, 0, Co, Ci, 0, dw);
+  if (r || !db) return r;
+  float* scratch = (float*)st.buf(colsum_scratch_bytes(P, Cop));
+  if (st.status) return st.status;
+  return launch_colsum(wp.dy, Cop, P, Cop, 1, 0, Co, scratch, db, st.s);
+}
+int ldmseg_op_conv_s2_wgrad(const float* x, const float* dy, int B, int Ci, int H, int W, int Co, int dtype, float* dw, float* db, void* stream) {
+  return ldmseg_op_conv_wgrad_ex(x, dy, B, Ci, H, W, Co, 2, dtype, dw, db, stream);
+}
+// NHWC [B][H2][W2][C] -> the top-left H x W of every map as NCHW [B][C][H][W] (an odd map's data gradient: the scatter fills 2 Ho x 2 Wo)
+static __global__ void crop_nhwc_kernel(const float* x, float* y, int C, int H, int W, int H2, int W2, size_t total) {
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    const int xx = (int)(e % W), yy = (int)((e / W) % H), c = (int)((e / ((size_t)W * H)) % C);
+    const size_t b = e / ((size_t)W * H * C);
+    y[e] = x[((b * H2 + yy) * W2 + xx) * C + c];
+  }
+}
+// grad of F.conv2d(x, w, stride=2, padding=1) with respect to x, the way ldmseg_vae_encode_backward runs it: one igemm launch over
+// dY [B,Co,Ho,Wo] (3x3 window, pad 1) on the phase packing, N = 4 Ci, scattered to the 2 Ho x 2 Wo map by EPI_CONVT2
+int ldmseg_op_conv_s2_dgrad(const float* dy, const float* w, int B, int Ci, int H, int W, int Co, int dtype, float* dx, void* stream) {
+  if (!dy || !w || !dx || B < 1 || Ci < 4 || Ci % 4 || Co < 1 || H < 1 || W < 1 || (dtype != 0 && dtype != 2 && dtype != 3)) return -2;
+  Stage st(stream, dtype, true);
+  hipStream_t s = st.s;
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  const int Cop = (int)rup(Co, 32), Np = (int)rup(4 * Ci, igemm_pick_bn(4 * Ci, EPI_CONVT2)), P = B * Ho * Wo;
+  float* wp = (float*)st.buf((size_t)Np * 9 * Cop * sizeof(float));
+  st.step([&] { return launch_pack_dgrad_conv_s2(w, wp, Co, Ci, Np, Cop, s) || (st.x3 == 2 && launch_split_planes(wp, (size_t)Np * 9 * Cop, s)); });
+  IgemmParams p;
+  p.src0 = st.nchw(dy, B, Co, Ho * Wo, Cop); p.C0 = Cop; p.B = B; p.Hi = p.Ho = Ho; p.Wi = p.Wo = Wo;
+  p.taps = 9; p.M = P; p.N = Np; p.n_valid = 4 * Ci; p.W = wp; p.epi = EPI_CONVT2; p.cout = Ci; p.x3 = st.x3;
+  float* op = (float*)st.buf((size_t)4 * P * Ci * sizeof(float));
+  p.out = op; p.ldo = Ci;
+  p.cf_ctr = op_cf_region();
+  if (st.status) return st.status;
+  const int r = launch_igemm(p, DT_F32, s);
+  if (r) return r;
+  if (H == 2 * Ho && W == 2 * Wo) return st.nchw_out(op, dx, B, Ci, H * W, Ci);
+  const size_t total = (size_t)B * Ci * H * W;
+  hipLaunchKernelGGL(crop_nhwc_kernel, dim3(rows_grid(total)), dim3(256), 0, s, op, dx, Ci, H, W, 2 * Ho, 2 * Wo, total);
+  return launch_status();
+}
+int ldmseg_op_silu_bwd(const float* u, const float* da, int64_t n, float* du, void* stream) {
+  if (!u || !da || !du || n < 1) return -2;
+  return launch_silu_bwd(u, da, du, (size_t)n, (hipStream_t)stream);
+}
+// a = silu(u): the launch that follows a SiLU-less conv inside the encoder's backward
+int ldmseg_op_silu_fwd(const float* u, int64_t n, float* a, void* stream) {
+  if (!u || !a || n < 1) return -2;
+  return launch_silu_fwd(u, a, (size_t)n, (hipStream_t)stream);
+}
+// ldmseg_op_wgrad_plan of the by-width rule (wgrad_choose_ex): P = the pixels of the OUTPUT map of a conv of stride 1 | 2
+int ldmseg_op_wgrad_plan_ex(int P, int N, int C, int taps, int x3, int stride, int cus, char* buf, int n, int64_t* macs_per_pixel) {
+  if (!buf || n < 1) return -2;
+  WgradPlan pl;
+  const int r = wgrad_choose_ex(WgradDescEx{P, N, C, taps, x3, stride}, cus, &pl);
+  if (r == 0) {
+    std::snprintf(buf, (size_t)n, "%s", wgrad_plan_line(pl).c_str());
+    if (macs_per_pixel) *macs_per_pixel = wgrad_plan_macs_per_pixel(pl);
+  }
+  return r;
+}
+
 // The two fp32 kernels of the time embedding (misc.hip) on the caller's device tensors: nothing is staged or converted.
 // _time_sinusoid: out [B][320] = [cos(t f_i) | sin(t f_i)] of t_dev (int64, t_count = 1 broadcasts, t_count = B per row) or, NULL, t_host.
 int ldmseg_op_time_sinusoid(const int64_t* t_dev, int t_count, int64_t t_host, int B, float* out, void* stream) {

@@ -23,6 +23,8 @@ struct ldmseg_vae : HandleBase {
   NormW ln[4], dec_gn;
   // fp32-storage handles: the decoder's convs packed a second time for their data gradients (ldmseg_vae_decode_backward)
   ConvW dec_in_d, dec_out_d, convt_d[4];
+  // ... and the encoder's (ldmseg_vae_encode_backward): enc_d[k] for enc[k], k = 1 .. 8 (the first conv's input is data)
+  ConvW enc_d[10];
 };
 
 // =================================================================== image VAE encoder (AutoencoderKL, SD-1.x)
@@ -51,6 +53,29 @@ void dgrad_convt_shape(ConvW* d, int Ci, int Co) {
 }
 size_t convw_floats(const ConvW& d) { return (size_t)d.N * d.taps * d.cin_pad; }
 
+// dX of a STRIDE-2 conv3x3 = the four output phases as 4 Ci columns of one 3x3 GEMM over dY, scattered by EPI_CONVT2
+void dgrad_conv_s2_shape(ConvW* d, int Co, int Ci) {
+  d->N = (int)rup(4 * Ci, igemm_pick_bn(4 * Ci, EPI_CONVT2)); d->n_valid = 4 * Ci; d->cin_pad = (int)rup(Co, bke(DT_F32)); d->taps = 9; d->cout = Ci;
+}
+
+// the encoder's nine convs in model order (vae.py:174-244): state-dict index, channels, stride, whether SiLU follows in the epilogue
+struct EncLayer { int idx, Co, Ci, stride, silu; };
+constexpr int kEncLayers = 9, kEncNormIdx = 13;
+std::vector<EncLayer> encoder_layers(const ldmseg_vae_cfg& c) {
+  const int* boc = c.block_out_channels;
+  std::vector<EncLayer> l;
+  l.push_back({0, boc[0], c.in_channels, 1, 1});
+  int idx = 2;
+  for (int i = 0; i < 3; ++i) {
+    l.push_back({idx, boc[i], boc[i], 1, 0});
+    l.push_back({idx + 1, boc[i + 1], boc[i], 2, 1});
+    idx += 3;
+  }
+  l.push_back({idx, c.int_channels, boc[3], 1, 0});
+  l.push_back({idx + 4, c.latent_channels * c.num_latents, c.int_channels, 1, 0});
+  return l;
+}
+
 // reference keys of the decoder in model order with their element counts: (conv_in w, b), per upscaler (convT w, b, LayerNorm w, b),
 // (GroupNorm w, b), (conv_out w, b)
 struct DecKey { std::string name; int64_t numel; };
@@ -71,6 +96,77 @@ std::vector<DecKey> decoder_keys(const ldmseg_vae_cfg& c) {
   add(idx, cin, cin);
   add(idx + 2, (int64_t)c.out_channels * cin * 9, c.out_channels);
   return k;
+}
+
+// ... and of the encoder: (conv w, b) of layers 0 .. 7 at slots 2 k, 2 k + 1, (GroupNorm w, b) at 16, 17, (head w, b) at 18, 19
+std::vector<DecKey> encoder_keys(const ldmseg_vae_cfg& c) {
+  std::vector<DecKey> k;
+  const std::vector<EncLayer> l = encoder_layers(c);
+  auto add = [&](int idx, int64_t wn, int64_t bn) {
+    k.push_back({"encoder." + std::to_string(idx) + ".weight", wn});
+    k.push_back({"encoder." + std::to_string(idx) + ".bias", bn});
+  };
+  for (int i = 0; i < kEncLayers - 1; ++i) add(l[i].idx, (int64_t)l[i].Co * l[i].Ci * 9, l[i].Co);
+  add(l[kEncLayers - 1].idx - 2, c.int_channels, c.int_channels);
+  add(l[kEncLayers - 1].idx, (int64_t)l[kEncLayers - 1].Co * l[kEncLayers - 1].Ci * 9, l[kEncLayers - 1].Co);
+  return k;
+}
+constexpr size_t kEncNormSlot = 16, kEncHeadSlot = 18;
+inline size_t enc_slot(int k) { return k == kEncLayers - 1 ? kEncHeadSlot : (size_t)2 * k; }
+
+// name -> slot of `keys`, with the checks the backward and the load entries share; -1 and the message set on a bad name or numel
+int key_slot(const std::vector<DecKey>& keys, const char* name, int64_t numel, const char* what) {
+  size_t k = 0;
+  while (name && k < keys.size() && keys[k].name != name) ++k;
+  if (!name) fail(LDMSEG_E_ARG, "null tensor name");
+  else if (k == keys.size()) fail(LDMSEG_E_ARG, std::string("not ") + what + " parameter: " + name);
+  else if (numel != keys[k].numel) fail(LDMSEG_E_ARG, keys[k].name + " has " + std::to_string(keys[k].numel) + " elements, got " + std::to_string(numel));
+  else return (int)k;
+  return -1;
+}
+
+// (Re)packs the encoder tensors `wm` holds into the buffers the handle owns, as vae_pack_decoder does for the decoder's
+int vae_pack_encoder(ldmseg_vae* v, const WeightMap& wm, hipStream_t s, bool forward_too) {
+  const ldmseg_vae_cfg& c = v->cfg;
+  const int dt = v->dt;
+  const bool f32 = dt == DT_F32;
+  const std::vector<DecKey> keys = encoder_keys(c);
+  const std::vector<EncLayer> l = encoder_layers(c);
+  auto has = [&](size_t slot, const float** p) {
+    auto it = wm.m.find(keys[slot].name);
+    if (it == wm.m.end()) return false;
+    *p = it->second.first;
+    return true;
+  };
+  auto planes = [&](void* w, size_t nfloats) { return (v->x3 && f32) ? launch_split_planes(w, nfloats, s) : 0; };
+  for (int k = 0; k < kEncLayers; ++k) {
+    const size_t slot = enc_slot(k);
+    ConvW& fw = v->enc[k];
+    ConvW& dg = v->enc_d[k];
+    const float* p;
+    if (has(slot, &p)) {
+      if (forward_too) {
+        TRY(launch_repack_conv(p, fw.w, l[k].Co, l[k].Ci, 3, 3, fw.N, fw.cin_pad, dt, s));
+        TRY(planes(fw.w, convw_floats(fw)));
+      }
+      if (f32 && dg.w) {
+        if (l[k].stride == 2) TRY(launch_pack_dgrad_conv_s2(p, (float*)dg.w, l[k].Co, l[k].Ci, dg.N, dg.cin_pad, s));
+        else TRY(launch_pack_dgrad_conv(p, (float*)dg.w, l[k].Co, l[k].Ci, dg.N, dg.cin_pad, s));
+        TRY(planes(dg.w, convw_floats(dg)));
+      }
+    }
+    if (forward_too && has(slot + 1, &p)) TRY(launch_padded_bias(p, l[k].Co, fw.bias, fw.N, s));
+  }
+  const float* p;
+  if (forward_too && has(kEncNormSlot, &p)) HIP_TRY(hipMemcpyAsync(v->enc_gn.g, p, c.int_channels * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (forward_too && has(kEncNormSlot + 1, &p)) HIP_TRY(hipMemcpyAsync(v->enc_gn.b, p, c.int_channels * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+// the encoder's backward needs every activation width to be its channel count (no padded channels between the layers)
+bool encoder_backward_ok(const ldmseg_vae_cfg& c) {
+  for (int i = 0; i < 4; ++i)
+    if (c.block_out_channels[i] % 32) return false;
+  return c.int_channels % 32 == 0 && c.latent_channels * c.num_latents <= 32;
 }
 
 // (Re)packs the decoder tensors `wm` holds into the buffers the handle owns - forward packing, data-gradient packing, the hi | lo
@@ -200,6 +296,15 @@ int vae_build(ldmseg_vae* v, const WeightMap& wm) {
       ci = c.upscale_channels;
     }
     TRY(vae_pack_decoder(v, wm, s, false));
+    if (encoder_backward_ok(c)) {
+      const std::vector<EncLayer> l = encoder_layers(c);
+      for (int i = 1; i < kEncLayers; ++i) {
+        if (l[i].stride == 2) dgrad_conv_s2_shape(&v->enc_d[i], l[i].Co, l[i].Ci);
+        else dgrad_conv_shape(&v->enc_d[i], l[i].Co, l[i].Ci, EPI_STORE);
+        TRY(v->arena.alloc(&v->enc_d[i].w, convw_floats(v->enc_d[i]) * sizeof(float)));
+      }
+      TRY(vae_pack_encoder(v, wm, s, false));
+    }
   }
   return b.finish(*v);
 }
@@ -308,7 +413,8 @@ int vae_decode(ldmseg_vae* v, const float* z, float z_scale, int B, int L, const
 struct WgradJob {
   const float* dy; int ldy, N;        // dY [P][ldy], N columns taken
   const float* x; int C;              // X [P][C]
-  int H, W, taps, form, n_real, c_real, co;
+  int H, W, taps, form, n_real, c_real, co;      // H x W: the map X lives on
+  int stride = 1, by_width = 0;                  // the encoder's launches (WgradParams)
 };
 int run_wgrad(Exec& ex, const WgradJob& j, float* out) {
   if (!out) return 0;
@@ -316,16 +422,17 @@ int run_wgrad(Exec& ex, const WgradJob& j, float* out) {
   const size_t m = ws->mark();
   WgradParams wp;
   wp.dy = j.dy; wp.ldy = j.ldy; wp.x = j.x; wp.B = ex.B; wp.H = j.H; wp.W = j.W; wp.N = j.N; wp.C = j.C; wp.taps = j.taps;
-  wp.x3 = ex.x3 ? 1 : 0;
+  wp.x3 = ex.x3 ? 1 : 0; wp.stride = j.stride; wp.by_width = j.by_width;
   WgradPlan pl;
   if (wgrad_plan(wp, num_cus(), &pl)) return fail(LDMSEG_E_SHAPE, "weight gradient: unsupported shape");
   wp.partial = (float*)ws->scratch(wgrad_partial_bytes(wp, pl));
-  const double P = (double)ex.B * j.H * j.W;
+  const double P = j.stride == 2 ? (double)ex.B * ((j.H - 1) / 2 + 1) * ((j.W - 1) / 2 + 1) : (double)ex.B * j.H * j.W;
   const int r = ex.launch("launch_wgrad failed", 0, 2.0 * P * j.n_real * j.c_real * j.taps, P * (j.N + j.C) * 4.0 * pl.tiles / pl.n_tiles,
                           [&] {      // (no commas: the profile dump is a CSV)
                             return std::string(pl.x3 ? "wgrad x3" : "wgrad f32") + " P=" + std::to_string((long long)P) + " N=" + std::to_string(j.N) +
                                    " C=" + std::to_string(j.C) + " taps=" + std::to_string(j.taps) + " slices=" + std::to_string(pl.slices) +
-                                   " grid=" + std::to_string(pl.grid_x);
+                                   " grid=" + std::to_string(pl.grid_x) +
+                                   (j.by_width ? " tile=" + std::to_string(pl.tile_n) + "x" + std::to_string(pl.tile_c) + " stride=" + std::to_string(j.stride) : std::string());
                           }, [&] {
     const int e = launch_wgrad(wp, pl, ex.s);
     return e ? e : launch_wgrad_finish(wp, pl, j.form, j.n_real, j.c_real, j.co, out, ex.s);
@@ -432,6 +539,92 @@ int vae_decode_backward_body(Exec& ex, ldmseg_vae* v, const float* z, float z_sc
     TRY(ex.igemm(p));
     if (z_scale != 1.0f)     // decode(z, z_scale) feeds z * z_scale
       TRY(ex.launch("launch_axpby failed", 4, 0, 0, no_label, [&] { return launch_axpby(grad_z, z_scale, 0.f, grad_z, (size_t)P0 * c.latent_channels, s); }));
+  }
+  return 0;
+}
+
+// ---- the encoder's backward.  One planned pass: the encoder forward again up to the GroupNorm output (the moments
+// themselves are not needed), the four conv + SiLU layers as a SiLU-less conv that keeps the pre-activation u plus one silu_fwd
+// launch, then the chain from d loss / d moments down to every parameter gradient asked for (g[slot], slots as encoder_keys; null =
+// skipped).  The chain stops below the lowest layer a gradient is asked of; the input is data.
+int vae_encode_backward_body(Exec& ex, ldmseg_vae* v, const float* x, float mul, float add, int H, const float* grad_moments, float* const* g) {
+  const int B = ex.B;
+  hipStream_t s = ex.s;
+  const int dt = v->dt;
+  const ldmseg_vae_cfg& c = v->cfg;
+  const std::vector<EncLayer> l = encoder_layers(c);
+  const int last = kEncLayers - 1;
+  // the lowest layer whose parameters are asked for (the GroupNorm sits between layers 7 and 8)
+  int lowest = kEncLayers;
+  for (int k = last; k >= 0; --k)
+    if (g[enc_slot(k)] || g[enc_slot(k) + 1]) lowest = k;
+  if ((g[kEncNormSlot] || g[kEncNormSlot + 1]) && lowest > last) lowest = last;
+  if (lowest == kEncLayers) return 0;
+  // ---- forward again, everything the backward reads is kept: in[k] = the input of layer k, u[k] = the pre-activation of a SiLU layer
+  Act in[kEncLayers], u[kEncLayers];
+  in[0] = ex.new_act(bke(dt), H, H, true);
+  TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, no_label, [&] { return launch_pack_nchw(x, in[0].p, B, c.in_channels, H * H, bke(dt), mul, add, dt, s); }));
+  Act h7;
+  for (int k = 0; k < last; ++k) {
+    Act o;
+    TRY(ex.conv(v->enc[k], in[k], &o, {.stride = l[k].stride}));
+    if (l[k].silu) {
+      u[k] = o;
+      Act a = ex.new_act(o.C, o.H, o.W, true);
+      const size_t n = (size_t)B * o.H * o.W * o.C;
+      TRY(ex.launch("launch_silu_fwd failed", 4, 0, 8.0 * n, no_label, [&] { return launch_silu_fwd((const float*)o.p, (float*)a.p, n, s); }));
+      o = a;
+    }
+    if (k + 1 < last) in[k + 1] = o; else h7 = o;
+  }
+  TRY(ex.groupnorm(v->enc_gn, h7, nullptr, 1e-6f, 1, &in[last]));
+  // ---- backward: the running gradient alternates between two buffers of the largest activation's size
+  Workspace* ws = ex.ws;
+  const int l8 = h7.H, P8 = B * l8 * l8, Cm = (int)rup(l[last].Co, bke(dt)), Ci8 = c.int_channels;
+  size_t gmax = (size_t)P8 * Ci8;
+  for (int k = 1; k < last; ++k) gmax = std::max(gmax, (size_t)B * in[k].H * in[k].W * in[k].C);
+  float* gb[2] = {(float*)ws->scratch(gmax * sizeof(float)), (float*)ws->scratch(gmax * sizeof(float))};
+  float* dm = (float*)ws->scratch((size_t)P8 * Cm * sizeof(float));
+  TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, [] { return std::string("pack grad_moments"); }, [&] { return launch_pack_nchw(grad_moments, dm, B, l[last].Co, l8 * l8, Cm, 1.f, 0.f, dt, s); }));
+  TRY(run_wgrad(ex, {dm, Cm, Cm, (const float*)in[last].p, Ci8, l8, l8, 9, 0, l[last].Co, Ci8, 0, 1, 1}, g[kEncHeadSlot]));
+  TRY(run_colsum(ex, dm, Cm, P8, 1, 0, l[last].Co, g[kEncHeadSlot + 1]));
+  if (lowest == last && !g[kEncNormSlot] && !g[kEncNormSlot + 1]) return 0;
+  {
+    IgemmParams p;
+    p.src0 = dm; p.C0 = Cm; p.B = B; p.Hi = p.Ho = l8; p.Wi = p.Wo = l8;
+    p.taps = 9; p.M = P8; p.N = v->enc_d[last].N; p.n_valid = Ci8; p.W = v->enc_d[last].w;
+    p.out = gb[0]; p.ldo = Ci8; p.epi = EPI_STORE;
+    TRY(ex.igemm(p));
+  }
+  {
+    const size_t m = ws->mark();
+    float* scratch = (float*)ws->scratch(gn_bwd_scratch_bytes(B, Ci8));
+    TRY(ex.launch("launch_gn_silu_bwd failed", 2, 0, 4.0 * P8 * Ci8 * 4.0, [&] { return "gn_silu_bwd HW=" + std::to_string(l8 * l8) + " C=" + std::to_string(Ci8); }, [&] {
+      return launch_gn_silu_bwd((const float*)h7.p, gb[0], v->enc_gn.g, v->enc_gn.b, gb[1], g[kEncNormSlot], g[kEncNormSlot + 1], B, l8 * l8, Ci8, 1e-6f,
+                                scratch, s);
+    }));
+    ws->reset(m);
+  }
+  int cur = 1;                                   // gb[cur] = d loss / d (output of layer k before its SiLU)
+  for (int k = last - 1; k >= lowest; --k) {
+    const Act& xi = in[k];                       // the layer's input, on the map H x W of X
+    const int Co = l[k].Co, st = l[k].stride;
+    const int Ho = st == 2 ? (xi.H - 1) / 2 + 1 : xi.H, Wo = st == 2 ? (xi.W - 1) / 2 + 1 : xi.W, Po = B * Ho * Wo;
+    TRY(run_wgrad(ex, {gb[cur], Co, Co, (const float*)xi.p, xi.C, xi.H, xi.W, 9, 0, Co, l[k].Ci, 0, st, 1}, g[enc_slot(k)]));
+    TRY(run_colsum(ex, gb[cur], Co, Po, 1, 0, Co, g[enc_slot(k) + 1]));
+    if (k == lowest) break;
+    const ConvW& d = v->enc_d[k];
+    IgemmParams p;
+    p.src0 = gb[cur]; p.C0 = Co; p.B = B; p.Hi = p.Ho = Ho; p.Wi = p.Wo = Wo;
+    p.taps = 9; p.M = Po; p.N = d.N; p.W = d.w; p.out = gb[1 - cur]; p.ldo = xi.C;
+    if (st == 2) { p.n_valid = 4 * xi.C; p.epi = EPI_CONVT2; p.cout = xi.C; }
+    else { p.n_valid = xi.C; p.epi = EPI_STORE; }
+    TRY(ex.igemm(p));
+    cur = 1 - cur;
+    if (l[k - 1].silu) {                         // the input was SiLU(u[k - 1]): in place
+      const size_t n = (size_t)B * xi.H * xi.W * xi.C;
+      TRY(ex.launch("launch_silu_bwd failed", 4, 0, 12.0 * n, no_label, [&] { return launch_silu_bwd((const float*)u[k - 1].p, gb[cur], gb[cur], n, s); }));
+    }
   }
   return 0;
 }
@@ -667,12 +860,8 @@ int ldmseg_vae_decode_backward(ldmseg_vae* h, const float* z, float z_scale, int
   const std::vector<DecKey> keys = decoder_keys(h->cfg);
   std::vector<float*> g(keys.size(), nullptr);
   for (int i = 0; i < n; ++i) {
-    if (!names[i]) return fail(LDMSEG_E_ARG, "null gradient name");
-    size_t k = 0;
-    while (k < keys.size() && keys[k].name != names[i]) ++k;
-    if (k == keys.size()) return fail(LDMSEG_E_ARG, std::string("not a decoder parameter: ") + names[i]);
-    if (numels[i] != keys[k].numel)
-      return fail(LDMSEG_E_ARG, keys[k].name + " has " + std::to_string(keys[k].numel) + " elements, the gradient buffer " + std::to_string(numels[i]));
+    const int k = key_slot(keys, names[i], numels[i], "a decoder");
+    if (k < 0) return LDMSEG_E_ARG;
     g[k] = grad_ptrs[i];
   }
   DeviceGuard dg(h->cfg.device);
@@ -688,12 +877,9 @@ int ldmseg_vae_load_decoder(ldmseg_vae* h, int n, const char* const* names, cons
   const std::vector<DecKey> keys = decoder_keys(h->cfg);
   WeightMap wm;
   for (int i = 0; i < n; ++i) {
-    if (!names[i] || !dev_ptrs[i]) return fail(LDMSEG_E_ARG, "null decoder tensor");
-    size_t k = 0;
-    while (k < keys.size() && keys[k].name != names[i]) ++k;
-    if (k == keys.size()) return fail(LDMSEG_E_ARG, std::string("not a decoder parameter: ") + names[i]);
-    if (numels[i] != keys[k].numel)
-      return fail(LDMSEG_E_ARG, keys[k].name + " has " + std::to_string(keys[k].numel) + " elements, got " + std::to_string(numels[i]));
+    if (!dev_ptrs[i]) return fail(LDMSEG_E_ARG, "null decoder tensor");
+    const int k = key_slot(keys, names[i], numels[i], "a decoder");
+    if (k < 0) return LDMSEG_E_ARG;
     wm.m[keys[k].name] = {(const float*)dev_ptrs[i], numels[i]};
   }
   DeviceGuard dg(h->cfg.device);
@@ -741,6 +927,51 @@ int ldmseg_vae_encode(ldmseg_vae* h, const float* x, float in_mul, float in_add,
     Exec ex = make_exec(*h, B, (hipStream_t)stream, dry, scratch_base);
     return vae_encode_body(ex, h, x, in_mul, in_add, H, moments);
   });
+}
+
+int ldmseg_vae_encode_backward(ldmseg_vae* h, const float* x, float in_mul, float in_add, int B, int H, const float* grad_moments, int n,
+                               const char* const* names, float* const* grad_ptrs, const int64_t* numels, void* stream) {
+  g_err.clear();
+  if (!h || !x || !grad_moments) return fail(LDMSEG_E_ARG, "null argument");
+  if (n < 0 || (n > 0 && (!names || !grad_ptrs || !numels))) return fail(LDMSEG_E_ARG, "null argument");
+  if (h->dt != DT_F32) return fail(LDMSEG_E_ARG, "the encoder backward needs an fp32-storage handle (compute_dtype fp32 or bf16x3), not bf16");
+  if (!encoder_backward_ok(h->cfg)) return fail(LDMSEG_E_ARG, "the encoder backward needs block_out_channels and int_channels that are multiples of 32");
+  if (B < 1 || H < 8 || H % 8) return fail(LDMSEG_E_SHAPE, "H must be a multiple of 8");
+  const std::vector<DecKey> keys = encoder_keys(h->cfg);
+  std::vector<float*> g(keys.size(), nullptr);
+  for (int i = 0; i < n; ++i) {
+    const int k = key_slot(keys, names[i], numels[i], "an encoder");
+    if (k < 0) return LDMSEG_E_ARG;
+    g[k] = grad_ptrs[i];
+  }
+  DeviceGuard dg(h->cfg.device);
+  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
+    Exec ex = make_exec(*h, B, (hipStream_t)stream, dry, scratch_base);
+    return vae_encode_backward_body(ex, h, x, in_mul, in_add, H, grad_moments, g.data());
+  });
+}
+
+int ldmseg_vae_load_encoder(ldmseg_vae* h, int n, const char* const* names, const void* const* dev_ptrs, const int64_t* numels, void* stream) {
+  g_err.clear();
+  if (!h || n < 0 || (n > 0 && (!names || !dev_ptrs || !numels))) return fail(LDMSEG_E_ARG, "null argument");
+  const std::vector<DecKey> keys = encoder_keys(h->cfg);
+  WeightMap wm;
+  for (int i = 0; i < n; ++i) {
+    if (!dev_ptrs[i]) return fail(LDMSEG_E_ARG, "null encoder tensor");
+    const int k = key_slot(keys, names[i], numels[i], "an encoder");
+    if (k < 0) return LDMSEG_E_ARG;
+    wm.m[keys[k].name] = {(const float*)dev_ptrs[i], numels[i]};
+  }
+  DeviceGuard dg(h->cfg.device);
+  return vae_pack_encoder(h, wm, (hipStream_t)stream, true);
+}
+
+int ldmseg_vae_posterior_backward(const float* moments, const float* noise, float scale, int B, int l, const float* grad_z, float* grad_moments,
+                                  void* stream) {
+  g_err.clear();
+  if (!moments || !grad_z || !grad_moments) return fail(LDMSEG_E_ARG, "null argument");
+  if (B < 1 || l < 1) return fail(LDMSEG_E_SHAPE, "bad B/l");
+  return launch_code(launch_posterior_backward(moments, noise, scale, grad_z, grad_moments, B, l * l, (hipStream_t)stream), "launch_posterior_backward failed");
 }
 
 int ldmseg_vae_decode_semseg(ldmseg_vae* h, const float* z, float z_scale, int B, int L, int out_h, int out_w, float mask_th,

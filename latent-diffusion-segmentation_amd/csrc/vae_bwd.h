@@ -1,5 +1,6 @@
-// Host-side launch API of the seg-VAE decoder's backward kernels (vae_bwd.hip).  Every tensor is fp32: the backward runs on
-// fp32-storage handles only ("fp32" and "bf16x3"); x3 selects the split-bf16 products of the weight gradient.
+// Host-side launch API of the seg-VAE's backward kernels (vae_bwd.hip): the decoder's and what the encoder's adds
+// (DESIGN 8.7).  Every tensor is fp32: the backward runs on fp32-storage handles only ("fp32" and "bf16x3"); x3 selects the
+// split-bf16 products of the weight gradient.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,6 +13,9 @@ namespace ldmseg {
 //   slab[s][n][tap * C + c] = sum over the pixels p of slice s of dy[p][n] * x[p + tap][c]   (zero outside the image)
 // dy [P][ldy] (the first N columns are taken, N <= ldy), x [P][C] on B maps of H x W pixels (P = B H W).  The slabs
 // (wgrad_partial_bytes) are added in slice order by launch_wgrad_finish.
+// stride 2 (taps 9): x lives on B maps of H x W, dy on the conv's output maps Ho x Wo = ((H - 1) / 2 + 1) x ((W - 1) / 2 + 1), and
+//   slab[s][n][tap * C + c] = sum over the OUTPUT pixels p = (oy, ox) of slice s of dy[p][n] * x[(2 oy + ty - 1, 2 ox + tx - 1)][c].
+// by_width: the tile follows the storage widths N and C (wgrad_choose_ex) instead of the decoder's fixed 128 x 128.
 struct WgradParams {
   const float* dy = nullptr; int ldy = 0;
   const float* x = nullptr;
@@ -19,6 +23,8 @@ struct WgradParams {
   int N = 0, C = 0, taps = 9;
   int x3 = 0;
   float* partial = nullptr;
+  int stride = 1;
+  int by_width = 0;
 };
 int wgrad_plan(const WgradParams& p, int cus, WgradPlan* pl);
 size_t wgrad_partial_bytes(const WgradParams& p, const WgradPlan& pl);
@@ -46,9 +52,23 @@ size_t gn_bwd_scratch_bytes(int B, int C);
 int launch_gn_silu_bwd(const float* x, const float* dy, const float* gamma, const float* beta, float* dx, float* dgamma, float* dbeta,
                        int B, int HW, int C, float eps, float* scratch, hipStream_t s);
 
+// du = da * silu'(u), elementwise on n floats (the four conv + SiLU layers of the encoder keep u); a = silu(u), its forward
+int launch_silu_bwd(const float* u, const float* da, float* du, size_t n, hipStream_t s);
+int launch_silu_fwd(const float* u, float* a, size_t n, hipStream_t s);
+
+// z = mean + exp(0.5 clamp(logvar, -30, 20)) noise, backward to the moments [B][8][HW] = (mean | logvar): d mean = dz,
+// d logvar = dz * noise * 0.5 * std where -30 <= logvar <= 20 and 0 elsewhere (noise null: zeros).  dz [B][4][HW] * scale.
+int launch_posterior_backward(const float* moments, const float* noise, float scale, const float* dz, float* dmoments, int B, int HW,
+                              hipStream_t s);
+
 // Weights of the data gradients, read by launch_igemm as ordinary [Npad][K] fp32 matrices:
 // Conv2d OIHW [Co][Ci][3][3] -> [Npad][9][Cop], row ci, column (tap', co) = w[co][ci][8 - tap'] (transposed, taps rotated by 180 degrees)
 int launch_pack_dgrad_conv(const float* w, float* out, int Co, int Ci, int Npad, int Cop, hipStream_t s);
+// Conv2d OIHW [Co][Ci][3][3] of a STRIDE-2 conv (pad 1) -> [Npad][9][Cop], row q * Ci + ci for the output phase q = 2 py + px of dX,
+// column (tap', co) = w[co][ci][py + 3 - 2 ty'][px + 3 - 2 tx'] where that tap exists and zero elsewhere (tap' = (ty', tx') is the
+// window position on dY, offsets ty' - 1): igemm over dY with EPI_CONVT2 then scatters row (y, x), column q * Ci + ci to
+// dX[2 y + py][2 x + px][ci].  Npad >= 4 Ci.
+int launch_pack_dgrad_conv_s2(const float* w, float* out, int Co, int Ci, int Npad, int Cop, hipStream_t s);
 // ConvTranspose2d [Ci][Co][2][2] -> [Npad][4 Co], row ci, column q * Co + co = w[ci][co][q]
 int launch_pack_dgrad_convt(const float* w, float* out, int Ci, int Co, int Npad, hipStream_t s);
 

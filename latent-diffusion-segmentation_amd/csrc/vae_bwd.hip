@@ -1,5 +1,6 @@
-// Backward kernels of the seg-VAE decoder: the conv / transposed-conv weight gradient, the LayerNorm2d + SiLU and
-// GroupNorm + SiLU backwards, the bias column sums and the weight packings of the data gradients (which run on igemm).
+// Backward kernels of the seg-VAE (decoder: DESIGN 8.6, encoder: 8.7): the conv / transposed-conv weight gradient (stride 1 | 2,
+// tiles of 32 | 64 | 128), the LayerNorm2d + SiLU, GroupNorm + SiLU and SiLU backwards, the posterior's backward, the bias column
+// sums and the weight packings of the data gradients (which run on igemm).
 // fp32 tensors throughout.  Every sum over pixels or rows is cut into runs whose partial sums are stored and then added in run
 // order by one thread per output: no float atomics, the results are bitwise repeatable.
 #include <algorithm>
@@ -14,76 +15,90 @@ namespace {
 // ------------------------------------------------------------------ weight gradient
 struct WgradArgs {
   const float* dy; const float* x; float* partial;
-  int ldy, P, H, W, N, C, taps;
+  int ldy, P, H, W, N, C, taps;      // P pixels of the map dY lives on; H x W: the map X lives on
+  int Ho, Wo;                        // the map dY lives on (stride 1: H x W)
   int n_tiles, c_tiles, tiles, steps, steps_per_slice, items;
-  FastDiv fd_hw, fd_w;
+  FastDiv fd_hw, fd_w;               // of Ho * Wo and Wo
 };
 
-// A workgroup of four waves owns a 128 (n) x 128 (c) output tile of one tap over one slice of the pixel axis; a wave owns 64 x 64
-// of it as 4 x 4 MFMA tiles.  The tap's shift is applied to the pixel of the X operand; a pixel whose neighbour lies outside ITS image
+// pixel `pix` of dY and tap offset (dy_, dx_) -> is the X pixel inside its image, and where (element offset / C)
+template <int S>
+__device__ __forceinline__ bool wgrad_x_pixel(const WgradArgs& p, int pix, int dy_, int dx_, long long shift, long long* xrow) {
+  const int HWo = p.Ho * p.Wo;
+  const int img = fd_div(pix, p.fd_hw);
+  const int r = pix - img * HWo;
+  const int y = fd_div(r, p.fd_w);
+  const int xx = r - y * p.Wo;
+  if (S == 1) {
+    *xrow = (long long)pix + shift;
+    return (unsigned)(y + dy_) < (unsigned)p.H && (unsigned)(xx + dx_) < (unsigned)p.W;
+  }
+  const int iy = S * y + dy_, ix = S * xx + dx_;
+  *xrow = ((long long)img * p.H + iy) * p.W + ix;
+  return (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
+}
+
+// A workgroup of four waves owns a 32 FA (n) x 32 FB (c) output tile of one tap over one slice of the pixel axis (FA, FB in 1 | 2 | 4:
+// tiles of 32, 64, 128); a wave owns a quarter of it as FA x FB MFMA tiles.  S: the conv's stride (dY on the output map).  The tap's shift is applied to the pixel of the X operand; a pixel whose neighbour lies outside ITS image
 // contributes zero (never the next row's or the next image's pixel).  Rows past P and columns past N / C read nothing and count as zero.
 //
 // The fp32 form: the contraction index is the pixel and both operands are stored pixel-major, so lane (lg, lr) of a 16-channel
 // fragment reads element [pixel(lg)][channel lr] straight from global memory and that value IS its operand of
 // v_mfma_f32_16x16x4_f32 (k = lg; eight MFMAs walk the 32 pixels of a step): no transpose, no LDS.
+template <int FA, int FB, int S>
 __global__ __launch_bounds__(256) void wgrad_f32_kernel(const WgradArgs p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lr = lane & 15, lg = lane >> 4;
-  const int HW = p.H * p.W;
   const int KK = p.taps * p.C;
   for (int item = blockIdx.x; item < p.items; item += gridDim.x) {
     const int slice = item / p.tiles, tile = item - slice * p.tiles;
     const int per_tap = p.n_tiles * p.c_tiles;
     const int tap = tile / per_tap, rem_t = tile - tap * per_tap;
     const int nt = rem_t / p.c_tiles, ct = rem_t - nt * p.c_tiles;
-    const int n0 = nt * kWgradTileN + (wave >> 1) * 64, c0 = ct * kWgradTileC + (wave & 1) * 64;
+    const int n0 = nt * (32 * FA) + (wave >> 1) * (16 * FA), c0 = ct * (32 * FB) + (wave & 1) * (16 * FB);
     const int dy_ = p.taps == 9 ? tap / 3 - 1 : 0, dx_ = p.taps == 9 ? tap % 3 - 1 : 0;
     const long long shift = (long long)dy_ * p.W + dx_;
-    bool nv[4], cv[4];
+    bool nv[FA], cv[FB];
 #pragma unroll
-    for (int f = 0; f < 4; ++f) { nv[f] = n0 + 16 * f + lr < p.N; cv[f] = c0 + 16 * f + lr < p.C; }
-    f32x4 acc[4][4];
+    for (int f = 0; f < FA; ++f) nv[f] = n0 + 16 * f + lr < p.N;
 #pragma unroll
-    for (int a = 0; a < 4; ++a)
+    for (int f = 0; f < FB; ++f) cv[f] = c0 + 16 * f + lr < p.C;
+    f32x4 acc[FA][FB];
 #pragma unroll
-      for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int a = 0; a < FA; ++a)
+#pragma unroll
+      for (int b = 0; b < FB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int s0 = slice * p.steps_per_slice, s1 = min(p.steps, s0 + p.steps_per_slice);
     for (int st = s0; st < s1; ++st) {
       const int pbase = st * kWgradStep;
-      float av[4][8], bv[4][8];
+      float av[FA][8], bv[FB][8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int pix = pbase + 4 * j + lg;
         const bool pv = pix < p.P;
         bool xv = pv;
-        if (p.taps == 9) {
-          const int img = fd_div(pix, p.fd_hw);
-          const int r = pix - img * HW;
-          const int y = fd_div(r, p.fd_w);
-          const int xx = r - y * p.W;
-          xv = pv && (unsigned)(y + dy_) < (unsigned)p.H && (unsigned)(xx + dx_) < (unsigned)p.W;
-        }
+        long long xrow = pix;
+        if (p.taps == 9) xv = wgrad_x_pixel<S>(p, pix, dy_, dx_, shift, &xrow) && pv;
         const float* ar = p.dy + (long long)pix * p.ldy + n0 + lr;
-        const float* br = p.x + ((long long)pix + shift) * p.C + c0 + lr;
+        const float* br = p.x + xrow * p.C + c0 + lr;
 #pragma unroll
-        for (int f = 0; f < 4; ++f) {
-          av[f][j] = (pv && nv[f]) ? ar[16 * f] : 0.f;
-          bv[f][j] = (xv && cv[f]) ? br[16 * f] : 0.f;
-        }
+        for (int f = 0; f < FA; ++f) av[f][j] = (pv && nv[f]) ? ar[16 * f] : 0.f;
+#pragma unroll
+        for (int f = 0; f < FB; ++f) bv[f][j] = (xv && cv[f]) ? br[16 * f] : 0.f;
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j)
 #pragma unroll
-        for (int a = 0; a < 4; ++a)
+        for (int a = 0; a < FA; ++a)
 #pragma unroll
-          for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], bv[b][j], acc[a][b], 0, 0, 0);
+          for (int b = 0; b < FB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], bv[b][j], acc[a][b], 0, 0, 0);
     }
     // acc[a][b][j] = tile element (row n0 + 16 a + 4 lg + j, column c0 + 16 b + lr)
     float* slab = p.partial + (size_t)slice * p.N * KK + (size_t)tap * p.C;
 #pragma unroll
-    for (int a = 0; a < 4; ++a)
+    for (int a = 0; a < FA; ++a)
 #pragma unroll
-      for (int b = 0; b < 4; ++b) {
+      for (int b = 0; b < FB; ++b) {
         const int c = c0 + 16 * b + lr;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -94,15 +109,17 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(const WgradArgs p) {
   }
 }
 
-// The split-bf16 form (hi = bf16(x), lo = bf16(x - hi), products lo.hi + hi.lo + hi.hi as igemm's), the split made ONCE per workgroup: the 256 threads load the 32-pixel x 128-channel tiles of both operands
-// with 16-byte loads (the next step's loads are in flight under this step's MFMAs), split every value into hi = bf16(x) and
-// lo = bf16(x - hi) and store four bf16 planes [pixel][channel] in LDS; the waves then take their operands with the transposed LDS
-// read (ds_read_b64_tr_b16: a 16-lane group reads 4 pixel rows x 16 channels and lane i receives channel i of the 4 rows), which
-// makes the pixel axis the lane's contiguous K axis.  Lane group lg takes pixel rows 4 lg .. 4 lg + 3 and 16 + 4 lg .. 16 + 4 lg + 3
-// of the step as its k = 8 lg .. 8 lg + 7 - any K permutation is legal as long as both operands use the same one - so the two groups
-// of a 32-lane half read 8 consecutive rows; rows are 288 bytes apart (128 bf16 + 32 B: 8 banks further per row), which spreads the
-// 32 lanes' 8-byte reads over all 64 banks.
-constexpr int kWgRow = 288, kWgPlane = 32 * kWgRow;
+// The split-bf16 form (hi = bf16(x), lo = bf16(x - hi), products lo.hi + hi.lo + hi.hi as igemm's), the split made ONCE per
+// workgroup: the 256 threads load the 32-pixel x 32 FA / 32 FB channel tiles of both operands with 16-byte loads (the next step's
+// loads are in flight under this step's MFMAs), split every value into hi = bf16(x) and lo = bf16(x - hi) and store four bf16
+// planes [pixel][channel] in LDS; the waves then take their operands with the transposed LDS read (ds_read_b64_tr_b16: a 16-lane
+// group reads 4 pixel rows x 16 channels and lane i receives channel i of the 4 rows), which makes the pixel axis the lane's
+// contiguous K axis.  Lane group lg takes pixel rows 4 lg .. 4 lg + 3 and 16 + 4 lg .. 16 + 4 lg + 3 of the step as its
+// k = 8 lg .. 8 lg + 7 - any K permutation is legal as long as both operands use the same one - so the two groups of a 32-lane half
+// read 8 consecutive rows; rows are the tile's bf16 width + 32 B apart (288, 160 or 96 bytes = 72, 40 or 24 banks: an odd multiple
+// of 8 in each case, so 8 consecutive rows start on the 8 different multiples of 8 banks), which spreads the 32 lanes' 8-byte reads
+// over all 64 banks.
+constexpr int wg_row(int F) { return 64 * F + 32; }     // bytes between pixel rows of a plane 32 F channels wide
 
 __device__ __forceinline__ void split4(const float4& v, uint2& hi, uint2& lo) {
   hi.x = pack_bf16x2(v.x, v.y);
@@ -111,86 +128,93 @@ __device__ __forceinline__ void split4(const float4& v, uint2& hi, uint2& lo) {
   lo.y = pack_bf16x2(v.z - bits_f32(hi.y << 16), v.w - bits_f32(hi.y & 0xffff0000u));
 }
 
+template <int FA, int FB, int S>
 __global__ __launch_bounds__(256) void wgrad_x3_kernel(const WgradArgs p) {
-  __shared__ __attribute__((aligned(16))) char lds[4 * kWgPlane];      // A hi | A lo | B hi | B lo
+  constexpr int RA = wg_row(FA), RB = wg_row(FB), PA = 32 * RA, PB = 32 * RB;
+  __shared__ __attribute__((aligned(16))) char lds[2 * PA + 2 * PB];      // A hi | A lo | B hi | B lo
   typedef short s16x4 __attribute__((ext_vector_type(4)));
   typedef __attribute__((address_space(3))) s16x4* lds_v4;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int lr = lane & 15, lg = lane >> 4;
-  const int HW = p.H * p.W;
   const int KK = p.taps * p.C;
   // transposed read: lane 4 q + pp of a group supplies row q, channels 4 pp .. 4 pp + 3 of the block
-  const int tr_off = (4 * lg + (lr >> 2)) * kWgRow + (lr & 3) * 8;
-  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int tr_a = (4 * lg + (lr >> 2)) * RA + (lr & 3) * 8, tr_b = (4 * lg + (lr >> 2)) * RB + (lr & 3) * 8;
   for (int item = blockIdx.x; item < p.items; item += gridDim.x) {
     const int slice = item / p.tiles, tile = item - slice * p.tiles;
     const int per_tap = p.n_tiles * p.c_tiles;
     const int tap = tile / per_tap, rem_t = tile - tap * per_tap;
     const int nt = rem_t / p.c_tiles, ct = rem_t - nt * p.c_tiles;
-    const int n0b = nt * kWgradTileN, c0b = ct * kWgradTileC;
-    const int wn = (wave >> 1) * 64, wc = (wave & 1) * 64;
+    const int n0b = nt * (32 * FA), c0b = ct * (32 * FB);
+    const int wn = (wave >> 1) * (16 * FA), wc = (wave & 1) * (16 * FB);
     const int dy_ = p.taps == 9 ? tap / 3 - 1 : 0, dx_ = p.taps == 9 ? tap % 3 - 1 : 0;
     const long long shift = (long long)dy_ * p.W + dx_;
-    f32x4 acc[4][4];
+    f32x4 acc[FA][FB];
 #pragma unroll
-    for (int a = 0; a < 4; ++a)
+    for (int a = 0; a < FA; ++a)
 #pragma unroll
-      for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int b = 0; b < FB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int s0 = slice * p.steps_per_slice, s1 = min(p.steps, s0 + p.steps_per_slice);
-    float4 ra[4], rb[4];
-    // thread t loads float4 (row, c4) = ((t + 256 i) / 32, (t + 256 i) % 32) of both tiles: rows t / 32 + 8 i, one column group
-    const int c4 = t & 31, row0 = t >> 5;
-    const bool a_ok = n0b + 4 * c4 < p.N, b_ok = c0b + 4 * c4 < p.C;
+    float4 ra[FA], rb[FB];
+    // thread t loads float4 number t + 256 i of a tile of 8 F float4 per pixel row: (row, c4) = (idx / 8 F, idx % 8 F)
     auto load = [&](int st) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int pix = st * kWgradStep + row0 + 8 * i;
-        const bool pv = pix < p.P;
-        bool xv = pv;
-        if (p.taps == 9) {
-          const int img = fd_div(pix, p.fd_hw);
-          const int r = pix - img * HW;
-          const int y = fd_div(r, p.fd_w);
-          const int xx = r - y * p.W;
-          xv = pv && (unsigned)(y + dy_) < (unsigned)p.H && (unsigned)(xx + dx_) < (unsigned)p.W;
-        }
-        ra[i] = (pv && a_ok) ? *(const float4*)(p.dy + (long long)pix * p.ldy + n0b + 4 * c4) : zero4;
-        rb[i] = (xv && b_ok) ? *(const float4*)(p.x + ((long long)pix + shift) * p.C + c0b + 4 * c4) : zero4;
+      for (int i = 0; i < FA; ++i) {
+        const int idx = t + 256 * i, c4 = idx % (8 * FA), row = idx / (8 * FA);
+        const int pix = st * kWgradStep + row;
+        ra[i] = (pix < p.P && n0b + 4 * c4 < p.N) ? *(const float4*)(p.dy + (long long)pix * p.ldy + n0b + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int i = 0; i < FB; ++i) {
+        const int idx = t + 256 * i, c4 = idx % (8 * FB), row = idx / (8 * FB);
+        const int pix = st * kWgradStep + row;
+        bool xv = pix < p.P;
+        long long xrow = pix;
+        if (p.taps == 9) xv = wgrad_x_pixel<S>(p, pix, dy_, dx_, shift, &xrow) && xv;
+        rb[i] = (xv && c0b + 4 * c4 < p.C) ? *(const float4*)(p.x + xrow * p.C + c0b + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
       }
     };
     load(s0);
     for (int st = s0; st < s1; ++st) {
       __syncthreads();                                   // the previous step's reads are done
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int off = (row0 + 8 * i) * kWgRow + c4 * 8;
+      for (int i = 0; i < FA; ++i) {
+        const int idx = t + 256 * i;
+        const int off = (idx / (8 * FA)) * RA + (idx % (8 * FA)) * 8;
         uint2 hi, lo;
         split4(ra[i], hi, lo);
         *(uint2*)(lds + off) = hi;
-        *(uint2*)(lds + kWgPlane + off) = lo;
+        *(uint2*)(lds + PA + off) = lo;
+      }
+#pragma unroll
+      for (int i = 0; i < FB; ++i) {
+        const int idx = t + 256 * i;
+        const int off = (idx / (8 * FB)) * RB + (idx % (8 * FB)) * 8;
+        uint2 hi, lo;
         split4(rb[i], hi, lo);
-        *(uint2*)(lds + 2 * kWgPlane + off) = hi;
-        *(uint2*)(lds + 3 * kWgPlane + off) = lo;
+        *(uint2*)(lds + 2 * PA + off) = hi;
+        *(uint2*)(lds + 2 * PA + PB + off) = lo;
       }
       __syncthreads();
       if (st + 1 < s1) load(st + 1);                     // in flight under the MFMAs below
-      bf16x8 ah[4], al[4], bh[4], bl[4];
+      bf16x8 ah[FA], al[FA], bh[FB], bl[FB];
+      auto frag = [&](const char* base, int row) {
+        const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(base));
+        const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(base + 16 * row));
+        const uint2 u0 = __builtin_bit_cast(uint2, v0), u1 = __builtin_bit_cast(uint2, v1);
+        return __builtin_bit_cast(bf16x8, make_uint4(u0.x, u0.y, u1.x, u1.y));
+      };
 #pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        auto frag = [&](int plane, int col) {
-          const char* base = lds + plane * kWgPlane + tr_off + col * 2;
-          const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(base));
-          const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(base + 16 * kWgRow));
-          const uint2 u0 = __builtin_bit_cast(uint2, v0), u1 = __builtin_bit_cast(uint2, v1);
-          return __builtin_bit_cast(bf16x8, make_uint4(u0.x, u0.y, u1.x, u1.y));
-        };
-        ah[f] = frag(0, wn + 16 * f); al[f] = frag(1, wn + 16 * f);
-        bh[f] = frag(2, wc + 16 * f); bl[f] = frag(3, wc + 16 * f);
+      for (int f = 0; f < FA; ++f) {
+        ah[f] = frag(lds + tr_a + (wn + 16 * f) * 2, RA); al[f] = frag(lds + PA + tr_a + (wn + 16 * f) * 2, RA);
       }
 #pragma unroll
-      for (int a = 0; a < 4; ++a)
+      for (int f = 0; f < FB; ++f) {
+        bh[f] = frag(lds + 2 * PA + tr_b + (wc + 16 * f) * 2, RB); bl[f] = frag(lds + 2 * PA + PB + tr_b + (wc + 16 * f) * 2, RB);
+      }
 #pragma unroll
-        for (int b = 0; b < 4; ++b) {
+      for (int a = 0; a < FA; ++a)
+#pragma unroll
+        for (int b = 0; b < FB; ++b) {
           acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[a], bh[b], acc[a][b], 0, 0, 0);
           acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[a], bl[b], acc[a][b], 0, 0, 0);
           acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[a], bh[b], acc[a][b], 0, 0, 0);
@@ -199,9 +223,9 @@ __global__ __launch_bounds__(256) void wgrad_x3_kernel(const WgradArgs p) {
     __syncthreads();                                     // (the next item writes the planes again)
     float* slab = p.partial + (size_t)slice * p.N * KK + (size_t)tap * p.C;
 #pragma unroll
-    for (int a = 0; a < 4; ++a)
+    for (int a = 0; a < FA; ++a)
 #pragma unroll
-      for (int b = 0; b < 4; ++b) {
+      for (int b = 0; b < FB; ++b) {
         const int c = c0b + wc + 16 * b + lr;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -209,6 +233,202 @@ __global__ __launch_bounds__(256) void wgrad_x3_kernel(const WgradArgs p) {
           if (n < p.N && c < p.C) slab[(size_t)n * KK + c] = acc[a][b][j];
         }
       }
+  }
+}
+
+// ------------------------------------------------------------------ the all-taps tiles of the narrow 3x3 layers
+// A workgroup owns ALL NINE taps of a 32 FA (n) x 32 FB (c) tile (FA, FB in 1 | 2: the whole layer) over one slice of the pixel
+// axis: N x 9 C outputs.  dY is read once per step and serves the nine taps; X is read at the nine shifted pixels (its halo), lines
+// the same workgroup read a row of the map earlier.  Waves split the tile 2 x 2 as above; a wave holds 9 x FA x FB accumulator tiles.
+// The fp32 form, register-only as wgrad_f32_kernel: per four pixels a lane loads its dY values once and one X value per tap.
+template <int FA, int FB, int S>
+__global__ __launch_bounds__(256) void wgrad9_f32_kernel(const WgradArgs p) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lr = lane & 15, lg = lane >> 4;
+  const int KK = 9 * p.C;
+  const int n0 = (wave >> 1) * (16 * FA), c0 = (wave & 1) * (16 * FB);
+  bool nv[FA], cv[FB];
+#pragma unroll
+  for (int f = 0; f < FA; ++f) nv[f] = n0 + 16 * f + lr < p.N;
+#pragma unroll
+  for (int f = 0; f < FB; ++f) cv[f] = c0 + 16 * f + lr < p.C;
+  for (int slice = blockIdx.x; slice < p.items; slice += gridDim.x) {
+    f32x4 acc[9][FA][FB];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+      for (int a = 0; a < FA; ++a)
+#pragma unroll
+        for (int b = 0; b < FB; ++b) acc[t][a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int s0 = slice * p.steps_per_slice, s1 = min(p.steps, s0 + p.steps_per_slice);
+    for (int st = s0; st < s1; ++st) {
+#pragma unroll 2
+      for (int j = 0; j < 8; ++j) {
+        const int pix = st * kWgradStep + 4 * j + lg;
+        const bool pv = pix < p.P;
+        const float* ar = p.dy + (long long)pix * p.ldy + n0 + lr;
+        float av[FA];
+#pragma unroll
+        for (int f = 0; f < FA; ++f) av[f] = (pv && nv[f]) ? ar[16 * f] : 0.f;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+          const int dy_ = t / 3 - 1, dx_ = t % 3 - 1;
+          long long xrow;
+          const bool xv = wgrad_x_pixel<S>(p, pix, dy_, dx_, (long long)dy_ * p.W + dx_, &xrow) && pv;
+          const float* br = p.x + xrow * p.C + c0 + lr;
+          float bv[FB];
+#pragma unroll
+          for (int f = 0; f < FB; ++f) bv[f] = (xv && cv[f]) ? br[16 * f] : 0.f;
+#pragma unroll
+          for (int a = 0; a < FA; ++a)
+#pragma unroll
+            for (int b = 0; b < FB; ++b) acc[t][a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a], bv[b], acc[t][a][b], 0, 0, 0);
+        }
+      }
+    }
+    float* slab = p.partial + (size_t)slice * p.N * KK;
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+      for (int a = 0; a < FA; ++a)
+#pragma unroll
+        for (int b = 0; b < FB; ++b) {
+          const int c = c0 + 16 * b + lr;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int n = n0 + 16 * a + 4 * lg + j;
+            if (n < p.N && c < p.C) slab[(size_t)n * KK + t * p.C + c] = acc[t][a][b][j];
+          }
+        }
+  }
+}
+
+// The split-bf16 form: per step the dY tile is loaded, split and stored to LDS ONCE and its fragments stay in registers for the nine
+// taps; the X planes are made per tap ROW (three taps: 6 planes of 32 pixels), so a step has three rounds of two barriers instead of
+// nine.  The next round's X loads (the next step's dY loads with the last round) are in flight under the MFMAs.  LDS: 2 A planes +
+// 6 B planes, 16 - 40 KB.
+template <int FA, int FB, int S>
+__global__ __launch_bounds__(256) void wgrad9_x3_kernel(const WgradArgs p) {
+  constexpr int RA = wg_row(FA), RB = wg_row(FB), PA = 32 * RA, PB = 32 * RB;
+  __shared__ __attribute__((aligned(16))) char lds[2 * PA + 6 * PB];      // A hi | A lo | B hi [3 taps] | B lo [3 taps]
+  typedef short s16x4 __attribute__((ext_vector_type(4)));
+  typedef __attribute__((address_space(3))) s16x4* lds_v4;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int lr = lane & 15, lg = lane >> 4;
+  const int KK = 9 * p.C;
+  const int tr_a = (4 * lg + (lr >> 2)) * RA + (lr & 3) * 8, tr_b = (4 * lg + (lr >> 2)) * RB + (lr & 3) * 8;
+  const int wn = (wave >> 1) * (16 * FA), wc = (wave & 1) * (16 * FB);
+  auto frag = [&](const char* base, int row) {
+    const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(base));
+    const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(base + 16 * row));
+    const uint2 u0 = __builtin_bit_cast(uint2, v0), u1 = __builtin_bit_cast(uint2, v1);
+    return __builtin_bit_cast(bf16x8, make_uint4(u0.x, u0.y, u1.x, u1.y));
+  };
+  for (int slice = blockIdx.x; slice < p.items; slice += gridDim.x) {
+    f32x4 acc[9][FA][FB];
+#pragma unroll
+    for (int q = 0; q < 9; ++q)
+#pragma unroll
+      for (int a = 0; a < FA; ++a)
+#pragma unroll
+        for (int b = 0; b < FB; ++b) acc[q][a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int s0 = slice * p.steps_per_slice, s1 = min(p.steps, s0 + p.steps_per_slice);
+    float4 ra[FA], rb[3][FB];
+    auto load_a = [&](int st) {
+#pragma unroll
+      for (int i = 0; i < FA; ++i) {
+        const int idx = t + 256 * i, c4 = idx % (8 * FA), row = idx / (8 * FA);
+        const int pix = st * kWgradStep + row;
+        ra[i] = (pix < p.P && 4 * c4 < p.N) ? *(const float4*)(p.dy + (long long)pix * p.ldy + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    };
+    auto load_b = [&](int st, int g) {                    // tap row g: taps 3 g .. 3 g + 2
+#pragma unroll
+      for (int i = 0; i < FB; ++i) {
+        const int idx = t + 256 * i, c4 = idx % (8 * FB), row = idx / (8 * FB);
+        const int pix = st * kWgradStep + row;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const int dy_ = g - 1, dx_ = q - 1;
+          long long xrow;
+          const bool xv = wgrad_x_pixel<S>(p, pix, dy_, dx_, (long long)dy_ * p.W + dx_, &xrow) && pix < p.P;
+          rb[q][i] = (xv && 4 * c4 < p.C) ? *(const float4*)(p.x + xrow * p.C + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+      }
+    };
+    load_a(s0);
+    load_b(s0, 0);
+    for (int st = s0; st < s1; ++st) {
+      bf16x8 ah[FA], al[FA];
+#pragma unroll
+      for (int g = 0; g < 3; ++g) {
+        __syncthreads();                                 // the previous round's reads are done
+        if (g == 0) {
+#pragma unroll
+          for (int i = 0; i < FA; ++i) {
+            const int idx = t + 256 * i;
+            const int off = (idx / (8 * FA)) * RA + (idx % (8 * FA)) * 8;
+            uint2 hi, lo;
+            split4(ra[i], hi, lo);
+            *(uint2*)(lds + off) = hi;
+            *(uint2*)(lds + PA + off) = lo;
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+#pragma unroll
+          for (int i = 0; i < FB; ++i) {
+            const int idx = t + 256 * i;
+            const int off = (idx / (8 * FB)) * RB + (idx % (8 * FB)) * 8;
+            uint2 hi, lo;
+            split4(rb[q][i], hi, lo);
+            *(uint2*)(lds + 2 * PA + q * PB + off) = hi;
+            *(uint2*)(lds + 2 * PA + (3 + q) * PB + off) = lo;
+          }
+        __syncthreads();
+        if (g < 2) load_b(st, g + 1);                    // in flight under the MFMAs below
+        else if (st + 1 < s1) { load_a(st + 1); load_b(st + 1, 0); }
+        if (g == 0) {
+#pragma unroll
+          for (int f = 0; f < FA; ++f) {
+            ah[f] = frag(lds + tr_a + (wn + 16 * f) * 2, RA); al[f] = frag(lds + PA + tr_a + (wn + 16 * f) * 2, RA);
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          bf16x8 bh[FB], bl[FB];
+#pragma unroll
+          for (int f = 0; f < FB; ++f) {
+            bh[f] = frag(lds + 2 * PA + q * PB + tr_b + (wc + 16 * f) * 2, RB);
+            bl[f] = frag(lds + 2 * PA + (3 + q) * PB + tr_b + (wc + 16 * f) * 2, RB);
+          }
+#pragma unroll
+          for (int a = 0; a < FA; ++a)
+#pragma unroll
+            for (int b = 0; b < FB; ++b) {
+              f32x4& c = acc[3 * g + q][a][b];
+              c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[a], bh[b], c, 0, 0, 0);
+              c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[a], bl[b], c, 0, 0, 0);
+              c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[a], bh[b], c, 0, 0, 0);
+            }
+        }
+      }
+    }
+    __syncthreads();                                     // (the next slice writes the planes again)
+    float* slab = p.partial + (size_t)slice * p.N * KK;
+#pragma unroll
+    for (int q = 0; q < 9; ++q)
+#pragma unroll
+      for (int a = 0; a < FA; ++a)
+#pragma unroll
+        for (int b = 0; b < FB; ++b) {
+          const int c = wc + 16 * b + lr;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int n = wn + 16 * a + 4 * lg + j;
+            if (n < p.N && c < p.C) slab[(size_t)n * KK + q * p.C + c] = acc[q][a][b][j];
+          }
+        }
   }
 }
 
@@ -251,6 +471,28 @@ __global__ void slab_sum_kernel(const float* __restrict__ part, int S, int strid
 __device__ __forceinline__ float silu_grad(float u) {
   const float sg = 1.0f / (1.0f + __expf(-u));
   return sg * (1.0f + u * (1.0f - sg));
+}
+
+// ------------------------------------------------------------------ SiLU forward / backward on kept pre-activations, posterior backward
+// (du may be da itself: no __restrict__ on the pair)
+__global__ void silu_bwd_kernel(const float* __restrict__ u, const float* da, float* du, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) du[i] = da[i] * silu_grad(u[i]);
+}
+__global__ void silu_fwd_kernel(const float* __restrict__ u, float* __restrict__ a, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) a[i] = silu_f(u[i]);   // igemm's epilogue form
+}
+// dmom [B][8][HW] from dz [B][4][HW]: one thread per element of dz writes the mean and the logvar gradient of its latent
+__global__ void posterior_bwd_kernel(const float* __restrict__ mom, const float* __restrict__ noise, float scale, const float* __restrict__ dz,
+                                     float* __restrict__ dmom, int HW, size_t total) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t pix = i % HW, r = i / HW;
+    const size_t c = r % 4, b = r / 4;
+    const float g = dz[i] * scale;
+    const float lv = mom[(b * 8 + 4 + c) * HW + pix];
+    dmom[(b * 8 + c) * HW + pix] = g;
+    // (a NaN logvar fails both comparisons: zero, as the clamp's mask gives)
+    dmom[(b * 8 + 4 + c) * HW + pix] = (noise && lv >= -30.f && lv <= 20.f) ? g * noise[i] * 0.5f * expf(0.5f * lv) : 0.f;
+  }
 }
 
 // ------------------------------------------------------------------ LayerNorm2d + SiLU backward
@@ -410,6 +652,16 @@ __global__ void pack_dgrad_conv_kernel(const float* __restrict__ w, float* __res
     out[i] = (n < Ci && co < Co) ? w[((size_t)co * Ci + n) * 9 + (8 - t)] : 0.f;
   }
 }
+__global__ void pack_dgrad_conv_s2_kernel(const float* __restrict__ w, float* __restrict__ out, int Co, int Ci, int Npad, int Cop) {
+  const size_t total = (size_t)Npad * 9 * Cop;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int co = (int)(i % Cop), t = (int)((i / Cop) % 9), n = (int)(i / ((size_t)9 * Cop));
+    const int q = n / Ci, ci = n - q * Ci;
+    const int ky = (q >> 1) + 3 - 2 * (t / 3), kx = (q & 1) + 3 - 2 * (t % 3);
+    const bool ok = q < 4 && co < Co && (unsigned)ky < 3u && (unsigned)kx < 3u;
+    out[i] = ok ? w[((size_t)co * Ci + ci) * 9 + ky * 3 + kx] : 0.f;
+  }
+}
 __global__ void pack_dgrad_convt_kernel(const float* __restrict__ w, float* __restrict__ out, int Ci, int Co, int Npad) {
   const size_t K = (size_t)4 * Co, total = (size_t)Npad * K;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -424,24 +676,65 @@ inline int grid_for(size_t n, int cap = 8192) { return (int)std::min<size_t>((si
 }  // namespace
 
 // ------------------------------------------------------------------ launchers
+static inline int out_dim(int h, int stride) { return stride == 2 ? (h - 1) / 2 + 1 : h; }
 int wgrad_plan(const WgradParams& p, int cus, WgradPlan* pl) {
   if (p.B < 1 || p.H < 1 || p.W < 1 || (long long)p.B * p.H * p.W >= (1ll << 30)) return -2;
   if (p.N > p.ldy) return -2;
-  return wgrad_choose(WgradDesc{p.B * p.H * p.W, p.N, p.C, p.taps, p.x3}, cus, pl);
+  if (!p.by_width) return p.stride == 1 ? wgrad_choose(WgradDesc{p.B * p.H * p.W, p.N, p.C, p.taps, p.x3}, cus, pl) : -2;
+  return wgrad_choose_ex(WgradDescEx{p.B * out_dim(p.H, p.stride) * out_dim(p.W, p.stride), p.N, p.C, p.taps, p.x3, p.stride}, cus, pl);
 }
 size_t wgrad_partial_bytes(const WgradParams& p, const WgradPlan& pl) {
   return (size_t)pl.slices * p.N * p.taps * p.C * sizeof(float);
 }
+
+namespace {
+template <int FA, int FB, int S>
+void wgrad_launch_one(const WgradPlan& pl, const WgradArgs& a, hipStream_t s) {
+  if (pl.x3) LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), (wgrad_x3_kernel<FA, FB, S>), dim3(pl.grid_x), dim3(pl.block), 0, s, a);
+  else LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), (wgrad_f32_kernel<FA, FB, S>), dim3(pl.grid_x), dim3(pl.block), 0, s, a);
+}
+template <int FA, int FB>
+void wgrad_launch_stride(const WgradPlan& pl, const WgradArgs& a, hipStream_t s) {
+  if (pl.stride == 2) wgrad_launch_one<FA, FB, 2>(pl, a, s);
+  else wgrad_launch_one<FA, FB, 1>(pl, a, s);
+}
+template <int FA, int FB>
+void wgrad9_launch(const WgradPlan& pl, const WgradArgs& a, hipStream_t s) {
+  if (pl.x3 && pl.stride == 2) LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), (wgrad9_x3_kernel<FA, FB, 2>), dim3(pl.grid_x), dim3(pl.block), 0, s, a);
+  else if (pl.x3) LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), (wgrad9_x3_kernel<FA, FB, 1>), dim3(pl.grid_x), dim3(pl.block), 0, s, a);
+  else if (pl.stride == 2) LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), (wgrad9_f32_kernel<FA, FB, 2>), dim3(pl.grid_x), dim3(pl.block), 0, s, a);
+  else LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), (wgrad9_f32_kernel<FA, FB, 1>), dim3(pl.grid_x), dim3(pl.block), 0, s, a);
+}
+template <int FA>
+void wgrad_launch_c(const WgradPlan& pl, const WgradArgs& a, hipStream_t s) {
+  if (pl.tile_c == 32) wgrad_launch_stride<FA, 1>(pl, a, s);
+  else if (pl.tile_c == 64) wgrad_launch_stride<FA, 2>(pl, a, s);
+  else wgrad_launch_stride<FA, 4>(pl, a, s);
+}
+}  // namespace
+
 int launch_wgrad(const WgradParams& p, const WgradPlan& pl, hipStream_t s) {
   if (!p.dy || !p.x || !p.partial) return -2;
+  if (pl.stride != p.stride || (pl.tile_n != 32 && pl.tile_n != 64 && pl.tile_n != 128) || (pl.tile_c != 32 && pl.tile_c != 64 && pl.tile_c != 128))
+    return -2;
   WgradArgs a;
   a.dy = p.dy; a.x = p.x; a.partial = p.partial;
-  a.ldy = p.ldy; a.P = p.B * p.H * p.W; a.H = p.H; a.W = p.W; a.N = p.N; a.C = p.C; a.taps = p.taps;
+  a.Ho = out_dim(p.H, p.stride); a.Wo = out_dim(p.W, p.stride);
+  a.ldy = p.ldy; a.P = p.B * a.Ho * a.Wo; a.H = p.H; a.W = p.W; a.N = p.N; a.C = p.C; a.taps = p.taps;
   a.n_tiles = pl.n_tiles; a.c_tiles = pl.c_tiles; a.tiles = pl.tiles; a.steps = pl.steps; a.steps_per_slice = pl.steps_per_slice;
   a.items = pl.items;
-  a.fd_hw = fastdiv_make(p.H * p.W); a.fd_w = fastdiv_make(p.W);
-  if (pl.x3) LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), wgrad_x3_kernel, dim3(pl.grid_x), dim3(pl.block), 0, s, a);
-  else LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), wgrad_f32_kernel, dim3(pl.grid_x), dim3(pl.block), 0, s, a);
+  a.fd_hw = fastdiv_make(a.Ho * a.Wo); a.fd_w = fastdiv_make(a.Wo);
+  if (pl.all_taps) {
+    if (p.taps != 9 || pl.n_tiles != 1 || pl.c_tiles != 1 || pl.tile_n > 64 || pl.tile_c > 64 || pl.items != pl.slices) return -2;
+    if (pl.tile_n == 32 && pl.tile_c == 32) wgrad9_launch<1, 1>(pl, a, s);
+    else if (pl.tile_n == 32) wgrad9_launch<1, 2>(pl, a, s);
+    else if (pl.tile_c == 32) wgrad9_launch<2, 1>(pl, a, s);
+    else wgrad9_launch<2, 2>(pl, a, s);
+    return launch_status();
+  }
+  if (pl.tile_n == 32) wgrad_launch_c<1>(pl, a, s);
+  else if (pl.tile_n == 64) wgrad_launch_c<2>(pl, a, s);
+  else wgrad_launch_c<4>(pl, a, s);
   return launch_status();
 }
 int launch_wgrad_finish(const WgradParams& p, const WgradPlan& pl, int form, int n_real, int c_real, int co, float* out, hipStream_t s) {
@@ -463,6 +756,24 @@ int launch_colsum(const float* a, int lda, int P, int N, int Q, int qstride, int
   const int S = (P + rows - 1) / rows;
   LDMSEG_LAUNCH("colsum_partial<f32>", colsum_partial_kernel, dim3(S, (N + 127) / 128), dim3(128), 0, s, a, lda, P, N, rows, scratch);
   LDMSEG_LAUNCH("slab_sum<f32>", slab_sum_kernel, dim3((n + 127) / 128), dim3(128), 0, s, scratch, S, N, Q, qstride, n, out);
+  return launch_status();
+}
+
+int launch_silu_bwd(const float* u, const float* da, float* du, size_t n, hipStream_t s) {
+  if (!u || !da || !du || n < 1) return -2;
+  LDMSEG_LAUNCH("silu_bwd<f32>", silu_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, s, u, da, du, n);
+  return launch_status();
+}
+int launch_silu_fwd(const float* u, float* a, size_t n, hipStream_t s) {
+  if (!u || !a || n < 1) return -2;
+  LDMSEG_LAUNCH("silu_fwd<f32>", silu_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, s, u, a, n);
+  return launch_status();
+}
+int launch_posterior_backward(const float* moments, const float* noise, float scale, const float* dz, float* dmoments, int B, int HW,
+                              hipStream_t s) {
+  if (!moments || !dz || !dmoments || B < 1 || HW < 1) return -2;
+  const size_t total = (size_t)B * 4 * HW;
+  LDMSEG_LAUNCH("posterior_bwd<f32>", posterior_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, s, moments, noise, scale, dz, dmoments, HW, total);
   return launch_status();
 }
 
@@ -505,6 +816,11 @@ int launch_gn_silu_bwd(const float* x, const float* dy, const float* gamma, cons
 int launch_pack_dgrad_conv(const float* w, float* out, int Co, int Ci, int Npad, int Cop, hipStream_t s) {
   if (Npad < Ci || Cop < Co) return -2;
   LDMSEG_LAUNCH("pack_dgrad_conv<f32>", pack_dgrad_conv_kernel, dim3(grid_for((size_t)Npad * 9 * Cop)), dim3(256), 0, s, w, out, Co, Ci, Npad, Cop);
+  return launch_status();
+}
+int launch_pack_dgrad_conv_s2(const float* w, float* out, int Co, int Ci, int Npad, int Cop, hipStream_t s) {
+  if (Npad < 4 * Ci || Cop < Co) return -2;
+  LDMSEG_LAUNCH("pack_dgrad_conv_s2<f32>", pack_dgrad_conv_s2_kernel, dim3(grid_for((size_t)Npad * 9 * Cop)), dim3(256), 0, s, w, out, Co, Ci, Npad, Cop);
   return launch_status();
 }
 int launch_pack_dgrad_convt(const float* w, float* out, int Ci, int Co, int Npad, hipStream_t s) {

@@ -7,6 +7,10 @@
 // [slice][N][taps * C]; wgrad_finish adds the slabs in slice order.  The slicing - and with it the order of every addition - is
 // a function of the SHAPE alone: it aims at kWgradTargetItems work items whatever the device; the CU count only decides how many
 // workgroups walk the items (one item per workgroup while they fit, a fixed-stride walk beyond).
+//
+// Two rules share one body.  wgrad_choose is the decoder's: the 128 x 128 tile, stride 1.  wgrad_choose_ex is the
+// encoder's: dY lives on the OUTPUT map of a stride-1 or stride-2 conv, and the tile follows the storage widths -
+// 32, 64 or 128 rows of dY by 32, 64 or 128 channels of X - so that a 32- or 64-channel layer does not pay for a 128-wide tile.
 #pragma once
 #include <cstdio>
 #include <string>
@@ -16,6 +20,8 @@ namespace ldmseg {
 // P pixels (B * H * W of the map X lives on), N rows of dY taken (storage width of dY), C storage channels of X, taps 9 (3x3, pad
 // 1) or 1, x3: 0 = exact fp32 MFMA, 1 = split-bf16 products
 struct WgradDesc { int P, N, C, taps, x3; };
+// the same with P = the pixels of the OUTPUT map (the map dY lives on) of a conv of stride 1 | 2 (2: taps 9 only)
+struct WgradDescEx { int P, N, C, taps, x3, stride; };
 
 constexpr int kWgradTileN = 128, kWgradTileC = 128;   // output tile of a workgroup: four waves of 64 x 64
 constexpr int kWgradStep = 32;                          // pixels per K step (one bf16 MFMA's K; eight fp32 MFMAs' K)
@@ -24,7 +30,10 @@ constexpr int kWgradTargetItems = 256;                  // work items the slicin
 
 struct WgradPlan {
   int x3 = 0;
-  int n_tiles = 1, c_tiles = 1, taps = 1, tiles = 1;    // tiles = n_tiles * c_tiles * taps
+  int tile_n = kWgradTileN, tile_c = kWgradTileC;       // output tile of a workgroup (per tap): 2 x 2 waves of tile_n/2 x tile_c/2
+  int stride = 1;
+  int n_tiles = 1, c_tiles = 1, taps = 1, tiles = 1;    // tiles = n_tiles * c_tiles * taps (all_taps: n_tiles * c_tiles)
+  int all_taps = 0;                                     // a workgroup owns the nine taps of its tile: tile_n x 9 tile_c outputs
   int steps = 1;                                        // K steps over all pixels
   int slices = 1, steps_per_slice = 1;                  // slice s takes steps [s * steps_per_slice, min(steps, (s + 1) * steps_per_slice))
   int items = 1;                                        // tiles * slices
@@ -32,17 +41,24 @@ struct WgradPlan {
   int one_per_cu = 1;                                   // every item has its own workgroup (grid_x == items <= CUs)
 };
 
-// 0 and *out filled, or -2: no such launch
-inline int wgrad_choose(const WgradDesc& q, int cus, WgradPlan* out) {
+// the narrowest of 32 | 64 | 128 that holds `width` (128 beyond)
+constexpr int wgrad_tile_for(int width) { return width <= 32 ? 32 : width <= 64 ? 64 : 128; }
+
+// 0 and *out filled, or -2: no such launch.  tile_n / tile_c: 32 | 64 | 128
+inline int wgrad_choose_tiled(const WgradDescEx& q, int tile_n, int tile_c, bool all_taps, int cus, WgradPlan* out) {
   if (q.P < 1 || q.N < 1 || q.C < 1 || (q.taps != 1 && q.taps != 9) || cus < 1) return -2;
+  if (q.stride != 1 && (q.stride != 2 || q.taps != 9)) return -2;
   if (q.N % 16 || q.C % 16) return -2;                  // operands are read as 16-channel MFMA fragments
   if ((long long)q.P + 2 * kWgradStep >= (1ll << 31)) return -2;
   WgradPlan p;
   p.x3 = q.x3 ? 1 : 0;
   p.taps = q.taps;
-  p.n_tiles = (q.N + kWgradTileN - 1) / kWgradTileN;
-  p.c_tiles = (q.C + kWgradTileC - 1) / kWgradTileC;
-  p.tiles = p.n_tiles * p.c_tiles * p.taps;
+  p.stride = q.stride;
+  p.tile_n = tile_n; p.tile_c = tile_c;
+  p.n_tiles = (q.N + tile_n - 1) / tile_n;
+  p.c_tiles = (q.C + tile_c - 1) / tile_c;
+  p.all_taps = all_taps ? 1 : 0;
+  p.tiles = p.n_tiles * p.c_tiles * (all_taps ? 1 : p.taps);
   p.steps = (q.P + kWgradStep - 1) / kWgradStep;
   int want = kWgradTargetItems / p.tiles;               // slices that fill the target
   const int worth = p.steps / kWgradMinSteps;           // slices the pixel axis is worth
@@ -56,10 +72,22 @@ inline int wgrad_choose(const WgradDesc& q, int cus, WgradPlan* out) {
   *out = p;
   return 0;
 }
+inline int wgrad_choose(const WgradDesc& q, int cus, WgradPlan* out) {
+  return wgrad_choose_tiled(WgradDescEx{q.P, q.N, q.C, q.taps, q.x3, 1}, kWgradTileN, kWgradTileC, false, cus, out);
+}
+// A 3x3 layer whose two widths fit 64 runs on the all-taps tile: one workgroup owns N x 9 C outputs of a slice, reads dY once per
+// step and X with its halo, so the operand traffic does not scale with the tap count (and the slicing aims at 256 slices, not 28).
+inline int wgrad_choose_ex(const WgradDescEx& q, int cus, WgradPlan* out) {
+  const int tn = wgrad_tile_for(q.N), tc = wgrad_tile_for(q.C);
+  return wgrad_choose_tiled(q, tn, tc, q.taps == 9 && tn <= 64 && tc <= 64, cus, out);
+}
+// MACs a plan executes for one pixel: tiles x tile area x taps (the chooser's cost, tests/test_wgrad_plan_ex_cpu.py)
+inline long long wgrad_plan_macs_per_pixel(const WgradPlan& p) { return (long long)p.n_tiles * p.c_tiles * p.taps * p.tile_n * p.tile_c; }
 
 inline std::string wgrad_plan_name(const WgradPlan& p) {
   char b[64];
-  std::snprintf(b, sizeof b, "wgrad<%s,%d,%d>/taps%d", p.x3 ? "x3" : "f32", kWgradTileN, kWgradTileC, p.taps);
+  std::snprintf(b, sizeof b, "wgrad%s<%s,%d,%d>/taps%d%s", p.all_taps ? "9" : "", p.x3 ? "x3" : "f32", p.tile_n, p.tile_c, p.taps,
+                p.stride == 2 ? "/s2" : "");
   return b;
 }
 // "name tiles=T slices=S steps=K/slice grid=G block=256 one_per_cu=0|1"

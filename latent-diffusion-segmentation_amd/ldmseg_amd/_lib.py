@@ -68,6 +68,9 @@ SIGNATURES = {
     "ldmseg_vae_decode": (_i, [_vp, _vp, _f, _i, _i, _i, _vp, _vp]),
     "ldmseg_vae_decode_backward": (_i, [_vp, _vp, _f, _i, _i, _vp, _vp, _i, C.POINTER(C.c_char_p), C.POINTER(_vp), C.POINTER(_i64), _vp]),
     "ldmseg_vae_load_decoder": (_i, [_vp, _i, C.POINTER(C.c_char_p), C.POINTER(_vp), C.POINTER(_i64), _vp]),
+    "ldmseg_vae_encode_backward": (_i, [_vp, _vp, _f, _f, _i, _i, _vp, _i, C.POINTER(C.c_char_p), C.POINTER(_vp), C.POINTER(_i64), _vp]),
+    "ldmseg_vae_load_encoder": (_i, [_vp, _i, C.POINTER(C.c_char_p), C.POINTER(_vp), C.POINTER(_i64), _vp]),
+    "ldmseg_vae_posterior_backward": (_i, [_vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "ldmseg_vae_decode_argmax": (_i, [_vp, _vp, _f, _i, _i, _f, _i64, _vp, _vp, _vp]),
     "ldmseg_vae_encode": (_i, [_vp, _vp, _f, _f, _i, _i, _vp, _vp]),
     "ldmseg_vae_posterior": (_i, [_vp, _vp, _f, _i, _i, _vp, _vp]),
@@ -184,6 +187,12 @@ SIGNATURES = {
     "ldmseg_op_groupnorm_silu_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "ldmseg_op_layernorm_silu_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ldmseg_op_wgrad_plan": (_i, [_i, _i, _i, _i, _i, _i, C.c_char_p, _i]),
+    "ldmseg_op_conv_wgrad_ex": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ldmseg_op_conv_s2_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ldmseg_op_conv_s2_dgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ldmseg_op_silu_bwd": (_i, [_vp, _vp, _i64, _vp, _vp]),
+    "ldmseg_op_silu_fwd": (_i, [_vp, _i64, _vp, _vp]),
+    "ldmseg_op_wgrad_plan_ex": (_i, [_i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i, C.POINTER(_i64)]),
     "ldmseg_igemm_log": (_i, [_i]),
     "ldmseg_igemm_log_read": (_i, [C.c_char_p, _i]),
 }

@@ -45,14 +45,22 @@ class DiagonalGaussianDistribution(object):
     def logvar(self):
         return torch.clamp(self.parameters[:, 4:], -30.0, 20.0)
 
+    def _draw(self, noise):
+        """mode() (noise None) / sample(): with grad mode on and `parameters` requiring grad the latents are differentiable with
+        respect to them (once: ldmseg_vae_posterior_backward; the noise is saved), the values are those of the no-grad path"""
+        p = self.parameters
+        if torch.is_grad_enabled() and isinstance(p, torch.Tensor) and p.requires_grad:
+            return _PosteriorFunction.apply(self, _lib.require_cuda_f32(p, "moments"), noise)
+        return self._posterior(noise)
+
     def mode(self):
-        return self._posterior(None)
+        return self._draw(None)
 
     def sample(self, generator: Optional[torch.Generator] = None) -> torch.Tensor:
         p = self.parameters
         shape = (p.shape[0], 4, p.shape[2], p.shape[3])
         noise = torch.randn(shape, generator=generator, device=p.device, dtype=p.dtype)
-        return self._posterior(noise)
+        return self._draw(noise)
 
     def kl(self, return_mean: bool = False):
         """:416-417: 0.5 * sum(mean^2 + var - 1 - logvar) per image, [B] on the device (ldmseg_gaussian_kl; fp64 sums).  With
@@ -104,6 +112,77 @@ class _GaussianKLFunction(torch.autograd.Function):
             _lib.check(_lib.lib().ldmseg_gaussian_kl_backward(_lib.ptr(p), B, C2 // 2, p[0, 0].numel(), _lib.ptr(g), _lib.ptr(grad),
                                                               _lib.stream_ptr(p.device)), "ldmseg_gaussian_kl_backward")
         return grad
+
+
+class _PosteriorFunction(torch.autograd.Function):
+    """z = mean + exp(0.5 clamp(logvar, -30, 20)) noise of fp32 contiguous moments with a backward to them: d mean = dz,
+    d logvar = dz noise std / 2 where the clamp passes gradient (bounds included), zeros elsewhere and for mode()."""
+
+    @staticmethod
+    def forward(ctx, dist, p, noise):
+        with torch.no_grad():
+            out = DiagonalGaussianDistribution(p)._posterior(noise)
+        ctx.noise = noise
+        ctx.save_for_backward(p)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_z):
+        p, = ctx.saved_tensors
+        if grad_z is None:
+            return None, None, None
+        g = grad_z.to(device=p.device, dtype=torch.float32).contiguous()
+        B, _, l, _ = p.shape
+        grad = torch.empty_like(p)
+        with torch.cuda.device(p.device):
+            _lib.check(_lib.lib().ldmseg_vae_posterior_backward(_lib.ptr(p), _lib.ptr(ctx.noise), 1.0, B, l, _lib.ptr(g), _lib.ptr(grad),
+                                                                _lib.stream_ptr(p.device)), "ldmseg_vae_posterior_backward")
+        return None, grad, None
+
+
+def _name_arrays(tensors):
+    """(n, names, ptrs, numels) of a {key: tensor} dict as the C ABI takes them (arrays of one dummy element when empty)"""
+    n = len(tensors)
+    names = (C.c_char_p * max(n, 1))(*[k.encode() for k in tensors])
+    ptrs = (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in tensors.values()])
+    numels = (C.c_int64 * max(n, 1))(*[t.numel() for t in tensors.values()])
+    return n, names, ptrs, numels
+
+
+class _EncodeFunction(torch.autograd.Function):
+    """encode_moments(x, in_mul, in_add) with a backward to the encoder parameters: forward is the no-grad path's own
+    ldmseg_vae_encode call, backward one ldmseg_vae_encode_backward call (stateless: the library runs the encoder forward again
+    inside it) that returns the parameter gradients autograd asks for.  The input is data: it gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, vae, in_mul, in_add, x, *params):
+        out = vae._encode_call(x, in_mul, in_add)
+        ctx.vae, ctx.in_mul, ctx.in_add = vae, in_mul, in_add
+        ctx.save_for_backward(x)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        vae = ctx.vae
+        x, = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        keys = list(vae._enc_params)
+        if grad is None:
+            return (None,) * len(need)
+        vae._check_encoder_fresh()
+        g = grad.to(device=x.device, dtype=torch.float32).contiguous()
+        B, _, H, _ = x.shape
+        grads = {k: torch.empty_like(vae._enc_params[k]) for i, k in enumerate(keys) if need[4 + i]}
+        n, names, ptrs, numels = _name_arrays(grads)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().ldmseg_vae_encode_backward(vae._h, _lib.ptr(x), float(ctx.in_mul), float(ctx.in_add), B, H, _lib.ptr(g),
+                                                             n, names, ptrs, numels, _lib.stream_ptr(x.device)),
+                       "ldmseg_vae_encode_backward")
+        return (None, None, None, None) + tuple(grads.get(k) for k in keys)
 
 
 class _DecodeFunction(torch.autograd.Function):
@@ -194,6 +273,11 @@ class GeneralVAESeg(object):
                                    for k in schema if k.startswith("decoder."))
         self._dec_params = None
         self._dec_versions = None
+        # ... and the encoder's (encoder_parameters())
+        self._enc_sd = OrderedDict((k, state_dict[k].detach().to(device=self.device, dtype=torch.float32).clone().contiguous())
+                                   for k in schema if k.startswith("encoder."))
+        self._enc_params = None
+        self._enc_versions = None
 
     @property
     def num_parameters(self) -> int:
@@ -215,10 +299,24 @@ class GeneralVAESeg(object):
             self._h = None
 
     def encode_moments(self, semseg: torch.Tensor, in_mul: float = 1.0, in_add: float = 0.0) -> torch.Tensor:
+        """Moments [B,8,H/8,H/8] of semseg * in_mul + in_add.  With grad mode on, once `encoder_parameters()` has been called and a
+        tensor of it requires grad, the result carries a graph to them (once differentiable): the values are bitwise those of the
+        no-grad path, the backward is one ldmseg_vae_encode_backward call.  bf16 objects raise NotImplementedError then."""
         x = _lib.require_cuda_f32(semseg, "semseg")
         B, Cin, H, W = x.shape
         if Cin != self._in_channels or H != W:
             raise ValueError(f"expected [B,{self._in_channels},H,H], got {tuple(x.shape)}")
+        if torch.is_grad_enabled() and self._enc_params is not None:
+            params = list(self._enc_params.values())
+            if any(p.requires_grad for p in params):
+                if self._bf16:
+                    raise NotImplementedError("the encoder backward needs an fp32-storage object (compute_dtype 'fp32' or 'bf16x3')")
+                self._check_encoder_fresh()
+                return _EncodeFunction.apply(self, float(in_mul), float(in_add), x, *params)
+        return self._encode_call(x, in_mul, in_add)
+
+    def _encode_call(self, x, in_mul, in_add):
+        B, _, H, _ = x.shape
         l = H // self.downsample_factor
         mom = torch.empty((B, 8, l, l), device=x.device, dtype=torch.float32)
         with torch.cuda.device(x.device):
@@ -228,6 +326,43 @@ class GeneralVAESeg(object):
 
     def encode(self, semseg: torch.Tensor) -> EncoderOutput:
         return EncoderOutput(latent_dist=DiagonalGaussianDistribution(self.encode_moments(semseg)))
+
+    def encoder_parameters(self):
+        """Ordered dict: reference key (encoder.0.weight ...) -> fp32 leaf tensor on the device with requires_grad=True, holding
+        the encoder tensors of the state dict the object was built from.  Once this has been called, `encode_moments` / `encode` /
+        `forward` under grad mode carry the encoder's graph to these tensors; after changing them in place (an optimiser step) call
+        `refresh_encoder()` (or `refresh()`) so that the handle computes with the new values."""
+        if self._enc_params is None:
+            self._enc_params = OrderedDict((k, v.requires_grad_(True)) for k, v in self._enc_sd.items())
+            self._enc_versions = {k: v._version for k, v in self._enc_params.items()}
+        return self._enc_params
+
+    def refresh_encoder(self):
+        """`refresh_decoder()` for the encoder's tensors (ldmseg_vae_load_encoder: nothing is allocated)."""
+        params = self.encoder_parameters()
+        ts = OrderedDict((k, p.detach()) for k, p in params.items())
+        n, names, ptrs, numels = _name_arrays(ts)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ldmseg_vae_load_encoder(self._h, n, names, ptrs, numels, _lib.stream_ptr(self.device)),
+                       "ldmseg_vae_load_encoder")
+        self._enc_versions = {k: v._version for k, v in params.items()}
+
+    def _check_encoder_fresh(self):
+        if self._enc_params is None:
+            return
+        stale = [k for k, v in self._enc_params.items() if v._version != self._enc_versions[k]]
+        if stale:
+            raise RuntimeError(f"encoder parameter {stale[0]} was modified in place since the last refresh_encoder(): the handle "
+                               "would compute with stale weights; call refresh_encoder() after the optimiser step")
+
+    def parameters(self):
+        """The 34 leaves of `encoder_parameters()` then `decoder_parameters()`, for `clip_grad_norm_` and an optimiser."""
+        return list(self.encoder_parameters().values()) + list(self.decoder_parameters().values())
+
+    def refresh(self):
+        """`refresh_encoder()` and `refresh_decoder()`: after an optimiser step on `parameters()`."""
+        self.refresh_encoder()
+        self.refresh_decoder()
 
     def decoder_parameters(self):
         """Ordered dict: reference key (decoder.0.weight ...) -> fp32 leaf tensor on the device with requires_grad=True, holding
@@ -443,8 +578,9 @@ class GeneralVAESeg(object):
 
     def forward(self, sample, sample_posterior: bool = True, return_dict: bool = True,
                 generator: Optional[torch.Generator] = None, rgb_sample=None, valid_mask=None):
-        """vae.py:273-307.  Under grad mode `.sample` carries the decoder's graph (see `decode`); the encoder half and the moments
-        stay without one."""
+        """vae.py:273-307.  Under grad mode `.sample` carries the decoder's graph (see `decode`) and, once `encoder_parameters()`
+        has been called, the posterior's and the encoder's behind it (see `encode_moments`): one graph from a loss on the output to
+        every tensor of `parameters()`."""
         if rgb_sample is not None:
             raise NotImplementedError("fuse_rgb is off in base.yaml:30")
         posterior = self.encode(sample).latent_dist

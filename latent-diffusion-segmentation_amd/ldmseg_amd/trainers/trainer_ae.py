@@ -4,7 +4,8 @@ Stands behind the evaluation half of the reference's ldmseg/trainers/trainers_ae
 (`compute_metrics` :546-569, `compute_pq` :580-680, `compute_miou` :728-803) - what `tools/main_ae.py` runs with
 `eval_only` (:189-190) - and behind the loss of its training step: `compute_point_loss` (:204-224), the number the stage-1
 loop logs and selects checkpoints by, differentiable with respect to the logits and the moments it is given (the `loss.backward()`
-of :286-296 as far as the loss goes).  Network backward, optimiser, image dumps and overlays (`save_images`) are not built.
+of :286-296) and behind the step itself: `training_step` (:285-321 without the fp16 scaler) on the library's forward and backward
+with a torch optimiser.  The loop around it, a fused optimiser, EMA, image dumps and overlays (`save_images`) are not built.
 
 Per batch ONE library call does encode -> posterior mode -> decode -> the metric's tail
 (`GeneralVAESeg.reconstruct_semseg` / `reconstruct_panoptic`); the [B,128,S,S] logits are never materialised and the
@@ -72,14 +73,34 @@ class TrainerAE(object):
         ce, mask, kl.  With grad mode on, the values are differentiable with respect to the logits and the posterior's moments
         where those require grad (`total.backward()`).  The library's own seg-VAE gives `.sample` the decoder's graph once
         `vae_model.decoder_parameters()` has been called (fp32 / bf16x3 objects): `total.backward()` then fills the `.grad` of every
-        decoder parameter through ldmseg_point_loss_backward and ldmseg_vae_decode_backward.  The encoder half and the moments
-        still come without a graph."""
+        decoder parameter through ldmseg_point_loss_backward and ldmseg_vae_decode_backward; once `vae_model.encoder_parameters()`
+        has been called too, the moments carry the encoder's graph and the `.grad` of every encoder parameter is filled as well
+        (ldmseg_vae_posterior_backward, ldmseg_gaussian_kl_backward, ldmseg_vae_encode_backward)."""
         parts = self.segmentation_losses.point_loss(outputs.sample, targets, do_matching, masks, generator=generator)
         ce, mask = parts['ce'], parts['mask']
         kl = outputs.posterior.kl(return_mean=True)[1]
         w = self.loss_weights
         total = w['ce'] * ce + w['mask'] * mask + w['kl'] * kl
         return total, ce, kl, mask
+
+    def training_step(self, images, targets, optimizer, clip_grad: float = 0.0, generator=None, point_generator=None):
+        """One stage-1 step, :285-321 without the fp16 scaler, on `images` [B,7,S,S] already in [-1, 1] (:256) and `targets` [B,h,w]:
+        forward with a sampled posterior, `compute_point_loss`, `backward()`, torch's `clip_grad_norm_` over `vae_model.parameters()`
+        when clip_grad > 0, `optimizer.step()`, `vae_model.refresh()`.  `optimizer` is a torch optimiser over
+        `vae_model.parameters()`; its gradients are zeroed first (:324-325, moved to the front).  generator: the DEVICE generator
+        of the posterior's noise; point_generator: the point sampler's (as `compute_point_loss` takes it).  Returns (loss, ce, kl, mask) as detached 0-d
+        device tensors."""
+        optimizer.zero_grad(set_to_none=True)
+        params = self.vae_model.parameters()
+        with torch.enable_grad():
+            output = self.vae_model(images, sample_posterior=True, generator=generator)
+            loss, ce, kl, mask = self.compute_point_loss(output, targets, generator=point_generator)
+            loss.backward()
+        if clip_grad > 0:
+            torch.nn.utils.clip_grad_norm_(params, clip_grad, norm_type=2)
+        optimizer.step()
+        self.vae_model.refresh()
+        return loss.detach(), ce.detach(), kl.detach(), mask.detach()
 
     @torch.no_grad()
     def validation_loss(self, dataloader, sample_posterior: bool = False, seed: int = 0) -> dict:
