@@ -630,9 +630,13 @@ int ldmseg_profile_dump(const char* path);
  * key 24 = tuning: every plain-store igemm launch runs entry (v & 0xff) of the instantiation list with (v >> 8) K slices as if the
  * launch table held that entry (-1 = off; unlike key 5 the extra-tap / phase-conv routes stay);
  * key 25 = separate-encoder handles in ldmseg_sample_loop: 0 (default) the image branch runs once per call, 1 in every step
- * (the reference's form; results are bit-identical). */
+ * (the reference's form; results are bit-identical);
+ * key 26 = weight gradient (ldmseg_vae_decode_backward / _encode_backward, ldmseg_op_conv*_wgrad*): the CU count handed to the
+ * launch chooser, 0 (default; values below 0 count as 0) = the device's.  A count below the item count makes every workgroup walk
+ * several (tile, slice) items - the path a smaller device or partition takes; the slicing, the scratch and every result bit stay
+ * what they are (csrc/wgrad_plan.h; tests). */
 int ldmseg_debug_set(int key, int value);
-/* current value of a knob (keys 1, 8, 9, 11, 12, 14, 15, 16, 19, 20, 21, 22, 23, 25); key -1 = the shipped default of key 1.  Tests restore through this, never a literal.
+/* current value of a knob (keys 1, 8, 9, 11, 12, 14, 15, 16, 19, 20, 21, 22, 23, 25, 26); key -1 = the shipped default of key 1.  Tests restore through this, never a literal.
  * key 10 = number of cooperative-GroupNorm workgroups that took the self-computing path in ldmseg_op_* launches so far. */
 int ldmseg_debug_get(int key);
 

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "runtime.h"
+#include "vae_bwd.h"
 
 using namespace ldmseg;
 using namespace ldmseg::rt;
@@ -56,6 +57,7 @@ const Knob kKnobs[] = {
        "Default 5", [](int v) { igemm_set_cf_mode(v); }, [] { return igemm_get_cf_mode(); }, true},
   {24, "igemm tuning: launch-table override, -1 = off (igemm_set_table_override)", [](int v) { igemm_set_table_override(v); }, nullptr, true},
   {25, "1: ldmseg_sample_loop runs the separate image encoder in every step; default 0 = once per call", [](int v) { g_sepenc_every_step = v ? 1 : 0; }, [] { return g_sepenc_every_step; }, false},
+  {26, "weight gradient: CU count handed to the launch chooser, 0 = the device's (tests: workgroups that walk several items)", [](int v) { wgrad_set_cus(v); }, [] { return wgrad_get_cus(); }, false},
 };
 // clang-format on
 

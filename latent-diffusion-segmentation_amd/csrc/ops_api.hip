@@ -1155,7 +1155,7 @@ static float* stage_phase_major(Stage& st, const float* dy, int B, int Co, int H
 }
 static int op_wgrad_run(Stage& st, WgradParams& wp, int form, int n_real, int c_real, int co, float* dw) {
   WgradPlan pl;
-  if (wgrad_plan(wp, num_cus(), &pl)) return -2;
+  if (wgrad_plan(wp, wgrad_cus(), &pl)) return -2;
   wp.partial = (float*)st.buf(wgrad_partial_bytes(wp, pl));
   if (st.status) return st.status;
   const int r = launch_wgrad(wp, pl, st.s);

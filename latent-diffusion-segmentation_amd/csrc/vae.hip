@@ -424,7 +424,7 @@ int run_wgrad(Exec& ex, const WgradJob& j, float* out) {
   wp.dy = j.dy; wp.ldy = j.ldy; wp.x = j.x; wp.B = ex.B; wp.H = j.H; wp.W = j.W; wp.N = j.N; wp.C = j.C; wp.taps = j.taps;
   wp.x3 = ex.x3 ? 1 : 0; wp.stride = j.stride; wp.by_width = j.by_width;
   WgradPlan pl;
-  if (wgrad_plan(wp, num_cus(), &pl)) return fail(LDMSEG_E_SHAPE, "weight gradient: unsupported shape");
+  if (wgrad_plan(wp, wgrad_cus(), &pl)) return fail(LDMSEG_E_SHAPE, "weight gradient: unsupported shape");
   wp.partial = (float*)ws->scratch(wgrad_partial_bytes(wp, pl));
   const double P = j.stride == 2 ? (double)ex.B * ((j.H - 1) / 2 + 1) * ((j.W - 1) / 2 + 1) : (double)ex.B * j.H * j.W;
   const int r = ex.launch("launch_wgrad failed", 0, 2.0 * P * j.n_real * j.c_real * j.taps, P * (j.N + j.C) * 4.0 * pl.tiles / pl.n_tiles,

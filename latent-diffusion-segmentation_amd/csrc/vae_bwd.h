@@ -27,6 +27,11 @@ struct WgradParams {
   int by_width = 0;
 };
 int wgrad_plan(const WgradParams& p, int cus, WgradPlan* pl);
+// The CU count the callers of wgrad_plan hand it: the device's, or what debug key 26 names (> 0; tests: a grid smaller than the
+// item count, i.e. workgroups that walk several items).  The slicing does not depend on it, so neither do the scratch or the bits.
+void wgrad_set_cus(int cus);          // <= 0: the device's
+int wgrad_get_cus();                  // the override, 0 = none
+int wgrad_cus();
 size_t wgrad_partial_bytes(const WgradParams& p, const WgradPlan& pl);
 int launch_wgrad(const WgradParams& p, const WgradPlan& pl, hipStream_t s);
 // out = the slabs added in slice order, in the state-dict layout: form 0 = Conv2d [n_real][c_real][3][3] (taps 9) or Linear

@@ -683,6 +683,10 @@ int wgrad_plan(const WgradParams& p, int cus, WgradPlan* pl) {
   if (!p.by_width) return p.stride == 1 ? wgrad_choose(WgradDesc{p.B * p.H * p.W, p.N, p.C, p.taps, p.x3}, cus, pl) : -2;
   return wgrad_choose_ex(WgradDescEx{p.B * out_dim(p.H, p.stride) * out_dim(p.W, p.stride), p.N, p.C, p.taps, p.x3, p.stride}, cus, pl);
 }
+static int g_wgrad_cus = 0;          // debug key 26
+void wgrad_set_cus(int cus) { g_wgrad_cus = cus < 0 ? 0 : cus; }
+int wgrad_get_cus() { return g_wgrad_cus; }
+int wgrad_cus() { return g_wgrad_cus > 0 ? g_wgrad_cus : num_cus(); }
 size_t wgrad_partial_bytes(const WgradParams& p, const WgradPlan& pl) {
   return (size_t)pl.slices * p.N * p.taps * p.C * sizeof(float);
 }

@@ -30,6 +30,8 @@ def _cases():
 
 
 def _id(v):
+    if isinstance(v, tuple):
+        return "x".join(map(str, v))
     return "-".join(f"{k}{x}" for k, x in v.items()) if isinstance(v, dict) else str(v)
 
 
@@ -41,6 +43,55 @@ def test_backward_operator_vs_fp64_autograd(lib, kind, q, mode):
 
 def test_layernorm_backward_in_row_order(lib):
     G.check_ln(lib, dict(M=2 * 12 * 12, C=256, H2=12), "fp32", pm=0)
+
+
+# ---- off the configurations' shapes.  GroupNorm + SiLU backward (B, C, HW): gn_silu_bwd_stats_kernel gives a channel PS = 512 / cpg
+# threads - cpg 1 with fewer pixels than PS; cpg 3 and 5, which do not divide 512 (510 of 512 threads active, the idle ones inside
+# the tree reduction); cpg 16; one pixel per channel
+GN_OFF = [(2, 32, 5), (3, 96, 35), (2, 160, 577), (1, 512, 100), (2, 256, 1)]
+
+
+@pytest.mark.parametrize("shape", GN_OFF, ids=_id)
+def test_groupnorm_backward_off_the_configurations(lib, shape):
+    B, C, HW = shape
+    G.check_gn(lib, dict(B=B, C=C, HW=HW), "fp32")
+
+
+def test_groupnorm_backward_far_from_zero(lib):
+    """every channel mean 1000, deviation 1: the statistics pass takes E[x^2] - E[x]^2 (in fp64); the reference sees the same fp32
+    inputs, so the bound is unchanged"""
+    G.check_gn(lib, dict(B=2, C=256, HW=144, far=1), "fp32")
+
+
+# LayerNorm2d + SiLU backward (M, C, pm, H2, W2): 1, 3 and 16 channels per lane; a second block of one row (65 = 64 + 1); the
+# phase-major store on maps that are not square - a swapped H2 / W2 in the row index moves rows there
+LN_OFF = [(1, 64, 0, 2, 2), (3, 192, 0, 2, 2), (65, 1024, 0, 2, 2), (2 * 4 * 6, 128, 1, 4, 6), (3 * 6 * 2, 256, 1, 6, 2)]
+
+
+@pytest.mark.parametrize("shape", LN_OFF, ids=_id)
+def test_layernorm_backward_off_the_configurations(lib, shape):
+    M, C, pm, H2, W2 = shape
+    G.check_ln(lib, dict(M=M, C=C, H2=H2, W2=W2), "fp32", pm=pm)
+
+
+# transposed conv (B, Ci, Co, H, W): weight, bias and data gradient on maps that are not square (stage_phase_major's H and W)
+CONVT_OFF = [(3, 64, 32, 3, 5), (2, 256, 256, 2, 6)]
+# ldmseg_op_conv_wgrad + ldmseg_op_conv_dgrad (B, Ci, Co, H, W, NCHW epilogue)
+CONV_OFF = [(3, 4, 256, 5, 7, 1), (2, 256, 128, 6, 10, 0)]
+
+
+@pytest.mark.parametrize("mode", R.MODES)
+@pytest.mark.parametrize("shape", CONVT_OFF, ids=_id)
+def test_transposed_conv_gradients_on_a_map_that_is_not_square(lib, shape, mode):
+    B, Ci, Co, H, W = shape
+    G.check_convt(lib, dict(B=B, Ci=Ci, Co=Co, H=H, W=W), mode)
+
+
+@pytest.mark.parametrize("mode", R.MODES)
+@pytest.mark.parametrize("shape", CONV_OFF, ids=_id)
+def test_conv_gradients_on_a_map_that_is_not_square(lib, shape, mode):
+    B, Ci, Co, H, W, nchw = shape
+    G.check_conv(lib, dict(B=B, Ci=Ci, Co=Co, H=H, W=W, nchw_dx=nchw), mode)
 
 
 def test_weight_gradient_is_repeatable_and_modes_differ_only_in_rounding(lib):

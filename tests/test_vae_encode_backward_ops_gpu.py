@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 import vae_backward_run as G
 import vae_encode_backward_ref as R
+from wgrad_cases import NARROW, STRIDE2      # (B, Ci, Co, H, W); the CPU suite reads them too
 
 pytestmark = pytest.mark.gpu
 P, dev, DEV = G.P, G.dev, G.DEV
@@ -21,25 +22,9 @@ def lib():
     return _lib.lib()
 
 
-def _conv_case(B, Ci, Co, H, W, stride):
-    g = G._gen("enc-conv", B, Ci, Co, H, W, stride)
-    x = torch.randn(B, Ci, H, W, generator=g)
-    w = torch.randn(Co, Ci, 3, 3, generator=g) / (9 * Ci) ** 0.5
-    b = torch.randn(Co, generator=g)
-    xd, wd, bd = (t.double().requires_grad_(True) for t in (x, w, b))
-    y = F.conv2d(xd, wd, bd, stride=stride, padding=1)
-    dy = torch.randn(y.shape, generator=g)
-    rx, rw, rb = torch.autograd.grad(y, [xd, wd, bd], dy.double())
-    return x, w, dy, rx, rw, rb
+_conv_case = R.conv_case          # (shared with tests/test_wgrad_kernels_gpu.py)
 
 
-# (B, Ci, Co, H, W): tiles 32 x 32, 64 x 64 and 32 x 32 with 7 real input channels (25 padded channels that never reach dW);
-# maps 16^2, 24^2 and the odd 5 x 7: a partial pixel step, borders a large share
-NARROW = [(1, 32, 32, 16, 16), (2, 32, 32, 24, 24), (3, 32, 32, 5, 7), (2, 64, 64, 16, 16), (1, 64, 64, 24, 24), (3, 64, 64, 5, 7),
-          (2, 7, 32, 16, 16), (1, 7, 32, 24, 24), (3, 7, 32, 5, 7)]
-# 32 -> 64 runs on the all-taps tile (64 x 32), the wider ones on one tile per tap; 7 -> 64 on the odd map: all-taps with the bottom
-# and right padding taps
-STRIDE2 = [(2, 32, 64, 16, 16), (3, 7, 64, 5, 7), (2, 64, 128, 12, 12), (2, 128, 256, 6, 6), (3, 128, 256, 5, 7)]
 
 
 @pytest.mark.parametrize("mode", R.MODES)
@@ -97,6 +82,10 @@ def test_silu_backward_vs_fp64(lib):
     g = torch.Generator().manual_seed(3)
     u = (torch.rand(n, generator=g) * 2 - 1) * 30.0
     u[:4] = torch.tensor([0.0, -30.0, 30.0, 1e-4])
+    # the ends of the range: exp(-u) overflows fp32 below u = -88.7 (and underflows above 88), and tiny arguments
+    ends = torch.tensor([88.0, -88.0, 89.0, -89.0, 100.0, -100.0, 1e4, -1e4])
+    u[4:12] = ends
+    u[12:76] = torch.logspace(-30, -20, 64)
     da = torch.randn(n, generator=g)
     ud = u.double().requires_grad_(True)
     ref, = torch.autograd.grad(F.silu(ud), [ud], da.double())
@@ -105,6 +94,12 @@ def test_silu_backward_vs_fp64(lib):
     assert G.report("silu_bwd", R.metric(du, ref)) < 1e-5        # elementwise fp32: a few ulp of the largest value
     sig = torch.sigmoid(u.double())
     assert torch.allclose(ref, da.double() * sig * (1 + u.double() * (1 - sig)))
+    du = du.cpu()
+    assert torch.isfinite(du).all()
+    low, high = u <= -100, u >= 100
+    assert low.sum() == 2 and high.sum() == 2
+    assert torch.equal(du[low], 0 * da[low])                     # a zero as a number (0 * da: either sign), no NaN from 0 * inf
+    assert R.metric(du[high], da[high].double()) < 1e-5
 
 
 @pytest.mark.parametrize("with_noise", [True, False])

@@ -5,6 +5,7 @@ import pytest
 
 import vae_backward_ref as RD
 import vae_encode_backward_ref as R
+import wgrad_cases as WC
 
 STEP, MIN_STEPS, TARGET = 32, 8, 256
 WORKLOAD = ("seg", 8, 512)
@@ -96,6 +97,73 @@ def test_gpu_shapes_hold_a_single_slice_and_a_multi_slice_full_resolution_layer(
         slices[name, B, H] = int(R.wgrad_plan_ex(lib, P, N, C, taps, stride)[2]["slices"])
     assert slices["seg", 1, 16] == 1
     assert slices["seg", 2, 24] > 1 and slices["seg", 3, 40] > 1
+
+
+def _names(lib, descs, x3):
+    return {R.wgrad_plan_ex(lib, P, N, C, taps, stride, x3)[1].split()[0] for P, N, C, taps, stride in descs}
+
+
+def _names_before(lib, x3):
+    """kernel names of the launches the suite compared with fp64 before tests/wgrad_cases.py had lists of its own: NARROW, STRIDE2
+    and the two encoder configurations at the shapes of tests/test_vae_encode_backward_gpu.py"""
+    descs = [WC.desc(B, Ci, Co, H, W, 1) for B, Ci, Co, H, W in WC.NARROW] + [WC.desc(B, Ci, Co, H, W, 2) for B, Ci, Co, H, W in WC.STRIDE2]
+    for name, B, H in R.SHAPES:
+        descs += R.wgrad_descs(name, B, H)
+    assert {name for name, _, _ in R.SHAPES} == set(R.CONFIGS)
+    return _names(lib, descs, x3)
+
+
+@pytest.mark.parametrize("x3", [0, 1])
+def test_every_kernel_the_chooser_can_name_has_a_gpu_case(lib, x3):
+    """ldmseg_op_wgrad_plan_ex over every pair of storage widths 32 .. 1024 of a 3x3 layer, both strides: 18 kernel names per mode,
+    each of them launched and compared with fp64 by a GPU test - a kernel added to the chooser without a case fails here.
+    launch_wgrad can also dispatch the per-tap form with BOTH tiles <= 64 (4 tile pairs x 2 strides x 2 modes = 16 instantiations):
+    the chooser gives every such 3x3 layer the all-taps tile and no entry passes by_width with one tap, so those 16 have no caller
+    and no test; the enumeration never names them."""
+    fam = "x3" if x3 else "f32"
+    named = set()
+    for stride in (1, 2):
+        for N in range(32, 1025, 32):
+            for C in range(32, 1025, 32):
+                code, line, _, _ = R.wgrad_plan_ex(lib, 1152, N, C, 9, stride, x3)
+                assert code == 0, (N, C, stride)
+                named.add(line.split()[0])
+    print(f"{fam}: {len(named)} kernel names: " + " ".join(sorted(named)))
+    assert len(named) == 18
+    for tn in (32, 64):
+        for tc in (32, 64):
+            for s2 in ("", "/s2"):
+                assert f"wgrad<{fam},{tn},{tc}>/taps9{s2}" not in named and f"wgrad9<{fam},{tn},{tc}>/taps9{s2}" in named
+    before = _names_before(lib, x3)
+    oracle = _names(lib, [WC.desc(*s) for s in WC.launches()], x3)          # tests/test_wgrad_kernels_gpu.py, against fp64
+    missing = {f"wgrad9<{fam},64,32>/taps9", f"wgrad9<{fam},32,64>/taps9/s2", f"wgrad<{fam},64,128>/taps9", f"wgrad<{fam},64,128>/taps9/s2",
+               f"wgrad<{fam},128,32>/taps9", f"wgrad<{fam},128,32>/taps9/s2", f"wgrad<{fam},128,64>/taps9", f"wgrad<{fam},32,128>/taps9/s2"}
+    assert len(before) == 10 and named - before == missing
+    assert missing <= oracle
+    assert named == before | oracle, sorted(named ^ (before | oracle))
+    assert named == _names(lib, [WC.desc(*s) for s in WC.walk_launches()], x3)        # and each has a multi-slice item-walk case
+
+
+def test_the_multi_slice_maps_are_cut_into_four_slices_and_the_wide_case_outnumbers_the_cus(lib):
+    for shape in WC.launches() + WC.walk_launches():
+        f = _ints(R.wgrad_plan_ex(lib, *WC.desc(*shape))[2])
+        if (shape[0], shape[3], shape[4]) == WC.ODD:
+            assert f["slices"] == 1
+        else:
+            assert f["slices"] == 4 and f["steps"] == 36, shape
+    B, H, W = WC.ODD
+    f = _ints(R.wgrad_plan_ex(lib, *WC.desc(B, WC.BIG[0], WC.BIG[1], H, W, WC.BIG[2]))[2])
+    assert f["tiles"] == 270 and f["one"] == 0 and f["grid"] == 256
+
+
+def test_the_chooser_cu_key_reads_back_and_counts_negative_values_as_zero(lib):
+    """debug key 26 (the CU count handed to the chooser; tests/test_wgrad_kernels_gpu.py): default 0 = the device's"""
+    try:
+        assert lib.ldmseg_debug_get(26) == 0
+        assert lib.ldmseg_debug_set(26, 7) == 0 and lib.ldmseg_debug_get(26) == 7
+        assert lib.ldmseg_debug_set(26, -3) == 0 and lib.ldmseg_debug_get(26) == 0
+    finally:
+        lib.ldmseg_debug_set(26, 0)
 
 
 def test_refusals(lib):

@@ -99,6 +99,11 @@ def _ok(lib, code):
     torch.cuda.synchronize()
 
 
+def _other(h, w):
+    """the second side of a map as part of a seed key, where it differs from the first (square maps keep the seeds they had)"""
+    return () if w == h else (w,)
+
+
 def report(what, e):
     print(f"{what}: {e:.3e}")
     return e
@@ -106,65 +111,66 @@ def report(what, e):
 
 def check_conv(lib, q, mode, forward=False):
     """3x3 conv: weight + bias gradient, data gradient (the latents' through the fp32 NCHW epilogue) vs F.conv2d under fp64 autograd"""
-    B, Ci, Co, H = q["B"], q["Ci"], q["Co"], q["H"]
-    g = _gen("conv", B, Ci, Co, H)
-    x = torch.randn(B, Ci, H, H, generator=g)
+    B, Ci, Co, H, W = q["B"], q["Ci"], q["Co"], q["H"], q.get("W", q["H"])
+    g = _gen("conv", B, Ci, Co, H, *_other(H, W))
+    x = torch.randn(B, Ci, H, W, generator=g)
     w = torch.randn(Co, Ci, 3, 3, generator=g) / (9 * Ci) ** 0.5
     b = torch.randn(Co, generator=g)
-    dy = torch.randn(B, Co, H, H, generator=g)
+    dy = torch.randn(B, Co, H, W, generator=g)
     xd, wd, bd = (t.double().requires_grad_(True) for t in (x, w, b))
     y = F.conv2d(xd, wd, bd, padding=1)
     rx, rw, rb = torch.autograd.grad(y, [xd, wd, bd], dy.double())
     dt = OP_DTYPE[mode]
     dx_, dw_, db_, dy_ = dev(x), dev(w), dev(b), dev(dy)
     if forward:
-        out = torch.empty(B, Co, H, H, device=DEV)
-        _ok(lib, lib.ldmseg_op_vae_conv(P(dx_), P(dw_), P(db_), None, B, Ci, H, H, Co, 3, 1, -1, 0, 0 if q["nchw_dx"] else 2, 0, dt, P(out), None))
+        out = torch.empty(B, Co, H, W, device=DEV)
+        _ok(lib, lib.ldmseg_op_vae_conv(P(dx_), P(dw_), P(db_), None, B, Ci, H, W, Co, 3, 1, -1, 0, 0 if q["nchw_dx"] else 2, 0, dt, P(out), None))
         assert report(f"conv fwd {q} {mode}", R.metric(out, y.detach())) < R.BOUND
-    gw, gb = torch.empty(Co, Ci, 3, 3, device=DEV), torch.empty(Co, device=DEV)
-    _ok(lib, lib.ldmseg_op_conv_wgrad(P(dx_), P(dy_), B, Ci, H, H, Co, dt, P(gw), P(gb), None))
+    gw, gb = torch.full((Co, Ci, 3, 3), float("nan"), device=DEV), torch.full((Co,), float("nan"), device=DEV)
+    _ok(lib, lib.ldmseg_op_conv_wgrad(P(dx_), P(dy_), B, Ci, H, W, Co, dt, P(gw), P(gb), None))
     assert report(f"conv wgrad {q} {mode}", R.metric(gw, rw)) < R.BOUND
     assert report(f"conv bgrad {q} {mode}", R.metric(gb, rb)) < R.BOUND
-    gx = torch.empty(B, Ci, H, H, device=DEV)
-    _ok(lib, lib.ldmseg_op_conv_dgrad(P(dy_), P(dw_), B, Ci, H, H, Co, q["nchw_dx"], dt, P(gx), None))
+    gx = torch.full((B, Ci, H, W), float("nan"), device=DEV)
+    _ok(lib, lib.ldmseg_op_conv_dgrad(P(dy_), P(dw_), B, Ci, H, W, Co, q["nchw_dx"], dt, P(gx), None))
     assert report(f"conv dgrad {q} {mode}", R.metric(gx, rx)) < R.BOUND
 
 
 def check_convt(lib, q, mode, forward=False):
-    B, Ci, Co, H = q["B"], q["Ci"], q["Co"], q["H"]
-    g = _gen("convt", B, Ci, Co, H)
-    x = torch.randn(B, Ci, H, H, generator=g)
+    B, Ci, Co, H, W = q["B"], q["Ci"], q["Co"], q["H"], q.get("W", q["H"])
+    g = _gen("convt", B, Ci, Co, H, *_other(H, W))
+    x = torch.randn(B, Ci, H, W, generator=g)
     w = torch.randn(Ci, Co, 2, 2, generator=g) / Ci ** 0.5
     b = torch.randn(Co, generator=g)
-    dy = torch.randn(B, Co, 2 * H, 2 * H, generator=g)
+    dy = torch.randn(B, Co, 2 * H, 2 * W, generator=g)
     xd, wd, bd = (t.double().requires_grad_(True) for t in (x, w, b))
     y = F.conv_transpose2d(xd, wd, bd, stride=2)
     rx, rw, rb = torch.autograd.grad(y, [xd, wd, bd], dy.double())
     dt = OP_DTYPE[mode]
     dx_, dw_, db_, dy_ = dev(x), dev(w), dev(b), dev(dy)
     if forward:
-        out = torch.empty(B, Co, 2 * H, 2 * H, device=DEV)
-        _ok(lib, lib.ldmseg_op_convt2(P(dx_), P(dw_), P(db_), B, Ci, H, H, Co, dt, P(out), None))
+        out = torch.empty(B, Co, 2 * H, 2 * W, device=DEV)
+        _ok(lib, lib.ldmseg_op_convt2(P(dx_), P(dw_), P(db_), B, Ci, H, W, Co, dt, P(out), None))
         assert report(f"convt fwd {q} {mode}", R.metric(out, y.detach())) < R.BOUND
-    gw, gb = torch.empty(Ci, Co, 2, 2, device=DEV), torch.empty(Co, device=DEV)
-    _ok(lib, lib.ldmseg_op_convt2_wgrad(P(dx_), P(dy_), B, Ci, H, H, Co, dt, P(gw), P(gb), None))
+    gw, gb = torch.full((Ci, Co, 2, 2), float("nan"), device=DEV), torch.full((Co,), float("nan"), device=DEV)
+    _ok(lib, lib.ldmseg_op_convt2_wgrad(P(dx_), P(dy_), B, Ci, H, W, Co, dt, P(gw), P(gb), None))
     assert report(f"convt wgrad {q} {mode}", R.metric(gw, rw)) < R.BOUND
     assert report(f"convt bgrad {q} {mode}", R.metric(gb, rb)) < R.BOUND
-    gx = torch.empty(B, Ci, H, H, device=DEV)
-    _ok(lib, lib.ldmseg_op_convt2_dgrad(P(dy_), P(dw_), B, Ci, H, H, Co, dt, P(gx), None))
+    gx = torch.full((B, Ci, H, W), float("nan"), device=DEV)
+    _ok(lib, lib.ldmseg_op_convt2_dgrad(P(dy_), P(dw_), B, Ci, H, W, Co, dt, P(gx), None))
     assert report(f"convt dgrad {q} {mode}", R.metric(gx, rx)) < R.BOUND
 
 
-def phase_major(t, B, H2, C):
-    """[B * H2 * H2, C] rows (image, Y, X) -> [B, H2/2, H2/2, 2x2, C] rows"""
-    return t.view(B, H2 // 2, 2, H2 // 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, C)
+def phase_major(t, B, H2, C, W2=None):
+    """[B * H2 * W2, C] rows (image, Y, X) -> [B, H2/2, W2/2, 2x2, C] rows (W2 = H2 where not given)"""
+    W2 = H2 if W2 is None else W2
+    return t.view(B, H2 // 2, 2, W2 // 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, C)
 
 
 def check_ln(lib, q, mode, forward=False, pm=1):
     """LayerNorm2d + SiLU backward over pixel rows, stored phase-major as the decoder's backward stores it (pm = 0: in row order)"""
-    M, Cn, H2 = q["M"], q["C"], q["H2"]
-    B = M // (H2 * H2)
-    g = _gen("ln", M, Cn)
+    M, Cn, H2, W2 = q["M"], q["C"], q["H2"], q.get("W2", q["H2"])
+    B = M // (H2 * W2)
+    g = _gen("ln", M, Cn, *_other(H2, W2))
     x = torch.randn(M, Cn, generator=g) * 3 + 1
     x[::7] *= 20.0                                             # rows of very different scale
     gamma = 1 + 0.1 * torch.randn(Cn, generator=g)
@@ -178,9 +184,9 @@ def check_ln(lib, q, mode, forward=False, pm=1):
         out = torch.empty(M, Cn, device=DEV)
         _ok(lib, lib.ldmseg_op_layernorm_io(P(dx_), P(dg_), P(db_), M, Cn, 1e-6, 1, 0, 0, P(out), None))
         assert report(f"ln fwd {q}", R.metric(out, y.detach())) < R.BOUND
-    gx, gg, gb = torch.full((M, Cn), float("nan"), device=DEV), torch.empty(Cn, device=DEV), torch.empty(Cn, device=DEV)
-    _ok(lib, lib.ldmseg_op_layernorm_silu_bwd(P(dx_), P(dy_), P(dg_), P(db_), M, Cn, 1e-6, pm, H2, H2, P(gx), P(gg), P(gb), None))
-    want = phase_major(rx, B, H2, Cn) if pm else rx
+    gx, gg, gb = (torch.full(s, float("nan"), device=DEV) for s in ((M, Cn), (Cn,), (Cn,)))
+    _ok(lib, lib.ldmseg_op_layernorm_silu_bwd(P(dx_), P(dy_), P(dg_), P(db_), M, Cn, 1e-6, pm, H2, W2, P(gx), P(gg), P(gb), None))
+    want = phase_major(rx, B, H2, Cn, W2) if pm else rx
     assert report(f"ln bwd dx {q} pm={pm}", R.metric(gx, want)) < R.BOUND
     assert report(f"ln bwd dgamma {q}", R.metric(gg, rg)) < R.BOUND
     assert report(f"ln bwd dbeta {q}", R.metric(gb, rb)) < R.BOUND
@@ -188,10 +194,12 @@ def check_ln(lib, q, mode, forward=False, pm=1):
 
 def check_gn(lib, q, mode, forward=False):
     B, Cn, HW = q["B"], q["C"], q["HW"]
-    g = _gen("gn", B, Cn, HW)
+    g = _gen("gn", B, Cn, HW, *(("far",) if q.get("far") else ()))
     grp = torch.arange(Cn) // (Cn // 32)
     mean = 2.0 - 4.0 * (grp % 2).float() + 0.5 * torch.randn(Cn, generator=g)      # neighbouring groups differ
     std = 0.5 + 1.5 * (grp % 3).float()
+    if q.get("far"):                                           # every channel mean 1000, deviation 1: E[x^2] - E[x]^2 cancels 6 digits
+        mean, std = torch.full((Cn,), 1000.0), torch.ones(Cn)
     x = torch.randn(B, Cn, HW, generator=g) * std[None, :, None] + mean[None, :, None]
     gamma = 1 + 0.1 * torch.randn(Cn, generator=g)
     beta = 0.1 * torch.randn(Cn, generator=g)
@@ -204,7 +212,7 @@ def check_gn(lib, q, mode, forward=False):
         out = torch.empty(B, Cn, HW, device=DEV)
         _ok(lib, lib.ldmseg_op_groupnorm(P(dx_), None, P(dg_), P(db_), B, Cn, 0, HW, 1e-5, 1, 0, P(out), None))
         assert report(f"gn fwd {q}", R.metric(out, y.detach())) < R.BOUND
-    gx, gg, gb = torch.empty(B, Cn, HW, device=DEV), torch.empty(Cn, device=DEV), torch.empty(Cn, device=DEV)
+    gx, gg, gb = (torch.full(s, float("nan"), device=DEV) for s in ((B, Cn, HW), (Cn,), (Cn,)))
     _ok(lib, lib.ldmseg_op_groupnorm_silu_bwd(P(dx_), P(dy_), P(dg_), P(db_), B, Cn, HW, 1e-5, P(gx), P(gg), P(gb), None))
     assert report(f"gn bwd dx {q}", R.metric(gx, rx)) < R.BOUND
     assert report(f"gn bwd dgamma {q}", R.metric(gg, rg)) < R.BOUND

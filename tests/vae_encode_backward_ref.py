@@ -119,6 +119,21 @@ def wgrad_plan_ex(lib, P, N, C, taps, stride, x3=0, cus=CUS):
     return code, line, fields, macs.value
 
 
+def conv_case(B, Ci, Co, H, W, stride):
+    """(x, w, dy, and the fp64 gradients of x, w, b) of F.conv2d(x, w, b, stride, padding=1) under torch-CPU autograd, seeded"""
+    import zlib
+    import torch.nn.functional as F
+    g = torch.Generator().manual_seed(zlib.crc32(repr(("enc-conv", B, Ci, Co, H, W, stride)).encode()) & 0xffffff)
+    x = torch.randn(B, Ci, H, W, generator=g)
+    w = torch.randn(Co, Ci, 3, 3, generator=g) / (9 * Ci) ** 0.5
+    b = torch.randn(Co, generator=g)
+    xd, wd, bd = (t.double().requires_grad_(True) for t in (x, w, b))
+    y = F.conv2d(xd, wd, bd, stride=stride, padding=1)
+    dy = torch.randn(y.shape, generator=g)
+    rx, rw, rb = torch.autograd.grad(y, [xd, wd, bd], dy.double())
+    return x, w, dy, rx, rw, rb
+
+
 def posterior_case(B=2, l=6, seed=5):
     """moments whose logvar half holds values inside, outside and exactly on the clamp bounds [-30, 20]; noise; grad_z"""
     g = torch.Generator().manual_seed(seed)
