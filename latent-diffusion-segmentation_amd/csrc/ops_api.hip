@@ -1136,11 +1136,7 @@ static __global__ void phase_major_rows_kernel(const float* x, float* y, int H2,
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
     const int c = (int)(e % C);
     const size_t r = e / C;
-    const int hw = H2 * W2;
-    const int img = (int)(r / hw), rem = (int)(r - (size_t)img * hw);
-    const int Y = rem / W2, X = rem - Y * W2;
-    const size_t ro = (((size_t)img * (H2 >> 1) + (Y >> 1)) * (W2 >> 1) + (X >> 1)) * 4 + 2 * (Y & 1) + (X & 1);
-    y[ro * C + c] = x[e];
+    y[phase_major_row(r, H2, W2) * C + c] = x[e];
   }
 }
 static float* stage_phase_major(Stage& st, const float* dy, int B, int Co, int H, int W) {
@@ -1158,24 +1154,33 @@ static int op_wgrad_run(Stage& st, WgradParams& wp, int form, int n_real, int c_
   if (wgrad_plan(wp, wgrad_cus(), &pl)) return -2;
   wp.partial = (float*)st.buf(wgrad_partial_bytes(wp, pl));
   if (st.status) return st.status;
-  const int r = launch_wgrad(wp, pl, st.s);
-  return r ? r : launch_wgrad_finish(wp, pl, form, n_real, c_real, co, dw, st.s);
+  return launch_wgrad(wp, pl, {form, n_real, c_real, co, dw}, st.s);
+}
+// the bias gradient that follows a weight gradient: db[j] = the sum over the P rows of dy [P][lda] and q < Q of column q * qstride + j
+static int op_bias_colsum(Stage& st, const float* dy, int lda, int P, int Q, int qstride, int n, float* db) {
+  float* scratch = (float*)st.buf(colsum_scratch_bytes(P, lda));
+  if (st.status) return st.status;
+  return launch_colsum(dy, lda, P, lda, Q, qstride, n, scratch, db, st.s);
+}
+// grads of F.conv2d(x, w, b, stride=stride, padding=1) with respect to w and b (arguments checked by the entries)
+static int op_conv_wgrad(const float* x, const float* dy, int B, int Ci, int H, int W, int Co, int stride, WgradRule rule, int dtype, float* dw,
+                         float* db, void* stream) {
+  Stage st(stream, dtype, true);
+  const int Ho = conv_out_dim(H, stride), Wo = conv_out_dim(W, stride);
+  const int Cip = (int)rup(Ci, 32), Cop = (int)rup(Co, 32), P = B * Ho * Wo;
+  WgradParams wp;
+  wp.x = (const float*)st.nchw(x, B, Ci, H * W, Cip); wp.C = Cip;
+  wp.dy = (const float*)st.nchw(dy, B, Co, Ho * Wo, Cop); wp.ldy = Cop; wp.N = Cop;
+  wp.B = B; wp.H = H; wp.W = W; wp.taps = 9; wp.x3 = st.x3 ? 1 : 0; wp.stride = stride; wp.rule = rule;
+  const int r = op_wgrad_run(st, wp, 0, Co, Ci, 0, dw);
+  if (r || !db) return r;
+  return op_bias_colsum(st, wp.dy, Cop, P, 1, 0, Co, db);
 }
 
 // grads of F.conv2d(x, w, b, padding=1) with respect to w and b: x [B,Ci,H,W], dy [B,Co,H,W] -> dw [Co,Ci,3,3], db [Co] or NULL
 int ldmseg_op_conv_wgrad(const float* x, const float* dy, int B, int Ci, int H, int W, int Co, int dtype, float* dw, float* db, void* stream) {
   if (!x || !dy || !dw || B < 1 || Ci < 1 || Co < 1 || H < 1 || W < 1 || (dtype != 0 && dtype != 2 && dtype != 3)) return -2;
-  Stage st(stream, dtype, true);
-  const int Cip = (int)rup(Ci, 32), Cop = (int)rup(Co, 32), P = B * H * W;
-  WgradParams wp;
-  wp.x = (const float*)st.nchw(x, B, Ci, H * W, Cip); wp.C = Cip;
-  wp.dy = (const float*)st.nchw(dy, B, Co, H * W, Cop); wp.ldy = Cop; wp.N = Cop;
-  wp.B = B; wp.H = H; wp.W = W; wp.taps = 9; wp.x3 = st.x3 ? 1 : 0;
-  const int r = op_wgrad_run(st, wp, 0, Co, Ci, 0, dw);
-  if (r || !db) return r;
-  float* scratch = (float*)st.buf(colsum_scratch_bytes(P, Cop));
-  if (st.status) return st.status;
-  return launch_colsum(wp.dy, Cop, P, Cop, 1, 0, Co, scratch, db, st.s);
+  return op_conv_wgrad(x, dy, B, Ci, H, W, Co, 1, kWgradFixedTile, dtype, dw, db, stream);
 }
 // grads of F.conv_transpose2d(x, w, b, stride=2) (kernel 2): x [B,Ci,H,W], dy [B,Co,2H,2W] -> dw [Ci,Co,2,2], db [Co] or NULL
 int ldmseg_op_convt2_wgrad(const float* x, const float* dy, int B, int Ci, int H, int W, int Co, int dtype, float* dw, float* db, void* stream) {
@@ -1188,9 +1193,7 @@ int ldmseg_op_convt2_wgrad(const float* x, const float* dy, int B, int Ci, int H
   wp.B = B; wp.H = H; wp.W = W; wp.taps = 1; wp.x3 = st.x3 ? 1 : 0;
   const int r = op_wgrad_run(st, wp, 1, 4 * Co, Ci, Co, dw);
   if (r || !db) return r;
-  float* scratch = (float*)st.buf(colsum_scratch_bytes(P, 4 * Co));
-  if (st.status) return st.status;
-  return launch_colsum(wp.dy, 4 * Co, P, 4 * Co, 4, Co, Co, scratch, db, st.s);
+  return op_bias_colsum(st, wp.dy, 4 * Co, P, 4, Co, Co, db);
 }
 // grad of F.conv2d(x, w, padding=1) with respect to x, the way ldmseg_vae_decode_backward runs it: igemm on the transposed, rotated
 // packing.  dy [B,Co,H,W], w [Co,Ci,3,3] -> dx [B,Ci,H,W]; nchw_epi: the fp32 NCHW store epilogue (the latents' gradient)
@@ -1265,7 +1268,7 @@ int ldmseg_op_layernorm_silu_bwd(const float* x, const float* dy, const float* g
 int ldmseg_op_wgrad_plan(int P, int N, int C, int taps, int x3, int cus, char* buf, int n) {
   if (!buf || n < 1) return -2;
   WgradPlan pl;
-  const int r = wgrad_choose(WgradDesc{P, N, C, taps, x3}, cus, &pl);
+  const int r = wgrad_choose(WgradDesc{P, N, C, taps, x3}, kWgradFixedTile, cus, &pl);
   if (r == 0) std::snprintf(buf, (size_t)n, "%s", wgrad_plan_line(pl).c_str());
   return r;
 }
@@ -1276,18 +1279,7 @@ int ldmseg_op_conv_wgrad_ex(const float* x, const float* dy, int B, int Ci, int 
                             void* stream) {
   if (!x || !dy || !dw || B < 1 || Ci < 1 || Co < 1 || H < 1 || W < 1 || (stride != 1 && stride != 2) || (dtype != 0 && dtype != 2 && dtype != 3))
     return -2;
-  Stage st(stream, dtype, true);
-  const int Ho = stride == 2 ? (H - 1) / 2 + 1 : H, Wo = stride == 2 ? (W - 1) / 2 + 1 : W;
-  const int Cip = (int)rup(Ci, 32), Cop = (int)rup(Co, 32), P = B * Ho * Wo;
-  WgradParams wp;
-  wp.x = (const float*)st.nchw(x, B, Ci, H * W, Cip); wp.C = Cip;
-  wp.dy = (const float*)st.nchw(dy, B, Co, Ho * Wo, Cop); wp.ldy = Cop; wp.N = Cop;
-  wp.B = B; wp.H = H; wp.W = W; wp.taps = 9; wp.x3 = st.x3 ? 1 : 0; wp.stride = stride; wp.by_width = 1;
-  const int r = op_wgrad_run(st, wp, 0, Co, Ci, 0, dw);
-  if (r || !db) return r;
-  float* scratch = (float*)st.buf(colsum_scratch_bytes(P, Cop));
-  if (st.status) return st.status;
-  return launch_colsum(wp.dy, Cop, P, Cop, 1, 0, Co, scratch, db, st.s);
+  return op_conv_wgrad(x, dy, B, Ci, H, W, Co, stride, kWgradByWidth, dtype, dw, db, stream);
 }
 int ldmseg_op_conv_s2_wgrad(const float* x, const float* dy, int B, int Ci, int H, int W, int Co, int dtype, float* dw, float* db, void* stream) {
   return ldmseg_op_conv_wgrad_ex(x, dy, B, Ci, H, W, Co, 2, dtype, dw, db, stream);
@@ -1306,7 +1298,7 @@ int ldmseg_op_conv_s2_dgrad(const float* dy, const float* w, int B, int Ci, int 
   if (!dy || !w || !dx || B < 1 || Ci < 4 || Ci % 4 || Co < 1 || H < 1 || W < 1 || (dtype != 0 && dtype != 2 && dtype != 3)) return -2;
   Stage st(stream, dtype, true);
   hipStream_t s = st.s;
-  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  const int Ho = conv_out_dim(H, 2), Wo = conv_out_dim(W, 2);
   const int Cop = (int)rup(Co, 32), Np = (int)rup(4 * Ci, igemm_pick_bn(4 * Ci, EPI_CONVT2)), P = B * Ho * Wo;
   float* wp = (float*)st.buf((size_t)Np * 9 * Cop * sizeof(float));
   st.step([&] { return launch_pack_dgrad_conv_s2(w, wp, Co, Ci, Np, Cop, s) || (st.x3 == 2 && launch_split_planes(wp, (size_t)Np * 9 * Cop, s)); });
@@ -1333,11 +1325,11 @@ int ldmseg_op_silu_fwd(const float* u, int64_t n, float* a, void* stream) {
   if (!u || !a || n < 1) return -2;
   return launch_silu_fwd(u, a, (size_t)n, (hipStream_t)stream);
 }
-// ldmseg_op_wgrad_plan of the by-width rule (wgrad_choose_ex): P = the pixels of the OUTPUT map of a conv of stride 1 | 2
+// ldmseg_op_wgrad_plan of the by-width rule (kWgradByWidth): P = the pixels of the OUTPUT map of a conv of stride 1 | 2
 int ldmseg_op_wgrad_plan_ex(int P, int N, int C, int taps, int x3, int stride, int cus, char* buf, int n, int64_t* macs_per_pixel) {
   if (!buf || n < 1) return -2;
   WgradPlan pl;
-  const int r = wgrad_choose_ex(WgradDescEx{P, N, C, taps, x3, stride}, cus, &pl);
+  const int r = wgrad_choose(WgradDesc{P, N, C, taps, x3, stride}, kWgradByWidth, cus, &pl);
   if (r == 0) {
     std::snprintf(buf, (size_t)n, "%s", wgrad_plan_line(pl).c_str());
     if (macs_per_pixel) *macs_per_pixel = wgrad_plan_macs_per_pixel(pl);

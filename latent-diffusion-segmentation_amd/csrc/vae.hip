@@ -414,7 +414,7 @@ struct WgradJob {
   const float* dy; int ldy, N;        // dY [P][ldy], N columns taken
   const float* x; int C;              // X [P][C]
   int H, W, taps, form, n_real, c_real, co;      // H x W: the map X lives on
-  int stride = 1, by_width = 0;                  // the encoder's launches (WgradParams)
+  int stride = 1; WgradRule rule = kWgradFixedTile;   // the encoder's launches (WgradParams)
 };
 int run_wgrad(Exec& ex, const WgradJob& j, float* out) {
   if (!out) return 0;
@@ -422,21 +422,18 @@ int run_wgrad(Exec& ex, const WgradJob& j, float* out) {
   const size_t m = ws->mark();
   WgradParams wp;
   wp.dy = j.dy; wp.ldy = j.ldy; wp.x = j.x; wp.B = ex.B; wp.H = j.H; wp.W = j.W; wp.N = j.N; wp.C = j.C; wp.taps = j.taps;
-  wp.x3 = ex.x3 ? 1 : 0; wp.stride = j.stride; wp.by_width = j.by_width;
+  wp.x3 = ex.x3 ? 1 : 0; wp.stride = j.stride; wp.rule = j.rule;
   WgradPlan pl;
   if (wgrad_plan(wp, wgrad_cus(), &pl)) return fail(LDMSEG_E_SHAPE, "weight gradient: unsupported shape");
   wp.partial = (float*)ws->scratch(wgrad_partial_bytes(wp, pl));
-  const double P = j.stride == 2 ? (double)ex.B * ((j.H - 1) / 2 + 1) * ((j.W - 1) / 2 + 1) : (double)ex.B * j.H * j.W;
+  const double P = (double)ex.B * conv_out_dim(j.H, j.stride) * conv_out_dim(j.W, j.stride);
   const int r = ex.launch("launch_wgrad failed", 0, 2.0 * P * j.n_real * j.c_real * j.taps, P * (j.N + j.C) * 4.0 * pl.tiles / pl.n_tiles,
                           [&] {      // (no commas: the profile dump is a CSV)
                             return std::string(pl.x3 ? "wgrad x3" : "wgrad f32") + " P=" + std::to_string((long long)P) + " N=" + std::to_string(j.N) +
                                    " C=" + std::to_string(j.C) + " taps=" + std::to_string(j.taps) + " slices=" + std::to_string(pl.slices) +
                                    " grid=" + std::to_string(pl.grid_x) +
-                                   (j.by_width ? " tile=" + std::to_string(pl.tile_n) + "x" + std::to_string(pl.tile_c) + " stride=" + std::to_string(j.stride) : std::string());
-                          }, [&] {
-    const int e = launch_wgrad(wp, pl, ex.s);
-    return e ? e : launch_wgrad_finish(wp, pl, j.form, j.n_real, j.c_real, j.co, out, ex.s);
-  });
+                                   (j.rule == kWgradByWidth ? " tile=" + std::to_string(pl.tile_n) + "x" + std::to_string(pl.tile_c) + " stride=" + std::to_string(j.stride) : std::string());
+                          }, [&] { return launch_wgrad(wp, pl, {j.form, j.n_real, j.c_real, j.co, out}, ex.s); });
   ws->reset(m);
   return r;
 }
@@ -586,7 +583,7 @@ int vae_encode_backward_body(Exec& ex, ldmseg_vae* v, const float* x, float mul,
   float* gb[2] = {(float*)ws->scratch(gmax * sizeof(float)), (float*)ws->scratch(gmax * sizeof(float))};
   float* dm = (float*)ws->scratch((size_t)P8 * Cm * sizeof(float));
   TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, [] { return std::string("pack grad_moments"); }, [&] { return launch_pack_nchw(grad_moments, dm, B, l[last].Co, l8 * l8, Cm, 1.f, 0.f, dt, s); }));
-  TRY(run_wgrad(ex, {dm, Cm, Cm, (const float*)in[last].p, Ci8, l8, l8, 9, 0, l[last].Co, Ci8, 0, 1, 1}, g[kEncHeadSlot]));
+  TRY(run_wgrad(ex, {dm, Cm, Cm, (const float*)in[last].p, Ci8, l8, l8, 9, 0, l[last].Co, Ci8, 0, 1, kWgradByWidth}, g[kEncHeadSlot]));
   TRY(run_colsum(ex, dm, Cm, P8, 1, 0, l[last].Co, g[kEncHeadSlot + 1]));
   if (lowest == last && !g[kEncNormSlot] && !g[kEncNormSlot + 1]) return 0;
   {
@@ -609,8 +606,8 @@ int vae_encode_backward_body(Exec& ex, ldmseg_vae* v, const float* x, float mul,
   for (int k = last - 1; k >= lowest; --k) {
     const Act& xi = in[k];                       // the layer's input, on the map H x W of X
     const int Co = l[k].Co, st = l[k].stride;
-    const int Ho = st == 2 ? (xi.H - 1) / 2 + 1 : xi.H, Wo = st == 2 ? (xi.W - 1) / 2 + 1 : xi.W, Po = B * Ho * Wo;
-    TRY(run_wgrad(ex, {gb[cur], Co, Co, (const float*)xi.p, xi.C, xi.H, xi.W, 9, 0, Co, l[k].Ci, 0, st, 1}, g[enc_slot(k)]));
+    const int Ho = conv_out_dim(xi.H, st), Wo = conv_out_dim(xi.W, st), Po = B * Ho * Wo;
+    TRY(run_wgrad(ex, {gb[cur], Co, Co, (const float*)xi.p, xi.C, xi.H, xi.W, 9, 0, Co, l[k].Ci, 0, st, kWgradByWidth}, g[enc_slot(k)]));
     TRY(run_colsum(ex, gb[cur], Co, Po, 1, 0, Co, g[enc_slot(k) + 1]));
     if (k == lowest) break;
     const ConvW& d = v->enc_d[k];

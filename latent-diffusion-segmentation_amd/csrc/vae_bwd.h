@@ -12,10 +12,10 @@ namespace ldmseg {
 // Weight gradient of a 3x3 conv (pad 1, stride 1; taps = 9) or of any GEMM over pixel rows (taps = 1):
 //   slab[s][n][tap * C + c] = sum over the pixels p of slice s of dy[p][n] * x[p + tap][c]   (zero outside the image)
 // dy [P][ldy] (the first N columns are taken, N <= ldy), x [P][C] on B maps of H x W pixels (P = B H W).  The slabs
-// (wgrad_partial_bytes) are added in slice order by launch_wgrad_finish.
-// stride 2 (taps 9): x lives on B maps of H x W, dy on the conv's output maps Ho x Wo = ((H - 1) / 2 + 1) x ((W - 1) / 2 + 1), and
+// (wgrad_partial_bytes) are then added in slice order by the same call.
+// stride 2 (taps 9): x lives on B maps of H x W, dy on the conv's output maps Ho x Wo (conv_out_dim of H and W), and
 //   slab[s][n][tap * C + c] = sum over the OUTPUT pixels p = (oy, ox) of slice s of dy[p][n] * x[(2 oy + ty - 1, 2 ox + tx - 1)][c].
-// by_width: the tile follows the storage widths N and C (wgrad_choose_ex) instead of the decoder's fixed 128 x 128.
+// rule: the decoder's fixed 128 x 128 tile, or the tile that follows the storage widths N and C (wgrad_plan.h).
 struct WgradParams {
   const float* dy = nullptr; int ldy = 0;
   const float* x = nullptr;
@@ -24,8 +24,11 @@ struct WgradParams {
   int x3 = 0;
   float* partial = nullptr;
   int stride = 1;
-  int by_width = 0;
+  WgradRule rule = kWgradFixedTile;
 };
+// out = the slabs added in slice order, in the state-dict layout: form 0 = Conv2d [n_real][c_real][3][3] (taps 9) or Linear
+// [n_real][c_real] (taps 1); form 1 = ConvTranspose2d k2 s2 [c_real][co][2][2] from rows n = q * co + o (taps 1, n_real = 4 co)
+struct WgradOut { int form, n_real, c_real, co; float* out; };
 int wgrad_plan(const WgradParams& p, int cus, WgradPlan* pl);
 // The CU count the callers of wgrad_plan hand it: the device's, or what debug key 26 names (> 0; tests: a grid smaller than the
 // item count, i.e. workgroups that walk several items).  The slicing does not depend on it, so neither do the scratch or the bits.
@@ -33,10 +36,18 @@ void wgrad_set_cus(int cus);          // <= 0: the device's
 int wgrad_get_cus();                  // the override, 0 = none
 int wgrad_cus();
 size_t wgrad_partial_bytes(const WgradParams& p, const WgradPlan& pl);
-int launch_wgrad(const WgradParams& p, const WgradPlan& pl, hipStream_t s);
-// out = the slabs added in slice order, in the state-dict layout: form 0 = Conv2d [n_real][c_real][3][3] (taps 9) or Linear
-// [n_real][c_real] (taps 1); form 1 = ConvTranspose2d k2 s2 [c_real][co][2][2] from rows n = q * co + o (taps 1, n_real = 4 co)
-int launch_wgrad_finish(const WgradParams& p, const WgradPlan& pl, int form, int n_real, int c_real, int co, float* out, hipStream_t s);
+// two launches: the plan's kernel (wgrad_plan_name) into the slabs, then wgrad_finish<conv | convt> into o.out
+int launch_wgrad(const WgradParams& p, const WgradPlan& pl, const WgradOut& o, hipStream_t s);
+
+// Row r = (image, Y, X) of maps H2 x W2 in phase-major order [image][H2/2][W2/2][2x2]: what launch_ln_silu_bwd stores with pm = 1
+// and both transposed-conv gradients read.  R: the row index's type (int where the rows fit one).
+template <typename R>
+__host__ __device__ inline size_t phase_major_row(R r, int H2, int W2) {
+  const int hw = H2 * W2;
+  const int img = (int)(r / hw), rem = (int)(r - (R)img * hw);
+  const int Y = rem / W2, X = rem - Y * W2;
+  return (((size_t)img * (H2 >> 1) + (Y >> 1)) * (W2 >> 1) + (X >> 1)) * 4 + 2 * (Y & 1) + (X & 1);
+}
 
 // out[j] = sum_p a[p][q * qstride + j] over rows p and q < Q, for j < n: the bias gradient of a conv (Q = 1) or a transposed conv
 // (Q = 4, qstride = Co).  Rows are cut into colsum_slices(P) runs whose sums (scratch: colsum_scratch_bytes) are added in order.
@@ -46,7 +57,7 @@ int launch_colsum(const float* a, int lda, int P, int N, int Q, int qstride, int
 
 // LayerNorm over the last dim of [M][C] followed by SiLU, backward: x = the forward's INPUT, dy = d / d SiLU(LN(x)).  dx, dgamma,
 // dbeta as DESIGN 8.6.  pm: dx row r = (image, Y, X) of a map H2 x W2 is stored phase-major, at row
-// ((image * H2/2 + Y/2) * W2/2 + X/2) * 4 + 2 (Y & 1) + (X & 1) - the [B, H, W, 2x2, C] order both transposed-conv gradients read.
+// phase_major_row(r, H2, W2) - the [B, H, W, 2x2, C] order both transposed-conv gradients read.
 // dgamma / dbeta null: not computed.  scratch: ln_bwd_scratch_bytes(M, C).  C a multiple of 64, at most 1024.
 size_t ln_bwd_scratch_bytes(int M, int C);
 int launch_ln_silu_bwd(const float* x, const float* dy, const float* gamma, const float* beta, float* dx, float* dgamma, float* dbeta,

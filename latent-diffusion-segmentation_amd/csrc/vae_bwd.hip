@@ -21,7 +21,13 @@ struct WgradArgs {
   FastDiv fd_hw, fd_w;               // of Ho * Wo and Wo
 };
 
-// pixel `pix` of dY and tap offset (dy_, dx_) -> is the X pixel inside its image, and where (element offset / C)
+// A workgroup of four waves owns a 32 FA (n) x 32 FB (c) output tile over one slice of the pixel axis; a wave owns a quarter of it
+// as FA x FB MFMA tiles (waves 2 x 2: wave >> 1 picks the rows, wave & 1 the columns).  Four kernels: the per-tap forms own the
+// tile of ONE tap (FA, FB in 1 | 2 | 4), the all-taps forms the tile of all nine (FA, FB in 1 | 2); each in fp32 and in split bf16.
+// S is the conv's stride (dY lives on the output map).  The pieces they share come first, each stated once.
+
+// pixel `pix` of dY and tap offset (dy_, dx_) -> is the X pixel inside its image, and where (element offset / C).  A pixel whose
+// neighbour lies outside ITS image contributes zero (never the next row's or the next image's pixel).
 template <int S>
 __device__ __forceinline__ bool wgrad_x_pixel(const WgradArgs& p, int pix, int dy_, int dx_, long long shift, long long* xrow) {
   const int HWo = p.Ho * p.Wo;
@@ -38,38 +44,150 @@ __device__ __forceinline__ bool wgrad_x_pixel(const WgradArgs& p, int pix, int d
   return (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
 }
 
-// A workgroup of four waves owns a 32 FA (n) x 32 FB (c) output tile of one tap over one slice of the pixel axis (FA, FB in 1 | 2 | 4:
-// tiles of 32, 64, 128); a wave owns a quarter of it as FA x FB MFMA tiles.  S: the conv's stride (dY on the output map).  The tap's shift is applied to the pixel of the X operand; a pixel whose neighbour lies outside ITS image
-// contributes zero (never the next row's or the next image's pixel).  Rows past P and columns past N / C read nothing and count as zero.
-//
-// The fp32 form: the contraction index is the pixel and both operands are stored pixel-major, so lane (lg, lr) of a 16-channel
+// the K steps [s0, s1) of a slice
+__device__ __forceinline__ void wgrad_steps(const WgradArgs& p, int slice, int* s0, int* s1) {
+  *s0 = slice * p.steps_per_slice;
+  *s1 = min(p.steps, *s0 + p.steps_per_slice);
+}
+// work item of a per-tap form -> slice, tap, n tile, c tile, the tap's offset on the map of X (and as a pixel shift), its steps
+struct WgradItem { int slice, tap, nt, ct, dy_, dx_, s0, s1; long long shift; };
+__device__ __forceinline__ WgradItem wgrad_item(const WgradArgs& p, int item) {
+  WgradItem w;
+  w.slice = item / p.tiles;
+  const int tile = item - w.slice * p.tiles;
+  const int per_tap = p.n_tiles * p.c_tiles;
+  w.tap = tile / per_tap;
+  const int rem_t = tile - w.tap * per_tap;
+  w.nt = rem_t / p.c_tiles; w.ct = rem_t - w.nt * p.c_tiles;
+  w.dy_ = p.taps == 9 ? w.tap / 3 - 1 : 0; w.dx_ = p.taps == 9 ? w.tap % 3 - 1 : 0;
+  w.shift = (long long)w.dy_ * p.W + w.dx_;
+  wgrad_steps(p, w.slice, &w.s0, &w.s1);
+  return w;
+}
+
+template <int FA, int FB>
+__device__ __forceinline__ void wgrad_clear(f32x4 (&acc)[FA][FB]) {
+#pragma unroll
+  for (int a = 0; a < FA; ++a)
+#pragma unroll
+    for (int b = 0; b < FB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+// acc[a][b][j] = tile element (row row0 + 16 a + j, column col0 + 16 b) for the lane's row0 = n0 + 4 lg, col0 = c0 + lr: stored to
+// slab[row][col] (KK floats per row) where row < N and col < C.  Rows past N and columns past C were computed from zeros.
+template <int FA, int FB>
+__device__ __forceinline__ void wgrad_store(const f32x4 (&acc)[FA][FB], float* slab, int KK, int row0, int col0, int N, int C) {
+#pragma unroll
+  for (int a = 0; a < FA; ++a)
+#pragma unroll
+    for (int b = 0; b < FB; ++b) {
+      const int c = col0 + 16 * b;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int n = row0 + 16 * a + j;
+        if (n < N && c < C) slab[(size_t)n * KK + c] = acc[a][b][j];
+      }
+    }
+}
+
+// The fp32 forms: the contraction index is the pixel and both operands are stored pixel-major, so lane (lg, lr) of a 16-channel
 // fragment reads element [pixel(lg)][channel lr] straight from global memory and that value IS its operand of
-// v_mfma_f32_16x16x4_f32 (k = lg; eight MFMAs walk the 32 pixels of a step): no transpose, no LDS.
+// v_mfma_f32_16x16x4_f32 (k = lg; eight MFMAs walk the 32 pixels of a step): no transpose, no LDS.  Rows past P and channels past
+// the operand's width read nothing and count as zero: v[f] = does the lane's channel ch0 + 16 f of fragment f exist.
+template <int F>
+__device__ __forceinline__ void wgrad_valid(bool (&v)[F], int ch0, int width) {
+#pragma unroll
+  for (int f = 0; f < F; ++f) v[f] = ch0 + 16 * f < width;
+}
+
+// The split-bf16 forms (hi = bf16(x), lo = bf16(x - hi), products lo.hi + hi.lo + hi.hi as igemm's), the split made ONCE per
+// workgroup: the 256 threads load a 32-pixel x 32 F channel tile of an operand with 16-byte loads, split every value and store two
+// bf16 planes [pixel][channel] in LDS; the waves then take their operands with the transposed LDS read (ds_read_b64_tr_b16: a
+// 16-lane group reads 4 pixel rows x 16 channels and lane i receives channel i of the 4 rows), which makes the pixel axis the lane's
+// contiguous K axis.  Lane group lg takes pixel rows 4 lg .. 4 lg + 3 and 16 + 4 lg .. 16 + 4 lg + 3 of the step as its
+// k = 8 lg .. 8 lg + 7 - any K permutation is legal as long as both operands use the same one - so the two groups of a 32-lane half
+// read 8 consecutive rows; rows are the tile's bf16 width + 32 B apart (288, 160 or 96 bytes = 72, 40 or 24 banks: an odd multiple
+// of 8 in each case, so 8 consecutive rows start on the 8 different multiples of 8 banks), which spreads the 32 lanes' 8-byte reads
+// over all 64 banks.
+constexpr int wg_row(int F) { return 64 * F + 32; }       // bytes between pixel rows of a plane 32 F channels wide
+constexpr int wg_plane(int F) { return 32 * wg_row(F); }  // bytes of a plane
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) s16x4* lds_v4;
+
+// thread t holds float4 number t + 256 i (i < F) of a tile of 8 F float4 per pixel row: its pixel row and first channel
+struct X3Slot { int row, ch; };
+template <int F>
+__device__ __forceinline__ X3Slot x3_slot(int t, int i) {
+  const int idx = t + 256 * i;
+  return {idx / (8 * F), 4 * (idx % (8 * F))};
+}
+// the 16-byte load of a slot: the caller names the source row (its first element and whether it exists) and the channel bound
+__device__ __forceinline__ float4 x3_load(bool ok, const float* base, long long at) {
+  return ok ? *(const float4*)(base + at) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+__device__ __forceinline__ void split4(const float4& v, uint2& hi, uint2& lo) {
+  hi.x = pack_bf16x2(v.x, v.y);
+  hi.y = pack_bf16x2(v.z, v.w);
+  lo.x = pack_bf16x2(v.x - bits_f32(hi.x << 16), v.y - bits_f32(hi.x & 0xffff0000u));
+  lo.y = pack_bf16x2(v.z - bits_f32(hi.y << 16), v.w - bits_f32(hi.y & 0xffff0000u));
+}
+// the thread's F loaded float4, split and stored into the planes at byte offsets hi and lo of the LDS block
+template <int F>
+__device__ __forceinline__ void x3_stage(char* lds, int hi, int lo, const float4 (&r)[F], int t) {
+#pragma unroll
+  for (int i = 0; i < F; ++i) {
+    const X3Slot s = x3_slot<F>(t, i);
+    const int off = s.row * wg_row(F) + s.ch * 2;
+    uint2 h, l;
+    split4(r[i], h, l);
+    *(uint2*)(lds + hi + off) = h;
+    *(uint2*)(lds + lo + off) = l;
+  }
+}
+// transposed read: lane 4 q + pp of a group supplies row q, channels 4 pp .. 4 pp + 3 of the block -> the lane's byte offset
+template <int F>
+__device__ __forceinline__ int x3_lane_offset(int lg, int lr) { return (4 * lg + (lr >> 2)) * wg_row(F) + (lr & 3) * 8; }
+// the lane's k = 8 lg .. 8 lg + 7 of a 16-channel block: two transposed reads 16 pixel rows apart
+__device__ __forceinline__ bf16x8 x3_frag(const char* base, int row) {
+  const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(base));
+  const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(base + 16 * row));
+  const uint2 u0 = __builtin_bit_cast(uint2, v0), u1 = __builtin_bit_cast(uint2, v1);
+  return __builtin_bit_cast(bf16x8, make_uint4(u0.x, u0.y, u1.x, u1.y));
+}
+// the wave's F fragments of a hi / lo plane pair; at = the lane's offset + 2 bytes x the wave's first channel
+template <int F>
+__device__ __forceinline__ void x3_frags(bf16x8 (&h)[F], bf16x8 (&l)[F], const char* lds, int hi, int lo, int at) {
+#pragma unroll
+  for (int f = 0; f < F; ++f) {
+    h[f] = x3_frag(lds + hi + at + 32 * f, wg_row(F));
+    l[f] = x3_frag(lds + lo + at + 32 * f, wg_row(F));
+  }
+}
+// c += lo.hi + hi.lo + hi.hi, smallest products first: this order is the bits.  (One accumulator tile per call, the loops over the
+// wave's tiles stay in the kernels: taken as a whole FA x FB update next to x3_frags, the 64 x 64 all-taps kernel came out with
+// another interleaving of reads, writes and MFMAs and 12 more AGPRs.)
+__device__ __forceinline__ void x3_mac(f32x4& c, const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl) {
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
+}
+
+// ------------------------------------------------------------------ one tile per tap
+// fp32, register-only: per step a lane loads its 8 pixels x (FA + FB) channels, then the 8 FA FB MFMAs run.  The tap's shift is
+// applied to the pixel of the X operand.
 template <int FA, int FB, int S>
 __global__ __launch_bounds__(256) void wgrad_f32_kernel(const WgradArgs p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lr = lane & 15, lg = lane >> 4;
   const int KK = p.taps * p.C;
   for (int item = blockIdx.x; item < p.items; item += gridDim.x) {
-    const int slice = item / p.tiles, tile = item - slice * p.tiles;
-    const int per_tap = p.n_tiles * p.c_tiles;
-    const int tap = tile / per_tap, rem_t = tile - tap * per_tap;
-    const int nt = rem_t / p.c_tiles, ct = rem_t - nt * p.c_tiles;
-    const int n0 = nt * (32 * FA) + (wave >> 1) * (16 * FA), c0 = ct * (32 * FB) + (wave & 1) * (16 * FB);
-    const int dy_ = p.taps == 9 ? tap / 3 - 1 : 0, dx_ = p.taps == 9 ? tap % 3 - 1 : 0;
-    const long long shift = (long long)dy_ * p.W + dx_;
+    const WgradItem w = wgrad_item(p, item);
+    const int n0 = w.nt * (32 * FA) + (wave >> 1) * (16 * FA), c0 = w.ct * (32 * FB) + (wave & 1) * (16 * FB);
     bool nv[FA], cv[FB];
-#pragma unroll
-    for (int f = 0; f < FA; ++f) nv[f] = n0 + 16 * f + lr < p.N;
-#pragma unroll
-    for (int f = 0; f < FB; ++f) cv[f] = c0 + 16 * f + lr < p.C;
+    wgrad_valid(nv, n0 + lr, p.N);
+    wgrad_valid(cv, c0 + lr, p.C);
     f32x4 acc[FA][FB];
-#pragma unroll
-    for (int a = 0; a < FA; ++a)
-#pragma unroll
-      for (int b = 0; b < FB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int s0 = slice * p.steps_per_slice, s1 = min(p.steps, s0 + p.steps_per_slice);
-    for (int st = s0; st < s1; ++st) {
+    wgrad_clear(acc);
+    for (int st = w.s0; st < w.s1; ++st) {
       const int pbase = st * kWgradStep;
       float av[FA][8], bv[FB][8];
 #pragma unroll
@@ -78,7 +196,7 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(const WgradArgs p) {
         const bool pv = pix < p.P;
         bool xv = pv;
         long long xrow = pix;
-        if (p.taps == 9) xv = wgrad_x_pixel<S>(p, pix, dy_, dx_, shift, &xrow) && pv;
+        if (p.taps == 9) xv = wgrad_x_pixel<S>(p, pix, w.dy_, w.dx_, w.shift, &xrow) && pv;
         const float* ar = p.dy + (long long)pix * p.ldy + n0 + lr;
         const float* br = p.x + xrow * p.C + c0 + lr;
 #pragma unroll
@@ -93,154 +211,70 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(const WgradArgs p) {
 #pragma unroll
           for (int b = 0; b < FB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a][j], bv[b][j], acc[a][b], 0, 0, 0);
     }
-    // acc[a][b][j] = tile element (row n0 + 16 a + 4 lg + j, column c0 + 16 b + lr)
-    float* slab = p.partial + (size_t)slice * p.N * KK + (size_t)tap * p.C;
-#pragma unroll
-    for (int a = 0; a < FA; ++a)
-#pragma unroll
-      for (int b = 0; b < FB; ++b) {
-        const int c = c0 + 16 * b + lr;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int n = n0 + 16 * a + 4 * lg + j;
-          if (n < p.N && c < p.C) slab[(size_t)n * KK + c] = acc[a][b][j];
-        }
-      }
+    wgrad_store(acc, p.partial + (size_t)w.slice * p.N * KK + (size_t)w.tap * p.C, KK, n0 + 4 * lg, c0 + lr, p.N, p.C);
   }
 }
 
-// The split-bf16 form (hi = bf16(x), lo = bf16(x - hi), products lo.hi + hi.lo + hi.hi as igemm's), the split made ONCE per
-// workgroup: the 256 threads load the 32-pixel x 32 FA / 32 FB channel tiles of both operands with 16-byte loads (the next step's
-// loads are in flight under this step's MFMAs), split every value into hi = bf16(x) and lo = bf16(x - hi) and store four bf16
-// planes [pixel][channel] in LDS; the waves then take their operands with the transposed LDS read (ds_read_b64_tr_b16: a 16-lane
-// group reads 4 pixel rows x 16 channels and lane i receives channel i of the 4 rows), which makes the pixel axis the lane's
-// contiguous K axis.  Lane group lg takes pixel rows 4 lg .. 4 lg + 3 and 16 + 4 lg .. 16 + 4 lg + 3 of the step as its
-// k = 8 lg .. 8 lg + 7 - any K permutation is legal as long as both operands use the same one - so the two groups of a 32-lane half
-// read 8 consecutive rows; rows are the tile's bf16 width + 32 B apart (288, 160 or 96 bytes = 72, 40 or 24 banks: an odd multiple
-// of 8 in each case, so 8 consecutive rows start on the 8 different multiples of 8 banks), which spreads the 32 lanes' 8-byte reads
-// over all 64 banks.
-constexpr int wg_row(int F) { return 64 * F + 32; }     // bytes between pixel rows of a plane 32 F channels wide
-
-__device__ __forceinline__ void split4(const float4& v, uint2& hi, uint2& lo) {
-  hi.x = pack_bf16x2(v.x, v.y);
-  hi.y = pack_bf16x2(v.z, v.w);
-  lo.x = pack_bf16x2(v.x - bits_f32(hi.x << 16), v.y - bits_f32(hi.x & 0xffff0000u));
-  lo.y = pack_bf16x2(v.z - bits_f32(hi.y << 16), v.w - bits_f32(hi.y & 0xffff0000u));
-}
-
+// split bf16: four planes (A hi | A lo | B hi | B lo), two barriers per step; the next step's loads are in flight under this step's
+// MFMAs.
 template <int FA, int FB, int S>
 __global__ __launch_bounds__(256) void wgrad_x3_kernel(const WgradArgs p) {
-  constexpr int RA = wg_row(FA), RB = wg_row(FB), PA = 32 * RA, PB = 32 * RB;
-  __shared__ __attribute__((aligned(16))) char lds[2 * PA + 2 * PB];      // A hi | A lo | B hi | B lo
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) s16x4* lds_v4;
+  constexpr int PA = wg_plane(FA), PB = wg_plane(FB);
+  constexpr int A_HI = 0, A_LO = PA, B_HI = 2 * PA, B_LO = 2 * PA + PB;
+  __shared__ __attribute__((aligned(16))) char lds[2 * PA + 2 * PB];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int lr = lane & 15, lg = lane >> 4;
   const int KK = p.taps * p.C;
-  // transposed read: lane 4 q + pp of a group supplies row q, channels 4 pp .. 4 pp + 3 of the block
-  const int tr_a = (4 * lg + (lr >> 2)) * RA + (lr & 3) * 8, tr_b = (4 * lg + (lr >> 2)) * RB + (lr & 3) * 8;
+  const int wn = (wave >> 1) * (16 * FA), wc = (wave & 1) * (16 * FB);
+  const int at_a = x3_lane_offset<FA>(lg, lr) + 2 * wn, at_b = x3_lane_offset<FB>(lg, lr) + 2 * wc;
   for (int item = blockIdx.x; item < p.items; item += gridDim.x) {
-    const int slice = item / p.tiles, tile = item - slice * p.tiles;
-    const int per_tap = p.n_tiles * p.c_tiles;
-    const int tap = tile / per_tap, rem_t = tile - tap * per_tap;
-    const int nt = rem_t / p.c_tiles, ct = rem_t - nt * p.c_tiles;
-    const int n0b = nt * (32 * FA), c0b = ct * (32 * FB);
-    const int wn = (wave >> 1) * (16 * FA), wc = (wave & 1) * (16 * FB);
-    const int dy_ = p.taps == 9 ? tap / 3 - 1 : 0, dx_ = p.taps == 9 ? tap % 3 - 1 : 0;
-    const long long shift = (long long)dy_ * p.W + dx_;
+    const WgradItem w = wgrad_item(p, item);
+    const int n0b = w.nt * (32 * FA), c0b = w.ct * (32 * FB);
     f32x4 acc[FA][FB];
-#pragma unroll
-    for (int a = 0; a < FA; ++a)
-#pragma unroll
-      for (int b = 0; b < FB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int s0 = slice * p.steps_per_slice, s1 = min(p.steps, s0 + p.steps_per_slice);
+    wgrad_clear(acc);
     float4 ra[FA], rb[FB];
-    // thread t loads float4 number t + 256 i of a tile of 8 F float4 per pixel row: (row, c4) = (idx / 8 F, idx % 8 F)
     auto load = [&](int st) {
 #pragma unroll
       for (int i = 0; i < FA; ++i) {
-        const int idx = t + 256 * i, c4 = idx % (8 * FA), row = idx / (8 * FA);
-        const int pix = st * kWgradStep + row;
-        ra[i] = (pix < p.P && n0b + 4 * c4 < p.N) ? *(const float4*)(p.dy + (long long)pix * p.ldy + n0b + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const X3Slot sl = x3_slot<FA>(t, i);
+        const int pix = st * kWgradStep + sl.row;
+        ra[i] = x3_load(pix < p.P && n0b + sl.ch < p.N, p.dy, (long long)pix * p.ldy + n0b + sl.ch);
       }
 #pragma unroll
       for (int i = 0; i < FB; ++i) {
-        const int idx = t + 256 * i, c4 = idx % (8 * FB), row = idx / (8 * FB);
-        const int pix = st * kWgradStep + row;
+        const X3Slot sl = x3_slot<FB>(t, i);
+        const int pix = st * kWgradStep + sl.row;
         bool xv = pix < p.P;
         long long xrow = pix;
-        if (p.taps == 9) xv = wgrad_x_pixel<S>(p, pix, dy_, dx_, shift, &xrow) && xv;
-        rb[i] = (xv && c0b + 4 * c4 < p.C) ? *(const float4*)(p.x + xrow * p.C + c0b + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (p.taps == 9) xv = wgrad_x_pixel<S>(p, pix, w.dy_, w.dx_, w.shift, &xrow) && xv;
+        rb[i] = x3_load(xv && c0b + sl.ch < p.C, p.x, xrow * p.C + c0b + sl.ch);
       }
     };
-    load(s0);
-    for (int st = s0; st < s1; ++st) {
+    load(w.s0);
+    for (int st = w.s0; st < w.s1; ++st) {
       __syncthreads();                                   // the previous step's reads are done
-#pragma unroll
-      for (int i = 0; i < FA; ++i) {
-        const int idx = t + 256 * i;
-        const int off = (idx / (8 * FA)) * RA + (idx % (8 * FA)) * 8;
-        uint2 hi, lo;
-        split4(ra[i], hi, lo);
-        *(uint2*)(lds + off) = hi;
-        *(uint2*)(lds + PA + off) = lo;
-      }
-#pragma unroll
-      for (int i = 0; i < FB; ++i) {
-        const int idx = t + 256 * i;
-        const int off = (idx / (8 * FB)) * RB + (idx % (8 * FB)) * 8;
-        uint2 hi, lo;
-        split4(rb[i], hi, lo);
-        *(uint2*)(lds + 2 * PA + off) = hi;
-        *(uint2*)(lds + 2 * PA + PB + off) = lo;
-      }
+      x3_stage<FA>(lds, A_HI, A_LO, ra, t);
+      x3_stage<FB>(lds, B_HI, B_LO, rb, t);
       __syncthreads();
-      if (st + 1 < s1) load(st + 1);                     // in flight under the MFMAs below
+      if (st + 1 < w.s1) load(st + 1);                   // in flight under the MFMAs below
       bf16x8 ah[FA], al[FA], bh[FB], bl[FB];
-      auto frag = [&](const char* base, int row) {
-        const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(base));
-        const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(base + 16 * row));
-        const uint2 u0 = __builtin_bit_cast(uint2, v0), u1 = __builtin_bit_cast(uint2, v1);
-        return __builtin_bit_cast(bf16x8, make_uint4(u0.x, u0.y, u1.x, u1.y));
-      };
-#pragma unroll
-      for (int f = 0; f < FA; ++f) {
-        ah[f] = frag(lds + tr_a + (wn + 16 * f) * 2, RA); al[f] = frag(lds + PA + tr_a + (wn + 16 * f) * 2, RA);
-      }
-#pragma unroll
-      for (int f = 0; f < FB; ++f) {
-        bh[f] = frag(lds + 2 * PA + tr_b + (wc + 16 * f) * 2, RB); bl[f] = frag(lds + 2 * PA + PB + tr_b + (wc + 16 * f) * 2, RB);
-      }
+      x3_frags<FA>(ah, al, lds, A_HI, A_LO, at_a);
+      x3_frags<FB>(bh, bl, lds, B_HI, B_LO, at_b);
 #pragma unroll
       for (int a = 0; a < FA; ++a)
 #pragma unroll
-        for (int b = 0; b < FB; ++b) {
-          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[a], bh[b], acc[a][b], 0, 0, 0);
-          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[a], bl[b], acc[a][b], 0, 0, 0);
-          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[a], bh[b], acc[a][b], 0, 0, 0);
-        }
+        for (int b = 0; b < FB; ++b) x3_mac(acc[a][b], ah[a], al[a], bh[b], bl[b]);
     }
     __syncthreads();                                     // (the next item writes the planes again)
-    float* slab = p.partial + (size_t)slice * p.N * KK + (size_t)tap * p.C;
-#pragma unroll
-    for (int a = 0; a < FA; ++a)
-#pragma unroll
-      for (int b = 0; b < FB; ++b) {
-        const int c = c0b + wc + 16 * b + lr;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int n = n0b + wn + 16 * a + 4 * lg + j;
-          if (n < p.N && c < p.C) slab[(size_t)n * KK + c] = acc[a][b][j];
-        }
-      }
+    wgrad_store(acc, p.partial + (size_t)w.slice * p.N * KK + (size_t)w.tap * p.C, KK, n0b + wn + 4 * lg, c0b + wc + lr, p.N, p.C);
   }
 }
 
 // ------------------------------------------------------------------ the all-taps tiles of the narrow 3x3 layers
-// A workgroup owns ALL NINE taps of a 32 FA (n) x 32 FB (c) tile (FA, FB in 1 | 2: the whole layer) over one slice of the pixel
-// axis: N x 9 C outputs.  dY is read once per step and serves the nine taps; X is read at the nine shifted pixels (its halo), lines
-// the same workgroup read a row of the map earlier.  Waves split the tile 2 x 2 as above; a wave holds 9 x FA x FB accumulator tiles.
-// The fp32 form, register-only as wgrad_f32_kernel: per four pixels a lane loads its dY values once and one X value per tap.
+// A workgroup owns ALL NINE taps of a 32 FA (n) x 32 FB (c) tile (the whole layer) over one slice of the pixel axis: N x 9 C
+// outputs, an item is a slice.  dY is read once per step and serves the nine taps; X is read at the nine shifted pixels (its halo),
+// lines the same workgroup read a row of the map earlier.  A wave holds 9 x FA x FB accumulator tiles.
+// fp32, register-only as wgrad_f32_kernel: per four pixels a lane loads its dY values once and one X value per tap.
 template <int FA, int FB, int S>
 __global__ __launch_bounds__(256) void wgrad9_f32_kernel(const WgradArgs p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -248,19 +282,14 @@ __global__ __launch_bounds__(256) void wgrad9_f32_kernel(const WgradArgs p) {
   const int KK = 9 * p.C;
   const int n0 = (wave >> 1) * (16 * FA), c0 = (wave & 1) * (16 * FB);
   bool nv[FA], cv[FB];
-#pragma unroll
-  for (int f = 0; f < FA; ++f) nv[f] = n0 + 16 * f + lr < p.N;
-#pragma unroll
-  for (int f = 0; f < FB; ++f) cv[f] = c0 + 16 * f + lr < p.C;
+  wgrad_valid(nv, n0 + lr, p.N);
+  wgrad_valid(cv, c0 + lr, p.C);
   for (int slice = blockIdx.x; slice < p.items; slice += gridDim.x) {
     f32x4 acc[9][FA][FB];
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-      for (int a = 0; a < FA; ++a)
-#pragma unroll
-        for (int b = 0; b < FB; ++b) acc[t][a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int s0 = slice * p.steps_per_slice, s1 = min(p.steps, s0 + p.steps_per_slice);
+    for (int t = 0; t < 9; ++t) wgrad_clear(acc[t]);
+    int s0, s1;
+    wgrad_steps(p, slice, &s0, &s1);
     for (int st = s0; st < s1; ++st) {
 #pragma unroll 2
       for (int j = 0; j < 8; ++j) {
@@ -288,71 +317,50 @@ __global__ __launch_bounds__(256) void wgrad9_f32_kernel(const WgradArgs p) {
     }
     float* slab = p.partial + (size_t)slice * p.N * KK;
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-      for (int a = 0; a < FA; ++a)
-#pragma unroll
-        for (int b = 0; b < FB; ++b) {
-          const int c = c0 + 16 * b + lr;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int n = n0 + 16 * a + 4 * lg + j;
-            if (n < p.N && c < p.C) slab[(size_t)n * KK + t * p.C + c] = acc[t][a][b][j];
-          }
-        }
+    for (int t = 0; t < 9; ++t) wgrad_store(acc[t], slab + t * p.C, KK, n0 + 4 * lg, c0 + lr, p.N, p.C);
   }
 }
 
-// The split-bf16 form: per step the dY tile is loaded, split and stored to LDS ONCE and its fragments stay in registers for the nine
-// taps; the X planes are made per tap ROW (three taps: 6 planes of 32 pixels), so a step has three rounds of two barriers instead of
+// split bf16: per step the dY tile is loaded, split and stored to LDS ONCE and its fragments stay in registers for the nine taps;
+// the X planes are made per tap ROW (three taps: 6 planes of 32 pixels), so a step has three rounds of two barriers instead of
 // nine.  The next round's X loads (the next step's dY loads with the last round) are in flight under the MFMAs.  LDS: 2 A planes +
-// 6 B planes, 16 - 40 KB.
+// 6 B planes (A hi | A lo | B hi [3 taps] | B lo [3 taps]), 24 - 40 KB.
 template <int FA, int FB, int S>
 __global__ __launch_bounds__(256) void wgrad9_x3_kernel(const WgradArgs p) {
-  constexpr int RA = wg_row(FA), RB = wg_row(FB), PA = 32 * RA, PB = 32 * RB;
-  __shared__ __attribute__((aligned(16))) char lds[2 * PA + 6 * PB];      // A hi | A lo | B hi [3 taps] | B lo [3 taps]
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) s16x4* lds_v4;
+  constexpr int PA = wg_plane(FA), PB = wg_plane(FB);
+  constexpr int A_HI = 0, A_LO = PA, B_HI = 2 * PA, B_LO = 2 * PA + 3 * PB;
+  __shared__ __attribute__((aligned(16))) char lds[2 * PA + 6 * PB];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int lr = lane & 15, lg = lane >> 4;
   const int KK = 9 * p.C;
-  const int tr_a = (4 * lg + (lr >> 2)) * RA + (lr & 3) * 8, tr_b = (4 * lg + (lr >> 2)) * RB + (lr & 3) * 8;
   const int wn = (wave >> 1) * (16 * FA), wc = (wave & 1) * (16 * FB);
-  auto frag = [&](const char* base, int row) {
-    const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(base));
-    const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(base + 16 * row));
-    const uint2 u0 = __builtin_bit_cast(uint2, v0), u1 = __builtin_bit_cast(uint2, v1);
-    return __builtin_bit_cast(bf16x8, make_uint4(u0.x, u0.y, u1.x, u1.y));
-  };
+  const int at_a = x3_lane_offset<FA>(lg, lr) + 2 * wn, at_b = x3_lane_offset<FB>(lg, lr) + 2 * wc;
   for (int slice = blockIdx.x; slice < p.items; slice += gridDim.x) {
     f32x4 acc[9][FA][FB];
 #pragma unroll
-    for (int q = 0; q < 9; ++q)
-#pragma unroll
-      for (int a = 0; a < FA; ++a)
-#pragma unroll
-        for (int b = 0; b < FB; ++b) acc[q][a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int s0 = slice * p.steps_per_slice, s1 = min(p.steps, s0 + p.steps_per_slice);
+    for (int q = 0; q < 9; ++q) wgrad_clear(acc[q]);
+    int s0, s1;
+    wgrad_steps(p, slice, &s0, &s1);
     float4 ra[FA], rb[3][FB];
     auto load_a = [&](int st) {
 #pragma unroll
       for (int i = 0; i < FA; ++i) {
-        const int idx = t + 256 * i, c4 = idx % (8 * FA), row = idx / (8 * FA);
-        const int pix = st * kWgradStep + row;
-        ra[i] = (pix < p.P && 4 * c4 < p.N) ? *(const float4*)(p.dy + (long long)pix * p.ldy + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const X3Slot sl = x3_slot<FA>(t, i);
+        const int pix = st * kWgradStep + sl.row;
+        ra[i] = x3_load(pix < p.P && sl.ch < p.N, p.dy, (long long)pix * p.ldy + sl.ch);
       }
     };
     auto load_b = [&](int st, int g) {                    // tap row g: taps 3 g .. 3 g + 2
 #pragma unroll
       for (int i = 0; i < FB; ++i) {
-        const int idx = t + 256 * i, c4 = idx % (8 * FB), row = idx / (8 * FB);
-        const int pix = st * kWgradStep + row;
+        const X3Slot sl = x3_slot<FB>(t, i);
+        const int pix = st * kWgradStep + sl.row;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           const int dy_ = g - 1, dx_ = q - 1;
           long long xrow;
           const bool xv = wgrad_x_pixel<S>(p, pix, dy_, dx_, (long long)dy_ * p.W + dx_, &xrow) && pix < p.P;
-          rb[q][i] = (xv && 4 * c4 < p.C) ? *(const float4*)(p.x + xrow * p.C + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+          rb[q][i] = x3_load(xv && sl.ch < p.C, p.x, xrow * p.C + sl.ch);
         }
       }
     };
@@ -363,72 +371,28 @@ __global__ __launch_bounds__(256) void wgrad9_x3_kernel(const WgradArgs p) {
 #pragma unroll
       for (int g = 0; g < 3; ++g) {
         __syncthreads();                                 // the previous round's reads are done
-        if (g == 0) {
+        if (g == 0) x3_stage<FA>(lds, A_HI, A_LO, ra, t);
 #pragma unroll
-          for (int i = 0; i < FA; ++i) {
-            const int idx = t + 256 * i;
-            const int off = (idx / (8 * FA)) * RA + (idx % (8 * FA)) * 8;
-            uint2 hi, lo;
-            split4(ra[i], hi, lo);
-            *(uint2*)(lds + off) = hi;
-            *(uint2*)(lds + PA + off) = lo;
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-#pragma unroll
-          for (int i = 0; i < FB; ++i) {
-            const int idx = t + 256 * i;
-            const int off = (idx / (8 * FB)) * RB + (idx % (8 * FB)) * 8;
-            uint2 hi, lo;
-            split4(rb[q][i], hi, lo);
-            *(uint2*)(lds + 2 * PA + q * PB + off) = hi;
-            *(uint2*)(lds + 2 * PA + (3 + q) * PB + off) = lo;
-          }
+        for (int q = 0; q < 3; ++q) x3_stage<FB>(lds, B_HI + q * PB, B_LO + q * PB, rb[q], t);
         __syncthreads();
         if (g < 2) load_b(st, g + 1);                    // in flight under the MFMAs below
         else if (st + 1 < s1) { load_a(st + 1); load_b(st + 1, 0); }
-        if (g == 0) {
-#pragma unroll
-          for (int f = 0; f < FA; ++f) {
-            ah[f] = frag(lds + tr_a + (wn + 16 * f) * 2, RA); al[f] = frag(lds + PA + tr_a + (wn + 16 * f) * 2, RA);
-          }
-        }
+        if (g == 0) x3_frags<FA>(ah, al, lds, A_HI, A_LO, at_a);
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           bf16x8 bh[FB], bl[FB];
-#pragma unroll
-          for (int f = 0; f < FB; ++f) {
-            bh[f] = frag(lds + 2 * PA + q * PB + tr_b + (wc + 16 * f) * 2, RB);
-            bl[f] = frag(lds + 2 * PA + (3 + q) * PB + tr_b + (wc + 16 * f) * 2, RB);
-          }
+          x3_frags<FB>(bh, bl, lds, B_HI + q * PB, B_LO + q * PB, at_b);
 #pragma unroll
           for (int a = 0; a < FA; ++a)
 #pragma unroll
-            for (int b = 0; b < FB; ++b) {
-              f32x4& c = acc[3 * g + q][a][b];
-              c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[a], bh[b], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[a], bl[b], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[a], bh[b], c, 0, 0, 0);
-            }
+            for (int b = 0; b < FB; ++b) x3_mac(acc[3 * g + q][a][b], ah[a], al[a], bh[b], bl[b]);
         }
       }
     }
     __syncthreads();                                     // (the next slice writes the planes again)
     float* slab = p.partial + (size_t)slice * p.N * KK;
 #pragma unroll
-    for (int q = 0; q < 9; ++q)
-#pragma unroll
-      for (int a = 0; a < FA; ++a)
-#pragma unroll
-        for (int b = 0; b < FB; ++b) {
-          const int c = wc + 16 * b + lr;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int n = wn + 16 * a + 4 * lg + j;
-            if (n < p.N && c < p.C) slab[(size_t)n * KK + q * p.C + c] = acc[q][a][b][j];
-          }
-        }
+    for (int q = 0; q < 9; ++q) wgrad_store(acc[q], slab + q * p.C, KK, wn + 4 * lg, wc + lr, p.N, p.C);
   }
 }
 
@@ -540,14 +504,7 @@ __global__ __launch_bounds__(256) void ln_silu_bwd_kernel(const float* __restric
       s1 += gh[i]; s2 += gh[i] * xh;
     }
     const float m1 = wave64_sum(s1) * inv_c, m2 = wave64_sum(s2) * inv_c;
-    size_t ro = (size_t)r;
-    if (pm) {
-      const int hw = H2 * W2;
-      const int img = r / hw, rem = r - img * hw;
-      const int Y = rem / W2, X = rem - Y * W2;
-      ro = (((size_t)img * (H2 >> 1) + (Y >> 1)) * (W2 >> 1) + (X >> 1)) * 4 + 2 * (Y & 1) + (X & 1);
-    }
-    float* o = dx + ro * C;
+    float* o = dx + (pm ? phase_major_row(r, H2, W2) : (size_t)r) * C;
 #pragma unroll
     for (int i = 0; i < kLnBwdPer; ++i) if (i < per) o[lane + 64 * i] = rstd * (gh[i] - m1 - xv[i] * m2);
   }
@@ -676,12 +633,11 @@ inline int grid_for(size_t n, int cap = 8192) { return (int)std::min<size_t>((si
 }  // namespace
 
 // ------------------------------------------------------------------ launchers
-static inline int out_dim(int h, int stride) { return stride == 2 ? (h - 1) / 2 + 1 : h; }
 int wgrad_plan(const WgradParams& p, int cus, WgradPlan* pl) {
   if (p.B < 1 || p.H < 1 || p.W < 1 || (long long)p.B * p.H * p.W >= (1ll << 30)) return -2;
   if (p.N > p.ldy) return -2;
-  if (!p.by_width) return p.stride == 1 ? wgrad_choose(WgradDesc{p.B * p.H * p.W, p.N, p.C, p.taps, p.x3}, cus, pl) : -2;
-  return wgrad_choose_ex(WgradDescEx{p.B * out_dim(p.H, p.stride) * out_dim(p.W, p.stride), p.N, p.C, p.taps, p.x3, p.stride}, cus, pl);
+  const int P = p.B * conv_out_dim(p.H, p.stride) * conv_out_dim(p.W, p.stride);
+  return wgrad_choose(WgradDesc{P, p.N, p.C, p.taps, p.x3, p.stride}, p.rule, cus, pl);
 }
 static int g_wgrad_cus = 0;          // debug key 26
 void wgrad_set_cus(int cus) { g_wgrad_cus = cus < 0 ? 0 : cus; }
@@ -692,72 +648,56 @@ size_t wgrad_partial_bytes(const WgradParams& p, const WgradPlan& pl) {
 }
 
 namespace {
-template <int FA, int FB, int S>
-void wgrad_launch_one(const WgradPlan& pl, const WgradArgs& a, hipStream_t s) {
-  if (pl.x3) LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), (wgrad_x3_kernel<FA, FB, S>), dim3(pl.grid_x), dim3(pl.block), 0, s, a);
-  else LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), (wgrad_f32_kernel<FA, FB, S>), dim3(pl.grid_x), dim3(pl.block), 0, s, a);
-}
-template <int FA, int FB>
-void wgrad_launch_stride(const WgradPlan& pl, const WgradArgs& a, hipStream_t s) {
-  if (pl.stride == 2) wgrad_launch_one<FA, FB, 2>(pl, a, s);
-  else wgrad_launch_one<FA, FB, 1>(pl, a, s);
-}
-template <int FA, int FB>
-void wgrad9_launch(const WgradPlan& pl, const WgradArgs& a, hipStream_t s) {
-  if (pl.x3 && pl.stride == 2) LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), (wgrad9_x3_kernel<FA, FB, 2>), dim3(pl.grid_x), dim3(pl.block), 0, s, a);
-  else if (pl.x3) LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), (wgrad9_x3_kernel<FA, FB, 1>), dim3(pl.grid_x), dim3(pl.block), 0, s, a);
-  else if (pl.stride == 2) LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), (wgrad9_f32_kernel<FA, FB, 2>), dim3(pl.grid_x), dim3(pl.block), 0, s, a);
-  else LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), (wgrad9_f32_kernel<FA, FB, 1>), dim3(pl.grid_x), dim3(pl.block), 0, s, a);
-}
-template <int FA>
-void wgrad_launch_c(const WgradPlan& pl, const WgradArgs& a, hipStream_t s) {
-  if (pl.tile_c == 32) wgrad_launch_stride<FA, 1>(pl, a, s);
-  else if (pl.tile_c == 64) wgrad_launch_stride<FA, 2>(pl, a, s);
-  else wgrad_launch_stride<FA, 4>(pl, a, s);
-}
+// Every weight-gradient kernel the library holds, one row each: (all_taps, x3, tile_n, tile_c, stride) -> kernel, the only place
+// that names template arguments.  The rows are what a chooser (wgrad_plan.h) can name: per tap the tile pairs with a 128 in them
+// ((128, 128) at stride 1 is also the decoder's rule and every one-tap launch), all taps the pairs within 64.  A per-tap kernel with
+// both tiles <= 64 has no caller, so it is not built; bringing one back is one row.
+typedef void (*WgradKernel)(const WgradArgs);
+struct WgradRow { int all_taps, x3, tile_n, tile_c, stride; WgradKernel kernel; };
+#define LDMSEG_WGRAD_ROWS(ALL, F32, X3, TN, TC)                                                         \
+  {ALL, 0, TN, TC, 1, F32<TN / 32, TC / 32, 1>}, {ALL, 0, TN, TC, 2, F32<TN / 32, TC / 32, 2>},         \
+  {ALL, 1, TN, TC, 1, X3<TN / 32, TC / 32, 1>}, {ALL, 1, TN, TC, 2, X3<TN / 32, TC / 32, 2>}
+#define LDMSEG_WGRAD_PER_TAP(TN, TC) LDMSEG_WGRAD_ROWS(0, wgrad_f32_kernel, wgrad_x3_kernel, TN, TC)
+#define LDMSEG_WGRAD_ALL_TAPS(TN, TC) LDMSEG_WGRAD_ROWS(1, wgrad9_f32_kernel, wgrad9_x3_kernel, TN, TC)
+const WgradRow kWgradKernels[] = {
+    LDMSEG_WGRAD_PER_TAP(128, 128), LDMSEG_WGRAD_PER_TAP(128, 64), LDMSEG_WGRAD_PER_TAP(128, 32),
+    LDMSEG_WGRAD_PER_TAP(64, 128),  LDMSEG_WGRAD_PER_TAP(32, 128),
+    LDMSEG_WGRAD_ALL_TAPS(64, 64),  LDMSEG_WGRAD_ALL_TAPS(64, 32), LDMSEG_WGRAD_ALL_TAPS(32, 64), LDMSEG_WGRAD_ALL_TAPS(32, 32)};
+#undef LDMSEG_WGRAD_ALL_TAPS
+#undef LDMSEG_WGRAD_PER_TAP
+#undef LDMSEG_WGRAD_ROWS
+static_assert(sizeof(kWgradKernels) / sizeof(kWgradKernels[0]) == 36, "weight-gradient kernel table");
 }  // namespace
 
-int launch_wgrad(const WgradParams& p, const WgradPlan& pl, hipStream_t s) {
-  if (!p.dy || !p.x || !p.partial) return -2;
-  if (pl.stride != p.stride || (pl.tile_n != 32 && pl.tile_n != 64 && pl.tile_n != 128) || (pl.tile_c != 32 && pl.tile_c != 64 && pl.tile_c != 128))
-    return -2;
+int launch_wgrad(const WgradParams& p, const WgradPlan& pl, const WgradOut& o, hipStream_t s) {
+  if (!p.dy || !p.x || !p.partial || !o.out || pl.stride != p.stride) return -2;
+  if (o.n_real > p.N || o.c_real > p.C || (o.form == 1 && (p.taps != 1 || o.co < 1 || o.n_real != 4 * o.co))) return -2;
+  if (pl.all_taps && (p.taps != 9 || pl.n_tiles != 1 || pl.c_tiles != 1 || pl.items != pl.slices)) return -2;
+  const WgradRow* row = nullptr;
+  for (const WgradRow& r : kWgradKernels)
+    if (r.all_taps == pl.all_taps && r.x3 == pl.x3 && r.tile_n == pl.tile_n && r.tile_c == pl.tile_c && r.stride == pl.stride) row = &r;
+  if (!row) return -2;
   WgradArgs a;
   a.dy = p.dy; a.x = p.x; a.partial = p.partial;
-  a.Ho = out_dim(p.H, p.stride); a.Wo = out_dim(p.W, p.stride);
+  a.Ho = conv_out_dim(p.H, p.stride); a.Wo = conv_out_dim(p.W, p.stride);
   a.ldy = p.ldy; a.P = p.B * a.Ho * a.Wo; a.H = p.H; a.W = p.W; a.N = p.N; a.C = p.C; a.taps = p.taps;
   a.n_tiles = pl.n_tiles; a.c_tiles = pl.c_tiles; a.tiles = pl.tiles; a.steps = pl.steps; a.steps_per_slice = pl.steps_per_slice;
   a.items = pl.items;
   a.fd_hw = fastdiv_make(a.Ho * a.Wo); a.fd_w = fastdiv_make(a.Wo);
-  if (pl.all_taps) {
-    if (p.taps != 9 || pl.n_tiles != 1 || pl.c_tiles != 1 || pl.tile_n > 64 || pl.tile_c > 64 || pl.items != pl.slices) return -2;
-    if (pl.tile_n == 32 && pl.tile_c == 32) wgrad9_launch<1, 1>(pl, a, s);
-    else if (pl.tile_n == 32) wgrad9_launch<1, 2>(pl, a, s);
-    else if (pl.tile_c == 32) wgrad9_launch<2, 1>(pl, a, s);
-    else wgrad9_launch<2, 2>(pl, a, s);
-    return launch_status();
-  }
-  if (pl.tile_n == 32) wgrad_launch_c<1>(pl, a, s);
-  else if (pl.tile_n == 64) wgrad_launch_c<2>(pl, a, s);
-  else wgrad_launch_c<4>(pl, a, s);
-  return launch_status();
-}
-int launch_wgrad_finish(const WgradParams& p, const WgradPlan& pl, int form, int n_real, int c_real, int co, float* out, hipStream_t s) {
-  if (n_real > p.N || c_real > p.C || (form == 1 && (p.taps != 1 || co < 1 || n_real != 4 * co))) return -2;
-  const int total = n_real * p.taps * c_real;
-  LDMSEG_LAUNCH(form ? "wgrad_finish<convt>" : "wgrad_finish<conv>", wgrad_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, s,
-                p.partial, pl.slices, p.N, p.C, p.taps, form, n_real, c_real, co, out);
+  LDMSEG_LAUNCH_GEMM(wgrad_plan_name(pl), row->kernel, dim3(pl.grid_x), dim3(pl.block), 0, s, a);
+  if (const int e = launch_status()) return e;
+  const int total = o.n_real * p.taps * o.c_real;
+  LDMSEG_LAUNCH(o.form ? "wgrad_finish<convt>" : "wgrad_finish<conv>", wgrad_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, s,
+                p.partial, pl.slices, p.N, p.C, p.taps, o.form, o.n_real, o.c_real, o.co, o.out);
   return launch_status();
 }
 
-int colsum_slices(int P) {
-  const int rows = std::max(kColsumRows, (P + kColsumMaxSlices - 1) / kColsumMaxSlices);
-  return (P + rows - 1) / rows;
-}
+static int colsum_rows(int P) { return std::max(kColsumRows, (P + kColsumMaxSlices - 1) / kColsumMaxSlices); }   // rows per run
+int colsum_slices(int P) { return (P + colsum_rows(P) - 1) / colsum_rows(P); }
 size_t colsum_scratch_bytes(int P, int N) { return (size_t)colsum_slices(P) * N * sizeof(float); }
 int launch_colsum(const float* a, int lda, int P, int N, int Q, int qstride, int n, float* scratch, float* out, hipStream_t s) {
   if (P < 1 || N < 1 || N > lda || (Q - 1) * qstride + n > N) return -2;
-  const int rows = std::max(kColsumRows, (P + kColsumMaxSlices - 1) / kColsumMaxSlices);
-  const int S = (P + rows - 1) / rows;
+  const int rows = colsum_rows(P), S = colsum_slices(P);
   LDMSEG_LAUNCH("colsum_partial<f32>", colsum_partial_kernel, dim3(S, (N + 127) / 128), dim3(128), 0, s, a, lda, P, N, rows, scratch);
   LDMSEG_LAUNCH("slab_sum<f32>", slab_sum_kernel, dim3((n + 127) / 128), dim3(128), 0, s, scratch, S, N, Q, qstride, n, out);
   return launch_status();

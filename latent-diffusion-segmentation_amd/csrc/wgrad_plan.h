@@ -8,20 +8,25 @@
 // a function of the SHAPE alone: it aims at kWgradTargetItems work items whatever the device; the CU count only decides how many
 // workgroups walk the items (one item per workgroup while they fit, a fixed-stride walk beyond).
 //
-// Two rules share one body.  wgrad_choose is the decoder's: the 128 x 128 tile, stride 1.  wgrad_choose_ex is the
-// encoder's: dY lives on the OUTPUT map of a stride-1 or stride-2 conv, and the tile follows the storage widths -
-// 32, 64 or 128 rows of dY by 32, 64 or 128 channels of X - so that a 32- or 64-channel layer does not pay for a 128-wide tile.
+// Two rules share one body (WgradRule).  The decoder's: the 128 x 128 tile, stride 1.  The encoder's: dY
+// lives on the OUTPUT map of a stride-1 or stride-2 conv, and the tile follows the storage widths - 32, 64 or 128 rows of dY by 32,
+// 64 or 128 channels of X - so that a 32- or 64-channel layer does not pay for a 128-wide tile.
 #pragma once
 #include <cstdio>
 #include <string>
 
 namespace ldmseg {
 
-// P pixels (B * H * W of the map X lives on), N rows of dY taken (storage width of dY), C storage channels of X, taps 9 (3x3, pad
-// 1) or 1, x3: 0 = exact fp32 MFMA, 1 = split-bf16 products
-struct WgradDesc { int P, N, C, taps, x3; };
-// the same with P = the pixels of the OUTPUT map (the map dY lives on) of a conv of stride 1 | 2 (2: taps 9 only)
-struct WgradDescEx { int P, N, C, taps, x3, stride; };
+// P pixels of the map dY lives on (the OUTPUT map of a conv of stride 1 | 2; stride 1: the map X lives on too), N rows of dY taken
+// (storage width of dY), C storage channels of X, taps 9 (3x3, pad 1) or 1, x3: 0 = exact fp32 MFMA, 1 = split-bf16 products,
+// stride 2: taps 9 only
+struct WgradDesc { int P, N, C, taps, x3, stride = 1; };
+enum WgradRule {
+  kWgradFixedTile = 0,   // the decoder's: the 128 x 128 tile per tap, stride 1
+  kWgradByWidth = 1,     // the encoder's: the tile follows N and C; all nine taps in one workgroup where both fit 64
+};
+// side of the output map of a 3x3 conv, pad 1, on a side of h pixels (odd h included)
+constexpr int conv_out_dim(int h, int stride) { return stride == 2 ? (h - 1) / 2 + 1 : h; }
 
 constexpr int kWgradTileN = 128, kWgradTileC = 128;   // output tile of a workgroup: four waves of 64 x 64
 constexpr int kWgradStep = 32;                          // pixels per K step (one bf16 MFMA's K; eight fp32 MFMAs' K)
@@ -44,21 +49,26 @@ struct WgradPlan {
 // the narrowest of 32 | 64 | 128 that holds `width` (128 beyond)
 constexpr int wgrad_tile_for(int width) { return width <= 32 ? 32 : width <= 64 ? 64 : 128; }
 
-// 0 and *out filled, or -2: no such launch.  tile_n / tile_c: 32 | 64 | 128
-inline int wgrad_choose_tiled(const WgradDescEx& q, int tile_n, int tile_c, bool all_taps, int cus, WgradPlan* out) {
+// 0 and *out filled, or -2: no such launch.
+// By width, a 3x3 layer whose two widths fit 64 runs on the all-taps tile: one workgroup owns N x 9 C outputs of a slice, reads dY
+// once per step and X with its halo, so the operand traffic does not scale with the tap count (and the slicing aims at 256 slices,
+// not 28).
+inline int wgrad_choose(const WgradDesc& q, WgradRule rule, int cus, WgradPlan* out) {
   if (q.P < 1 || q.N < 1 || q.C < 1 || (q.taps != 1 && q.taps != 9) || cus < 1) return -2;
-  if (q.stride != 1 && (q.stride != 2 || q.taps != 9)) return -2;
+  if (q.stride != 1 && (rule != kWgradByWidth || q.stride != 2 || q.taps != 9)) return -2;
   if (q.N % 16 || q.C % 16) return -2;                  // operands are read as 16-channel MFMA fragments
   if ((long long)q.P + 2 * kWgradStep >= (1ll << 31)) return -2;
+  const bool by_width = rule == kWgradByWidth;
   WgradPlan p;
   p.x3 = q.x3 ? 1 : 0;
   p.taps = q.taps;
   p.stride = q.stride;
-  p.tile_n = tile_n; p.tile_c = tile_c;
-  p.n_tiles = (q.N + tile_n - 1) / tile_n;
-  p.c_tiles = (q.C + tile_c - 1) / tile_c;
-  p.all_taps = all_taps ? 1 : 0;
-  p.tiles = p.n_tiles * p.c_tiles * (all_taps ? 1 : p.taps);
+  p.tile_n = by_width ? wgrad_tile_for(q.N) : kWgradTileN;
+  p.tile_c = by_width ? wgrad_tile_for(q.C) : kWgradTileC;
+  p.n_tiles = (q.N + p.tile_n - 1) / p.tile_n;
+  p.c_tiles = (q.C + p.tile_c - 1) / p.tile_c;
+  p.all_taps = by_width && q.taps == 9 && p.tile_n <= 64 && p.tile_c <= 64 ? 1 : 0;
+  p.tiles = p.n_tiles * p.c_tiles * (p.all_taps ? 1 : p.taps);
   p.steps = (q.P + kWgradStep - 1) / kWgradStep;
   int want = kWgradTargetItems / p.tiles;               // slices that fill the target
   const int worth = p.steps / kWgradMinSteps;           // slices the pixel axis is worth
@@ -71,15 +81,6 @@ inline int wgrad_choose_tiled(const WgradDescEx& q, int tile_n, int tile_c, bool
   p.grid_x = p.one_per_cu ? p.items : cus;
   *out = p;
   return 0;
-}
-inline int wgrad_choose(const WgradDesc& q, int cus, WgradPlan* out) {
-  return wgrad_choose_tiled(WgradDescEx{q.P, q.N, q.C, q.taps, q.x3, 1}, kWgradTileN, kWgradTileC, false, cus, out);
-}
-// A 3x3 layer whose two widths fit 64 runs on the all-taps tile: one workgroup owns N x 9 C outputs of a slice, reads dY once per
-// step and X with its halo, so the operand traffic does not scale with the tap count (and the slicing aims at 256 slices, not 28).
-inline int wgrad_choose_ex(const WgradDescEx& q, int cus, WgradPlan* out) {
-  const int tn = wgrad_tile_for(q.N), tc = wgrad_tile_for(q.C);
-  return wgrad_choose_tiled(q, tn, tc, q.taps == 9 && tn <= 64 && tc <= 64, cus, out);
 }
 // MACs a plan executes for one pixel: tiles x tile area x taps (the chooser's cost, tests/test_wgrad_plan_ex_cpu.py)
 inline long long wgrad_plan_macs_per_pixel(const WgradPlan& p) { return (long long)p.n_tiles * p.c_tiles * p.taps * p.tile_n * p.tile_c; }

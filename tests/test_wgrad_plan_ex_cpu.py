@@ -1,4 +1,4 @@
-"""The by-width weight-gradient chooser (csrc/wgrad_plan.h wgrad_choose_ex) without a GPU: ``ldmseg_op_wgrad_plan_ex``
+"""The by-width weight-gradient chooser (csrc/wgrad_plan.h wgrad_choose) without a GPU: ``ldmseg_op_wgrad_plan_ex``
 answers, for a launch of the encoder's backward, the tile (32 | 64 | 128 rows of dY by 32 | 64 | 128 channels of X), the slicing of
 the OUTPUT map's pixel axis and the grid.  The decoder's rule (``ldmseg_op_wgrad_plan``) is restated here and held unchanged."""
 import pytest
@@ -117,9 +117,9 @@ def _names_before(lib, x3):
 def test_every_kernel_the_chooser_can_name_has_a_gpu_case(lib, x3):
     """ldmseg_op_wgrad_plan_ex over every pair of storage widths 32 .. 1024 of a 3x3 layer, both strides: 18 kernel names per mode,
     each of them launched and compared with fp64 by a GPU test - a kernel added to the chooser without a case fails here.
-    launch_wgrad can also dispatch the per-tap form with BOTH tiles <= 64 (4 tile pairs x 2 strides x 2 modes = 16 instantiations):
-    the chooser gives every such 3x3 layer the all-taps tile and no entry passes by_width with one tap, so those 16 have no caller
-    and no test; the enumeration never names them."""
+    The per-tap form with BOTH tiles <= 64 (4 tile pairs x 2 strides x 2 modes = 16 instantiations) is not built: the chooser gives
+    every such 3x3 layer the all-taps tile and no entry passes the by-width rule with one tap, so launch_wgrad's table has no row
+    for them and the enumeration never names them."""
     fam = "x3" if x3 else "f32"
     named = set()
     for stride in (1, 2):
