@@ -535,6 +535,46 @@ int ldmseg_point_loss_backward(const float* x, int B, int C, int H, int W, const
 int ldmseg_gaussian_kl_backward(const float* moments, int B, int latent_channels, int HW, const float* grad_per_image_dev,
                                 float* grad_moments, void* stream);
 
+/* ---- weight update: gradient-norm clipping + AdamW over a list of tensors (optim.py, trainers_ae.py:305-325) ------------ */
+/* The list: n fp32 device tensors of numels[i] >= 0 elements each, at any 4-byte aligned address (16-byte loads and stores are
+ * used where a tensor's addresses allow, scalar ones at its head and tail).  A tensor whose grads[i] is NULL is skipped wholly -
+ * it does not enter the norm, its moments and parameter are not touched, its hyper entry is not read - which is torch's rule for a
+ * parameter without .grad; numels[i] == 0 is allowed.
+ *   norm pass    each workgroup squares and adds one chunk of one tensor in fp64 and stores one partial per chunk; the partials
+ *                are then added in one fixed order.  No float atomics: two calls on the same inputs agree bit for bit, and the
+ *                three entries below give the same norm bits for the same gradients.
+ *   total_norm   (float)sqrt(sum): what clip_grad_norm_(..., norm_type=2) returns, up to the summation order.
+ *   clipping     coef = min(1.0f, max_norm / (total_norm + 1e-6f)) in fp32; grads[i] *= coef is stored back, so that the gradients
+ *                afterwards are what clip_grad_norm_ leaves (with coef == 1 the same bits).
+ *   AdamW        per element, every operation rounded separately to fp32, in torch.optim.AdamW's order:
+ *                  p = p * (1 - lr * wd);  m = m + (g - m) * (1 - beta1);  v = v * beta2 + (g * g) * (1 - beta2);
+ *                  p = p - step_size * (m / (sqrt(v) / bc2_sqrt + eps)),
+ *                step_size = lr / (1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) computed on the host in double, per
+ *                tensor.  hyper[i].step is the count AFTER this update (>= 1); the caller keeps the counts.
+ * scratch: ldmseg_multi_tensor_scratch_bytes(n, numels) bytes of device memory (0 for arguments the calls would refuse), owned by
+ * the caller, reusable by a later call on the same stream.  Pointers and per-tensor scalars travel in the kernel arguments, at
+ * most LDMSEG_MULTI_TENSOR_PER_LAUNCH tensors per launch: a list up to that length takes one launch per pass (ldmseg_grad_norm
+ * one more, for the result), longer lists ceil(n / LDMSEG_MULTI_TENSOR_PER_LAUNCH) per pass plus one that adds the partials.
+ * No host-device copy, no host synchronisation, no allocation.  LDMSEG_E_ARG: a null array, a negative numel, a pointer that is
+ * not 4-byte aligned, a null parameter / moment of a tensor that is not skipped, step < 1, a beta outside [0, 1), a negative or
+ * non-finite lr / eps / weight_decay, clipping (max_norm > 0) without total_norm_dev or scratch. */
+#define LDMSEG_MULTI_TENSOR_PER_LAUNCH 48
+typedef struct {
+  double lr, beta1, beta2, eps, weight_decay;
+  int64_t step;                  /* the count AFTER this update, >= 1 */
+} ldmseg_adamw_hyper;
+size_t ldmseg_multi_tensor_scratch_bytes(int n, const int64_t* numels);
+/* total_norm_dev[0] = the L2 norm of all gradients of the list (0 for an empty one) */
+int ldmseg_grad_norm(int n, const float* const* grads, const int64_t* numels, float* total_norm_dev, void* scratch, void* stream);
+/* clip_grad_norm_(grads, max_norm): the norm to total_norm_dev, the gradients scaled in place.  max_norm must be positive. */
+int ldmseg_grad_clip(int n, float* const* grads, const int64_t* numels, float max_norm, float* total_norm_dev, void* scratch,
+                     void* stream);
+/* clip (max_norm > 0; with max_norm <= 0 the norm pass is skipped, the gradients are not written and total_norm_dev may be NULL)
+ * and one AdamW update of every tensor.  hyper: n entries on the host. */
+int ldmseg_adamw_step(int n, float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                      const int64_t* numels, const ldmseg_adamw_hyper* hyper, float max_norm, float* total_norm_dev, void* scratch,
+                      void* stream);
+
 /* ---- sampler: TrainerDiffusion.sample (trainers_ldm_cond.py:1045-1170) -------------------- */
 typedef struct {
   int32_t n_steps;               /* len(scheduler.timesteps) */

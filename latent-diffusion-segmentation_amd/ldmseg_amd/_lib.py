@@ -51,6 +51,11 @@ class SampleCfg(C.Structure):
                 ("paste_coef", C.POINTER(C.c_float))]
 
 
+class AdamWHyper(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("step", C.c_int64)]
+
+
 _vp, _i, _i64, _f, _sz, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes); mirrors include/ldmseg_hip.h and include/ldmseg_hip_ops.h
@@ -91,6 +96,10 @@ SIGNATURES = {
     "ldmseg_point_loss_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _f,
                                         _d, _vp, _vp, _vp, _vp, _vp]),
     "ldmseg_gaussian_kl_backward": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "ldmseg_multi_tensor_scratch_bytes": (_sz, [_i, C.POINTER(_i64)]),
+    "ldmseg_grad_norm": (_i, [_i, C.POINTER(_vp), C.POINTER(_i64), _vp, _vp, _vp]),
+    "ldmseg_grad_clip": (_i, [_i, C.POINTER(_vp), C.POINTER(_i64), _f, _vp, _vp, _vp]),
+    "ldmseg_adamw_step": (_i, [_i] + [C.POINTER(_vp)] * 4 + [C.POINTER(_i64), C.POINTER(AdamWHyper), _f, _vp, _vp, _vp]),
     "ldmseg_unet_reserve": (_i, [_vp, _i, _i]),
     "ldmseg_unet_set_attention_fp8": (_i, [_vp, _i]),
     "ldmseg_unet_gn_fallbacks": (_i, [_vp, _vp]),

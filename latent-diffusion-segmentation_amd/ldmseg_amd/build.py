@@ -13,12 +13,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.normpath(os.path.join(HERE, "..", "csrc"))
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "..", "include"))
 LIB_PATH = os.path.join(HERE, "libldmseg_hip.so")
-SOURCES = ["igemm.hip", "tfuse.hip", "tproj.hip", "tail.hip", "norm.hip", "attention.hip", "attention3.hip", "attention4.hip", "attention_fp8.hip", "attention_mx.hip", "attention_cross.hip", "clip_vision.hip", "clip_text.hip", "guided.hip", "misc.hip", "skipadd.hip", "postproc.hip", "pq_meter.hip", "sched.hip", "loss.hip", "point_loss.hip", "point_loss_bwd.hip", "vae_bwd.hip", "runtime.hip", "unet_build.hip", "unet.hip", "vae.hip", "clip.hip", "debug_knobs.hip", "ops_api.hip"]
+SOURCES = ["igemm.hip", "tfuse.hip", "tproj.hip", "tail.hip", "norm.hip", "attention.hip", "attention3.hip", "attention4.hip", "attention_fp8.hip", "attention_mx.hip", "attention_cross.hip", "clip_vision.hip", "clip_text.hip", "guided.hip", "misc.hip", "skipadd.hip", "postproc.hip", "pq_meter.hip", "sched.hip", "loss.hip", "optim.hip", "point_loss.hip", "point_loss_bwd.hip", "vae_bwd.hip", "runtime.hip", "unet_build.hip", "unet.hip", "vae.hip", "clip.hip", "debug_knobs.hip", "ops_api.hip"]
 EXTRA_FLAGS = {
     "sched.hip": ["-ffp-contract=off"],                       # bit-exact scheduler arithmetic
     "tail.hip": ["-ffp-contract=off"],                        # the fused step tail carries the same arithmetic
     "guided.hip": ["-ffp-contract=off"],                      # and the guided step
     "loss.hip": ["-ffp-contract=off"],                        # element loss and remove_noise of the loss tail, bit-exact too
+    "optim.hip": ["-ffp-contract=off"],                       # AdamW's element update rounds every operation, like torch's
     "point_loss.hip": ["-ffp-contract=off"],                  # the tap rule rounds like torch's grid_sample
     "point_loss_bwd.hip": ["-ffp-contract=off"],              # the backward evaluates the same taps and points
     "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],    # scores feed VALU softmax: keep MFMA results in VGPRs

@@ -364,6 +364,38 @@ class GeneralVAESeg(object):
         self.refresh_encoder()
         self.refresh_decoder()
 
+    def state_dict(self):
+        """Ordered dict of every schema key (encoder.0.weight ... decoder.N.bias, the reference's names without `module.`) -> a CPU
+        fp32 clone of the tensor's CURRENT values: those of `parameters()`, optimiser steps included.  What `TrainerAE.save` writes
+        as 'vae' and `GeneralVAESeg(state_dict)` / `load_state_dict` take back."""
+        both = list(self._enc_sd.items()) + list(self._dec_sd.items())
+        return OrderedDict((k, v.detach().to("cpu", copy=True)) for k, v in both)
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """Copies `state_dict` (every schema key, `module.` prefixes allowed, shapes as built) into the object's own tensors - the
+        leaves of `parameters()` stay the same objects, so an optimiser over them stays valid - and repacks them into the handle as `refresh()`
+        does: every entry then computes with the new values, bitwise as an object built from that state dict."""
+        sd = {k.replace('module.', ''): v for k, v in state_dict.items()}
+        both = list(self._enc_sd.items()) + list(self._dec_sd.items())
+        missing = [k for k, _ in both if k not in sd]
+        if missing:
+            raise KeyError(f"state dict lacks seg-VAE tensors, e.g. {missing[:3]}")
+        for k, t in both:
+            if tuple(sd[k].shape) != tuple(t.shape):
+                raise ValueError(f"{k}: shape {tuple(sd[k].shape)} != expected {tuple(t.shape)}")
+        for k, t in both:
+            t.copy_(sd[k].detach().to(device=self.device, dtype=torch.float32))
+        # refresh() without making leaves of the tensors (an object that never asked for its parameters keeps none)
+        for entry, part in (("ldmseg_vae_load_encoder", self._enc_sd), ("ldmseg_vae_load_decoder", self._dec_sd)):
+            n, names, ptrs, numels = _name_arrays(OrderedDict((k, v.detach()) for k, v in part.items()))
+            with torch.cuda.device(self.device):
+                _lib.check(getattr(_lib.lib(), entry)(self._h, n, names, ptrs, numels, _lib.stream_ptr(self.device)), entry)
+        if self._enc_params is not None:
+            self._enc_versions = {k: v._version for k, v in self._enc_params.items()}
+        if self._dec_params is not None:
+            self._dec_versions = {k: v._version for k, v in self._dec_params.items()}
+
     def decoder_parameters(self):
         """Ordered dict: reference key (decoder.0.weight ...) -> fp32 leaf tensor on the device with requires_grad=True, holding
         the decoder tensors of the state dict the object was built from.  Once this has been called, `decode` / `forward` under

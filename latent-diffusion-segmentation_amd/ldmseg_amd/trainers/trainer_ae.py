@@ -5,7 +5,9 @@ Stands behind the evaluation half of the reference's ldmseg/trainers/trainers_ae
 `eval_only` (:189-190) - and behind the loss of its training step: `compute_point_loss` (:204-224), the number the stage-1
 loop logs and selects checkpoints by, differentiable with respect to the logits and the moments it is given (the `loss.backward()`
 of :286-296) and behind the step itself: `training_step` (:285-321 without the fp16 scaler) on the library's forward and backward
-with a torch optimiser.  The loop around it, a fused optimiser, EMA, image dumps and overlays (`save_images`) are not built.
+with a torch optimiser or the library's fused clip + AdamW (ldmseg_amd/optim.py), and `save` / `resume` in the reference's model.pt
+layout (:491-530).  The loop around it (tools/main_ae_train.py is a plain one), EMA, gradient accumulation, image dumps and overlays
+(`save_images`) are not built.
 
 Per batch ONE library call does encode -> posterior mode -> decode -> the metric's tail
 (`GeneralVAESeg.reconstruct_semseg` / `reconstruct_panoptic`); the [B,128,S,S] logits are never materialised and the
@@ -38,6 +40,7 @@ class TrainerAE(object):
         self.class_names = class_names if class_names is not None else [str(i) for i in range(num_classes)]
         self.device = torch.device(device) if device is not None else getattr(vae_model, "device", None)
         self.loss_weights = dict(LOSS_WEIGHTS if loss_weights is None else loss_weights)
+        self.last_grad_norm = None                                  # training_step with the library's AdamW and clip_grad > 0
         # :195; the trainer's ignore_label is the one that counts (an 'ignore_label' among loss_kwargs is overridden)
         self.segmentation_losses = SegmentationLosses(**{**(LOSS_KWARGS if loss_kwargs is None else loss_kwargs),
                                                          'ignore_label': ignore_label})
@@ -83,13 +86,29 @@ class TrainerAE(object):
         total = w['ce'] * ce + w['mask'] * mask + w['kl'] * kl
         return total, ce, kl, mask
 
-    def training_step(self, images, targets, optimizer, clip_grad: float = 0.0, generator=None, point_generator=None):
+    def training_step(self, images, targets, optimizer, clip_grad: float = 0.0, generator=None, point_generator=None, lr=None):
         """One stage-1 step, :285-321 without the fp16 scaler, on `images` [B,7,S,S] already in [-1, 1] (:256) and `targets` [B,h,w]:
         forward with a sampled posterior, `compute_point_loss`, `backward()`, torch's `clip_grad_norm_` over `vae_model.parameters()`
         when clip_grad > 0, `optimizer.step()`, `vae_model.refresh()`.  `optimizer` is a torch optimiser over
         `vae_model.parameters()`; its gradients are zeroed first (:324-325, moved to the front).  generator: the DEVICE generator
         of the posterior's noise; point_generator: the point sampler's (as `compute_point_loss` takes it).  Returns (loss, ce, kl, mask) as detached 0-d
-        device tensors."""
+        device tensors.
+        With the library's own `ldmseg_amd.optim.AdamW` as `optimizer`, clipping and update are its one `step(max_norm=clip_grad)`
+        (one ldmseg_adamw_step call); the norm before clipping, a 0-d device tensor, is kept in `self.last_grad_norm` (None without
+        clipping).  lr: when given, written to every param group first (:305-307, the schedule's entry of this step)."""
+        from ..optim import AdamW
+        if lr is not None:
+            for group in optimizer.param_groups:
+                group["lr"] = float(lr)
+        if isinstance(optimizer, AdamW):
+            optimizer.zero_grad(set_to_none=True)
+            with torch.enable_grad():
+                output = self.vae_model(images, sample_posterior=True, generator=generator)
+                loss, ce, kl, mask = self.compute_point_loss(output, targets, generator=point_generator)
+                loss.backward()
+            self.last_grad_norm = optimizer.step(max_norm=clip_grad)
+            self.vae_model.refresh()
+            return loss.detach(), ce.detach(), kl.detach(), mask.detach()
         optimizer.zero_grad(set_to_none=True)
         params = self.vae_model.parameters()
         with torch.enable_grad():
@@ -101,6 +120,32 @@ class TrainerAE(object):
         optimizer.step()
         self.vae_model.refresh()
         return loss.detach(), ce.detach(), kl.detach(), mask.detach()
+
+    def save(self, path, optimizer=None, epoch: int = 0, step: int = 0, p: Optional[dict] = None) -> None:
+        """:491-505: writes the reference's model.pt layout {'step', 'epoch', 'vae', 'opt', 'p', 'scaler': None} - 'vae' the
+        seg-VAE's `state_dict()`, 'opt' the optimiser's (torch's AdamW layout with CPU tensors; None without an optimiser), 'p' the
+        run's configuration dict.  Tensors and plain containers only: `checkpoint.load_ae_checkpoint(path)` and every
+        `weights_only=True` reader take the file."""
+        opt = None
+        if optimizer is not None:
+            opt = optimizer.state_dict()
+            opt = {"state": {i: {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in s.items()}
+                             for i, s in opt["state"].items()},
+                   "param_groups": opt["param_groups"]}
+        data = {"step": int(step), "epoch": int(epoch), "vae": self.vae_model.state_dict(), "opt": opt,
+                "p": dict(p) if p is not None else {}, "scaler": None}
+        torch.save(data, path)
+
+    def resume(self, path, optimizer=None):
+        """:507-530: reads a file `save` (or the reference's trainer) wrote: the seg-VAE's tensors into `vae_model`
+        (`load_state_dict`: the handle computes with them), the 'opt' entry - if there is one and an optimiser is given - into
+        `optimizer`.  Returns (epoch, step) as saved."""
+        from ..checkpoint import _load, vae_state_from
+        data = _load(path)
+        self.vae_model.load_state_dict(vae_state_from(data))
+        if optimizer is not None and data.get("opt") is not None:
+            optimizer.load_state_dict(data["opt"])
+        return int(data.get("epoch", 0)), int(data.get("step", 0))
 
     @torch.no_grad()
     def validation_loss(self, dataloader, sample_posterior: bool = False, seed: int = 0) -> dict:
