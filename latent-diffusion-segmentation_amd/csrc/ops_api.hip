@@ -1203,7 +1203,8 @@ int ldmseg_op_conv_dgrad(const float* dy, const float* w, int B, int Ci, int H, 
   Stage st(stream, dtype, true);
   hipStream_t s = st.s;
   const int epi = nchw_epi ? EPI_NCHW_F32 : EPI_STORE;
-  const int Cop = (int)rup(Co, 32), Np = (int)rup(Ci, igemm_pick_bn(Ci, epi)), P = B * H * W;
+  const DgradShape ds = dgrad_conv_shape(Co, Ci, epi);
+  const int Cop = ds.cin_pad, Np = ds.N, P = B * H * W;
   float* wp = (float*)st.buf((size_t)Np * 9 * Cop * sizeof(float));
   st.step([&] { return launch_pack_dgrad_conv(w, wp, Co, Ci, Np, Cop, s) || (st.x3 == 2 && launch_split_planes(wp, (size_t)Np * 9 * Cop, s)); });
   IgemmParams p;
@@ -1223,7 +1224,7 @@ int ldmseg_op_convt2_dgrad(const float* dy, const float* w, int B, int Ci, int H
   if (!dy || !w || !dx || B < 1 || Ci < 4 || Ci % 4 || Co < 8 || Co % 8 || H < 1 || W < 1 || (dtype != 0 && dtype != 2 && dtype != 3)) return -2;
   Stage st(stream, dtype, true);
   hipStream_t s = st.s;
-  const int Np = (int)rup(Ci, igemm_pick_bn(Ci, EPI_STORE)), P = B * H * W;
+  const int Np = dgrad_convt_shape(Ci, Co).N, P = B * H * W;
   float* wp = (float*)st.buf((size_t)Np * 4 * Co * sizeof(float));
   st.step([&] { return launch_pack_dgrad_convt(w, wp, Ci, Co, Np, s) || (st.x3 == 2 && launch_split_planes(wp, (size_t)Np * 4 * Co, s)); });
   IgemmParams p;
@@ -1299,7 +1300,8 @@ int ldmseg_op_conv_s2_dgrad(const float* dy, const float* w, int B, int Ci, int 
   Stage st(stream, dtype, true);
   hipStream_t s = st.s;
   const int Ho = conv_out_dim(H, 2), Wo = conv_out_dim(W, 2);
-  const int Cop = (int)rup(Co, 32), Np = (int)rup(4 * Ci, igemm_pick_bn(4 * Ci, EPI_CONVT2)), P = B * Ho * Wo;
+  const DgradShape ds = dgrad_conv_s2_shape(Co, Ci);
+  const int Cop = ds.cin_pad, Np = ds.N, P = B * Ho * Wo;
   float* wp = (float*)st.buf((size_t)Np * 9 * Cop * sizeof(float));
   st.step([&] { return launch_pack_dgrad_conv_s2(w, wp, Co, Ci, Np, Cop, s) || (st.x3 == 2 && launch_split_planes(wp, (size_t)Np * 9 * Cop, s)); });
   IgemmParams p;

@@ -153,6 +153,15 @@ struct ConvW {
   int xt_cin = 0;         // extra-tap packings (ResnetW::conv2x): input channels of the 1x1 part behind the nine taps' columns
 };
 struct NormW { float* g = nullptr; float* b = nullptr; int C = 0; };
+// the shape of a Conv2d / Linear packing [Npad][k*k][cin_pad]: n_store >= Co forces explicit zero output channels, epi decides the N tile
+inline void conv_shape(int Co, int k, int cin_pad, int n_store, int epi, ConvW* out) {
+  const int nreal = n_store > Co ? n_store : Co;
+  out->N = (int)rup(nreal, igemm_pick_bn(nreal, epi));
+  out->n_valid = nreal;
+  out->cin_pad = cin_pad;
+  out->taps = k * k;
+  out->cout = Co;
+}
 
 // What every handle owns: its device and compute mode, the parameter arena, the workspace with its cached plan and the two
 // hand-off regions of its launches.  The four public handle types derive from it.
@@ -226,14 +235,8 @@ struct Builder {      // repacks a state dict into the arena of the handle it is
            int n_store = 0, int epi = EPI_STORE, bool cm = false) {
     const float* w;
     TRY(wm->get(prefix + ".weight", (int64_t)Co * Ci * k * k, &w));
-    const int nreal = n_store > Co ? n_store : Co;
-    const int bn = igemm_pick_bn(nreal, epi);
-    const int Npad = (int)rup(nreal, bn);
-    out->N = Npad;
-    out->n_valid = nreal;
-    out->cin_pad = cin_pad;
-    out->taps = k * k;
-    out->cout = Co;
+    conv_shape(Co, k, cin_pad, n_store, epi, out);
+    const int Npad = out->N;
     TRY(arena->alloc(&out->w, (size_t)Npad * k * k * cin_pad * esize(dt)));
     TRY(launch_repack_conv(w, out->w, Co, Ci, k, k, Npad, cin_pad, dt, s));
     weights(out->w, (size_t)Npad * k * k * cin_pad);
@@ -423,6 +426,20 @@ struct Exec {
     if (o.resid) { p.resid = o.resid->p; p.ldr = o.resid->C; }
     p.out = out->p; p.ldo = w.n_valid;
     p.epi = EPI_STORE; p.silu = o.silu;
+    return igemm(p);
+  }
+
+  // A GEMM over the B x H x W map `src` (C stored channels a pixel) with `w` as packed, into memory the caller names, for the
+  // launches Exec::conv does not make: a head conv into caller memory (EPI_NCHW_F32: fp32 NCHW, or EPI_STORE rows of n_valid),
+  // the ConvTranspose2d scatter (EPI_CONVT2: rows of w.cout on the 2H x 2W map), a data gradient on its own packing (no bias).
+  int gemm(const ConvW& w, const void* src, int C, int H, int W, void* out, int epi) {
+    IgemmParams p;
+    p.src0 = src; p.C0 = C; p.B = B; p.Hi = p.Ho = H; p.Wi = p.Wo = W;
+    p.taps = w.taps; p.M = B * H * W; p.N = w.N; p.n_valid = w.n_valid;
+    p.W = w.w; p.bias = w.bias;
+    p.out = out; p.epi = epi;
+    if (epi == EPI_CONVT2) p.ldo = p.cout = w.cout;
+    else if (epi != EPI_NCHW_F32) p.ldo = w.n_valid;
     return igemm(p);
   }
 

@@ -11,20 +11,23 @@ using namespace ldmseg;
 using namespace ldmseg::rt;
 
 // =================================================================== seg-VAE
+// One row of a half's layer table (encoder_rows / decoder_rows below: the model's layers in order) and what the handle holds for
+// it.  Row i's reference keys are prefix.weight and prefix.bias: slots 2 i and 2 i + 1 of the name lists the ABI takes.
+enum RowKind { ROW_CONV3, ROW_CONVT2, ROW_LN, ROW_GN };     // Conv2d 3x3 pad 1 | ConvTranspose2d k2 s2 | LayerNorm2d | GroupNorm
+struct VaeRow {
+  RowKind kind;
+  std::string prefix;
+  int Co, Ci;              // (a norm row: both its channel count)
+  int stride, silu;        // silu: SiLU follows - in the conv's epilogue, inside the norm's launch
+  int cin_pad, n_store;    // storage widths of a conv: the input's channels as stored, the output channels stored (0: Co)
+  int dgrad_epi;           // the epilogue of the row's data-gradient GEMM, -1: the handle packs none (bf16 storage, or the input is data)
+  float eps;               // norm rows
+};
+struct RowW { ConvW w, d; NormW n; };       // forward packing, data-gradient packing (ldmseg_vae_*_backward), norm vectors
+struct VaeHalf { std::vector<VaeRow> rows; std::vector<RowW> w; };       // w[i] belongs to rows[i]; the last row is the head conv
 struct ldmseg_vae : HandleBase {
   ldmseg_vae_cfg cfg{};
-  // encoder
-  ConvW enc[10];          // encoder.{0,2,3,5,6,8,9,11,15} in order (9 used)
-  NormW enc_gn;
-  int enc_ch[5]{};        // storage channel counts
-  // decoder
-  ConvW dec_in, dec_out;
-  ConvW convt[4];
-  NormW ln[4], dec_gn;
-  // fp32-storage handles: the decoder's convs packed a second time for their data gradients (ldmseg_vae_decode_backward)
-  ConvW dec_in_d, dec_out_d, convt_d[4];
-  // ... and the encoder's (ldmseg_vae_encode_backward): enc_d[k] for enc[k], k = 1 .. 8 (the first conv's input is data)
-  ConvW enc_d[10];
+  VaeHalf enc, dec;
 };
 
 // =================================================================== image VAE encoder (AutoencoderKL, SD-1.x)
@@ -41,81 +44,76 @@ struct ldmseg_vae_image : HandleBase {
 namespace {
 
 inline int cstore(int c, int dt) { return (int)rup(c, bke(dt)); }
-
-// ---- the decoder's data-gradient packings: the same igemm reads them as ordinary [N][K] weights
-// dX = conv3x3(dY, W transposed and rotated by 180 degrees): N = Ci, K = 9 * Co (Co padded to a K tile)
-void dgrad_conv_shape(ConvW* d, int Co, int Ci, int epi) {
-  d->N = (int)rup(Ci, igemm_pick_bn(Ci, epi)); d->n_valid = Ci; d->cin_pad = (int)rup(Co, bke(DT_F32)); d->taps = 9; d->cout = Ci;
-}
-// dX[p] = dY[p, 2x2, :] W[ci][co][q]: N = Ci, K = 4 * Co on the phase-major dY
-void dgrad_convt_shape(ConvW* d, int Ci, int Co) {
-  d->N = (int)rup(Ci, igemm_pick_bn(Ci, EPI_STORE)); d->n_valid = Ci; d->cin_pad = 4 * Co; d->taps = 1; d->cout = Ci;
-}
 size_t convw_floats(const ConvW& d) { return (size_t)d.N * d.taps * d.cin_pad; }
 
-// dX of a STRIDE-2 conv3x3 = the four output phases as 4 Ci columns of one 3x3 GEMM over dY, scattered by EPI_CONVT2
-void dgrad_conv_s2_shape(ConvW* d, int Co, int Ci) {
-  d->N = (int)rup(4 * Ci, igemm_pick_bn(4 * Ci, EPI_CONVT2)); d->n_valid = 4 * Ci; d->cin_pad = (int)rup(Co, bke(DT_F32)); d->taps = 9; d->cout = Ci;
+// the encoder's backward needs every activation width to be its channel count (no padded channels between the layers)
+bool encoder_backward_ok(const ldmseg_vae_cfg& c) {
+  for (int i = 0; i < 4; ++i)
+    if (c.block_out_channels[i] % 32) return false;
+  return c.int_channels % 32 == 0 && c.latent_channels * c.num_latents <= 32;
 }
 
-// the encoder's nine convs in model order (vae.py:174-244): state-dict index, channels, stride, whether SiLU follows in the epilogue
-struct EncLayer { int idx, Co, Ci, stride, silu; };
-constexpr int kEncLayers = 9, kEncNormIdx = 13;
-std::vector<EncLayer> encoder_layers(const ldmseg_vae_cfg& c) {
+// ---- the two layer tables, pure functions of the configuration.  Everything that walks a half - build, (re)pack, the forward,
+// the backward, the ABI's name lists - reads these rows; the state-dict indices appear nowhere else.
+// encoder (vae.py:174-244): conv+SiLU, [conv, stride-2 conv+SiLU] x 3, conv, GroupNorm+SiLU, conv
+std::vector<VaeRow> encoder_rows(const ldmseg_vae_cfg& c) {
+  const int dt = c.compute_dtype == LDMSEG_BF16 ? DT_BF16 : DT_F32;
+  const bool dgrad = dt == DT_F32 && encoder_backward_ok(c);
   const int* boc = c.block_out_channels;
-  std::vector<EncLayer> l;
-  l.push_back({0, boc[0], c.in_channels, 1, 1});
+  std::vector<VaeRow> r;
+  auto conv = [&](int idx, int Co, int Ci, int stride, int silu, int cin_pad, int n_store) {
+    const int epi = (!dgrad || idx == 0) ? -1 : stride == 2 ? EPI_CONVT2 : EPI_STORE;      // (the first conv's input is data)
+    r.push_back({ROW_CONV3, "encoder." + std::to_string(idx), Co, Ci, stride, silu, cin_pad, n_store, epi, 0.f});
+  };
+  conv(0, boc[0], c.in_channels, 1, 1, bke(dt), cstore(boc[0], dt));
   int idx = 2;
   for (int i = 0; i < 3; ++i) {
-    l.push_back({idx, boc[i], boc[i], 1, 0});
-    l.push_back({idx + 1, boc[i + 1], boc[i], 2, 1});
+    conv(idx, boc[i], boc[i], 1, 0, cstore(boc[i], dt), cstore(boc[i], dt));
+    conv(idx + 1, boc[i + 1], boc[i], 2, 1, cstore(boc[i], dt), cstore(boc[i + 1], dt));
     idx += 3;
   }
-  l.push_back({idx, c.int_channels, boc[3], 1, 0});
-  l.push_back({idx + 4, c.latent_channels * c.num_latents, c.int_channels, 1, 0});
-  return l;
+  conv(idx, c.int_channels, boc[3], 1, 0, cstore(boc[3], dt), 0);
+  r.push_back({ROW_GN, "encoder." + std::to_string(idx + 2), c.int_channels, c.int_channels, 1, 1, 0, 0, -1, 1e-6f});
+  conv(idx + 4, c.latent_channels * c.num_latents, c.int_channels, 1, 0, c.int_channels, 0);
+  return r;
 }
-
-// reference keys of the decoder in model order with their element counts: (conv_in w, b), per upscaler (convT w, b, LayerNorm w, b),
-// (GroupNorm w, b), (conv_out w, b)
-struct DecKey { std::string name; int64_t numel; };
-std::vector<DecKey> decoder_keys(const ldmseg_vae_cfg& c) {
-  std::vector<DecKey> k;
-  auto add = [&](int idx, int64_t wn, int64_t bn) {
-    k.push_back({"decoder." + std::to_string(idx) + ".weight", wn});
-    k.push_back({"decoder." + std::to_string(idx) + ".bias", bn});
+// decoder (vae.py:123-172): conv, [ConvTranspose2d, LayerNorm2d+SiLU] x num_upscalers, GroupNorm+SiLU, conv
+std::vector<VaeRow> decoder_rows(const ldmseg_vae_cfg& c) {
+  const int dt = c.compute_dtype == LDMSEG_BF16 ? DT_BF16 : DT_F32;
+  std::vector<VaeRow> r;
+  auto row = [&](RowKind kind, int idx, int Co, int Ci, int stride, int cin_pad, int dgrad_epi, float eps) {
+    const bool norm = kind == ROW_LN || kind == ROW_GN;
+    r.push_back({kind, "decoder." + std::to_string(idx), Co, Ci, stride, norm, cin_pad, 0, (norm || dt != DT_F32) ? -1 : dgrad_epi, eps});
   };
-  add(0, (int64_t)c.int_channels * c.latent_channels * 9, c.int_channels);
+  row(ROW_CONV3, 0, c.int_channels, c.latent_channels, 1, bke(dt), EPI_NCHW_F32, 0.f);      // (its data gradient is grad_z)
   int idx = 2, cin = c.int_channels;
   for (int i = 0; i < c.num_upscalers; ++i) {
-    add(idx, (int64_t)cin * c.upscale_channels * 4, c.upscale_channels);
-    add(idx + 1, c.upscale_channels, c.upscale_channels);
+    row(ROW_CONVT2, idx, c.upscale_channels, cin, 2, cin, EPI_STORE, 0.f);
+    row(ROW_LN, idx + 1, c.upscale_channels, c.upscale_channels, 1, 0, -1, 1e-6f);
     cin = c.upscale_channels;
     idx += 3;
   }
-  add(idx, cin, cin);
-  add(idx + 2, (int64_t)c.out_channels * cin * 9, c.out_channels);
-  return k;
+  row(ROW_GN, idx, cin, cin, 1, 0, -1, 1e-5f);
+  row(ROW_CONV3, idx + 2, c.out_channels, cin, 1, cin, EPI_STORE, 0.f);
+  return r;
 }
 
-// ... and of the encoder: (conv w, b) of layers 0 .. 7 at slots 2 k, 2 k + 1, (GroupNorm w, b) at 16, 17, (head w, b) at 18, 19
-std::vector<DecKey> encoder_keys(const ldmseg_vae_cfg& c) {
-  std::vector<DecKey> k;
-  const std::vector<EncLayer> l = encoder_layers(c);
-  auto add = [&](int idx, int64_t wn, int64_t bn) {
-    k.push_back({"encoder." + std::to_string(idx) + ".weight", wn});
-    k.push_back({"encoder." + std::to_string(idx) + ".bias", bn});
-  };
-  for (int i = 0; i < kEncLayers - 1; ++i) add(l[i].idx, (int64_t)l[i].Co * l[i].Ci * 9, l[i].Co);
-  add(l[kEncLayers - 1].idx - 2, c.int_channels, c.int_channels);
-  add(l[kEncLayers - 1].idx, (int64_t)l[kEncLayers - 1].Co * l[kEncLayers - 1].Ci * 9, l[kEncLayers - 1].Co);
+// reference keys of a half in model order with their element counts: (weight, bias) of every row
+struct VaeKey { std::string name; int64_t numel; };
+int64_t weight_numel(const VaeRow& r) {
+  return r.kind == ROW_CONV3 ? (int64_t)r.Co * r.Ci * 9 : r.kind == ROW_CONVT2 ? (int64_t)r.Ci * r.Co * 4 : r.Co;
+}
+std::vector<VaeKey> row_keys(const std::vector<VaeRow>& rows) {
+  std::vector<VaeKey> k;
+  for (const VaeRow& r : rows) {
+    k.push_back({r.prefix + ".weight", weight_numel(r)});
+    k.push_back({r.prefix + ".bias", r.Co});
+  }
   return k;
 }
-constexpr size_t kEncNormSlot = 16, kEncHeadSlot = 18;
-inline size_t enc_slot(int k) { return k == kEncLayers - 1 ? kEncHeadSlot : (size_t)2 * k; }
 
 // name -> slot of `keys`, with the checks the backward and the load entries share; -1 and the message set on a bad name or numel
-int key_slot(const std::vector<DecKey>& keys, const char* name, int64_t numel, const char* what) {
+int key_slot(const std::vector<VaeKey>& keys, const char* name, int64_t numel, const char* what) {
   size_t k = 0;
   while (name && k < keys.size() && keys[k].name != name) ++k;
   if (!name) fail(LDMSEG_E_ARG, "null tensor name");
@@ -124,186 +122,109 @@ int key_slot(const std::vector<DecKey>& keys, const char* name, int64_t numel, c
   else return (int)k;
   return -1;
 }
-
-// (Re)packs the encoder tensors `wm` holds into the buffers the handle owns, as vae_pack_decoder does for the decoder's
-int vae_pack_encoder(ldmseg_vae* v, const WeightMap& wm, hipStream_t s, bool forward_too) {
-  const ldmseg_vae_cfg& c = v->cfg;
-  const int dt = v->dt;
-  const bool f32 = dt == DT_F32;
-  const std::vector<DecKey> keys = encoder_keys(c);
-  const std::vector<EncLayer> l = encoder_layers(c);
-  auto has = [&](size_t slot, const float** p) {
-    auto it = wm.m.find(keys[slot].name);
-    if (it == wm.m.end()) return false;
-    *p = it->second.first;
-    return true;
-  };
-  auto planes = [&](void* w, size_t nfloats) { return (v->x3 && f32) ? launch_split_planes(w, nfloats, s) : 0; };
-  for (int k = 0; k < kEncLayers; ++k) {
-    const size_t slot = enc_slot(k);
-    ConvW& fw = v->enc[k];
-    ConvW& dg = v->enc_d[k];
-    const float* p;
-    if (has(slot, &p)) {
-      if (forward_too) {
-        TRY(launch_repack_conv(p, fw.w, l[k].Co, l[k].Ci, 3, 3, fw.N, fw.cin_pad, dt, s));
-        TRY(planes(fw.w, convw_floats(fw)));
-      }
-      if (f32 && dg.w) {
-        if (l[k].stride == 2) TRY(launch_pack_dgrad_conv_s2(p, (float*)dg.w, l[k].Co, l[k].Ci, dg.N, dg.cin_pad, s));
-        else TRY(launch_pack_dgrad_conv(p, (float*)dg.w, l[k].Co, l[k].Ci, dg.N, dg.cin_pad, s));
-        TRY(planes(dg.w, convw_floats(dg)));
-      }
-    }
-    if (forward_too && has(slot + 1, &p)) TRY(launch_padded_bias(p, l[k].Co, fw.bias, fw.N, s));
+// The (n, names, ptrs, numels) of a backward or load entry as pointers by slot (null: a name that was not given).  null_ok: a
+// null pointer may come with a name (a gradient that is not wanted).
+int by_slot(const std::vector<VaeRow>& rows, bool decoder, int n, const char* const* names, void* const* ptrs, const int64_t* numels, bool null_ok,
+            std::vector<void*>* out) {
+  const std::vector<VaeKey> keys = row_keys(rows);
+  out->assign(keys.size(), nullptr);
+  for (int i = 0; i < n; ++i) {
+    if (!null_ok && !ptrs[i]) return fail(LDMSEG_E_ARG, decoder ? "null decoder tensor" : "null encoder tensor");
+    const int k = key_slot(keys, names[i], numels[i], decoder ? "a decoder" : "an encoder");
+    if (k < 0) return LDMSEG_E_ARG;
+    (*out)[k] = ptrs[i];
   }
-  const float* p;
-  if (forward_too && has(kEncNormSlot, &p)) HIP_TRY(hipMemcpyAsync(v->enc_gn.g, p, c.int_channels * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (forward_too && has(kEncNormSlot + 1, &p)) HIP_TRY(hipMemcpyAsync(v->enc_gn.b, p, c.int_channels * sizeof(float), hipMemcpyDeviceToDevice, s));
   return 0;
 }
-// the encoder's backward needs every activation width to be its channel count (no padded channels between the layers)
-bool encoder_backward_ok(const ldmseg_vae_cfg& c) {
-  for (int i = 0; i < 4; ++i)
-    if (c.block_out_channels[i] % 32) return false;
-  return c.int_channels % 32 == 0 && c.latent_channels * c.num_latents <= 32;
+
+// ---- one pack path: a row's source tensors (state-dict layout, fp32, on the device; null: left as it is) into the buffers the
+// handle owns - forward packing, data-gradient packing where the row has one, padded bias, norm vectors - for vae_build and
+// ldmseg_vae_load_* alike.  A bf16x3 handle's matrices become hi | lo planes right here, once per packing (a second split would
+// destroy them: nothing of the seg-VAE is registered with Builder::weights).
+int split_x3(const ldmseg_vae* v, const ConvW& m, hipStream_t s) {
+  return (v->x3 && v->dt == DT_F32) ? launch_split_planes(m.w, convw_floats(m), s) : 0;
+}
+int pack_conv3(const ldmseg_vae* v, const VaeRow& r, const RowW& o, const float* w, const float* bias, hipStream_t s) {
+  if (w) {
+    TRY(launch_repack_conv(w, o.w.w, r.Co, r.Ci, 3, 3, o.w.N, o.w.cin_pad, v->dt, s));
+    TRY(split_x3(v, o.w, s));
+    if (o.d.w) {
+      if (r.stride == 2) TRY(launch_pack_dgrad_conv_s2(w, (float*)o.d.w, r.Co, r.Ci, o.d.N, o.d.cin_pad, s));
+      else TRY(launch_pack_dgrad_conv(w, (float*)o.d.w, r.Co, r.Ci, o.d.N, o.d.cin_pad, s));
+      TRY(split_x3(v, o.d, s));
+    }
+  }
+  if (bias) TRY(launch_padded_bias(bias, r.Co, o.w.bias, o.w.N, s));
+  return 0;
+}
+int pack_convt2(const ldmseg_vae* v, const VaeRow& r, const RowW& o, const float* w, const float* bias, hipStream_t s) {
+  if (w) {
+    TRY(launch_repack_convt2(w, o.w.w, r.Ci, r.Co, v->dt, s));
+    TRY(split_x3(v, o.w, s));
+    if (o.d.w) {
+      TRY(launch_pack_dgrad_convt(w, (float*)o.d.w, r.Ci, r.Co, o.d.N, s));
+      TRY(split_x3(v, o.d, s));
+    }
+  }
+  if (bias)       // one copy per output phase
+    for (int q = 0; q < 4; ++q) HIP_TRY(hipMemcpyAsync(o.w.bias + q * r.Co, bias, r.Co * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+int pack_norm(const VaeRow& r, const RowW& o, const float* w, const float* bias, hipStream_t s) {
+  if (w) HIP_TRY(hipMemcpyAsync(o.n.g, w, r.Co * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (bias) HIP_TRY(hipMemcpyAsync(o.n.b, bias, r.Co * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+int pack_row(const ldmseg_vae* v, const VaeRow& r, const RowW& o, const float* w, const float* bias, hipStream_t s) {
+  return r.kind == ROW_CONV3 ? pack_conv3(v, r, o, w, bias, s) : r.kind == ROW_CONVT2 ? pack_convt2(v, r, o, w, bias, s) : pack_norm(r, o, w, bias, s);
 }
 
-// (Re)packs the decoder tensors `wm` holds into the buffers the handle owns - forward packing, data-gradient packing, the hi | lo
-// planes of a bf16x3 handle, norm and bias vectors - with the launches the build uses.  Keys that are absent are left alone.
-int vae_pack_decoder(ldmseg_vae* v, const WeightMap& wm, hipStream_t s, bool forward_too) {
-  const ldmseg_vae_cfg& c = v->cfg;
-  const int dt = v->dt;
-  const bool f32 = dt == DT_F32;
-  const std::vector<DecKey> keys = decoder_keys(c);
-  auto has = [&](size_t slot, const float** p) {
-    auto it = wm.m.find(keys[slot].name);
-    if (it == wm.m.end()) return false;
-    *p = it->second.first;
-    return true;
-  };
-  auto planes = [&](void* w, size_t nfloats) { return (v->x3 && f32) ? launch_split_planes(w, nfloats, s) : 0; };
-  auto conv3 = [&](size_t slot, ConvW& fw, ConvW& dg, int Co, int Ci) -> int {
-    const float* p;
-    if (has(slot, &p)) {
-      if (forward_too) {
-        TRY(launch_repack_conv(p, fw.w, Co, Ci, 3, 3, fw.N, fw.cin_pad, dt, s));
-        TRY(planes(fw.w, convw_floats(fw)));
-      }
-      if (f32) {
-        TRY(launch_pack_dgrad_conv(p, (float*)dg.w, Co, Ci, dg.N, dg.cin_pad, s));
-        TRY(planes(dg.w, convw_floats(dg)));
-      }
-    }
-    if (forward_too && has(slot + 1, &p)) TRY(launch_padded_bias(p, Co, fw.bias, fw.N, s));
+// the shapes of a row's packings and their buffers in the handle's arena, unfilled
+int alloc_row(ldmseg_vae* v, const VaeRow& r, RowW* o) {
+  auto floats = [&](float** p, size_t n) {
+    void* q;
+    TRY(v->arena.alloc(&q, n * sizeof(float)));
+    *p = (float*)q;
     return 0;
   };
-  auto vec = [&](size_t slot, float* dst, int n) -> int {
-    const float* p;
-    if (forward_too && has(slot, &p)) HIP_TRY(hipMemcpyAsync(dst, p, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return 0;
-  };
-  size_t slot = 0;
-  TRY(conv3(slot, v->dec_in, v->dec_in_d, c.int_channels, c.latent_channels));
-  slot += 2;
-  int cin = c.int_channels;
-  for (int i = 0; i < c.num_upscalers; ++i) {
-    const int Co = c.upscale_channels;
-    ConvW& t = v->convt[i];
-    const float* p;
-    if (has(slot, &p)) {
-      if (forward_too) {
-        TRY(launch_repack_convt2(p, t.w, cin, Co, dt, s));
-        TRY(planes(t.w, (size_t)4 * Co * cin));
-      }
-      if (f32) {
-        TRY(launch_pack_dgrad_convt(p, (float*)v->convt_d[i].w, cin, Co, v->convt_d[i].N, s));
-        TRY(planes(v->convt_d[i].w, convw_floats(v->convt_d[i])));
-      }
-    }
-    if (forward_too && has(slot + 1, &p))
-      for (int q = 0; q < 4; ++q) HIP_TRY(hipMemcpyAsync(t.bias + q * Co, p, Co * sizeof(float), hipMemcpyDeviceToDevice, s));
-    TRY(vec(slot + 2, v->ln[i].g, Co));
-    TRY(vec(slot + 3, v->ln[i].b, Co));
-    cin = Co;
-    slot += 4;
+  if (r.kind == ROW_LN || r.kind == ROW_GN) {
+    o->n.C = r.Co;
+    TRY(floats(&o->n.g, r.Co));
+    return floats(&o->n.b, r.Co);
   }
-  TRY(vec(slot, v->dec_gn.g, cin));
-  TRY(vec(slot + 1, v->dec_gn.b, cin));
-  TRY(conv3(slot + 2, v->dec_out, v->dec_out_d, c.out_channels, cin));
-  return 0;
+  ConvW& f = o->w;
+  if (r.kind == ROW_CONV3) {
+    conv_shape(r.Co, 3, r.cin_pad, r.n_store, EPI_STORE, &f);
+  } else {      // [4 phases x Co][Ci], the bias once per phase
+    f.N = f.n_valid = 4 * r.Co; f.cin_pad = r.cin_pad; f.taps = 1; f.cout = r.Co;
+  }
+  TRY(v->arena.alloc(&f.w, convw_floats(f) * esize(v->dt)));
+  TRY(floats(&f.bias, f.N));
+  if (r.dgrad_epi < 0) return 0;
+  const DgradShape d = r.kind == ROW_CONVT2 ? dgrad_convt_shape(r.Ci, r.Co) : r.stride == 2 ? dgrad_conv_s2_shape(r.Co, r.Ci) : dgrad_conv_shape(r.Co, r.Ci, r.dgrad_epi);
+  o->d.N = d.N; o->d.n_valid = d.n_valid; o->d.cin_pad = d.cin_pad; o->d.taps = d.taps; o->d.cout = d.cout;
+  return v->arena.alloc(&o->d.w, convw_floats(o->d) * sizeof(float));
 }
 
 int vae_build(ldmseg_vae* v, const WeightMap& wm) {
   Builder b(*v, wm);
-  hipStream_t s = b.s;
   const ldmseg_vae_cfg& c = v->cfg;
   const int dt = v->dt;
   if (c.in_channels > bke(dt) || c.latent_channels > bke(dt)) return fail(LDMSEG_E_ARG, "too many boundary channels");
   if (c.int_channels % 64 || c.upscale_channels % 64 || c.num_upscalers < 1 || c.num_upscalers > 4)
     return fail(LDMSEG_E_ARG, "unsupported seg-VAE configuration");
-  // ---- encoder (vae.py:174-244) ----
-  const int* boc = c.block_out_channels;
-  int k = 0;
-  TRY(b.conv("encoder.0", boc[0], c.in_channels, 3, bke(dt), &v->enc[k++], true, cstore(boc[0], dt)));
-  int idx = 2;
-  for (int i = 0; i < 3; ++i) {
-    TRY(b.conv("encoder." + std::to_string(idx), boc[i], boc[i], 3, cstore(boc[i], dt), &v->enc[k++], true, cstore(boc[i], dt)));
-    TRY(b.conv("encoder." + std::to_string(idx + 1), boc[i + 1], boc[i], 3, cstore(boc[i], dt), &v->enc[k++], true,
-               cstore(boc[i + 1], dt)));
-    idx += 3;
-  }
-  TRY(b.conv("encoder." + std::to_string(idx), c.int_channels, boc[3], 3, cstore(boc[3], dt), &v->enc[k++]));
-  TRY(b.norm("encoder." + std::to_string(idx + 2), c.int_channels, &v->enc_gn));
-  TRY(b.conv("encoder." + std::to_string(idx + 4), c.latent_channels * c.num_latents, c.int_channels, 3, c.int_channels,
-             &v->enc[k++]));
-  // ---- decoder (vae.py:123-172) ----
-  TRY(b.conv("decoder.0", c.int_channels, c.latent_channels, 3, bke(dt), &v->dec_in));
-  idx = 2;
-  int cin = c.int_channels;
-  for (int i = 0; i < c.num_upscalers; ++i) {
-    ConvW& t = v->convt[i];
-    const int Co = c.upscale_channels;
-    const float *w, *bias;
-    TRY(wm.get("decoder." + std::to_string(idx) + ".weight", (int64_t)cin * Co * 4, &w));
-    TRY(wm.get("decoder." + std::to_string(idx) + ".bias", Co, &bias));
-    t.N = 4 * Co; t.n_valid = 4 * Co; t.cin_pad = cin; t.taps = 1; t.cout = Co;
-    TRY(v->arena.alloc(&t.w, (size_t)4 * Co * cin * esize(dt)));
-    TRY(launch_repack_convt2(w, t.w, cin, Co, dt, s));
-    b.weights(t.w, (size_t)4 * Co * cin);
-    void* pb;
-    TRY(v->arena.alloc(&pb, (size_t)4 * Co * sizeof(float)));
-    for (int q = 0; q < 4; ++q)
-      HIP_TRY(hipMemcpyAsync((float*)pb + q * Co, bias, Co * sizeof(float), hipMemcpyDeviceToDevice, s));
-    t.bias = (float*)pb;
-    b.nparams += (int64_t)cin * Co * 4 + Co;
-    TRY(b.norm("decoder." + std::to_string(idx + 1), Co, &v->ln[i]));
-    cin = Co;
-    idx += 3;
-  }
-  TRY(b.norm("decoder." + std::to_string(idx), cin, &v->dec_gn));
-  TRY(b.conv("decoder." + std::to_string(idx + 2), c.out_channels, cin, 3, cin, &v->dec_out));
-  if (dt == DT_F32) {
-    // the data-gradient packings (the planes of a bf16x3 handle are made by vae_pack_decoder itself: not registered with b.weights)
-    dgrad_conv_shape(&v->dec_in_d, c.int_channels, c.latent_channels, EPI_NCHW_F32);
-    dgrad_conv_shape(&v->dec_out_d, c.out_channels, cin, EPI_STORE);
-    TRY(v->arena.alloc(&v->dec_in_d.w, convw_floats(v->dec_in_d) * sizeof(float)));
-    TRY(v->arena.alloc(&v->dec_out_d.w, convw_floats(v->dec_out_d) * sizeof(float)));
-    int ci = c.int_channels;
-    for (int i = 0; i < c.num_upscalers; ++i) {
-      dgrad_convt_shape(&v->convt_d[i], ci, c.upscale_channels);
-      TRY(v->arena.alloc(&v->convt_d[i].w, convw_floats(v->convt_d[i]) * sizeof(float)));
-      ci = c.upscale_channels;
-    }
-    TRY(vae_pack_decoder(v, wm, s, false));
-    if (encoder_backward_ok(c)) {
-      const std::vector<EncLayer> l = encoder_layers(c);
-      for (int i = 1; i < kEncLayers; ++i) {
-        if (l[i].stride == 2) dgrad_conv_s2_shape(&v->enc_d[i], l[i].Co, l[i].Ci);
-        else dgrad_conv_shape(&v->enc_d[i], l[i].Co, l[i].Ci, EPI_STORE);
-        TRY(v->arena.alloc(&v->enc_d[i].w, convw_floats(v->enc_d[i]) * sizeof(float)));
-      }
-      TRY(vae_pack_encoder(v, wm, s, false));
+  v->enc.rows = encoder_rows(c);
+  v->dec.rows = decoder_rows(c);
+  for (VaeHalf* h : {&v->enc, &v->dec}) {
+    h->w.resize(h->rows.size());
+    for (size_t i = 0; i < h->rows.size(); ++i) {
+      const VaeRow& r = h->rows[i];
+      const float *w, *bias;
+      TRY(wm.get(r.prefix + ".weight", weight_numel(r), &w));
+      TRY(wm.get(r.prefix + ".bias", r.Co, &bias));
+      TRY(alloc_row(v, r, &h->w[i]));
+      TRY(pack_row(v, r, h->w[i], w, bias, b.s));
+      b.nparams += weight_numel(r) + r.Co;
     }
   }
   return b.finish(*v);
@@ -337,44 +258,64 @@ struct DecodeTail {
   const SemsegOut* so = nullptr;
 };
 
-// the decoder on an executor that is already set up (the reconstruct chain runs encoder and decoder on ONE workspace pass)
+// the half's input, fp32 NCHW [B, C, H, H] * mul + add, as the packed NHWC activation of one K tile
+int vae_input(Exec& ex, const float* x, int C, int H, float mul, float add, Act* a) {
+  *a = ex.new_act(bke(ex.dt), H, H, true);
+  return ex.launch("launch_pack_nchw failed", 4, 0, 0, no_label, [&] { return launch_pack_nchw(x, a->p, ex.B, C, H * H, bke(ex.dt), mul, add, ex.dt, ex.s); });
+}
+
+// what a backward keeps of its half's forward: in[i] = the input of row i (the head's too), pre[i] = the output of a conv + SiLU row before the SiLU
+struct Keep {
+  std::vector<Act> in, pre;
+  explicit Keep(size_t rows) : in(rows), pre(rows) {}
+};
+// The forward walk of a half from its packed input `h` up to the head conv's input *out (the GroupNorm's output).  keep null: the
+// launches of a forward - SiLU in the conv's epilogue, LayerNorm in place.  With keep, what a backward replays: a conv + SiLU row is
+// the SiLU-less conv, whose output stays, and one silu_fwd launch; LayerNorm out of place; every row's input retained.
+int vae_trunk(Exec& ex, const VaeHalf& half, Act h, Keep* keep, Act* out) {
+  for (size_t i = 0;; ++i) {
+    if (keep) keep->in[i] = h;
+    if (i + 1 == half.rows.size()) break;
+    const VaeRow& r = half.rows[i];
+    const RowW& w = half.w[i];
+    Act o;
+    if (r.kind == ROW_CONV3) {
+      TRY(ex.conv(w.w, h, &o, {.stride = r.stride, .silu = keep ? 0 : r.silu}));
+      if (keep && r.silu) {
+        const Act u = keep->pre[i] = o;
+        o = ex.new_act(u.C, u.H, u.W, true);
+        const size_t n = (size_t)ex.B * u.H * u.W * u.C;
+        TRY(ex.launch("launch_silu_fwd failed", 4, 0, 8.0 * n, no_label, [&] { return launch_silu_fwd((const float*)u.p, (float*)o.p, n, ex.s); }));
+      }
+    } else if (r.kind == ROW_CONVT2) {
+      o = ex.new_act(r.Co, 2 * h.H, 2 * h.W, true);
+      TRY(ex.gemm(w.w, h.p, h.C, h.H, h.W, o.p, EPI_CONVT2));
+    } else if (r.kind == ROW_LN) {
+      TRY(ex.layernorm(w.n, h, r.eps, r.silu, &o, !keep));      // (kept: the transposed conv's own output is the backward's input)
+    } else {
+      TRY(ex.groupnorm(w.n, h, nullptr, r.eps, r.silu, &o));
+    }
+    h = o;
+  }
+  *out = h;
+  return 0;
+}
+
+// the decoder on an executor that is already set up (the reconstruct chain runs encoder and decoder on ONE workspace pass): trunk, head, tail
 int vae_decode_body(Exec& ex, ldmseg_vae* v, const float* z, float z_scale, int L, const DecodeTail& tail) {
   const int B = ex.B;
   hipStream_t s = ex.s;
   const int dt = v->dt;
   const ldmseg_vae_cfg& c = v->cfg;
-  Act zin = ex.new_act(bke(dt), L, L, true);
-  TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, no_label, [&] { return launch_pack_nchw(z, zin.p, B, c.latent_channels, L * L, bke(dt), z_scale, 0.f, dt, s); }));
-  Act h;
-  TRY(ex.conv(v->dec_in, zin, &h));
-  for (int i = 0; i < c.num_upscalers; ++i) {
-    const ConvW& t = v->convt[i];
-    Act o = ex.new_act(t.cout, 2 * h.H, 2 * h.W, true);
-    IgemmParams p;
-    p.src0 = h.p; p.C0 = h.C; p.B = B; p.Hi = p.Ho = h.H; p.Wi = p.Wo = h.W;
-    p.M = B * h.H * h.W; p.N = t.N; p.n_valid = t.N; p.W = t.w; p.bias = t.bias;
-    p.out = o.p; p.ldo = t.cout; p.epi = EPI_CONVT2; p.cout = t.cout;
-    TRY(ex.igemm(p));
-    Act n;
-    TRY(ex.layernorm(v->ln[i], o, 1e-6f, 1, &n, true));   // LayerNorm2d + SiLU, in place
-    h = n;
-  }
-  Act g;
-  TRY(ex.groupnorm(v->dec_gn, h, nullptr, 1e-5f, 1, &g));
-  const int H4 = h.H, W4 = h.W, Co = c.out_channels;
-  IgemmParams p;
-  p.src0 = g.p; p.C0 = g.C; p.B = B; p.Hi = p.Ho = H4; p.Wi = p.Wo = W4;
-  p.taps = 9; p.M = B * H4 * W4; p.N = v->dec_out.N; p.n_valid = Co;
-  p.W = v->dec_out.w; p.bias = v->dec_out.bias;
-  if (tail.kind == DecodeTail::LOGITS) {
-    p.out = tail.logits; p.epi = EPI_NCHW_F32;
-    TRY(ex.igemm(p));
-    return 0;
-  }
+  Act zin, g;
+  TRY(vae_input(ex, z, c.latent_channels, L, z_scale, 0.f, &zin));
+  TRY(vae_trunk(ex, v->dec, zin, nullptr, &g));
+  const ConvW& head = v->dec.w.back().w;
+  const int H4 = g.H, W4 = g.W, Co = c.out_channels;
+  if (tail.kind == DecodeTail::LOGITS) return ex.gemm(head, g.p, g.C, H4, W4, tail.logits, EPI_NCHW_F32);
   // every other tail reads NHWC logits at 4L
   Act lo = ex.new_act(Co, H4, W4, false);
-  p.out = lo.p; p.ldo = Co; p.epi = EPI_STORE;
-  TRY(ex.igemm(p));
+  TRY(ex.gemm(head, g.p, g.C, H4, W4, lo.p, EPI_STORE));
   const double lo_bytes = (double)B * H4 * W4 * Co * esize(dt);
   if (tail.kind == DecodeTail::PANOPTIC) {
     const PanopticOut* po = tail.po;
@@ -407,9 +348,9 @@ int vae_decode(ldmseg_vae* v, const float* z, float z_scale, int B, int L, const
   });
 }
 
-// ---- the decoder's backward.  One planned pass: the decoder forward again up to the GroupNorm output (the logits
-// themselves are not needed), keeping what the backward reads, then the chain from d loss / d logits down to every parameter
-// gradient asked for (g[slot], slots as decoder_keys; null = skipped) and to grad_z.
+// ---- the decoder's backward.  One planned pass: the decoder's trunk again, keeping what the backward reads (the
+// logits themselves are not needed), then the chain from d loss / d logits down to every parameter gradient asked for (g[2 i],
+// g[2 i + 1]: weight and bias of row i; null = skipped) and to grad_z.
 struct WgradJob {
   const float* dy; int ldy, N;        // dY [P][ldy], N columns taken
   const float* x; int C;              // X [P][C]
@@ -454,202 +395,131 @@ int vae_decode_backward_body(Exec& ex, ldmseg_vae* v, const float* z, float z_sc
   hipStream_t s = ex.s;
   const int dt = v->dt;
   const ldmseg_vae_cfg& c = v->cfg;
-  const int U = c.num_upscalers, Cu = c.upscale_channels, Co = c.out_channels;
-  // ---- forward again, everything the backward reads is kept
-  Act zin = ex.new_act(bke(dt), L, L, true);
-  TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, no_label, [&] { return launch_pack_nchw(z, zin.p, B, c.latent_channels, L * L, bke(dt), z_scale, 0.f, dt, s); }));
-  Act h;
-  TRY(ex.conv(v->dec_in, zin, &h));
-  Act hin[4], pre[4];
-  for (int i = 0; i < U; ++i) {
-    const ConvW& t = v->convt[i];
-    hin[i] = h;
-    pre[i] = ex.new_act(t.cout, 2 * h.H, 2 * h.W, true);
-    IgemmParams p;
-    p.src0 = h.p; p.C0 = h.C; p.B = B; p.Hi = p.Ho = h.H; p.Wi = p.Wo = h.W;
-    p.M = B * h.H * h.W; p.N = t.N; p.n_valid = t.N; p.W = t.w; p.bias = t.bias;
-    p.out = pre[i].p; p.ldo = t.cout; p.epi = EPI_CONVT2; p.cout = t.cout;
-    TRY(ex.igemm(p));
-    Act n;
-    TRY(ex.layernorm(v->ln[i], pre[i], 1e-6f, 1, &n, false));   // out of place: the transposed conv's own output is the backward's input
-    h = n;
-  }
-  Act gact;
-  TRY(ex.groupnorm(v->dec_gn, h, nullptr, 1e-5f, 1, &gact));
+  const std::vector<VaeRow>& rows = v->dec.rows;
+  const std::vector<RowW>& w = v->dec.w;
+  const int head = (int)rows.size() - 1, gn = head - 1;      // rows: conv_in, (transposed conv, LayerNorm) per upscaler, GroupNorm, head
+  const int Cu = c.upscale_channels, Co = c.out_channels;
+  Keep keep(rows.size());
+  Act zin, gact;
+  TRY(vae_input(ex, z, c.latent_channels, L, z_scale, 0.f, &zin));
+  TRY(vae_trunk(ex, v->dec, zin, &keep, &gact));
   // ---- backward
   Workspace* ws = ex.ws;
+  const Act& h = keep.in[gn];
   const int H4 = h.H, W4 = h.W, P4 = B * H4 * W4;
   const int Cop = (int)rup(Co, bke(dt));
-  const size_t last = (size_t)2 + 4 * U;          // slot of the GroupNorm weight
   float* dyp = (float*)ws->scratch((size_t)P4 * Cop * sizeof(float));
   TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, [] { return std::string("pack grad_logits"); }, [&] { return launch_pack_nchw(grad_logits, dyp, B, Co, H4 * W4, Cop, 1.f, 0.f, dt, s); }));
-  TRY(run_wgrad(ex, {dyp, Cop, Cop, (const float*)gact.p, Cu, H4, W4, 9, 0, Co, Cu, 0}, g[last + 2]));
-  TRY(run_colsum(ex, dyp, Cop, P4, 1, 0, Co, g[last + 3]));
+  TRY(run_wgrad(ex, {dyp, Cop, Cop, (const float*)gact.p, Cu, H4, W4, 9, 0, Co, Cu, 0}, g[2 * head]));
+  TRY(run_colsum(ex, dyp, Cop, P4, 1, 0, Co, g[2 * head + 1]));
   Act dg = ex.new_act(Cu, H4, W4, false);
-  {
-    IgemmParams p;
-    p.src0 = dyp; p.C0 = Cop; p.B = B; p.Hi = p.Ho = H4; p.Wi = p.Wo = W4;
-    p.taps = 9; p.M = P4; p.N = v->dec_out_d.N; p.n_valid = Cu; p.W = v->dec_out_d.w;
-    p.out = dg.p; p.ldo = Cu; p.epi = EPI_STORE;
-    TRY(ex.igemm(p));
-  }
+  TRY(ex.gemm(w[head].d, dyp, Cop, H4, W4, dg.p, EPI_STORE));
   Act dh = ex.new_act(Cu, H4, W4, false);
   {
     float* scratch = (float*)ws->scratch(gn_bwd_scratch_bytes(B, Cu));
     TRY(ex.launch("launch_gn_silu_bwd failed", 2, 0, 4.0 * P4 * Cu * 4.0, [&] { return "gn_silu_bwd HW=" + std::to_string(H4 * W4) + " C=" + std::to_string(Cu); }, [&] {
-      return launch_gn_silu_bwd((const float*)h.p, (const float*)dg.p, v->dec_gn.g, v->dec_gn.b, (float*)dh.p, g[last], g[last + 1], B, H4 * W4, Cu,
-                                1e-5f, scratch, s);
+      return launch_gn_silu_bwd((const float*)h.p, (const float*)dg.p, w[gn].n.g, w[gn].n.b, (float*)dh.p, g[2 * gn], g[2 * gn + 1], B, H4 * W4, Cu,
+                                rows[gn].eps, scratch, s);
     }));
   }
-  for (int i = U - 1; i >= 0; --i) {
-    const size_t slot = (size_t)2 + 4 * i;
-    const Act& x = hin[i];                         // the transposed conv's input, on the low-resolution map
+  for (int ln = gn - 1; ln > 0; ln -= 2) {           // the upscalers, last first: rows ln - 1 (transposed conv) and ln (LayerNorm2d + SiLU)
+    const int ct = ln - 1;
+    const Act& x = keep.in[ct];                      // the transposed conv's input, on the low-resolution map
+    const Act& pre = keep.in[ln];                    // ... and its output
     const int Pl = B * x.H * x.W, M = 4 * Pl;
     // LayerNorm2d + SiLU backward; its result is stored phase-major [B, H, W, 2x2, Cu]: both transposed-conv gradients read it as
     // a [Pl][4 Cu] matrix without a repack
-    Act dpre = ex.new_act(Cu, pre[i].H, pre[i].W, false);
+    Act dpre = ex.new_act(Cu, pre.H, pre.W, false);
     {
       float* scratch = (float*)ws->scratch(ln_bwd_scratch_bytes(M, Cu));
       TRY(ex.launch("launch_ln_silu_bwd failed", 3, 0, 3.0 * M * Cu * 4.0, [&] { return "ln_silu_bwd M=" + std::to_string(M) + " C=" + std::to_string(Cu); }, [&] {
-        return launch_ln_silu_bwd((const float*)pre[i].p, (const float*)dh.p, v->ln[i].g, v->ln[i].b, (float*)dpre.p, g[slot + 2], g[slot + 3], M, Cu,
-                                  1e-6f, 1, pre[i].H, pre[i].W, scratch, s);
+        return launch_ln_silu_bwd((const float*)pre.p, (const float*)dh.p, w[ln].n.g, w[ln].n.b, (float*)dpre.p, g[2 * ln], g[2 * ln + 1], M, Cu,
+                                  rows[ln].eps, 1, pre.H, pre.W, scratch, s);
       }));
     }
-    TRY(run_wgrad(ex, {(const float*)dpre.p, 4 * Cu, 4 * Cu, (const float*)x.p, x.C, x.H, x.W, 1, 1, 4 * Cu, x.C, Cu}, g[slot]));
-    TRY(run_colsum(ex, (const float*)dpre.p, 4 * Cu, Pl, 4, Cu, Cu, g[slot + 1]));
+    TRY(run_wgrad(ex, {(const float*)dpre.p, 4 * Cu, 4 * Cu, (const float*)x.p, x.C, x.H, x.W, 1, 1, 4 * Cu, x.C, Cu}, g[2 * ct]));
+    TRY(run_colsum(ex, (const float*)dpre.p, 4 * Cu, Pl, 4, Cu, Cu, g[2 * ct + 1]));
     Act dx = ex.new_act(x.C, x.H, x.W, false);
-    IgemmParams p;
-    p.src0 = dpre.p; p.C0 = 4 * Cu; p.B = B; p.Hi = p.Ho = x.H; p.Wi = p.Wo = x.W;
-    p.taps = 1; p.M = Pl; p.N = v->convt_d[i].N; p.n_valid = x.C; p.W = v->convt_d[i].w;
-    p.out = dx.p; p.ldo = x.C; p.epi = EPI_STORE;
-    TRY(ex.igemm(p));
+    TRY(ex.gemm(w[ct].d, dpre.p, 4 * Cu, x.H, x.W, dx.p, EPI_STORE));
     dh = dx;
   }
   const int P0 = B * L * L, Ci = c.int_channels;
   TRY(run_wgrad(ex, {(const float*)dh.p, Ci, Ci, (const float*)zin.p, zin.C, L, L, 9, 0, Ci, c.latent_channels, 0}, g[0]));
   TRY(run_colsum(ex, (const float*)dh.p, Ci, P0, 1, 0, Ci, g[1]));
   if (grad_z) {
-    IgemmParams p;
-    p.src0 = dh.p; p.C0 = Ci; p.B = B; p.Hi = p.Ho = L; p.Wi = p.Wo = L;
-    p.taps = 9; p.M = P0; p.N = v->dec_in_d.N; p.n_valid = c.latent_channels; p.W = v->dec_in_d.w;
-    p.out = grad_z; p.epi = EPI_NCHW_F32;
-    TRY(ex.igemm(p));
+    TRY(ex.gemm(w[0].d, dh.p, Ci, L, L, grad_z, rows[0].dgrad_epi));
     if (z_scale != 1.0f)     // decode(z, z_scale) feeds z * z_scale
       TRY(ex.launch("launch_axpby failed", 4, 0, 0, no_label, [&] { return launch_axpby(grad_z, z_scale, 0.f, grad_z, (size_t)P0 * c.latent_channels, s); }));
   }
   return 0;
 }
 
-// ---- the encoder's backward.  One planned pass: the encoder forward again up to the GroupNorm output (the moments
-// themselves are not needed), the four conv + SiLU layers as a SiLU-less conv that keeps the pre-activation u plus one silu_fwd
-// launch, then the chain from d loss / d moments down to every parameter gradient asked for (g[slot], slots as encoder_keys; null =
-// skipped).  The chain stops below the lowest layer a gradient is asked of; the input is data.
+// ---- the encoder's backward.  One planned pass: the encoder's trunk again, keeping every row's input and the
+// pre-activation u of the four conv + SiLU rows (the moments themselves are not needed), then the chain from d loss / d moments down
+// to every parameter gradient asked for (g[2 i], g[2 i + 1]: weight and bias of row i; null = skipped).  The chain stops below the
+// lowest row a gradient is asked of; the input is data.
 int vae_encode_backward_body(Exec& ex, ldmseg_vae* v, const float* x, float mul, float add, int H, const float* grad_moments, float* const* g) {
   const int B = ex.B;
   hipStream_t s = ex.s;
   const int dt = v->dt;
   const ldmseg_vae_cfg& c = v->cfg;
-  const std::vector<EncLayer> l = encoder_layers(c);
-  const int last = kEncLayers - 1;
-  // the lowest layer whose parameters are asked for (the GroupNorm sits between layers 7 and 8)
-  int lowest = kEncLayers;
-  for (int k = last; k >= 0; --k)
-    if (g[enc_slot(k)] || g[enc_slot(k) + 1]) lowest = k;
-  if ((g[kEncNormSlot] || g[kEncNormSlot + 1]) && lowest > last) lowest = last;
-  if (lowest == kEncLayers) return 0;
-  // ---- forward again, everything the backward reads is kept: in[k] = the input of layer k, u[k] = the pre-activation of a SiLU layer
-  Act in[kEncLayers], u[kEncLayers];
-  in[0] = ex.new_act(bke(dt), H, H, true);
-  TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, no_label, [&] { return launch_pack_nchw(x, in[0].p, B, c.in_channels, H * H, bke(dt), mul, add, dt, s); }));
-  Act h7;
-  for (int k = 0; k < last; ++k) {
-    Act o;
-    TRY(ex.conv(v->enc[k], in[k], &o, {.stride = l[k].stride}));
-    if (l[k].silu) {
-      u[k] = o;
-      Act a = ex.new_act(o.C, o.H, o.W, true);
-      const size_t n = (size_t)B * o.H * o.W * o.C;
-      TRY(ex.launch("launch_silu_fwd failed", 4, 0, 8.0 * n, no_label, [&] { return launch_silu_fwd((const float*)o.p, (float*)a.p, n, s); }));
-      o = a;
-    }
-    if (k + 1 < last) in[k + 1] = o; else h7 = o;
-  }
-  TRY(ex.groupnorm(v->enc_gn, h7, nullptr, 1e-6f, 1, &in[last]));
+  const std::vector<VaeRow>& rows = v->enc.rows;
+  const std::vector<RowW>& w = v->enc.w;
+  const int R = (int)rows.size(), head = R - 1, gn = R - 2;      // rows: the convs 0 .. gn - 1, GroupNorm, head
+  int lowest = R;                                  // the lowest row whose parameters are asked for
+  for (int i = head; i >= 0; --i)
+    if (g[2 * i] || g[2 * i + 1]) lowest = i;
+  if (lowest == R) return 0;
+  Keep keep(rows.size());
+  Act xin, hin;
+  TRY(vae_input(ex, x, c.in_channels, H, mul, add, &xin));
+  TRY(vae_trunk(ex, v->enc, xin, &keep, &hin));
   // ---- backward: the running gradient alternates between two buffers of the largest activation's size
   Workspace* ws = ex.ws;
-  const int l8 = h7.H, P8 = B * l8 * l8, Cm = (int)rup(l[last].Co, bke(dt)), Ci8 = c.int_channels;
+  const Act& h7 = keep.in[gn];
+  const int l8 = h7.H, P8 = B * l8 * l8, Cm = (int)rup(rows[head].Co, bke(dt)), Ci8 = c.int_channels;
   size_t gmax = (size_t)P8 * Ci8;
-  for (int k = 1; k < last; ++k) gmax = std::max(gmax, (size_t)B * in[k].H * in[k].W * in[k].C);
+  for (int k = 1; k < gn; ++k) gmax = std::max(gmax, (size_t)B * keep.in[k].H * keep.in[k].W * keep.in[k].C);
   float* gb[2] = {(float*)ws->scratch(gmax * sizeof(float)), (float*)ws->scratch(gmax * sizeof(float))};
   float* dm = (float*)ws->scratch((size_t)P8 * Cm * sizeof(float));
-  TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, [] { return std::string("pack grad_moments"); }, [&] { return launch_pack_nchw(grad_moments, dm, B, l[last].Co, l8 * l8, Cm, 1.f, 0.f, dt, s); }));
-  TRY(run_wgrad(ex, {dm, Cm, Cm, (const float*)in[last].p, Ci8, l8, l8, 9, 0, l[last].Co, Ci8, 0, 1, kWgradByWidth}, g[kEncHeadSlot]));
-  TRY(run_colsum(ex, dm, Cm, P8, 1, 0, l[last].Co, g[kEncHeadSlot + 1]));
-  if (lowest == last && !g[kEncNormSlot] && !g[kEncNormSlot + 1]) return 0;
-  {
-    IgemmParams p;
-    p.src0 = dm; p.C0 = Cm; p.B = B; p.Hi = p.Ho = l8; p.Wi = p.Wo = l8;
-    p.taps = 9; p.M = P8; p.N = v->enc_d[last].N; p.n_valid = Ci8; p.W = v->enc_d[last].w;
-    p.out = gb[0]; p.ldo = Ci8; p.epi = EPI_STORE;
-    TRY(ex.igemm(p));
-  }
+  TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, [] { return std::string("pack grad_moments"); }, [&] { return launch_pack_nchw(grad_moments, dm, B, rows[head].Co, l8 * l8, Cm, 1.f, 0.f, dt, s); }));
+  TRY(run_wgrad(ex, {dm, Cm, Cm, (const float*)hin.p, Ci8, l8, l8, 9, 0, rows[head].Co, Ci8, 0, 1, kWgradByWidth}, g[2 * head]));
+  TRY(run_colsum(ex, dm, Cm, P8, 1, 0, rows[head].Co, g[2 * head + 1]));
+  if (lowest == head) return 0;
+  TRY(ex.gemm(w[head].d, dm, Cm, l8, l8, gb[0], rows[head].dgrad_epi));
   {
     const size_t m = ws->mark();
     float* scratch = (float*)ws->scratch(gn_bwd_scratch_bytes(B, Ci8));
     TRY(ex.launch("launch_gn_silu_bwd failed", 2, 0, 4.0 * P8 * Ci8 * 4.0, [&] { return "gn_silu_bwd HW=" + std::to_string(l8 * l8) + " C=" + std::to_string(Ci8); }, [&] {
-      return launch_gn_silu_bwd((const float*)h7.p, gb[0], v->enc_gn.g, v->enc_gn.b, gb[1], g[kEncNormSlot], g[kEncNormSlot + 1], B, l8 * l8, Ci8, 1e-6f,
+      return launch_gn_silu_bwd((const float*)h7.p, gb[0], w[gn].n.g, w[gn].n.b, gb[1], g[2 * gn], g[2 * gn + 1], B, l8 * l8, Ci8, rows[gn].eps,
                                 scratch, s);
     }));
     ws->reset(m);
   }
-  int cur = 1;                                   // gb[cur] = d loss / d (output of layer k before its SiLU)
-  for (int k = last - 1; k >= lowest; --k) {
-    const Act& xi = in[k];                       // the layer's input, on the map H x W of X
-    const int Co = l[k].Co, st = l[k].stride;
+  int cur = 1;                                   // gb[cur] = d loss / d (output of row k before its SiLU)
+  for (int k = gn - 1; k >= lowest; --k) {
+    const Act& xi = keep.in[k];                  // the row's input, on the map H x W of X
+    const int Co = rows[k].Co, st = rows[k].stride;
     const int Ho = conv_out_dim(xi.H, st), Wo = conv_out_dim(xi.W, st), Po = B * Ho * Wo;
-    TRY(run_wgrad(ex, {gb[cur], Co, Co, (const float*)xi.p, xi.C, xi.H, xi.W, 9, 0, Co, l[k].Ci, 0, st, kWgradByWidth}, g[enc_slot(k)]));
-    TRY(run_colsum(ex, gb[cur], Co, Po, 1, 0, Co, g[enc_slot(k) + 1]));
+    TRY(run_wgrad(ex, {gb[cur], Co, Co, (const float*)xi.p, xi.C, xi.H, xi.W, 9, 0, Co, rows[k].Ci, 0, st, kWgradByWidth}, g[2 * k]));
+    TRY(run_colsum(ex, gb[cur], Co, Po, 1, 0, Co, g[2 * k + 1]));
     if (k == lowest) break;
-    const ConvW& d = v->enc_d[k];
-    IgemmParams p;
-    p.src0 = gb[cur]; p.C0 = Co; p.B = B; p.Hi = p.Ho = Ho; p.Wi = p.Wo = Wo;
-    p.taps = 9; p.M = Po; p.N = d.N; p.W = d.w; p.out = gb[1 - cur]; p.ldo = xi.C;
-    if (st == 2) { p.n_valid = 4 * xi.C; p.epi = EPI_CONVT2; p.cout = xi.C; }
-    else { p.n_valid = xi.C; p.epi = EPI_STORE; }
-    TRY(ex.igemm(p));
+    TRY(ex.gemm(w[k].d, gb[cur], Co, Ho, Wo, gb[1 - cur], rows[k].dgrad_epi));      // (stride 2: the four phases, scattered)
     cur = 1 - cur;
-    if (l[k - 1].silu) {                         // the input was SiLU(u[k - 1]): in place
+    if (rows[k - 1].silu) {                      // the input was SiLU(u[k - 1]): in place
       const size_t n = (size_t)B * xi.H * xi.W * xi.C;
-      TRY(ex.launch("launch_silu_bwd failed", 4, 0, 12.0 * n, no_label, [&] { return launch_silu_bwd((const float*)u[k - 1].p, gb[cur], gb[cur], n, s); }));
+      TRY(ex.launch("launch_silu_bwd failed", 4, 0, 12.0 * n, no_label, [&] { return launch_silu_bwd((const float*)keep.pre[k - 1].p, gb[cur], gb[cur], n, s); }));
     }
   }
   return 0;
 }
 
+// the encoder on an executor that is already set up: trunk, then the head straight into the caller's moments
 int vae_encode_body(Exec& ex, ldmseg_vae* v, const float* x, float mul, float add, int H, float* moments) {
-  const int B = ex.B;
-  hipStream_t s = ex.s;
-  const int dt = v->dt;
-  const ldmseg_vae_cfg& c = v->cfg;
-  Act xin = ex.new_act(bke(dt), H, H, true);
-  TRY(ex.launch("launch_pack_nchw failed", 4, 0, 0, no_label, [&] { return launch_pack_nchw(x, xin.p, B, c.in_channels, H * H, bke(dt), mul, add, dt, s); }));
-  Act h, o;
-  int k = 0;
-  TRY(ex.conv(v->enc[k++], xin, &h, {.silu = 1}));  // conv + SiLU
-  for (int i = 0; i < 3; ++i) {
-    TRY(ex.conv(v->enc[k++], h, &o)); h = o;
-    TRY(ex.conv(v->enc[k++], h, &o, {.stride = 2, .silu = 1})); h = o;
-  }
-  TRY(ex.conv(v->enc[k++], h, &o)); h = o;
-  Act g;
-  TRY(ex.groupnorm(v->enc_gn, h, nullptr, 1e-6f, 1, &g));
-  const ConvW& last = v->enc[k];
-  IgemmParams p;
-  p.src0 = g.p; p.C0 = g.C; p.B = B; p.Hi = p.Ho = h.H; p.Wi = p.Wo = h.W;
-  p.taps = 9; p.M = B * h.H * h.W; p.N = last.N; p.n_valid = c.latent_channels * c.num_latents;
-  p.W = last.w; p.bias = last.bias; p.out = moments; p.epi = EPI_NCHW_F32;
-  TRY(ex.igemm(p));
-  return 0;
+  Act xin, g;
+  TRY(vae_input(ex, x, v->cfg.in_channels, H, mul, add, &xin));
+  TRY(vae_trunk(ex, v->enc, xin, nullptr, &g));
+  return ex.gemm(v->enc.w.back().w, g.p, g.C, g.H, g.W, moments, EPI_NCHW_F32);
 }
 
 // vae_model(images, sample_posterior=False).sample (vae.py:273-307) behind one workspace plan: encode -> posterior mode -> decode
@@ -814,11 +684,39 @@ int klenc_encode_impl(ldmseg_vae_image* v, const float* x, float mul, float add,
   Act g, c8;
   TRY(ex.groupnorm(v->norm_out, h, nullptr, 1e-6f, 1, &g));
   TRY(ex.conv(v->conv_out, g, &c8));
-  IgemmParams p;
-  p.src0 = c8.p; p.C0 = c8.C; p.B = B; p.Hi = p.Ho = h.H; p.Wi = p.Wo = h.W;
-  p.taps = 1; p.M = B * h.H * h.W; p.N = v->quant.N; p.n_valid = 8;
-  p.W = v->quant.w; p.bias = v->quant.bias; p.out = moments; p.epi = EPI_NCHW_F32;
-  TRY(ex.igemm(p));
+  return ex.gemm(v->quant, c8.p, c8.C, h.H, h.W, moments, EPI_NCHW_F32);
+}
+
+// ---- what the ABI's pairs share.  ldmseg_vae_{decode,encode}_backward: the argument checks, the gradients by slot, one planned pass
+// around `chain` (the half's backward body on an executor).  tensors_ok: the entry's input and output-gradient pointers are there.
+template <typename Chain>
+int vae_backward(ldmseg_vae* h, bool decoder, bool tensors_ok, bool shape_ok, const char* shape_msg, int B, int n, const char* const* names,
+                 float* const* grad_ptrs, const int64_t* numels, void* stream, Chain&& chain) {
+  g_err.clear();
+  if (!h || !tensors_ok) return fail(LDMSEG_E_ARG, "null argument");
+  if (n < 0 || (n > 0 && (!names || !grad_ptrs || !numels))) return fail(LDMSEG_E_ARG, "null argument");
+  if (h->dt != DT_F32)
+    return fail(LDMSEG_E_ARG, std::string("the ") + (decoder ? "decoder" : "encoder") + " backward needs an fp32-storage handle (compute_dtype fp32 or bf16x3), not bf16");
+  if (!decoder && !encoder_backward_ok(h->cfg)) return fail(LDMSEG_E_ARG, "the encoder backward needs block_out_channels and int_channels that are multiples of 32");
+  if (!shape_ok) return fail(LDMSEG_E_SHAPE, shape_msg);
+  std::vector<void*> g;
+  TRY(by_slot(decoder ? h->dec.rows : h->enc.rows, decoder, n, names, (void* const*)grad_ptrs, numels, true, &g));
+  DeviceGuard dg(h->cfg.device);
+  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
+    Exec ex = make_exec(*h, B, (hipStream_t)stream, dry, scratch_base);
+    return chain(ex, (float* const*)g.data());
+  });
+}
+// ldmseg_vae_load_{decoder,encoder}: the given tensors of that half through the build's pack path; absent keys are left alone
+int vae_load(ldmseg_vae* h, bool decoder, int n, const char* const* names, const void* const* dev_ptrs, const int64_t* numels, void* stream) {
+  g_err.clear();
+  if (!h || n < 0 || (n > 0 && (!names || !dev_ptrs || !numels))) return fail(LDMSEG_E_ARG, "null argument");
+  const VaeHalf& half = decoder ? h->dec : h->enc;
+  std::vector<void*> t;
+  TRY(by_slot(half.rows, decoder, n, names, (void* const*)dev_ptrs, numels, false, &t));
+  DeviceGuard dg(h->cfg.device);
+  for (size_t i = 0; i < half.rows.size(); ++i)
+    TRY(pack_row(h, half.rows[i], half.w[i], (const float*)t[2 * i], (const float*)t[2 * i + 1], (hipStream_t)stream));
   return 0;
 }
 
@@ -849,38 +747,12 @@ int ldmseg_vae_decode(ldmseg_vae* h, const float* z, float z_scale, int B, int L
 
 int ldmseg_vae_decode_backward(ldmseg_vae* h, const float* z, float z_scale, int B, int L, const float* grad_logits, float* grad_z, int n,
                                const char* const* names, float* const* grad_ptrs, const int64_t* numels, void* stream) {
-  g_err.clear();
-  if (!h || !z || !grad_logits) return fail(LDMSEG_E_ARG, "null argument");
-  if (n < 0 || (n > 0 && (!names || !grad_ptrs || !numels))) return fail(LDMSEG_E_ARG, "null argument");
-  if (h->dt != DT_F32) return fail(LDMSEG_E_ARG, "the decoder backward needs an fp32-storage handle (compute_dtype fp32 or bf16x3), not bf16");
-  if (B < 1 || L < 1) return fail(LDMSEG_E_SHAPE, "bad B/L");
-  const std::vector<DecKey> keys = decoder_keys(h->cfg);
-  std::vector<float*> g(keys.size(), nullptr);
-  for (int i = 0; i < n; ++i) {
-    const int k = key_slot(keys, names[i], numels[i], "a decoder");
-    if (k < 0) return LDMSEG_E_ARG;
-    g[k] = grad_ptrs[i];
-  }
-  DeviceGuard dg(h->cfg.device);
-  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
-    Exec ex = make_exec(*h, B, (hipStream_t)stream, dry, scratch_base);
-    return vae_decode_backward_body(ex, h, z, z_scale, L, grad_logits, grad_z, g.data());
-  });
+  return vae_backward(h, true, z && grad_logits, B >= 1 && L >= 1, "bad B/L", B, n, names, grad_ptrs, numels, stream,
+                      [&](Exec& ex, float* const* g) { return vae_decode_backward_body(ex, h, z, z_scale, L, grad_logits, grad_z, g); });
 }
 
 int ldmseg_vae_load_decoder(ldmseg_vae* h, int n, const char* const* names, const void* const* dev_ptrs, const int64_t* numels, void* stream) {
-  g_err.clear();
-  if (!h || n < 0 || (n > 0 && (!names || !dev_ptrs || !numels))) return fail(LDMSEG_E_ARG, "null argument");
-  const std::vector<DecKey> keys = decoder_keys(h->cfg);
-  WeightMap wm;
-  for (int i = 0; i < n; ++i) {
-    if (!dev_ptrs[i]) return fail(LDMSEG_E_ARG, "null decoder tensor");
-    const int k = key_slot(keys, names[i], numels[i], "a decoder");
-    if (k < 0) return LDMSEG_E_ARG;
-    wm.m[keys[k].name] = {(const float*)dev_ptrs[i], numels[i]};
-  }
-  DeviceGuard dg(h->cfg.device);
-  return vae_pack_decoder(h, wm, (hipStream_t)stream, true);
+  return vae_load(h, true, n, names, dev_ptrs, numels, stream);
 }
 
 int ldmseg_vae_decode_argmax(ldmseg_vae* h, const float* z, float z_scale, int B, int L, float mask_th, int64_t ignore_label,
@@ -928,39 +800,12 @@ int ldmseg_vae_encode(ldmseg_vae* h, const float* x, float in_mul, float in_add,
 
 int ldmseg_vae_encode_backward(ldmseg_vae* h, const float* x, float in_mul, float in_add, int B, int H, const float* grad_moments, int n,
                                const char* const* names, float* const* grad_ptrs, const int64_t* numels, void* stream) {
-  g_err.clear();
-  if (!h || !x || !grad_moments) return fail(LDMSEG_E_ARG, "null argument");
-  if (n < 0 || (n > 0 && (!names || !grad_ptrs || !numels))) return fail(LDMSEG_E_ARG, "null argument");
-  if (h->dt != DT_F32) return fail(LDMSEG_E_ARG, "the encoder backward needs an fp32-storage handle (compute_dtype fp32 or bf16x3), not bf16");
-  if (!encoder_backward_ok(h->cfg)) return fail(LDMSEG_E_ARG, "the encoder backward needs block_out_channels and int_channels that are multiples of 32");
-  if (B < 1 || H < 8 || H % 8) return fail(LDMSEG_E_SHAPE, "H must be a multiple of 8");
-  const std::vector<DecKey> keys = encoder_keys(h->cfg);
-  std::vector<float*> g(keys.size(), nullptr);
-  for (int i = 0; i < n; ++i) {
-    const int k = key_slot(keys, names[i], numels[i], "an encoder");
-    if (k < 0) return LDMSEG_E_ARG;
-    g[k] = grad_ptrs[i];
-  }
-  DeviceGuard dg(h->cfg.device);
-  return plan_and_run(*h, nullptr, [&](bool dry, size_t scratch_base) {
-    Exec ex = make_exec(*h, B, (hipStream_t)stream, dry, scratch_base);
-    return vae_encode_backward_body(ex, h, x, in_mul, in_add, H, grad_moments, g.data());
-  });
+  return vae_backward(h, false, x && grad_moments, B >= 1 && H >= 8 && H % 8 == 0, "H must be a multiple of 8", B, n, names, grad_ptrs, numels, stream,
+                      [&](Exec& ex, float* const* g) { return vae_encode_backward_body(ex, h, x, in_mul, in_add, H, grad_moments, g); });
 }
 
 int ldmseg_vae_load_encoder(ldmseg_vae* h, int n, const char* const* names, const void* const* dev_ptrs, const int64_t* numels, void* stream) {
-  g_err.clear();
-  if (!h || n < 0 || (n > 0 && (!names || !dev_ptrs || !numels))) return fail(LDMSEG_E_ARG, "null argument");
-  const std::vector<DecKey> keys = encoder_keys(h->cfg);
-  WeightMap wm;
-  for (int i = 0; i < n; ++i) {
-    if (!dev_ptrs[i]) return fail(LDMSEG_E_ARG, "null encoder tensor");
-    const int k = key_slot(keys, names[i], numels[i], "an encoder");
-    if (k < 0) return LDMSEG_E_ARG;
-    wm.m[keys[k].name] = {(const float*)dev_ptrs[i], numels[i]};
-  }
-  DeviceGuard dg(h->cfg.device);
-  return vae_pack_encoder(h, wm, (hipStream_t)stream, true);
+  return vae_load(h, false, n, names, dev_ptrs, numels, stream);
 }
 
 int ldmseg_vae_posterior_backward(const float* moments, const float* noise, float scale, int B, int l, const float* grad_z, float* grad_moments,

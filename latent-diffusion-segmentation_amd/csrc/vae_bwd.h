@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernels.h"
 #include "wgrad_plan.h"
 
 namespace ldmseg {
@@ -87,5 +88,19 @@ int launch_pack_dgrad_conv(const float* w, float* out, int Co, int Ci, int Npad,
 int launch_pack_dgrad_conv_s2(const float* w, float* out, int Co, int Ci, int Npad, int Cop, hipStream_t s);
 // ConvTranspose2d [Ci][Co][2][2] -> [Npad][4 Co], row ci, column q * Co + co = w[ci][co][q]
 int launch_pack_dgrad_convt(const float* w, float* out, int Ci, int Co, int Npad, hipStream_t s);
+
+// The shapes of those three packings as igemm takes them (the fields of the runtime's ConvW): N rows padded to the launch's N tile,
+// n_valid real ones, K = taps * cin_pad.  The handles' packings and the ldmseg_op_*_dgrad operators are sized by them.
+struct DgradShape { int N, n_valid, cin_pad, taps, cout; };
+constexpr int kDgradKTile = 32;      // fp32 channels per 128-B K tile
+inline int dgrad_pad(int n, int to) { return (n + to - 1) / to * to; }
+// dX = conv3x3(dY, W transposed and rotated by 180 degrees): N = Ci, K = 9 * Co (Co padded to a K tile); epi: the launch's epilogue
+inline DgradShape dgrad_conv_shape(int Co, int Ci, int epi) { return {dgrad_pad(Ci, igemm_pick_bn(Ci, epi)), Ci, dgrad_pad(Co, kDgradKTile), 9, Ci}; }
+// dX of a STRIDE-2 conv3x3 = the four output phases as 4 Ci columns of one 3x3 GEMM over dY, scattered by EPI_CONVT2
+inline DgradShape dgrad_conv_s2_shape(int Co, int Ci) {
+  return {dgrad_pad(4 * Ci, igemm_pick_bn(4 * Ci, EPI_CONVT2)), 4 * Ci, dgrad_pad(Co, kDgradKTile), 9, Ci};
+}
+// dX[p] = dY[p, 2x2, :] W[ci][co][q]: N = Ci, K = 4 * Co on the phase-major dY
+inline DgradShape dgrad_convt_shape(int Ci, int Co) { return {dgrad_pad(Ci, igemm_pick_bn(Ci, EPI_STORE)), Ci, 4 * Co, 1, Ci}; }
 
 }  // namespace ldmseg

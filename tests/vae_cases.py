@@ -4,7 +4,7 @@ layer walk of oracle/vae.py and oracle/vae_image.py, tests/test_vae_shapes_gpu.p
 csrc/ops_api.hip and compares it with the torch-CPU op.
 
 An entry is a namedtuple; maps are (H, W) of the launch's INPUT.  `tile` on a conv: the layer stores its output channels rounded up
-to the K tile of the compute dtype (64 bf16 / 32 fp32) as explicit zeros (Builder::conv n_store) - the seg-VAE encoder's 32-channel
+to the K tile of the compute dtype (64 bf16 / 32 fp32) as explicit zeros (conv_shape n_store) - the seg-VAE encoder's 32-channel
 level and the image VAE's conv_out; the operator dtype decides the number, so the list only carries the flag."""
 from collections import namedtuple
 
@@ -45,7 +45,7 @@ def conv_out_hw(c):
 
 
 def seg_encode(B, H, W=None):
-    """ldmseg_vae_encode (vae_encode_body): square maps only (W is accepted for symmetry and must equal H)"""
+    """ldmseg_vae_encode (vae_encode_body: vae_trunk over encoder_rows, then the head conv): square maps only (W is accepted for symmetry and must equal H)"""
     assert W in (None, H) and H % 8 == 0
     c = SEG
     boc = c["block_out_channels"]
@@ -62,7 +62,7 @@ def seg_encode(B, H, W=None):
 
 
 def seg_decode(B, L, tail):
-    """ldmseg_vae_decode* (vae_decode_body) on [B, 4, L, L] latents"""
+    """ldmseg_vae_decode* (vae_decode_body: vae_trunk over decoder_rows, the head conv, the tail) on [B, 4, L, L] latents"""
     assert tail in DECODE_TAILS
     c = SEG
     out = [Pack(B, c["latent_channels"], L * L), conv(B, c["latent_channels"], c["int_channels"], L, L)]

@@ -4,7 +4,7 @@ profiler on, on inputs and weights drawn from fixed seeds.  A child records, per
 (family, label) sequence of ldmseg_profile_dump and the workspace bytes the library reports; this process compares the two
 records and prints one table row per scenario.  Equal means equal: there is no tolerance.
 
-    python tools/runtime_ab.py [--groups unet,cross,...] [--table profiles/runtime_split_ab.txt]
+    python tools/runtime_ab.py [--groups unet,cross,...] [--table profiles/runtime_split_ab.txt] [--host-times]
 
 Each child runs under its own time limit and the run stops at the first child that fails, faults or is killed."""
 import argparse
@@ -17,7 +17,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARENT_LIB = os.path.join(ROOT, "tools", "ab", "lib_parent.so")
-GROUPS = ["unet", "cross", "sepenc", "loops", "guided", "fallbacks", "vae", "clip", "knobs"]
+GROUPS = ["unet", "cross", "sepenc", "loops", "guided", "fallbacks", "vae", "vae_train", "clip", "knobs"]
 CHILD_SECONDS = 400
 KW = dict(prediction_type="epsilon", beta_schedule="scaled_linear", num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012,
           clip_sample=False, set_alpha_to_one=False)
@@ -240,7 +240,7 @@ def g_vae(rec):
     from ldmseg_amd.models import GeneralVAESeg
     from ldmseg_amd.models.vae import GeneralVAEImage
     B, L, H = 2, 8, 64
-    for mode in MODES2:
+    for mode in MODES3:
         v = GeneralVAESeg(state_dict("vae"), scaling_factor=0.2, device="cuda:0", compute_dtype=mode)
         z = randn((B, 4, L, L), 61)
         x = (torch.rand((B, 7, H, H), generator=torch.Generator().manual_seed(62)) > 0.5).float().to("cuda:0")
@@ -280,6 +280,81 @@ def g_vae(rec):
         del k
 
 
+def g_vae_train(rec):
+    """The seg-VAE's training entries on fp32-storage handles (fp32 and bf16x3, whose hi | lo planes the build and the load entries
+    split), at a power-of-two shape and at H = 40 (maps 40 / 20 / 10 / 5): both backwards with every gradient and with the single
+    gradients at which the encoder's chain ends early, the load entries followed by a forward (those also in bf16) and by both
+    backwards on the reloaded handle, and one TrainerAE.training_step with the library's optimiser."""
+    import torch
+    from collections import OrderedDict
+    from ldmseg_amd import _lib
+    from ldmseg_amd.models import GeneralVAESeg
+    from ldmseg_amd.models.vae import _name_arrays
+    from ldmseg_amd.optim import AdamW
+    from ldmseg_amd.trainers import TrainerAE
+    lib, sd = _lib.lib(), state_dict("vae")
+    enc, dec = [k for k in sd if k.startswith("encoder.")], [k for k in sd if k.startswith("decoder.")]
+    assert len(enc) == 20 and len(dec) == 14
+    stream = lambda: _lib.stream_ptr(torch.device("cuda:0"))
+
+    def make(mode):
+        return GeneralVAESeg(sd, scaling_factor=0.2, device="cuda:0", compute_dtype=mode)
+
+    def backward(v, first, grad, names, grad_z=None):
+        """one ldmseg_vae_{decode,encode}_backward call (decode: `first` has the 4 latent channels) for the gradients of `names`"""
+        grads = OrderedDict((k, torch.full(tuple(sd[k].shape), float("nan"), device="cuda:0")) for k in names)
+        n, c_names, c_ptrs, c_numels = _name_arrays(grads)
+        B, C, S, _ = first.shape
+        if C == 4:
+            code = lib.ldmseg_vae_decode_backward(v._h, _lib.ptr(first), 5.0, B, S, _lib.ptr(grad), _lib.ptr(grad_z), n, c_names, c_ptrs, c_numels, stream())
+        else:
+            code = lib.ldmseg_vae_encode_backward(v._h, _lib.ptr(first), 2.0, -1.0, B, S, _lib.ptr(grad), n, c_names, c_ptrs, c_numels, stream())
+        _lib.check(code, "backward")
+        return list(grads.values()) + [grad_z], None
+
+    def load(v, half, names, seed):
+        ts = OrderedDict((k, randn(tuple(sd[k].shape), seed + i, 0.05)) for i, k in enumerate(names))
+        n, c_names, c_ptrs, c_numels = _name_arrays(ts)
+        _lib.check(getattr(lib, "ldmseg_vae_load_" + half)(v._h, n, c_names, c_ptrs, c_numels, stream()), "load_" + half)
+        torch.cuda.synchronize()          # (the sources live until the packs have read them)
+
+    for B, H in ((2, 64), (1, 40)):
+        L = H // 8
+        x = (torch.rand((B, 7, H, H), generator=torch.Generator().manual_seed(81)) > 0.5).float().to("cuda:0")
+        z, gl, gm = randn((B, 4, L, L), 82), randn((B, 128, 4 * L, 4 * L), 83), randn((B, 8, L, L), 84)
+        for mode in MODES3:
+            tag = f"{mode} B{B} H{H}"
+            v = make(mode)
+            if mode != "bf16":
+                rec.record(f"decode_backward every gradient, grad_z, z_scale=5 {tag}", lambda: backward(v, z, gl, dec, torch.empty_like(z)))
+                rec.record(f"decode_backward decoder.6.bias only, grad_z null {tag}", lambda: backward(v, z, gl, ["decoder.6.bias"]))
+                rec.record(f"encode_backward every gradient {tag}", lambda: backward(v, x, gm, enc))
+                for k in ("encoder.15.weight", "encoder.13.weight", "encoder.8.weight", "encoder.0.bias"):      # head, GroupNorm, layer 5, layer 0
+                    rec.record(f"encode_backward {k} only {tag}", lambda: backward(v, x, gm, [k]))
+            load(v, "decoder", ["decoder.2.weight", "decoder.10.bias"], 90)
+            rec.record(f"load_decoder decoder.2.weight + decoder.10.bias, decode {tag}", lambda: (v.decode(z, interpolate=False, z_scale=5.0), None))
+            load(v, "encoder", ["encoder.3.weight"], 95)
+            rec.record(f"load_encoder encoder.3.weight, encode {tag}", lambda: (v.encode_moments(x, 2.0, -1.0), None))
+            if mode == "bf16":
+                continue
+            rec.record(f"encode_backward every gradient, reloaded handle {tag}", lambda: backward(v, x, gm, enc))
+            rec.record(f"decode_backward every gradient, reloaded handle {tag}", lambda: backward(v, z, gl, dec, torch.empty_like(z)))
+            del v
+            t = make(mode)
+            tr = TrainerAE(t, loss_weights={"ce": 1.0, "mask": 1.0, "kl": 1e-4},
+                           loss_kwargs=dict(num_points=64, oversample_ratio=3, importance_sample_ratio=0.75, temperature=1.0))
+            opt = AdamW(t.parameters(), lr=1e-3)
+            ids = torch.randint(0, 12, (B, L, L), generator=torch.Generator().manual_seed(85)).repeat_interleave(8, 1).repeat_interleave(8, 2)
+            bits = (2.0 * torch.stack([(ids >> i) % 2 for i in range(7)], dim=1).float() - 1.0).to("cuda:0")
+
+            def step():
+                losses = tr.training_step(bits, ids.to("cuda:0"), opt, clip_grad=1.0, generator=torch.Generator(device="cuda:0").manual_seed(20),
+                                          point_generator=torch.Generator().manual_seed(0))
+                return list(losses) + [tr.last_grad_norm] + list(t.parameters()), None
+            rec.record(f"training_step library AdamW, clip 1.0 {tag}", step)
+            del t, tr, opt
+
+
 def g_clip(rec):
     import torch
     from ldmseg_amd import weights as W
@@ -316,8 +391,48 @@ def g_knobs(rec):
     rec.out["debug_get of keys -1..26"] = {"hashes": [], "launches": [], "bytes": [shipped, codes, unknown, msg, after]}
 
 
+def host_times(out_path, calls=200, repeats=5):
+    """Host cost of the seg-VAE entries (the launch sequences being equal, the GPU time is): wall-clock milliseconds of `calls`
+    back-to-back calls with one final synchronize, `repeats` times per entry, at B = 2, H = 64 in fp32, profiler off."""
+    import time
+    import torch
+    from ldmseg_amd import _lib
+    from ldmseg_amd.models import GeneralVAESeg
+    from ldmseg_amd.models.vae import _name_arrays
+    lib, sd = _lib.lib(), state_dict("vae")
+    v = GeneralVAESeg(sd, scaling_factor=0.2, device="cuda:0", compute_dtype="fp32")
+    B, H, L = 2, 64, 8
+    x = (torch.rand((B, 7, H, H), generator=torch.Generator().manual_seed(81)) > 0.5).float().to("cuda:0")
+    z, gl, gm = randn((B, 4, L, L), 82), randn((B, 128, 4 * L, 4 * L), 83), randn((B, 8, L, L), 84)
+    gz, s = torch.empty_like(z), _lib.stream_ptr(torch.device("cuda:0"))
+    ge = {k: torch.empty(tuple(t.shape), device="cuda:0") for k, t in sd.items() if k.startswith("encoder.")}
+    gd = {k: torch.empty(tuple(t.shape), device="cuda:0") for k, t in sd.items() if k.startswith("decoder.")}
+    ae, ad = _name_arrays(ge), _name_arrays(gd)
+    entries = {
+        "encode": lambda: v.encode_moments(x, 2.0, -1.0),
+        "decode": lambda: v.decode(z, interpolate=False, z_scale=5.0),
+        "encode_backward": lambda: _lib.check(lib.ldmseg_vae_encode_backward(v._h, _lib.ptr(x), 2.0, -1.0, B, H, _lib.ptr(gm), *ae, s)),
+        "decode_backward": lambda: _lib.check(lib.ldmseg_vae_decode_backward(v._h, _lib.ptr(z), 5.0, B, L, _lib.ptr(gl), _lib.ptr(gz), *ad, s)),
+    }
+    out = {}
+    for name, fn in entries.items():
+        fn()
+        torch.cuda.synchronize()
+        out[name] = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                fn()
+            torch.cuda.synchronize()
+            out[name].append(round((time.perf_counter() - t0) * 1e3, 3))
+    with open(out_path, "w") as f:
+        json.dump(out, f)
+
+
 def child(group, out_path):
     sys.path[:0] = [ROOT, os.path.join(ROOT, "latent-diffusion-segmentation_amd")]
+    if group == "host_times":
+        return host_times(out_path)
     rec = Recorder()
     globals()["g_" + group](rec)
     with open(out_path, "w") as f:
@@ -329,6 +444,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--groups", default=",".join(GROUPS))
     ap.add_argument("--table", default=None)
+    ap.add_argument("--host-times", action="store_true", help="also time the seg-VAE entries' host cost under both libraries")
     ap.add_argument("--child", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -337,7 +453,9 @@ def main():
     assert os.path.exists(PARENT_LIB), "build the parent commit's library into tools/ab/lib_parent.so first"
     rows, all_equal = [], True
     tmp = tempfile.mkdtemp()
-    for g in a.groups.split(","):
+
+    def both(g):
+        """the records of child `g` under the parent's library, then under this tree's; None when one of them did not end well"""
         recs = {}
         for side in ("parent", "tree"):
             env = dict(os.environ)
@@ -350,9 +468,15 @@ def main():
             r = subprocess.run(cmd, env=env)
             if r.returncode != 0:
                 print(f"child {side}/{g} ended with status {r.returncode}: stopping here", flush=True)
-                return 2
+                return None
             with open(out) as f:
                 recs[side] = json.load(f)
+        return recs
+
+    for g in a.groups.split(","):
+        recs = both(g)
+        if recs is None:
+            return 2
         p, t = recs["parent"], recs["tree"]
         if list(p) != list(t):
             print(f"group {g}: the two builds ran different scenarios")
@@ -370,6 +494,14 @@ def main():
     w = max(len(r[0]) for r in rows)
     lines = [f"{'scenario':<{w}}  outputs  launches  parent vs this tree"] + [f"{n:<{w}}  {h:>7}  {l:>8}  {e}" for n, h, l, e in rows]
     lines.append(f"{len(rows)} scenarios: " + ("every hash, launch sequence and byte count equal" if all_equal else "DIFFERENCES, see above"))
+    if a.host_times:
+        recs = both("host_times")
+        if recs is None:
+            return 2
+        lines += ["", "host time: ms of 200 back-to-back calls + one synchronize, B = 2, H = 64, fp32, five repeats (parent | this tree)"]
+        for name in recs["parent"]:
+            pt, tt = recs["parent"][name], recs["tree"][name]
+            lines.append(f"{name:<16} parent {pt} min {min(pt)} max {max(pt)} | tree {tt} median {sorted(tt)[len(tt) // 2]}")
     print("\n".join(lines))
     if a.table:
         with open(a.table, "w") as f:
